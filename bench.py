@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - headline benchmark of the MI355X tinyimgcodec hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -36,6 +36,16 @@ to HBM).  `cpu_baseline` / `cpu_baseline_threads` = the oracle (C restatement of
 row bands on this process's CPU share (at most 16 threads: a GPU box gives one GPU 16 of its cores; `cores` says how many);
 `cpu_baseline_numpy_scipy` = oracle/np_encode.py, a numpy/scipy restatement of encode() on the reference's own library stack,
 where scipy is importable.  `config4` = the 256-frame shard of this rank, kernel-only and host -> host.
+
+PLAIN RUN vs --full (N = 1): a plain run sets up, settles the clocks, runs the W warm-up and K timed steps, writes the outputs if asked and prints
+the line (`value`, `ms_per_step`, `roofline.achieved`).  Everything else - the statistics launch (`fallback_blocks_per_launch`), the parity of the
+timed launches' coefficients (`config.parity`), the per-launch pass (`per_launch_us`, unless --per-launch same), `roofline.cold`, `config4`,
+`codec_resident`, `bench_set` and the CPU baselines - runs only with --full.  The N > 1 / config-4 line is the same either way.
+
+--dump-outputs DIR: after the timed steps, the coefficients the last timed launch left in its buffer (the (blocks, 64) int16 zig-zag array a caller
+of tic_dctq receives; at N > 1 / config 4 the rank's whole shard, files prefixed rank<r>_ at N > 1) as .npy: block_checksums (float64, per block
+sum over k of (k + 1) x coefficient k; per run of consecutive blocks if one per block would not fit), coefficients_sample (float32, the blocks of a
+fixed sample, seed 0, or every block where they fit) and coefficients_sample_blocks (float64, their indices); at most 60 MB in all.
 """
 import argparse
 import ctypes as C
@@ -55,6 +65,7 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 TB/s measured copy)
 BYTES_PER_PIXEL = 3.0  # 1 B uint8 read + 2 B int16 written
 COLD_PAIRS = 12        # 12 x (16.8 MB frame + 33.6 MB coefficients) = 604 MB in rotation
+DUMP_BYTES = 60_000_000  # --dump-outputs: .npy payload of one run, all ranks together
 
 
 def rand_frame(seed, h, w):
@@ -93,6 +104,9 @@ def main():
                     "(default: a dispatch that carries events is followed by a 5 us gap, profiles/r06_driver_flags.txt), on the timed launches themselves, or not at all")
     ap.add_argument("--no-preroll", dest="preroll", action="store_false", help="do not put 32 more settling launches into the timed submission")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="--gpus N > 1 without a launcher: watchdog over the N rank processes (s)")
+    ap.add_argument("--full", action="store_true", help="N = 1: also the statistics launch, parity, per-launch pass, cold figure, config4, "
+                    "codec_resident, bench_set and CPU baselines (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -169,13 +183,13 @@ def main():
     out = None
     if not multi:
         out = bench_config2(args, ctx, L, N, q, variant, barrier, ms)
-        if not args.no_config4:
+        if args.full and not args.no_config4:
             out["config4"] = shard_measurements(args, ctx, L, N, T, q, variant, 0, args.shard_frames, ms, steps=50)[0]
             out["config4"]["note"] = "the N = 1 baseline of every N > 1 line (scaling_baseline): same 256-frame shard, one GPU"
-        if not args.no_config4:
+        if args.full and not args.no_config4:
             out["codec_resident"] = codec_resident(args, ctx, L, N, q)
             out["bench_set"] = bench_set(args, ctx, L)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             img = rand_frame(1234, args.height, args.width)
             out["cpu_baseline"] = cpu_baseline(img, q, args.cpu_seconds, 1)
             out["cpu_baseline_threads"] = cpu_baseline(img, q, args.cpu_seconds, 0)
@@ -186,8 +200,12 @@ def main():
     else:
         n_total = args.shard_frames * world
         lo, hi = shard_range(n_total, rank, world)
+        dump = None
+        if args.dump_outputs:
+            def dump(zz):
+                dump_coefficients(args.dump_outputs, zz, prefix="rank%d_" % rank if world > 1 else "", budget=DUMP_BYTES // world)
         info, t_wall, kernel_ms, sizes_mine = shard_measurements(args, ctx, L, N, T, q, variant, lo, hi - lo, ms, steps=args.steps,
-                                                                 warmup=args.warmup, barrier=barrier, timed=True)
+                                                                 warmup=args.warmup, barrier=barrier, timed=True, dump=dump)
         node_i, ncpu_i = C.c_int(), C.c_int()
         ctx.check(L.tic_numa_info(ctx.handle, C.byref(node_i), C.byref(ncpu_i)))
         pci = L.tic_pci_bus_id(ctx.handle).decode()
@@ -301,7 +319,7 @@ def bench_config2(args, ctx, L, N, q, variant, barrier, ms):
     nblk = L.tic_num_blocks(h, w)
     # rotating pairs for the cold figure: 12 at 4096^2 (604 MB); frames whose pair alone exceeds the 256 MiB Infinity Cache need
     # only a few - three 16384^2 pairs are 2.4 GB in rotation
-    pairs = 1 if args.no_cold else (COLD_PAIRS if 3 * h * w * COLD_PAIRS < (3 << 30) else 3)
+    pairs = 1 if args.no_cold or not args.full else (COLD_PAIRS if 3 * h * w * COLD_PAIRS < (3 << 30) else 3)
     d_imgs, d_outs = (C.c_void_p * pairs)(), (C.c_void_p * pairs)()
     for k in range(pairs):
         a, b = C.c_void_p(), C.c_void_p()
@@ -311,13 +329,14 @@ def bench_config2(args, ctx, L, N, q, variant, barrier, ms):
         d_imgs[k], d_outs[k] = a, b
     d_img, d_out = d_imgs[0], d_outs[0]
 
-    # one untimed launch with the diagnostic counter on: how many blocks leave the fast path on this frame
+    # --full: one untimed launch with the diagnostic counter on: how many blocks leave the fast path on this frame
     fb = C.c_ulonglong(0)
-    ctx.check(L.tic_set_stats(ctx.handle, 1))
-    ctx.check(L.tic_last_fallback_blocks(ctx.handle, C.byref(fb)))  # resets the counter
-    ctx.check(L.tic_dctq_dev(ctx.handle, d_img, h, w, pitch, q, d_out, variant))
-    ctx.check(L.tic_last_fallback_blocks(ctx.handle, C.byref(fb)))
-    ctx.check(L.tic_set_stats(ctx.handle, 0))
+    if args.full:
+        ctx.check(L.tic_set_stats(ctx.handle, 1))
+        ctx.check(L.tic_last_fallback_blocks(ctx.handle, C.byref(fb)))  # resets the counter
+        ctx.check(L.tic_dctq_dev(ctx.handle, d_img, h, w, pitch, q, d_out, variant))
+        ctx.check(L.tic_last_fallback_blocks(ctx.handle, C.byref(fb)))
+        ctx.check(L.tic_set_stats(ctx.handle, 0))
 
     def burst():
         ctx.check(L.tic_dctq_dev_timed(ctx.handle, d_img, h, w, pitch, q, d_out, variant, 256, C.byref(ms)))
@@ -339,9 +358,15 @@ def bench_config2(args, ctx, L, N, q, variant, barrier, ms):
     wall_s = time.perf_counter() - t0
     ms_total_timed = ms.value
     kernel_ms = ms_total_timed / args.steps
-    parity = coefficient_parity(ctx, L, d_out, h, w, q, nblk)  # the buffer the timed launches just wrote
+    if args.dump_outputs:
+        zz = np.empty((nblk, 64), dtype=np.int16)
+        ctx.check(L.tic_memcpy_d2h(ctx.handle, zz.ctypes.data, d_out, nblk * 128))
+        dump_coefficients(args.dump_outputs, zz)
+    parity = {"status": "unchecked", "why": "checked with --full"}
+    if args.full:
+        parity = coefficient_parity(ctx, L, d_out, h, w, q, nblk)  # the buffer the timed launches just wrote
     per_launch = None
-    if args.per_launch != "off":
+    if args.per_launch == "same" or (args.per_launch == "separate" and args.full):
         kp = args.steps if args.per_launch == "same" else min(args.steps, 1000)
         if per is None:  # a pass of its own behind the timed one, never `value`
             settle(args, ctx, L, burst)  # (the parity check above left the device idle for ~100 ms: clocks settled again, as in front of the timed pass)
@@ -360,7 +385,7 @@ def bench_config2(args, ctx, L, N, q, variant, barrier, ms):
                       "a pass of its own behind the timed one (same untimed launches in front) and never `value`; ms_per_step - median = what the queue "
                       "adds between two back-to-back launches of the timed pass")}
     cold = None
-    if not args.no_cold:
+    if args.full and not args.no_cold:
         for _ in range(3):  # settle + warm-up of the rotating variant
             ctx.check(L.tic_dctq_dev_timed_rotating(ctx.handle, d_imgs, d_outs, pairs, h, w, pitch, q, variant, 600 if 3 * h * w < (200 << 20) else 20, C.byref(ms)))
         kcold = max(600, min(args.steps, 3000)) if 3 * h * w < (200 << 20) else max(args.steps, 20)
@@ -401,9 +426,9 @@ def bench_config2(args, ctx, L, N, q, variant, barrier, ms):
             "kernel": args.variant,
             "frames_per_step_per_gpu": 1,
             "settle_ms": args.settle_ms,
-            "untimed_launches": untimed + 1,
-            "untimed_note": "back-to-back launches of the same kernel before the W warm-up steps (clock settling) + 1 statistics launch",
-            "fallback_blocks_per_launch": fb.value,
+            "untimed_launches": untimed + (1 if args.full else 0),
+            "untimed_note": "back-to-back launches of the same kernel before the W warm-up steps (clock settling) + 1 statistics launch with --full",
+            "fallback_blocks_per_launch": fb.value if args.full else None,
             "parity": parity,
             "device": ctx.arch,
             "timed_region": "the last %d settling launches, the W warm-up launches, HIP event, the K timed launches, HIP event - one submission on the "
@@ -445,9 +470,10 @@ def bench_config2(args, ctx, L, N, q, variant, barrier, ms):
     return out
 
 
-def shard_measurements(args, ctx, L, N, T, q, variant, first, count, ms, steps, warmup=10, barrier=None, timed=False):
+def shard_measurements(args, ctx, L, N, T, q, variant, first, count, ms, steps, warmup=10, barrier=None, timed=False, dump=None):
     """BASELINE config 4, this rank's shard: frames first .. first+count-1 (1080x1920, seed 1234 + i).
-    Kernel-only: the shard resident in HBM, one batched launch per step.  Host -> host: tic_compress_batch on the same frames."""
+    Kernel-only: the shard resident in HBM, one batched launch per step.  Host -> host: tic_compress_batch on the same frames.
+    dump: called with the (count x blocks, 64) coefficients the last timed launch wrote."""
     h, w = 1080, 1920
     frames = [rand_frame(1234 + first + i, h, w) for i in range(count)]
     nblk = L.tic_num_blocks(h, w)
@@ -473,6 +499,10 @@ def shard_measurements(args, ctx, L, N, T, q, variant, first, count, ms, steps, 
         barrier()
     t_wall = time.perf_counter() - t0
     kernel_ms = ms.value / steps
+    if dump is not None:
+        zz = np.empty((count * nblk, 64), dtype=np.int16)
+        ctx.check(L.tic_memcpy_d2h(ctx.handle, zz.ctypes.data, d_out, coef_bytes * count))
+        dump(zz)
     ctx.check(L.tic_dev_free(ctx.handle, d_in))
     ctx.check(L.tic_dev_free(ctx.handle, d_out))
     # whole pipeline host -> host through the C-ABI (caller-owned worst-case sized output buffers, as a C caller would hold
@@ -575,6 +605,25 @@ def frame_nodes(frames):
         return sorted(set(int(v) for v in status))
     except Exception:  # noqa: BLE001
         return None
+
+
+def dump_coefficients(dirname, zz, prefix="", budget=DUMP_BYTES):
+    """--dump-outputs: (blocks, 64) int16 coefficients as .npy files of at most `budget` bytes together: the checksums of all blocks (at
+    most half of it), the sampled blocks in what is left (module docstring).  The checksums are integers below 2^27, exact in float64."""
+    os.makedirs(dirname, exist_ok=True)
+    n = zz.shape[0]
+    weights = np.arange(1, 65, dtype=np.int32)
+    sums = np.empty(n, dtype=np.float64)
+    for a in range(0, n, 1 << 20):
+        sums[a:a + (1 << 20)] = zz[a:a + (1 << 20)].astype(np.int32) @ weights
+    group = -(-n * 8 // (budget // 2))  # consecutive blocks per checksum
+    if group > 1:
+        sums = np.add.reduceat(sums, np.arange(0, n, group))
+    s = min(n, (budget - sums.nbytes - 1024) // (64 * 4 + 8))  # (1024: the three .npy headers)
+    idx = np.arange(n) if s == n else np.sort(np.random.default_rng(0).choice(n, s, replace=False))
+    np.save(os.path.join(dirname, prefix + "block_checksums.npy"), sums)
+    np.save(os.path.join(dirname, prefix + "coefficients_sample.npy"), zz[idx].astype(np.float32))
+    np.save(os.path.join(dirname, prefix + "coefficients_sample_blocks.npy"), idx.astype(np.float64))
 
 
 def coefficient_parity(ctx, L, d_out, h, w, q, nblk):

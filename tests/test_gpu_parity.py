@@ -1367,6 +1367,48 @@ def test_bench_lines_name_their_scaling_baseline(tmp_path):
     assert three["config"]["gathered_sizes"] == two["config"]["gathered_sizes"]
 
 
+def test_bench_plain_run_dumps_its_outputs_and_full_run_keeps_its_legs(tmp_path, oracle):
+    """bench.py --gpus 1 --steps K --warmup W measures the headline only; with --dump-outputs it writes what the last timed launch left in its
+    coefficient buffer: the sampled blocks are the oracle's coefficients, the checksums those of every block of the oracle's, and a second
+    run writes the same files.  --full keeps the legs behind the headline: parity of the timed launches, per-launch pass, cold figure."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    plain = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + plain + ["--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=300, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    line = lines[0]
+    assert line["steps"] == 20 and line["warmup"] == 5 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["config"]["launches_in_the_timed_submission"]["timed"] == 20
+    for leg in ("config4", "codec_resident", "bench_set", "cpu_baseline"):
+        assert leg not in line
+    assert "cold" not in line["roofline"] and line["config"]["per_launch_us"] is None and line["config"]["parity"]["status"] == "unchecked"
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["block_checksums.npy", "coefficients_sample.npy", "coefficients_sample_blocks.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64e6
+    got = {f: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert got[f].dtype in (np.float32, np.float64)
+        assert np.array_equal(got[f], np.load(tmp_path / "b" / f))
+    want = oracle.encode_zz16(rand_frame(1234, 4096, 4096), 50)
+    assert np.array_equal(got["block_checksums.npy"], want.astype(np.int64) @ np.arange(1, 65, dtype=np.int64))
+    blocks = got["coefficients_sample_blocks.npy"].astype(np.int64)
+    assert len(blocks) > len(want) // 2
+    assert np.array_equal(got["coefficients_sample.npy"], want[blocks].astype(np.float32))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + plain + ["--full", "--no-config4", "--no-cpu-baseline"],
+                       capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    full = json.loads(r.stdout.strip().splitlines()[-1])
+    assert full["config"]["parity"]["status"] == "ok" and full["config"]["per_launch_us"]["launches"] == 20
+    assert full["roofline"]["cold"]["launches"] >= 600 and isinstance(full["config"]["fallback_blocks_per_launch"], int)
+
+
 def test_decoder_edges_round3(ctx, golden, monkeypatch):
     """decoder_edges.npz (reference-generated, round 3): same exception class as the reference for streams shorter than the header
     (struct.error) and for streams flagged as carrying a Huffman table (ValueError); same pixels for the stream the reference's

@@ -6,6 +6,7 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
 mkdir -p gpurun_out
+TRACES=${TIC_TRACES:-traces}  # rocprofv3 directories of the steps that run bench.py --full (driver_prof, prof_cold)
 export TMPDIR=/tmp
 run() { # name timeout cmd...
   local name=$1 t=$2; shift 2
@@ -44,22 +45,22 @@ for step in "$@"; do
     tests_fast) run pytest_gpu_fast 600 python -m pytest tests -m gpu -x -q -k "not 16384" ;;
     tests_all)  run pytest_gpu_all 900 python -m pytest tests -m gpu -q ;;
     smoke)      run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)      run bench 300 python bench.py ;;
-    bench_cold) run bench_cold 300 python bench.py --steps 50 --warmup 10 --settle-ms 1 --no-cpu-baseline --no-config4 ;;
-    bench_exact) run bench_exact 300 python bench.py --variant exact --no-cpu-baseline ;;
-    bench16k)   run bench16k 300 python bench.py --height 16384 --width 16384 --steps 20 --warmup 3 --no-cpu-baseline ;;
+    bench)      run bench 300 python bench.py --full ;;
+    bench_cold) run bench_cold 300 python bench.py --full --steps 50 --warmup 10 --settle-ms 1 --no-cpu-baseline --no-config4 ;;
+    bench_exact) run bench_exact 300 python bench.py --full --variant exact --no-cpu-baseline ;;
+    bench16k)   run bench16k 300 python bench.py --full --height 16384 --width 16384 --steps 20 --warmup 3 --no-cpu-baseline ;;
     config5)    for q in 10 50 90; do
                   rm -rf gpurun_out/c5_prof_q$q gpurun_out/c5_rd_q$q gpurun_out/c5_wr_q$q
                   C5="bench.py --height 16384 --width 16384 --quality $q --steps 20 --warmup 3 --no-cpu-baseline --no-config4 --no-cold"
-                  run c5_cold_q$q 300 python bench.py --height 16384 --width 16384 --quality $q --steps 20 --warmup 3 --no-cpu-baseline --no-config4
+                  run c5_cold_q$q 300 python bench.py --full --height 16384 --width 16384 --quality $q --steps 20 --warmup 3 --no-cpu-baseline --no-config4
                   run c5_prof_q$q 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/c5_prof_q$q -- python $C5
                   run c5_rd_q$q 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/c5_rd_q$q -- python bench.py --height 16384 --width 16384 --quality $q --steps 3 --warmup 1 --settle-ms 1 --no-cpu-baseline --no-config4 --no-cold
                   run c5_wr_q$q 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/c5_wr_q$q -- python bench.py --height 16384 --width 16384 --quality $q --steps 3 --warmup 1 --settle-ms 1 --no-cpu-baseline --no-config4 --no-cold
                 done ;;
     driver_flags) T=${TIC_TAG:-a}
                 run df_tool_$T 300 python tools/driver_flags.py 5
-                for i in 1 2 3; do run df_short_${T}$i 200 python3 bench.py --gpus 1 --steps 20 --warmup 5; done
-                run df_long_$T 300 python3 bench.py --gpus 1 --steps 5000 --warmup 2000 --no-cpu-baseline ;;
+                for i in 1 2 3; do run df_short_${T}$i 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full; done
+                run df_long_$T 300 python3 bench.py --gpus 1 --steps 5000 --warmup 2000 --full --no-cpu-baseline ;;
     clock_profile) run clock_profile 120 python tools/clock_profile.py 500 300 ;;
     bench_set)  run bench_set 300 python tools/bench_set_timing.py ;;
     tests_dec)  run pytest_gpu_dec 900 python -m pytest tests -m gpu -x -q -k "decompress or decoder or benchmark_set or truncated or scaled or config5_frame or shipped" ;;
@@ -67,10 +68,10 @@ for step in "$@"; do
     small_probe) run small_probe 120 python tools/small_compress_probe.py ;;
     ab_r4)      run ab_r4 400 python tools/ab_libs.py tools/bin/lib_r4.so --rounds 7; run ab_r4_q90 300 python tools/ab_libs.py tools/bin/lib_r4.so --rounds 5 --quality 90 ;;
     kernarg)    export HIP_FORCE_DEV_KERNARG=0; run kernarg0 120 python tools/driver_flags.py 3; export HIP_FORCE_DEV_KERNARG=1; run kernarg1 120 python tools/driver_flags.py 3; unset HIP_FORCE_DEV_KERNARG ;;
-    driver_prof) rm -rf gpurun_out/df_prof; run df_prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/df_prof -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-cold --no-config4 ;;
+    driver_prof) rm -rf "$TRACES/df_prof"; run df_prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$TRACES/df_prof" -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-cold --no-config4 ;;
     sweep)      run sweep 600 python tools/sweep.py ;;
     prof)       rm -rf gpurun_out/prof; run prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -- python bench.py --no-cpu-baseline --no-cold --no-config4 ;;
-    prof_cold)  rm -rf gpurun_out/prof_cold; run prof_cold 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_cold -- python bench.py --steps 50 --warmup 10 --settle-ms 1 --no-cpu-baseline --no-config4 ;;
+    prof_cold)  rm -rf "$TRACES/prof_cold"; run prof_cold 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$TRACES/prof_cold" -- python bench.py --full --steps 50 --warmup 10 --settle-ms 1 --no-cpu-baseline --no-config4 ;;
     pmc_rd)     rm -rf gpurun_out/pmc_rd; run pmc_rd 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_rd -- python bench.py --steps 5 --warmup 1 --settle-ms 1 --no-cpu-baseline --no-cold --no-config4 ;;
     pmc_wr)     rm -rf gpurun_out/pmc_wr; run pmc_wr 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_wr -- python bench.py --steps 5 --warmup 1 --settle-ms 1 --no-cpu-baseline --no-cold --no-config4 ;;
     pmc_sq)     rm -rf gpurun_out/pmc_sq; run pmc_sq 400 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES --output-format csv -d gpurun_out/pmc_sq -- python bench.py --steps 5 --warmup 1 --settle-ms 1 --no-cpu-baseline --no-cold --no-config4 ;;

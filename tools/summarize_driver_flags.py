@@ -32,7 +32,8 @@ for tag in tags:
         keep = [l.rstrip() for l in open(tool) if re.match(r"^(idle|warm|preroll|steps)\s", l)]
         out.append("tools/driver_flags.py in one process (5 rounds, 60 ms of settling in front of every measurement):")
         out += ["  " + l for l in keep]
-prof = sorted(glob.glob(os.path.join(root, "gpurun_out", "df_prof", "*", "*_kernel_trace.csv")), key=os.path.getmtime, reverse=True)
+traces = os.environ.get("TIC_TRACES", os.path.join(root, "traces"))  # where tools/gpu_run.sh puts the rocprofv3 directory of driver_prof
+prof = sorted(glob.glob(os.path.join(traces, "df_prof", "*", "*_kernel_trace.csv")), key=os.path.getmtime, reverse=True)
 line = None
 pth = os.path.join(root, "gpurun_out", "df_prof.txt")
 if os.path.exists(pth):

@@ -79,7 +79,8 @@ if kt and bench_line:
             json.dump(bench_line, f)
     else:
         out["timed_steps"] = {"error": "the trace holds %d launches, the timed submission would end at launch %d" % (len(rows), first + want)}
-kc = sorted(glob.glob(os.path.join(G, "prof_cold", "*", "*kernel_stats.csv")), key=os.path.getmtime, reverse=True)
+TRACES = os.environ.get("TIC_TRACES", os.path.join(ROOT, "traces"))  # where tools/gpu_run.sh puts the rocprofv3 directory of prof_cold
+kc = sorted(glob.glob(os.path.join(TRACES, "prof_cold", "*", "*kernel_stats.csv")), key=os.path.getmtime, reverse=True)
 if kc:
     shutil.copy(kc[0], os.path.join(P, f"{tag}_rocprofv3_kernel_stats_cold.csv"))
     for r in csv.DictReader(open(kc[0])):
