@@ -295,6 +295,42 @@ int tic_decompress_dev_async(tic_ctx *ctx, const void *d_stream, size_t len, voi
                              long long *ticket);
 int tic_decompress_async_result(tic_ctx *ctx, long long ticket, int wait, int *h_out, int *w_out);
 
+/* ---- per-image Huffman tables: compress(image, quality, auto_generate_huffman_table=True), codec.py:133-164 ----------------
+ *      Stream: the 16-byte header with the flag word written most significant bit first (write_uint(1 << 31, 32), codec.py:111: bytes
+ *      80 00 00 00), the table of write_huffman_table (codec.py:73-84: DC u16 count, per entry category:4 length:4 code; AC u16 count,
+ *      per entry run:4 size:4 length:8 code; entries in the tree's depth-first leaf order), not byte-aligned, then the payload of
+ *      encode_huffman (huffman.py:41-63) with the frame's own codes, zero-padded to a byte.  The tree is HuffmanTree's
+ *      (huffman.py:137-194): leaves in first-occurrence order into heapq, ties broken by the heap's mechanics.  A code plus its value
+ *      bits may take up to 64 bits; a deeper tree gives TIC_E_RANGE, as does a DC category or AC size above 15 (which
+ *      write_huffman_table cannot store).  An image without blocks is TIC_E_ARG (the reference raises IndexError in
+ *      calc_huffman_table, huffman.py:101-108).  The reference's own decompress() misreads these streams (it reads the flag
+ *      little-endian, codec.py:119); tic_decompress keeps that behaviour, tic_decompress_adaptive reads them as written. */
+/* Upper bound of an adaptive stream's size. */
+size_t tic_compress_adaptive_bound(int h, int w);
+/* Host buffers, as tic_compress: GPU transform stage, GPU symbol statistics, the table built on the host (one read-back of the
+ * statistics), GPU packing with the table, download of the stream.  TIC_E_SPACE when the stream does not fit `cap` (*out_len then
+ * receives the bytes needed; nothing is written). */
+int tic_compress_adaptive(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int quality, uint8_t *out,
+                          size_t cap, size_t *out_len);
+/* The same from int16 [N][64] zig-zag coefficients with absolute DC (the layout of tic_dctq; DPCM as codec.py:34-35): the adaptive twin
+ * of tic_entropy_encode, on the GPU. */
+int tic_entropy_encode_adaptive(tic_ctx *ctx, const int16_t *coeffs_zz, int h, int w, int quality, uint8_t *out, size_t cap,
+                                size_t *out_len);
+/* The table alone, on the host (calc_huffman_table huffman.py:101-108 + write_huffman_table codec.py:73-84): per symbol its count and
+ * first-occurrence key (DC: index = size category, key = block; AC: index = (run << 4) | size, key = block * 64 + ordinal of the symbol
+ * in the block's run-length list) -> per symbol codeword (right-aligned) and length (0 for symbols that do not occur, and for the
+ * single symbol of a one-symbol tree), and the serialized table bits (MSB first, zero-padded; *table_bits = their number).
+ * TIC_E_ARG when either histogram is empty, TIC_E_RANGE for a code too long (see above), TIC_E_SPACE when table_cap is short
+ * (2,610 bytes always suffice). */
+int tic_huffman_table_build(const uint64_t *dc_count /*16*/, const uint64_t *dc_first /*16*/, const uint64_t *ac_count /*256*/,
+                            const uint64_t *ac_first /*256*/, uint64_t *dc_code /*16*/, uint8_t *dc_len /*16*/, uint64_t *ac_code /*256*/,
+                            uint8_t *ac_len /*256*/, uint8_t *table, size_t table_cap, size_t *table_bits);
+/* decompress() codec.py:167-189 for streams with an embedded table, read as written: host Huffman decode (codes up to 64 bits), GPU
+ * dequantise + inverse DCT as tic_decompress.  Strict where the reference is not: a malformed table (not a prefix code, counts out of
+ * range, a code the payload meets without a symbol), a truncated stream, a block of more than 63 AC coefficients or a DC outside int16
+ * give TIC_E_STREAM.  out: uint8[h*w]. */
+int tic_decompress_adaptive(tic_ctx *ctx, const uint8_t *data, size_t len, uint8_t *out, size_t cap);
+
 /* ---- multi-GPU (the reference has no counterpart: it is single-process, codec.py:133-164 runs one image
  *      at a time).  One process per GPU; a batch shards by independent frames (frame i -> rank i / ceil(B/G)) with no
  *      data-path collective.  The one exchange is an all-gather of per-frame compressed sizes, so that every rank knows every

@@ -143,6 +143,18 @@ SIGNATURES = {
     "tic_set_decode_guess": (C.c_int, [_ctxp, C.c_int]),
     "tic_decompress_dev_async": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_ssize_t, C.c_size_t, C.POINTER(C.c_longlong)]),
     "tic_decompress_async_result": (C.c_int, [_ctxp, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tic_compress_adaptive_bound": (C.c_size_t, [C.c_int, C.c_int]),
+    "tic_compress_adaptive": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    ),
+    "tic_entropy_encode_adaptive": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tic_huffman_table_build": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+         C.POINTER(C.c_size_t)],
+    ),
+    "tic_decompress_adaptive": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "tic_selftest_transpose": (C.c_int, [_ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "tic_comm_create": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]),
     "tic_comm_create_ex": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]),

@@ -7,6 +7,13 @@ Same names, argument meaning and error behaviour as the reference so that it is 
     encode(image, quality=50) -> {"height","width","quality","dc","ac"}          codec.py:26-43
     decode(data) -> np.ndarray[uint8]                                            codec.py:46-70
 
+and, for the reference's per-image Huffman tables (compress(image, q, auto_generate_huffman_table=True), codec.py:133-164,
+huffman.py:101-194), under names of their own because compress() keeps raising for that flag:
+
+    compress_adaptive(image, quality=50) -> bytes   the reference's adaptive stream, byte for byte
+    entropy_encode_adaptive(coeffs_zz, height, width, quality) -> bytes   the same from int16 [N, 64] zig-zag coefficients
+    decompress_adaptive(data) -> np.ndarray[uint8]  reads such a stream as written
+
 The transform stage (pad, level shift, DCT, quantise, zig-zag) and the entropy stage (DPCM, run lengths, Huffman codes, bit
 packing; the Huffman decode and the inverse transform of decompress()) run in hand-written gfx950 kernels; the library's host
 entropy coder (C++) serves encode()-style callers that hold coefficients on the host, and streams the device decoder hands back
@@ -20,7 +27,10 @@ Documented differences from the reference (all outside its working domain):
     constants of a non-integral quality in [1, 99] are built per call, tic_set_custom_quality); qualities below 1 or negative (for
     which the reference computes with huge or negative divisors) raise ValueError;
   * auto_generate_huffman_table=True raises NotImplementedError (that path is broken in the reference:
-    the table flag is written big-endian and read little-endian, codec.py:111/119);
+    the table flag is written big-endian and read little-endian, codec.py:111/119); compress_adaptive() writes the reference's
+    stream, and decompress() reads it back as the reference does (garbage pixels, flag misread);
+  * decompress_adaptive() has no working counterpart in the reference and is strict, unlike decompress(): a malformed table or a
+    truncated or damaged stream raises ValueError instead of decoding to garbage;
   * quality > 100 raises ValueError (the reference produces streams with negative divisors);
   * streams whose little-endian flag word has bit 31 set (an embedded Huffman table) raise ValueError in decompress() - what the
     reference raises for every such stream that does not hold a well-formed table; scaled_dct streams (the reference's C encoder) are
@@ -152,7 +162,8 @@ def compress(image, quality=50, auto_generate_huffman_table=False, ctx=None):
     img, h, w, wide = _as_image(image)
     q = _check_quality(quality, packs_header=True)
     if auto_generate_huffman_table:
-        raise NotImplementedError("auto_generate_huffman_table=True is not supported (broken in the reference)")
+        raise NotImplementedError("auto_generate_huffman_table=True is not supported by compress() (broken in the reference): "
+                                  "use compress_adaptive()")
     ctx = _ctx(ctx)
     L = N.load()
     if wide:  # integer pixels outside 0..255: exact float64 transform on the device, host entropy coder
@@ -263,6 +274,76 @@ def entropy_encode(coeffs_zz, height, width, quality):
     if rc != N.TIC_OK:
         raise N.NativeError(rc, "tic_entropy_encode failed")
     return out[: n.value].tobytes()
+
+
+def _adaptive_encode(ctx, fn, args, cap):
+    """fn(ctx, *args, out, cap, &len) of an adaptive entry point (call with ctx.lock held); once more with the exact size when the
+    first guess of the stream's size was short (the library reports it and writes nothing)."""
+    for _ in range(2):
+        out = getattr(ctx, "_adapt_buf", None)  # kept on the context, as compress()'s landing buffer (first-touch page faults)
+        if out is None or out.size < cap:
+            out = ctx._adapt_buf = np.empty(cap, dtype=np.uint8)
+        n = C.c_size_t(0)
+        rc = fn(ctx.handle, *args, out.ctypes.data, cap, C.byref(n))
+        if rc == N.TIC_E_SPACE and n.value > cap:
+            cap = n.value
+            continue
+        break
+    if rc == N.TIC_E_RANGE:  # a category above 15 (int2ba in write_huffman_table, codec.py:73-84), or a code past 64 bits
+        raise OverflowError(N.load().tic_last_error(ctx.handle).decode())
+    ctx.check(rc)
+    return out[: n.value].tobytes()
+
+
+def compress_adaptive(image, quality=50, ctx=None):
+    """compress(image, quality, auto_generate_huffman_table=True) of the reference (codec.py:133-164): the stream with the image's own
+    Huffman tables (huffman.py:101-194), byte for byte.  Transform, symbol statistics and packing on the GPU, the table on the host."""
+    img, h, w = _as_u8_image(image)  # 8-bit pixels only (ValueError otherwise), as compress_batch
+    q = _check_quality(quality, packs_header=True)
+    L = N.load()
+    if L.tic_num_blocks(h, w) == 0:
+        raise IndexError("index -1 is out of bounds for axis 0 with size 0")  # calc_huffman_table on an empty symbol list
+    ctx = _ctx(ctx)
+    with ctx.lock:
+        return _adaptive_encode(ctx, L.tic_compress_adaptive, (img.ctypes.data, h, w, img.strides[0], q), L.tic_compress_bound(h, w) + 4096)
+
+
+def entropy_encode_adaptive(coeffs_zz, height, width, quality, ctx=None):
+    """The adaptive twin of entropy_encode(), on the GPU: int16 [N, 64] zig-zag coefficients (absolute DC) -> adaptive stream."""
+    L = N.load()
+    height, width = int(height), int(width)
+    q = _check_quality(quality, packs_header=True)
+    n = L.tic_num_blocks(height, width)
+    zz = np.ascontiguousarray(coeffs_zz, dtype=np.int16)
+    if zz.shape != (n, 64):
+        raise ValueError("coefficients of shape %r do not match %d blocks of 64" % (zz.shape, n))
+    if n == 0:
+        raise IndexError("index -1 is out of bounds for axis 0 with size 0")
+    ctx = _ctx(ctx)
+    with ctx.lock:
+        return _adaptive_encode(ctx, L.tic_entropy_encode_adaptive, (zz.ctypes.data, height, width, q),
+                                L.tic_compress_bound(height, width) + 4096)
+
+
+def decompress_adaptive(data, ctx=None):
+    """Reads a stream of compress_adaptive() (or of the reference's compress(..., auto_generate_huffman_table=True)) as written: host
+    Huffman decode with the embedded table, inverse transform on the GPU.  Strict: ValueError for a malformed table, a truncated or
+    damaged stream - the reference has no working counterpart, and decompress() keeps the reference's reading (garbage)."""
+    ctx = _ctx(ctx)
+    buf = _as_bytes_view(data)
+    if buf.size < 16:
+        raise ValueError("stream shorter than its 16-byte header")
+    hdr = parse_header(buf)
+    h, w = hdr["height"], hdr["width"]
+    if h < 0 or w < 0:
+        raise ValueError("negative image size in the header")
+    out = np.zeros((h, w), dtype=np.uint8)
+    with ctx.lock:
+        rc = N.load().tic_decompress_adaptive(ctx.handle, buf.ctypes.data, buf.size, out.ctypes.data, out.size)
+        if rc in (N.TIC_E_STREAM, N.TIC_E_SPACE):
+            raise ValueError(N.load().tic_last_error(ctx.handle).decode())
+        ctx.check(rc)
+    return out
 
 
 def _as_bytes_view(data):

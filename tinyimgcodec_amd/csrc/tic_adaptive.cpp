@@ -1,0 +1,308 @@
+// tic_adaptive.cpp - host half of the per-image Huffman tables: the tree of the reference's HuffmanTree (huffman.py:137-194) built
+// from symbol statistics, the table serialization of write_huffman_table (codec.py:73-84), and a strict decoder of such streams.
+//
+// Byte-exactness is decided by the tree: leaves enter a queue.PriorityQueue (CPython heapq) in first-occurrence order and are
+// compared by frequency alone, so equal frequencies are ordered by the heap's own mechanics.  Heap::push / Heap::pop below are
+// heapq.heappush / heappop (_siftdown / _siftup of Lib/heapq.py) step for step.
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/tinyimgcodec_hip.h"
+#include "tic_adaptive.h"
+#include "tic_entropy.h"
+
+namespace tic {
+namespace {
+
+struct Node {
+    unsigned long long freq;
+    int left, right; // children (-1: leaf)
+    int sym;         // bin of a leaf
+};
+
+struct Heap {
+    std::vector<Node> &nodes;
+    std::vector<int> h;
+    bool lt(int a, int b) const { return nodes[a].freq < nodes[b].freq; } // HuffmanTree.__Node.__lt__ (huffman.py:127-128)
+    void siftdown(size_t startpos, size_t pos) {
+        const int item = h[pos];
+        while (pos > startpos) {
+            const size_t parentpos = (pos - 1) >> 1;
+            const int parent = h[parentpos];
+            if (lt(item, parent)) {
+                h[pos] = parent;
+                pos = parentpos;
+                continue;
+            }
+            break;
+        }
+        h[pos] = item;
+    }
+    void siftup(size_t pos) {
+        const size_t endpos = h.size(), startpos = pos;
+        const int item = h[pos];
+        size_t childpos = 2 * pos + 1;
+        while (childpos < endpos) {
+            const size_t rightpos = childpos + 1;
+            if (rightpos < endpos && !lt(h[childpos], h[rightpos])) childpos = rightpos;
+            h[pos] = h[childpos];
+            pos = childpos;
+            childpos = 2 * pos + 1;
+        }
+        h[pos] = item;
+        siftdown(startpos, pos);
+    }
+    void push(int x) {
+        h.push_back(x);
+        siftdown(0, h.size() - 1);
+    }
+    int pop() {
+        const int last = h.back();
+        h.pop_back();
+        if (h.empty()) return last;
+        const int ret = h[0];
+        h[0] = last;
+        siftup(0);
+        return ret;
+    }
+};
+
+struct BitOut {
+    uint8_t *p;
+    size_t cap_bits, n = 0;
+    bool overflow = false;
+    void put(unsigned long long v, int bits) { // MSB first
+        for (int i = bits - 1; i >= 0; i--) {
+            if (n >= cap_bits) {
+                overflow = true;
+                return;
+            }
+            const uint8_t mask = (uint8_t)(0x80u >> (n & 7));
+            if ((v >> i) & 1ull)
+                p[n >> 3] |= mask;
+            else
+                p[n >> 3] &= (uint8_t)~mask;
+            n++;
+        }
+    }
+};
+
+// One tree (HuffmanTree.__init__ + __create_huffman_table): codes of the bins [0, nbins) that occur; `order` receives the leaves in
+// depth-first order, left (0) first - the insertion order of the reference's bidict.  False when a code exceeds max_len(bin).
+template <typename MaxLen>
+bool build_tree(const unsigned long long *count, const unsigned long long *first, int nbins, unsigned long long *code, uint8_t *len,
+                std::vector<int> &order, MaxLen max_len) {
+    std::vector<int> leaves;
+    for (int b = 0; b < nbins; b++) {
+        code[b] = 0;
+        len[b] = 0;
+        if (count[b]) leaves.push_back(b);
+    }
+    // __calc_freq's dict: first-occurrence order
+    std::stable_sort(leaves.begin(), leaves.end(), [&](int a, int b) { return first[a] < first[b]; });
+    std::vector<Node> nodes;
+    nodes.reserve(2 * leaves.size());
+    Heap q{nodes, {}};
+    for (int b : leaves) {
+        nodes.push_back({count[b], -1, -1, b});
+        q.push((int)nodes.size() - 1);
+    }
+    while (q.h.size() >= 2) {
+        const int u = q.pop(), v = q.pop();
+        nodes.push_back({nodes[u].freq + nodes[v].freq, u, v, -1});
+        q.push((int)nodes.size() - 1);
+    }
+    const int root = q.pop();
+    struct Item { int node, depth; unsigned long long code; };
+    std::vector<Item> stack{{root, 0, 0ull}};
+    order.clear();
+    bool ok = true;
+    while (!stack.empty()) {
+        const Item it = stack.back();
+        stack.pop_back();
+        const Node &nd = nodes[it.node];
+        if (nd.left < 0) {
+            if (it.depth > max_len(nd.sym)) ok = false;
+            code[nd.sym] = it.code;
+            len[nd.sym] = (uint8_t)std::min(it.depth, 255);
+            order.push_back(nd.sym);
+            continue;
+        }
+        const unsigned long long c = it.depth < 64 ? it.code << 1 : 0ull;
+        stack.push_back({nd.right, it.depth + 1, c | 1ull}); // right after left
+        stack.push_back({nd.left, it.depth + 1, c});
+    }
+    return ok;
+}
+
+struct BitIn {
+    const uint8_t *p;
+    size_t nbits, pos = 0;
+    bool get(int n, unsigned long long &v) { // n <= 64
+        if (n < 0 || pos + (size_t)n > nbits) return false;
+        v = 0;
+        for (int i = 0; i < n; i++, pos++) v = (v << 1) | ((p[pos >> 3] >> (7 - (pos & 7))) & 1u);
+        return true;
+    }
+};
+
+// Prefix-code decoder: a binary trie of the table's codewords.
+struct Trie {
+    struct T { int child[2] = {-1, -1}; int sym = -1; };
+    std::vector<T> t{T{}};
+    bool add(unsigned long long code, int n, int sym) {
+        int at = 0;
+        for (int i = n - 1; i >= 0; i--) {
+            if (t[at].sym >= 0) return false; // a code runs through another's leaf
+            const int b = (int)((code >> i) & 1ull);
+            if (t[at].child[b] < 0) {
+                t[at].child[b] = (int)t.size();
+                t.push_back(T{});
+            }
+            at = t[at].child[b];
+        }
+        if (t[at].sym >= 0 || t[at].child[0] >= 0 || t[at].child[1] >= 0) return false; // duplicate, or a prefix of another
+        t[at].sym = sym;
+        return true;
+    }
+    bool read(BitIn &r, int &sym) const {
+        int at = 0;
+        while (t[at].sym < 0) {
+            unsigned long long b;
+            if (!r.get(1, b)) return false;
+            at = t[at].child[b];
+            if (at < 0) return false; // a path without a codeword
+        }
+        sym = t[at].sym;
+        return true;
+    }
+};
+
+// BitBuffer.read_int (bitbuffer.py:56-66): one's complement for negatives
+inline int read_value(unsigned long long bits, int size) {
+    if (size == 0) return 0;
+    if ((bits >> (size - 1)) & 1ull) return (int)bits;
+    return -(int)((~bits) & ((1ull << size) - 1ull));
+}
+
+} // namespace
+
+int huffman_table_build(const unsigned long long *dc_count, const unsigned long long *dc_first, const unsigned long long *ac_count,
+                        const unsigned long long *ac_first, unsigned long long *dc_code, uint8_t *dc_len, unsigned long long *ac_code,
+                        uint8_t *ac_len, uint8_t *table, size_t table_cap, size_t *table_bits) {
+    if (!dc_count || !dc_first || !ac_count || !ac_first || !dc_code || !dc_len || !ac_code || !ac_len || !table_bits) return TIC_E_ARG;
+    if (!table && table_cap) return TIC_E_ARG;
+    if (std::none_of(dc_count, dc_count + 16, [](unsigned long long c) { return c != 0; }) ||
+        std::none_of(ac_count, ac_count + 256, [](unsigned long long c) { return c != 0; }))
+        return TIC_E_ARG; // no symbol: the reference's calc_huffman_table raises IndexError
+    std::vector<int> dc_order, ac_order;
+    // code + value bits of one symbol fit kAdaptMaxSymbolBits; a DC code also fits write_huffman_table's 4-bit length (always: at
+    // most 16 leaves), an AC code its 8 bits
+    const bool dc_ok = build_tree(dc_count, dc_first, 16, dc_code, dc_len, dc_order,
+                                  [](int c) { return std::min(15, kAdaptMaxSymbolBits - c); });
+    const bool ac_ok = build_tree(ac_count, ac_first, 256, ac_code, ac_len, ac_order,
+                                  [](int rs) { return kAdaptMaxSymbolBits - (rs & 15); });
+    if (!dc_ok || !ac_ok) return TIC_E_RANGE;
+    BitOut o{table, table_cap * 8};
+    o.put(dc_order.size(), 16); // codec.py:74-78
+    for (int c : dc_order) {
+        o.put((unsigned)c, 4);
+        o.put(dc_len[c], 4);
+        o.put(dc_code[c], dc_len[c]);
+    }
+    o.put(ac_order.size(), 16); // codec.py:79-84
+    for (int rs : ac_order) {
+        o.put((unsigned)(rs >> 4), 4);
+        o.put((unsigned)(rs & 15), 4);
+        o.put(ac_len[rs], 8);
+        o.put(ac_code[rs], ac_len[rs]);
+    }
+    if (o.overflow) return TIC_E_SPACE;
+    if (o.n & 7) o.p[o.n >> 3] &= (uint8_t)(0xff00u >> (o.n & 7)); // zero padding of the last byte
+    *table_bits = o.n;
+    return TIC_OK;
+}
+
+int adaptive_decode(const uint8_t *data, size_t len, int h, int w, int16_t *zz, const char **why) {
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!data || len < 16) {
+        *why = "stream shorter than its 16-byte header";
+        return TIC_E_STREAM;
+    }
+    if (!(data[12] & 0x80)) { // write_uint(1 << 31, 32): bit 31 most significant bit first (codec.py:111)
+        *why = "the header carries no embedded Huffman table";
+        return TIC_E_STREAM;
+    }
+    BitIn r{data, len * 8, 128};
+    Trie dc, ac;
+    unsigned long long v, cnt;
+    // read_huffman_table (codec.py:87-99)
+    if (!r.get(16, cnt) || cnt == 0 || cnt > 16) {
+        *why = "DC table: entry count missing or outside 1..16";
+        return TIC_E_STREAM;
+    }
+    for (unsigned long long i = 0; i < cnt; i++) {
+        unsigned long long cat, n, code;
+        if (!r.get(4, cat) || !r.get(4, n) || !r.get((int)n, code)) {
+            *why = "DC table truncated";
+            return TIC_E_STREAM;
+        }
+        if (!dc.add(code, (int)n, (int)cat) || cat + n > (unsigned long long)kAdaptMaxSymbolBits) {
+            *why = "DC table is not a prefix code";
+            return TIC_E_STREAM;
+        }
+    }
+    if (!r.get(16, cnt) || cnt == 0 || cnt > 256) {
+        *why = "AC table: entry count missing or outside 1..256";
+        return TIC_E_STREAM;
+    }
+    for (unsigned long long i = 0; i < cnt; i++) {
+        unsigned long long rs, n, code;
+        if (!r.get(8, rs) || !r.get(8, n) || n + (rs & 15) > (unsigned long long)kAdaptMaxSymbolBits || !r.get((int)n, code)) {
+            *why = "AC table truncated or a code longer than 64 bits";
+            return TIC_E_STREAM;
+        }
+        if (!ac.add(code, (int)n, (int)rs)) {
+            *why = "AC table is not a prefix code";
+            return TIC_E_STREAM;
+        }
+    }
+    const size_t nb = num_blocks(h, w);
+    long long dc_run = 0;
+    for (size_t b = 0; b < nb; b++) {
+        int16_t *c = zz + b * 64;
+        memset(c, 0, 128);
+        int sym;
+        if (!dc.read(r, sym) || !r.get(sym, v)) {
+            *why = "stream truncated or a code without a symbol (DC)";
+            return TIC_E_STREAM;
+        }
+        dc_run += read_value(v, sym); // np.cumsum (codec.py:53)
+        if (dc_run < -32768 || dc_run > 32767) {
+            *why = "DC outside int16";
+            return TIC_E_STREAM;
+        }
+        c[0] = (int16_t)dc_run;
+        int pos = 1; // decode_run_length (huffman.py:36-38): l zeros then k per symbol, EOB's trailing 0 dropped
+        for (;;) {
+            if (!ac.read(r, sym) || !r.get(sym & 15, v)) {
+                *why = "stream truncated or a code without a symbol (AC)";
+                return TIC_E_STREAM;
+            }
+            if (sym == 0) break; // EOB (huffman.py:92-94)
+            pos += sym >> 4;
+            if (pos > 63) {
+                *why = "block of more than 63 AC coefficients";
+                return TIC_E_STREAM;
+            }
+            c[pos++] = (int16_t)read_value(v, sym & 15);
+        }
+    }
+    return TIC_OK;
+}
+
+} // namespace tic

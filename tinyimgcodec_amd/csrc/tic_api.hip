@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/tinyimgcodec_hip.h"
+#include "tic_adaptive.h"
 #include "tic_entropy.h"
 #include "tic_entropy_dec_gpu.h"
 #include "tic_entropy_gpu.h"
@@ -230,6 +231,15 @@ struct tic_ctx {
     char pci[32] = {0};
     std::string err;
     char arch[128] = {0};
+    // per-image Huffman tables (tic_compress_adaptive): statistics, the frame's table and an error word in one allocation, the packing
+    // workspace and the stream, kept across calls
+    AdaptStats *d_adapt_stats = nullptr;
+    HuffWide *d_adapt_tab = nullptr;
+    uint32_t *d_adapt_err = nullptr;
+    void *d_adapt_work = nullptr;
+    size_t adapt_work_bytes = 0;
+    uint32_t *d_adapt_out = nullptr;
+    size_t adapt_out_bytes = 0;
 };
 
 // NUMA node of a device (its PCI function's numa_node in sysfs) and the CPUs of that node within this process's affinity mask.
@@ -401,6 +411,9 @@ void tic_destroy(tic_ctx *ctx) {
     if (ctx->dbat.d_desc) (void)hipFree(ctx->dbat.d_desc);
     if (ctx->dbat.h_status) (void)hipHostFree(ctx->dbat.h_status);
     if (ctx->dec_order) (void)hipEventDestroy(ctx->dec_order);
+    if (ctx->d_adapt_stats) (void)hipFree(ctx->d_adapt_stats); // table and error word live in the same block
+    if (ctx->d_adapt_work) (void)hipFree(ctx->d_adapt_work);
+    if (ctx->d_adapt_out) (void)hipFree(ctx->d_adapt_out);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -2844,6 +2857,155 @@ int tic_selftest_transpose(tic_ctx *ctx, const void *host_in, void *host_dpp, vo
     (void)hipFree(d_a);
     (void)hipFree(d_b);
     return TIC_OK;
+}
+
+// ---- per-image Huffman tables: compress(..., auto_generate_huffman_table=True), codec.py:133-164 / huffman.py:101-194 ----------------
+size_t tic_compress_adaptive_bound(int h, int w) {
+    // header, the largest table, and per block at most 65 symbols (DC, 63 AC, EOB) of at most kAdaptMaxSymbolBits each
+    return 16 + kAdaptMaxTableBytes + num_blocks(h, w) * (65 * kAdaptMaxSymbolBits / 8) + 8;
+}
+
+int tic_huffman_table_build(const uint64_t *dc_count, const uint64_t *dc_first, const uint64_t *ac_count, const uint64_t *ac_first,
+                            uint64_t *dc_code, uint8_t *dc_len, uint64_t *ac_code, uint8_t *ac_len, uint8_t *table, size_t table_cap,
+                            size_t *table_bits) {
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "64-bit words");
+    return huffman_table_build((const unsigned long long *)dc_count, (const unsigned long long *)dc_first, (const unsigned long long *)ac_count,
+                               (const unsigned long long *)ac_first, (unsigned long long *)dc_code, dc_len, (unsigned long long *)ac_code, ac_len,
+                               table, table_cap, table_bits);
+}
+
+// Statistics, table, packing of the n blocks in ctx->d_coef; the stream goes to the caller's host buffer.  One read-back in between:
+// the 4.4 KB of statistics the host builds the table from (it also yields the stream's exact length, checked against `cap` before
+// anything is packed).
+static int adaptive_encode_dev(tic_ctx *ctx, size_t n, int h, int w, int quality, uint8_t *out, size_t cap, size_t *out_len) {
+    if (!ctx->d_adapt_stats) {
+        char *p = nullptr;
+        const size_t a = align_up(sizeof(AdaptStats), 256), b = align_up(sizeof(HuffWide), 256);
+        HIPCHK(ctx, hipMalloc((void **)&p, a + b + 256));
+        ctx->d_adapt_stats = (AdaptStats *)p;
+        ctx->d_adapt_tab = (HuffWide *)(p + a);
+        ctx->d_adapt_err = (uint32_t *)(p + a + b);
+    }
+    const size_t wb = adaptive_work_bytes(n);
+    if (wb > ctx->adapt_work_bytes) {
+        if (ctx->d_adapt_work) HIPCHK(ctx, hipFree(ctx->d_adapt_work));
+        ctx->d_adapt_work = nullptr;
+        ctx->adapt_work_bytes = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->d_adapt_work, wb));
+        ctx->adapt_work_bytes = wb;
+    }
+    AdaptStats *st = ctx->d_adapt_stats;
+    HIPCHK(ctx, hipMemsetAsync(st, 0, sizeof(AdaptStats), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(st->first, 0xff, sizeof(st->first), ctx->stream));
+    HIPCHK(ctx, adaptive_stats((const int16_t *)ctx->d_coef, n, st, ctx->stream));
+    AdaptStats hs;
+    HIPCHK(ctx, hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (hs.err) return set_err(ctx, TIC_E_RANGE, "a DC category or AC size above 15 (write_huffman_table has 4 bits for it, codec.py:73-84)");
+    std::vector<uint8_t> head(16 + kAdaptMaxTableBytes, 0);
+    write_header(head.data(), h, w, quality);
+    head[12] = 0x80; // write_uint(1 << 31, 32): most significant bit first (codec.py:111)
+    unsigned long long dc_code[16], ac_code[256];
+    uint8_t dc_len[16], ac_len[256];
+    size_t tbits = 0;
+    int rc = huffman_table_build(hs.count + kAdaptDcBin, hs.first + kAdaptDcBin, hs.count, hs.first, dc_code, dc_len, ac_code, ac_len,
+                                 head.data() + 16, kAdaptMaxTableBytes, &tbits);
+    if (rc == TIC_E_RANGE)
+        return set_err(ctx, rc, "a Huffman code of this frame and its value bits exceed %d bits", kAdaptMaxSymbolBits);
+    if (rc) return set_err(ctx, rc, "Huffman table build failed");
+    HuffWide tab;
+    unsigned long long payload = 0;
+    for (int i = 0; i < kAdaptBins; i++) {
+        const bool dc = i >= kAdaptDcBin;
+        tab.code[i] = dc ? dc_code[i - kAdaptDcBin] : ac_code[i];
+        tab.len[i] = dc ? dc_len[i - kAdaptDcBin] : ac_len[i];
+        payload += hs.count[i] * (tab.len[i] + (unsigned)(dc ? i - kAdaptDcBin : i & 15));
+    }
+    const unsigned long long base = 128 + tbits, total = base + payload;
+    const size_t bytes = (size_t)((total + 7) / 8), words = (size_t)((total + 31) / 32);
+    if (bytes > cap) {
+        *out_len = bytes;
+        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", bytes, cap);
+    }
+    if (words * 4 > ctx->adapt_out_bytes) {
+        if (ctx->d_adapt_out) HIPCHK(ctx, hipFree(ctx->d_adapt_out));
+        ctx->d_adapt_out = nullptr;
+        ctx->adapt_out_bytes = 0;
+        HIPCHK(ctx, hipMalloc((void **)&ctx->d_adapt_out, words * 4));
+        ctx->adapt_out_bytes = words * 4;
+    }
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_adapt_out, 0, words * 4, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_adapt_out, head.data(), (size_t)((base + 7) / 8), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_adapt_tab, &tab, sizeof tab, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_adapt_err, 0, 4, ctx->stream));
+    HIPCHK(ctx, adaptive_pack((const int16_t *)ctx->d_coef, n, ctx->d_adapt_tab, ctx->d_adapt_work, ctx->d_adapt_out, base, words,
+                              ctx->d_adapt_err, ctx->stream));
+    uint32_t herr = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&herr, ctx->d_adapt_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_adapt_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (herr) return set_err(ctx, TIC_E_HIP, "packing reached past the stream's computed length (statistics and packing disagree)");
+    *out_len = bytes;
+    return TIC_OK;
+}
+
+int tic_compress_adaptive(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int quality, uint8_t *out, size_t cap,
+                          size_t *out_len) {
+    TIC_LOCK(ctx);
+    int rc = check_stream_geometry(ctx, h, w, row_stride, quality);
+    if (rc) return rc;
+    if (!out || !out_len) return set_err(ctx, TIC_E_ARG, "null output pointer");
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return set_err(ctx, TIC_E_ARG, "an image without blocks has no symbols to build a table from (the reference raises IndexError)");
+    if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t pitch = align_up((size_t)w, 256);
+    rc = ensure_scratch(ctx, pitch * (size_t)h, n * 128);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_img, pitch, image, (size_t)row_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    DctqArgs a = make_args(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, quality, ctx->d_coef);
+    HIPCHK(ctx, launch_dctq(a, 2, ctx->stream));
+    return adaptive_encode_dev(ctx, n, h, w, quality, out, cap, out_len);
+}
+
+int tic_entropy_encode_adaptive(tic_ctx *ctx, const int16_t *coeffs_zz, int h, int w, int quality, uint8_t *out, size_t cap,
+                                size_t *out_len) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (h < 0 || w < 0) return set_err(ctx, TIC_E_ARG, "negative image size");
+    if (quality < 1 || quality > 99) return set_err(ctx, TIC_E_QUALITY, "quality %d outside 1..99", quality);
+    if (!out || !out_len) return set_err(ctx, TIC_E_ARG, "null output pointer");
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return set_err(ctx, TIC_E_ARG, "an image without blocks has no symbols to build a table from (the reference raises IndexError)");
+    if (!coeffs_zz) return set_err(ctx, TIC_E_ARG, "null coefficient pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_scratch(ctx, 0, n * 128);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, coeffs_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
+    return adaptive_encode_dev(ctx, n, h, w, quality, out, cap, out_len);
+}
+
+int tic_decompress_adaptive(tic_ctx *ctx, const uint8_t *data, size_t len, uint8_t *out, size_t cap) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    int h = 0, w = 0, q = 0;
+    uint32_t flag = 0;
+    if (parse_header(data, len, &h, &w, &q, &flag) != TIC_OK) return set_err(ctx, TIC_E_STREAM, "stream shorter than its 16-byte header");
+    if (h < 0 || w < 0) return set_err(ctx, TIC_E_STREAM, "negative image size in the header");
+    if (q < 1 || q > 99) return set_err(ctx, TIC_E_STREAM, "quality %d in the header outside 1..99", q);
+    if ((size_t)h * (size_t)w > cap || (!out && h && w)) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
+    const size_t n = num_blocks(h, w);
+    std::vector<int16_t> zz;
+    try {
+        zz.resize(n * 64);
+    } catch (...) {
+        return set_err(ctx, TIC_E_ARG, "out of host memory for %zu blocks", n);
+    }
+    const char *why = "";
+    const int rc = adaptive_decode(data, len, h, w, zz.data(), &why);
+    if (rc) return set_err(ctx, rc, "adaptive stream: %s", why);
+    if (n == 0) return TIC_OK;
+    return idctq_impl(ctx, zz.data(), h, w, q, -1, out, cap);
 }
 
 } // extern "C"
