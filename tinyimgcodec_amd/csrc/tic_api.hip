@@ -77,6 +77,22 @@ struct Slot {
     int remaining = 0;        // frames of the chunk not yet consumed; 0 = slot free
     size_t rb_row = 0;        // row pitch of the streams read back into pin_out (0: they went straight to the caller)
 };
+// Workspace of the device Huffman decoder (tic_entropy_dec_gpu.hip), one per user: the single-frame calls, every asynchronous decode slot
+// and the batch.  Nothing of an earlier run may be in flight when it grows or a run begins.
+struct DecWorkspace {
+    void *work = nullptr;
+    size_t work_bytes = 0;
+    unsigned long long *desc = nullptr; // look-back words of the decoder's scans: an array of their own, zero or stamped with a past epoch
+    size_t desc_words = 0;
+    uint32_t epoch = 0;                 // runs on these words (the single-launch scans tell their words by it)
+    DecStatus *h_status = nullptr, *d_status = nullptr; // host-mapped, one entry per frame of a run
+    size_t status_bytes = 0;
+    // at least `work_need` bytes of work buffer (`work_alloc` when it grows), `desc_need` look-back words (max(8192, 2 x desc_need) when they
+    // grow: zeroed, epoch 0) and `status` status entries (`status_alloc`)
+    int grow(tic_ctx *ctx, size_t work_need, size_t work_alloc, size_t desc_need, size_t status, size_t status_alloc);
+    int begin(tic_ctx *ctx, hipStream_t stream, size_t status); // a run of `status` frames on `stream`
+    void release();
+};
 } // namespace
 
 struct tic_ctx {
@@ -145,13 +161,8 @@ struct tic_ctx {
     size_t d_stream_cap = 0;
     // device Huffman decoder (tic_decompress of long streams): tables, workspace, status
     DecLutsDev *d_dec_luts = nullptr;
-    void *d_dec_work = nullptr;
-    size_t dec_work_bytes = 0;
+    DecWorkspace dec_ws;
     uint8_t *h_dec_tail = nullptr;                              // pinned: kDecTailEnd bytes of stream end + kDecTailCoef bytes of tail coefficients
-    unsigned long long *d_dec_desc = nullptr;                   // look-back words of the device decoder's single-launch scans (nothing else lives there)
-    size_t dec_desc_words = 0;
-    uint32_t dec_epoch = 0;                                     // calls of the device decoder on this workspace (its single-launch scans tell their words by it)
-    DecStatus *h_dec_status = nullptr, *d_dec_status = nullptr; // host-mapped
     int last_decode_path = 0;                                  // 0 none, 1 device decoder, 2 host decoder (tic_last_decode_path)
     // asynchronous device-resident decodes (tic_decompress_dev_async): ticket t lives in slot t % kDecSlots; every slot has its own HIP
     // stream, workspace, look-back words and status words, so that the frames of a burst overlap (the measure kernel is one wave per
@@ -160,12 +171,7 @@ struct tic_ctx {
         long long ticket = -1;
         hipStream_t stream = nullptr;
         hipEvent_t done = nullptr;
-        void *work = nullptr;
-        size_t work_bytes = 0;
-        unsigned long long *desc = nullptr;
-        size_t desc_words = 0;
-        uint32_t epoch = 0;
-        DecStatus *h_status = nullptr, *d_status = nullptr;
+        DecWorkspace ws;
         bool launched = false;   // false: the call ran synchronously (no guess to launch on): rc / h / w are its outcome
         int rc = TIC_OK, h = 0, w = 0;
         uint8_t head[16] = {0};  // the header the launch guessed
@@ -199,13 +205,7 @@ struct tic_ctx {
         size_t in_cap = 0;
         uint8_t *d_pix = nullptr, *h_pix = nullptr;
         size_t pix_cap = 0, hpix_cap = 0;
-        void *d_work = nullptr;
-        size_t work_bytes = 0;
-        unsigned long long *d_desc = nullptr;
-        size_t desc_words = 0;
-        uint32_t epoch = 0;
-        DecStatus *h_status = nullptr, *d_status = nullptr;
-        size_t status_cap = 0;
+        DecWorkspace ws;
     } dbat;
     int last_dbatch_frames = 0, last_dbatch_fallback = 0, last_dbatch_chunks = 0, last_dbatch_direct = 0;
     // batch pipeline buffers, kept across calls (pinned allocations are expensive)
@@ -318,6 +318,70 @@ static int set_err(tic_ctx *ctx, int code, const char *fmt, ...) {
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Buffers that grow on demand, one helper per kind of memory: when `need` bytes exceed `cap`, the buffer is freed and one of `alloc`
+// bytes (0: `need`) takes its place.  Nothing may be in flight on the old buffer.  A failed allocation leaves it null and `cap` 0.
+template <class T> static int grow_dev(tic_ctx *ctx, T *&p, size_t &cap, size_t need, size_t alloc = 0) {
+    if (need <= cap) return TIC_OK;
+    if (p) HIPCHK(ctx, hipFree(p));
+    p = nullptr, cap = 0;
+    alloc = alloc ? alloc : need;
+    HIPCHK(ctx, hipMalloc((void **)&p, alloc));
+    cap = alloc;
+    return TIC_OK;
+}
+template <class T> static int grow_pinned(tic_ctx *ctx, T *&p, size_t &cap, size_t need, size_t alloc = 0) {
+    if (need <= cap) return TIC_OK;
+    if (p) HIPCHK(ctx, hipHostFree(p));
+    p = nullptr, cap = 0;
+    alloc = alloc ? alloc : need;
+    HIPCHK(ctx, hipHostMalloc((void **)&p, alloc, hipHostMallocDefault));
+    cap = alloc;
+    return TIC_OK;
+}
+// ... host-mapped: `h` for the host, `d` for the kernels; coherent, because the host reads it behind a polled or drained stream
+template <class T> static int grow_mapped(tic_ctx *ctx, T *&h, T *&d, size_t &cap, size_t need, size_t alloc = 0) {
+    if (need <= cap) return TIC_OK;
+    if (h) HIPCHK(ctx, hipHostFree(h));
+    h = d = nullptr, cap = 0;
+    alloc = alloc ? alloc : need;
+    HIPCHK(ctx, hipHostMalloc((void **)&h, alloc, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(ctx, hipHostGetDevicePointer((void **)&d, h, 0));
+    cap = alloc;
+    return TIC_OK;
+}
+
+int DecWorkspace::grow(tic_ctx *ctx, size_t work_need, size_t work_alloc, size_t desc_need, size_t status, size_t status_alloc) {
+    int rc = grow_dev(ctx, work, work_bytes, work_need, work_alloc);
+    if (rc) return rc;
+    if (desc_need > desc_words) {
+        const size_t dw = desc_need < 8192 ? 8192 : 2 * desc_need;
+        size_t bytes = desc_words * 8;
+        desc_words = 0; // (counted only once the new words are zero)
+        rc = grow_dev(ctx, desc, bytes, desc_need * 8, dw * 8);
+        if (rc) return rc;
+        HIPCHK(ctx, hipMemset(desc, 0, dw * 8));
+        desc_words = dw;
+        epoch = 0;
+    }
+    return grow_mapped(ctx, h_status, d_status, status_bytes, status * sizeof(DecStatus), status_alloc * sizeof(DecStatus));
+}
+
+int DecWorkspace::begin(tic_ctx *ctx, hipStream_t stream, size_t status) {
+    if (++epoch >= (1u << 22)) { // (the scans carry 24 bits of 2 x epoch: start over on clean words long before a value could recur)
+        HIPCHK(ctx, hipMemsetAsync(desc, 0, desc_words * 8, stream));
+        epoch = 1;
+    }
+    memset(h_status, 0, status * sizeof(DecStatus)); // (host-mapped; nothing of an earlier run is in flight)
+    return TIC_OK;
+}
+
+void DecWorkspace::release() {
+    if (work) (void)hipFree(work);
+    if (desc) (void)hipFree(desc);
+    if (h_status) (void)hipHostFree(h_status);
+    *this = DecWorkspace();
+}
+
 extern "C" {
 
 const char *tic_version(void) { return "tinyimgcodec_amd 0.1.0 (gfx950)"; }
@@ -390,26 +454,20 @@ void tic_destroy(tic_ctx *ctx) {
     if (ctx->h_zz) (void)hipHostFree(ctx->h_zz);
     if (ctx->d_stream_buf) (void)hipFree(ctx->d_stream_buf);
     if (ctx->d_dec_luts) (void)hipFree(ctx->d_dec_luts);
-    if (ctx->d_dec_work) (void)hipFree(ctx->d_dec_work);
-    if (ctx->d_dec_desc) (void)hipFree(ctx->d_dec_desc);
+    ctx->dec_ws.release();
     if (ctx->h_dec_tail) (void)hipHostFree(ctx->h_dec_tail);
-    if (ctx->h_dec_status) (void)hipHostFree(ctx->h_dec_status);
     if (ctx->h_small) (void)hipHostFree(ctx->h_small);
     for (auto &sl : ctx->dec_slots) {
         if (sl.stream) (void)hipStreamSynchronize(sl.stream);
         if (sl.done) (void)hipEventDestroy(sl.done);
-        if (sl.work) (void)hipFree(sl.work);
-        if (sl.desc) (void)hipFree(sl.desc);
-        if (sl.h_status) (void)hipHostFree(sl.h_status);
+        sl.ws.release();
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
     }
     if (ctx->dbat.h_in) (void)hipHostFree(ctx->dbat.h_in);
     if (ctx->dbat.d_in) (void)hipFree(ctx->dbat.d_in);
     if (ctx->dbat.d_pix) (void)hipFree(ctx->dbat.d_pix);
     if (ctx->dbat.h_pix) (void)hipHostFree(ctx->dbat.h_pix);
-    if (ctx->dbat.d_work) (void)hipFree(ctx->dbat.d_work);
-    if (ctx->dbat.d_desc) (void)hipFree(ctx->dbat.d_desc);
-    if (ctx->dbat.h_status) (void)hipHostFree(ctx->dbat.h_status);
+    ctx->dbat.ws.release();
     if (ctx->dec_order) (void)hipEventDestroy(ctx->dec_order);
     if (ctx->d_adapt_stats) (void)hipFree(ctx->d_adapt_stats); // table and error word live in the same block
     if (ctx->d_adapt_work) (void)hipFree(ctx->d_adapt_work);
@@ -903,33 +961,11 @@ int tic_last_fallback_blocks(tic_ctx *ctx, unsigned long long *count) {
 
 constexpr size_t kDecHostPixBytes = 1u << 20; // tic_decompress: images of at most this many bytes leave through tic_ctx::h_small as well
 constexpr size_t kSmallHostBytes = 2u << 20; // tic_compress: frames whose stream bound is at most this go through tic_ctx::h_small
-static int ensure_small(tic_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->small_cap) return TIC_OK;
-    if (ctx->h_small) HIPCHK(ctx, hipHostFree(ctx->h_small));
-    ctx->h_small = ctx->d_small = nullptr;
-    ctx->small_cap = 0;
-    HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_small, bytes, hipHostMallocMapped | hipHostMallocCoherent)); // (read by the host behind a polled stream)
-    HIPCHK(ctx, hipHostGetDevicePointer((void **)&ctx->d_small, ctx->h_small, 0));
-    ctx->small_cap = bytes;
-    return TIC_OK;
-}
+static int ensure_small(tic_ctx *ctx, size_t bytes) { return grow_mapped(ctx, ctx->h_small, ctx->d_small, ctx->small_cap, bytes); }
 
 static int ensure_scratch(tic_ctx *ctx, size_t img_bytes, size_t coef_bytes) {
-    if (img_bytes > ctx->d_img_cap) {
-        if (ctx->d_img) HIPCHK(ctx, hipFree(ctx->d_img));
-        ctx->d_img = nullptr;
-        ctx->d_img_cap = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->d_img, img_bytes));
-        ctx->d_img_cap = img_bytes;
-    }
-    if (coef_bytes > ctx->d_coef_cap) {
-        if (ctx->d_coef) HIPCHK(ctx, hipFree(ctx->d_coef));
-        ctx->d_coef = nullptr;
-        ctx->d_coef_cap = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->d_coef, coef_bytes));
-        ctx->d_coef_cap = coef_bytes;
-    }
-    return TIC_OK;
+    const int rc = grow_dev(ctx, ctx->d_img, ctx->d_img_cap, img_bytes);
+    return rc ? rc : grow_dev(ctx, ctx->d_coef, ctx->d_coef_cap, coef_bytes);
 }
 
 int tic_dctq(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int quality, int16_t *coeffs_zz) {
@@ -1042,14 +1078,8 @@ int tic_entropy_encode_dev(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, 
         return TIC_OK;
     }
     if (!d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "null coefficient pointer");
-    const size_t wb = entropy_fused_work_bytes(n);
-    if (wb > ctx->ent_work_bytes) {
-        if (ctx->d_ent_work) HIPCHK(ctx, hipFree(ctx->d_ent_work));
-        ctx->d_ent_work = nullptr;
-        ctx->ent_work_bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->d_ent_work, wb));
-                ctx->ent_work_bytes = wb;
-    }
+    const int rc = grow_dev(ctx, ctx->d_ent_work, ctx->ent_work_bytes, entropy_fused_work_bytes(n));
+    if (rc) return rc;
     // three launches, no host round trip and no copy: pack (one walk over the symbols), tile sums, place; the placing kernel
     // writes the header and puts {payload bits, error} into the host-mapped status block; nothing is written past the
     // caller's buffer
@@ -1140,12 +1170,8 @@ int tic_compress_dev_async(tic_ctx *ctx, const void *d_image, int h, int w, ptrd
         if (coef_bytes > ln.coef_cap || wb > ln.work_bytes) { // (grows only between bursts of one geometry: frames in flight still use the old buffers)
             HIPCHK(ctx, hipStreamSynchronize(ln.stream));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            if (coef_bytes > ln.coef_cap) {
-                if (ln.d_coef) HIPCHK(ctx, hipFree(ln.d_coef));
-                ln.d_coef = nullptr, ln.coef_cap = 0;
-                HIPCHK(ctx, hipMalloc(&ln.d_coef, coef_bytes));
-                ln.coef_cap = coef_bytes;
-            }
+            const int rc = grow_dev(ctx, ln.d_coef, ln.coef_cap, coef_bytes);
+            if (rc) return rc;
             if (wb > ln.work_bytes) {
                 for (int k = 0; k < 2; k++) {
                     if (ln.d_work[k]) HIPCHK(ctx, hipFree(ln.d_work[k]));
@@ -1235,16 +1261,8 @@ int tic_compress(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row
     if (rc) return rc;
     const size_t need = compress_bound(h, w);
     const bool small = need <= kSmallHostBytes && !test_hook("TIC_NO_SMALL_PATH"); // the placing kernel writes the stream into host memory itself
-    if (small) {
-        rc = ensure_small(ctx, kSmallHostBytes);
-        if (rc) return rc;
-    } else if (need > ctx->d_stream_cap) {
-        if (ctx->d_stream_buf) HIPCHK(ctx, hipFree(ctx->d_stream_buf));
-        ctx->d_stream_buf = nullptr;
-        ctx->d_stream_cap = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->d_stream_buf, need));
-        ctx->d_stream_cap = need;
-    }
+    rc = small ? ensure_small(ctx, kSmallHostBytes) : grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, need);
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_img, pitch, image, (size_t)row_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice,
                                  ctx->stream));
     size_t len = 0;
@@ -1959,30 +1977,92 @@ int tic_dctq_batch(tic_ctx *ctx, const uint8_t *const *images, int n, int h, int
 }
 
 // ---- decode ---------------------------------------------------------------------------------------------
-// Inverse stage on coefficients that already sit in ctx->d_coef (int16 [N][64] zig-zag, DC integrated) -> pixels in `out`.
-// scaled_exp < 0: decode() proper; >= 0: its scaled_dct branch with 2 ** scaled_exp (codec.py:59-62)
-static int idct_from_device(tic_ctx *ctx, int h, int w, int quality, int scaled_exp, uint8_t *out, bool out_on_device = false,
-                            size_t out_stride = 0) {
-    const size_t pitch = align_up((size_t)w, 256);
-    IdctArgs a;
-    a.coeffs = (const int16_t *)ctx->d_coef;
-    a.out = (uint8_t *)ctx->d_img;
+// What a stream's 16-byte header asks for.  scaled_exp < 0: decode() proper; >= 0: its scaled_dct branch with 2 ** scaled_exp
+// (codec.py:59-62), whose constants are those of quality 50 - `quality` is the one the constants are taken at.
+struct StreamHead {
+    int h, w, quality, scaled_exp;
+};
+
+// The header checks of tic_decompress, tic_decompress_batch and tic_decompress_dev (tic_decompress_adaptive, the strict decoder, has
+// its own).  frame >= 0: the messages name the frame of a batch.
+static int check_header(tic_ctx *ctx, const uint8_t *data, size_t len, StreamHead *sh, int frame = -1) {
+    char pre[32] = "";
+    if (frame >= 0) snprintf(pre, sizeof pre, "frame %d: ", frame);
+    int h, w, quality;
+    uint32_t flag;
+    if (parse_header(data, len, &h, &w, &quality, &flag) != TIC_OK) return set_err(ctx, TIC_E_STREAM, "%sstream shorter than the 16-byte header", pre);
+    if (flag & (1u << 31)) return set_err(ctx, TIC_E_STREAM, "%sstreams with an embedded Huffman table are not supported", pre);
+    const bool scaled = (flag & (1u << 30)) != 0; // a stream of the reference's C encoder (codec.py:127-128): quality = exponent
+    if (h < 0 || w < 0) return set_err(ctx, TIC_E_STREAM, "%sbad geometry in header", pre);
+    if (scaled && (quality < 0 || quality > 62)) return set_err(ctx, TIC_E_QUALITY, "%sscaled_dct exponent %d in header outside 0..62", pre, quality);
+    if (!scaled && (quality < 1 || quality > 99)) return set_err(ctx, TIC_E_QUALITY, "%squality %d in header outside 1..99", pre, quality);
+    *sh = {h, w, scaled ? 50 : quality, scaled ? quality : -1};
+    return TIC_OK;
+}
+
+// The device decoder's tables go up with the context's first device decode.  ctx->d_dec_luts is set only once they are there.
+static int ensure_dec_tables(tic_ctx *ctx) {
+    if (ctx->d_dec_luts) return TIC_OK;
+    std::unique_ptr<DecLutsDev> l(new DecLutsDev());
+    dec_luts_fill(l->dc11, l->ac11, l->ac16);
+    dec_chain_luts_fill(l->mdc, l->mac, l->mlong);
+    dec_pair_luts_fill(l->ac2, l->long32); // (new DecLutsDev() zeroed the entries behind the long codewords)
+    DecLutsDev *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, sizeof(DecLutsDev));
+    if (e == hipSuccess) {
+        e = hipMemcpy(d, l.get(), sizeof(DecLutsDev), hipMemcpyHostToDevice);
+        if (e != hipSuccess) (void)hipFree(d);
+    }
+    if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "device decoder set-up failed: %s", hipGetErrorString(e));
+    ctx->d_dec_luts = d;
+    return TIC_OK;
+}
+
+// The inverse stage's arguments for the device decoder's kernels: pixels into `out`, rows `stride` bytes apart; `head` (may be null)
+// is the 16-byte header h, w, quality and scaled_exp came from - the fused kernel writes pixels only under it.
+static DecIdctArgs dec_idct_args(const tic_ctx *ctx, int h, int w, int quality, int scaled_exp, uint8_t *out, long stride, const uint8_t *head) {
+    DecIdctArgs a{};
+    a.out = out;
     a.h = h;
     a.w = w;
-    a.stride = (long)pitch;
+    a.stride = stride;
     a.bw = (w + 7) / 8;
-    a.tiles_x = (a.bw + 7) / 8;
-    a.ntiles = ((h + 7) / 8) * a.tiles_x;
     a.aligned8 = 1;
     a.consts = ctx->d_consts + (scaled_exp >= 0 ? 50 : quality); // codec.py:62: quality = 50 on the scaled branch
     a.scaled = scaled_exp >= 0;
     a.pow2 = scaled_exp >= 0 ? ldexp(1.0, scaled_exp) : 1.0;
+    if (head) memcpy(a.head, head, 16);
+    return a;
+}
+
+// ... and the same for idct_kernel, which reads the coefficients from `coeffs`: the whole frame
+static IdctArgs idct_args(const DecIdctArgs &d, const int16_t *coeffs) {
+    IdctArgs a;
+    a.coeffs = coeffs;
+    a.out = d.out;
+    a.h = d.h;
+    a.w = d.w;
+    a.stride = d.stride;
+    a.bw = d.bw;
+    a.tiles_x = (a.bw + 7) / 8;
+    a.ntiles = ((d.h + 7) / 8) * a.tiles_x;
+    a.aligned8 = d.aligned8;
+    a.consts = d.consts;
+    a.scaled = d.scaled;
+    a.pow2 = d.pow2;
+    return a;
+}
+
+// Inverse stage on coefficients that already sit in ctx->d_coef (int16 [N][64] zig-zag, DC integrated) -> pixels in `out`.
+// quality and scaled_exp as StreamHead.
+static int idct_from_device(tic_ctx *ctx, int h, int w, int quality, int scaled_exp, uint8_t *out, bool out_on_device = false,
+                            size_t out_stride = 0) {
+    const size_t pitch = align_up((size_t)w, 256);
     // a device destination whose rows are 8-byte aligned takes the pixels straight from the kernel (its row stores are cropped to w)
     const bool direct = out_on_device && out_stride % 8 == 0 && (uintptr_t)out % 8 == 0;
-    if (direct) {
-        a.out = out;
-        a.stride = (long)out_stride;
-    }
+    const IdctArgs a = idct_args(dec_idct_args(ctx, h, w, quality, scaled_exp, direct ? out : (uint8_t *)ctx->d_img,
+                                               direct ? (long)out_stride : (long)pitch, nullptr),
+                                 (const int16_t *)ctx->d_coef);
     HIPCHK(ctx, launch_idct(a, ctx->stream));
     if (!direct)
         HIPCHK(ctx, hipMemcpy2DAsync(out, out_on_device ? out_stride : (size_t)w, ctx->d_img, pitch, (size_t)w, (size_t)h,
@@ -2051,67 +2131,37 @@ static int decode_range_bits(size_t len, size_t n, size_t mult = 2, size_t floor
     return (int)(k < floor_words ? floor_words : (k > 63 ? 63 : k)) * 32;
 }
 
-static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, int h, int w, int quality, int scaled_exp, uint8_t *out,
-                            bool out_on_device, size_t out_stride, bool *done, const uint8_t *head16 /* the 16 header bytes h, w, quality came from */,
-                            bool src_on_device = false, bool head_is_guess = false, bool *guess_held = nullptr) {
+static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const StreamHead &sh, uint8_t *out, bool out_on_device, size_t out_stride,
+                            bool *done, const uint8_t *head16 /* the 16 header bytes sh came from */, bool src_on_device = false,
+                            bool head_is_guess = false, bool *guess_held = nullptr) {
     *done = false;
+    const int h = sh.h, w = sh.w;
     if (guess_held) *guess_held = false;
     const uint8_t *guessed_head = head_is_guess ? head16 : nullptr;
     const size_t n = num_blocks(h, w);
     // the host parallel decoder's own threshold: shorter streams are decoded serially in well under a millisecond
     if (!device_decoder_takes(n, len) || test_hook("TIC_DECODE_SERIAL") || test_hook("TIC_DECODE_HOST")) return TIC_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_dec_luts) {
-        DecLutsDev *l = new DecLutsDev();
-        dec_luts_fill(l->dc11, l->ac11, l->ac16);
-        dec_chain_luts_fill(l->mdc, l->mac, l->mlong);
-        dec_pair_luts_fill(l->ac2, l->long32); // (new DecLutsDev() zeroed the entries behind the long codewords)
-        hipError_t e = hipMalloc((void **)&ctx->d_dec_luts, sizeof(DecLutsDev));
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_dec_luts, l, sizeof(DecLutsDev), hipMemcpyHostToDevice);
-        delete l;
-        if (e == hipSuccess) e = hipHostMalloc((void **)&ctx->h_dec_status, 64, hipHostMallocMapped | hipHostMallocCoherent);
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&ctx->d_dec_status, ctx->h_dec_status, 0);
-        if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "device decoder set-up failed: %s", hipGetErrorString(e));
-    }
+    int rc = ensure_dec_tables(ctx);
+    if (rc) return rc;
     const size_t pitch = align_up((size_t)w, 256);
-    int rc = ensure_scratch(ctx, pitch * (size_t)h, n * 128);
+    rc = ensure_scratch(ctx, pitch * (size_t)h, n * 128);
     if (rc) return rc;
     // The stream is decoded where it lies when it is in device memory at a 4-byte aligned address (the kernels mask the bytes behind
     // its end themselves); a host stream, or an odd address, goes through the context's stream buffer.
     const bool in_place = src_on_device && ((uintptr_t)data & 3u) == 0;
     if (!in_place) {
-        const size_t padded = align_up(len, 4) + 16;
-        if (padded > ctx->d_stream_cap) {
-            if (ctx->d_stream_buf) HIPCHK(ctx, hipFree(ctx->d_stream_buf));
-            ctx->d_stream_buf = nullptr;
-            ctx->d_stream_cap = 0;
-            HIPCHK(ctx, hipMalloc(&ctx->d_stream_buf, padded));
-            ctx->d_stream_cap = padded;
-        }
+        rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, align_up(len, 4) + 16);
+        if (rc) return rc;
     }
     const void *d_stream = in_place ? (const void *)data : (const void *)ctx->d_stream_buf;
     if (!ctx->h_dec_tail) { // pinned: the stream's last bytes on their way down (device source), the tail's coefficients on their way up
         HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_dec_tail, kDecTailEnd + kDecTailCoef, hipHostMallocDefault));
     }
+    DecWorkspace &ws = ctx->dec_ws;
     const size_t wb = entropy_decode_gpu_work_bytes(len, n);
-    if (wb > ctx->dec_work_bytes) {
-        if (ctx->d_dec_work) HIPCHK(ctx, hipFree(ctx->d_dec_work));
-        ctx->d_dec_work = nullptr;
-        ctx->dec_work_bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->d_dec_work, wb));
-        ctx->dec_work_bytes = wb;
-    }
-    size_t dw = entropy_decode_gpu_desc_words(len, n);
-    if (dw > ctx->dec_desc_words) { // the look-back words of the decoder's scans: an array of their own, zero or stamped with a past epoch
-        dw = dw < 8192 ? 8192 : 2 * dw;
-        if (ctx->d_dec_desc) HIPCHK(ctx, hipFree(ctx->d_dec_desc));
-        ctx->d_dec_desc = nullptr;
-        ctx->dec_desc_words = 0;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_dec_desc, dw * 8));
-        HIPCHK(ctx, hipMemset(ctx->d_dec_desc, 0, dw * 8));
-        ctx->dec_desc_words = dw;
-        ctx->dec_epoch = 0;
-    }
+    rc = ws.grow(ctx, wb, wb, entropy_decode_gpu_desc_words(len, n), 1, 1);
+    if (rc) return rc;
     if (!in_place) HIPCHK(ctx, hipMemcpyAsync(ctx->d_stream_buf, data, len, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
     // The blocks that start in the stream's last 2048 bits are decoded on the host (below): with a device source their bytes - the
     // last 256 of the stream, 512 taken - come down NOW, in front of the kernels, instead of in a synchronous copy behind them
@@ -2130,17 +2180,9 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, int h
         rc = ensure_small(ctx, kSmallHostBytes);
         if (rc) return rc;
     }
-    DecIdctArgs ia;
-    ia.out = direct ? out : host_pix ? ctx->d_small : (uint8_t *)ctx->d_img;
-    ia.h = h;
-    ia.w = w;
-    ia.stride = direct ? (long)out_stride : host_pix ? (long)pitch8 : (long)pitch;
-    ia.bw = (w + 7) / 8;
-    ia.aligned8 = 1;
-    ia.consts = ctx->d_consts + (scaled_exp >= 0 ? 50 : quality); // codec.py:62: quality = 50 on the scaled branch
-    ia.scaled = scaled_exp >= 0;
-    ia.pow2 = scaled_exp >= 0 ? ldexp(1.0, scaled_exp) : 1.0;
-    memcpy(ia.head, head16, 16); // the header these were derived from (a guess, or the stream's own): the fused kernel writes pixels only under it
+    // (head16 is a guess, or the stream's own header)
+    const DecIdctArgs ia = dec_idct_args(ctx, h, w, sh.quality, sh.scaled_exp, direct ? out : host_pix ? ctx->d_small : (uint8_t *)ctx->d_img,
+                                         direct ? (long)out_stride : host_pix ? (long)pitch8 : (long)pitch, head16);
     // stream bits per lane (decode_range_bits): 2 average blocks, at least 288 bits, as an odd number of 32-bit words up to 63 (noise at q = 50,
     // 220 bits per block: 480; tiled Lenna, 41, and noise at q = 10, 70: 288; noise at q = 90, 404: 864).  The decoder's kernels are one
     // dependent chain per lane, so their time goes with this number (profiles/r04_decoder.txt: the measure kernel 57 us at 672 bits,
@@ -2168,17 +2210,14 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, int h
             HIPCHK(ctx, hipMemcpyAsync(ctx->h_dec_tail, (const char *)data + (len - end_bytes), end_bytes, hipMemcpyDeviceToHost, ctx->stream));
             tail_prefetched = true;
         }
-        memset(ctx->h_dec_status, 0, sizeof(DecStatus)); // (host-mapped; nothing of an earlier call is in flight: every call ends with a drained stream)
-        if (++ctx->dec_epoch >= (1u << 22)) { // (the scans carry 24 bits of 2 x epoch: start over on clean words long before a value could recur)
-            HIPCHK(ctx, hipMemsetAsync(ctx->d_dec_desc, 0, ctx->dec_desc_words * 8, ctx->stream));
-            ctx->dec_epoch = 1;
-        }
+        rc = ws.begin(ctx, ctx->stream, 1); // (every call ends with a drained stream)
+        if (rc) return rc;
         ctx->last_decode_tries++;
         ctx->last_decode_range = range_bits;
-        HIPCHK(ctx, entropy_decode_idct_gpu(d_stream, len, n, ctx->d_dec_luts, ctx->d_dec_work, ctx->dec_work_bytes, ctx->d_dec_desc,
-                                            ctx->dec_desc_words, ctx->dec_epoch, ia, ctx->d_dec_status, range_bits, margin_bits, ctx->stream, flat_grid));
+        HIPCHK(ctx, entropy_decode_idct_gpu(d_stream, len, n, ctx->d_dec_luts, ws.work, ws.work_bytes, ws.desc, ws.desc_words, ws.epoch, ia,
+                                            ws.d_status, range_bits, margin_bits, ctx->stream, flat_grid));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        memcpy(&st, ctx->h_dec_status, sizeof st); // (host-mapped: the stream has drained)
+        memcpy(&st, ws.h_status, sizeof st); // (host-mapped: the stream has drained)
         if (guessed_head) { // geometry and quality were a guess (tic_decompress_dev): what this run produced counts only if the stream's header is the guessed one
             if (memcmp(st.head, guessed_head, 16) != 0) return TIC_OK;
             *guess_held = true;
@@ -2218,21 +2257,10 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, int h
             entropy_decode_tail(data, len, h, w, (size_t)st.m, (size_t)st.pos_out, st.dc_out, tail);
         }
         HIPCHK(ctx, hipMemcpyAsync((char *)ctx->d_coef + (size_t)st.m * 128, tail, tail_bytes, hipMemcpyHostToDevice, ctx->stream));
-        IdctArgs a;
-        a.coeffs = (const int16_t *)ctx->d_coef;
-        a.out = ia.out;
-        a.h = h;
-        a.w = w;
-        a.stride = ia.stride;
-        a.bw = ia.bw;
-        a.tiles_x = (a.bw + 7) / 8;
+        IdctArgs a = idct_args(ia, (const int16_t *)ctx->d_coef);
         a.first_block = (long)st.m;
         a.nblocks_sel = (long)(n - (size_t)st.m);
         a.ntiles = (int)((a.nblocks_sel + 7) / 8);
-        a.aligned8 = 1;
-        a.consts = ia.consts;
-        a.scaled = ia.scaled;
-        a.pow2 = ia.pow2;
         HIPCHK(ctx, launch_idct(a, ctx->stream));
         if (direct || host_pix || !big.empty()) HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (the caller's pixels are complete when this returns)
     }
@@ -2295,45 +2323,41 @@ int tic_set_decode_guess(tic_ctx *ctx, int enable) {
     return TIC_OK;
 }
 
+// The host decoder (short streams, anything the device decoder hands back: the reference's behaviour on malformed streams lives there),
+// then the inverse stage on the device; `data` is in host memory, `out` / `out_on_device` / `out_stride` as idct_from_device.
+static int decode_on_host(tic_ctx *ctx, const uint8_t *data, size_t len, const StreamHead &sh, uint8_t *out, bool out_on_device,
+                          size_t out_stride) {
+    const size_t n = num_blocks(sh.h, sh.w);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // coefficients land in a pinned buffer kept on the context: no page faults on a fresh 32 MB vector per call, and the upload
+    // runs at PCIe speed instead of through the runtime's staging of pageable memory
+    int rc = grow_pinned(ctx, ctx->h_zz, ctx->h_zz_bytes, n * 128);
+    if (rc) return rc;
+    entropy_decode(data, len, sh.h, sh.w, ctx->h_zz);
+    ctx->last_decode_path = 2;
+    rc = ensure_scratch(ctx, align_up((size_t)sh.w, 256) * (size_t)sh.h, n * 128);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, ctx->h_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
+    return idct_from_device(ctx, sh.h, sh.w, sh.quality, sh.scaled_exp, out, out_on_device, out_stride);
+}
+
 int tic_decompress(tic_ctx *ctx, const uint8_t *data, size_t len, uint8_t *out, size_t cap) {
     TIC_LOCK(ctx);
     if (!ctx) return TIC_E_ARG;
     ctx->last_decode_giveup = 0;
     ctx->last_decode_tries = 0;
-    int h, w, quality;
-    uint32_t flag;
-    if (parse_header(data, len, &h, &w, &quality, &flag) != TIC_OK)
-        return set_err(ctx, TIC_E_STREAM, "stream shorter than the 16-byte header");
-    if (flag & (1u << 31)) return set_err(ctx, TIC_E_STREAM, "streams with an embedded Huffman table are not supported");
-    const bool scaled = (flag & (1u << 30)) != 0; // a stream of the reference's C encoder (codec.py:127-128): quality = exponent
-    if (h < 0 || w < 0) return set_err(ctx, TIC_E_STREAM, "bad geometry in header");
-    if (scaled && (quality < 0 || quality > 62)) return set_err(ctx, TIC_E_QUALITY, "scaled_dct exponent %d in header outside 0..62", quality);
-    if (!scaled && (quality < 1 || quality > 99)) return set_err(ctx, TIC_E_QUALITY, "quality %d in header outside 1..99", quality);
-    const size_t n = num_blocks(h, w);
-    if (n == 0) return TIC_OK;
-    if (!out || (size_t)h * (size_t)w > cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
-    {   // long streams: the Huffman decode runs on the device too; only the stream goes up and the pixels come down
-        bool done = false;
-        const int rc = decode_on_device(ctx, data, len, h, w, scaled ? 50 : quality, scaled ? quality : -1, out, false, 0, &done, data);
-        if (rc) return rc;
-        if (done) {
-            ctx->last_decode_path = 1;
-            return TIC_OK;
-        }
-    }
-    // coefficients land in a pinned buffer kept on the context: no page faults on a fresh 32 MB vector per call, and the upload
-    // runs at PCIe speed instead of through the runtime's staging of pageable memory
-    if (n * 128 > ctx->h_zz_bytes) {
-        if (ctx->h_zz) (void)hipHostFree(ctx->h_zz);
-        ctx->h_zz = nullptr;
-        ctx->h_zz_bytes = 0;
-        HIPCHK(ctx, hipSetDevice(ctx->device));
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_zz, n * 128, hipHostMallocDefault));
-        ctx->h_zz_bytes = n * 128;
-    }
-    entropy_decode(data, len, h, w, ctx->h_zz);
-    ctx->last_decode_path = 2;
-    return idctq_impl(ctx, ctx->h_zz, h, w, scaled ? 50 : quality, scaled ? quality : -1, out, cap);
+    StreamHead sh;
+    int rc = check_header(ctx, data, len, &sh);
+    if (rc) return rc;
+    if (num_blocks(sh.h, sh.w) == 0) return TIC_OK;
+    if (!out || (size_t)sh.h * (size_t)sh.w > cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
+    // long streams: the Huffman decode runs on the device too; only the stream goes up and the pixels come down
+    bool done = false;
+    rc = decode_on_device(ctx, data, len, sh, out, false, 0, &done, data);
+    if (rc) return rc;
+    if (!done) return decode_on_host(ctx, data, len, sh, out, false, 0);
+    ctx->last_decode_path = 1;
+    return TIC_OK;
 }
 
 // decompress() of MANY streams at once (the mirror of tic_compress_batch; the reference's benchmark loop, tests/benchmark.py:12-23, decodes
@@ -2356,48 +2380,20 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
     struct Fr { int h, w, q; size_t nblk; bool batch; };
     std::vector<Fr> fr((size_t)n);
     for (int i = 0; i < n; i++) { // the checks of tic_decompress, for every frame, before any work
-        int h, w, quality;
-        uint32_t flag;
-        if (!streams[i] || parse_header(streams[i], lens[i], &h, &w, &quality, &flag) != TIC_OK) return set_err(ctx, TIC_E_STREAM, "frame %d: stream shorter than the 16-byte header", i);
-        if (flag & (1u << 31)) return set_err(ctx, TIC_E_STREAM, "frame %d: streams with an embedded Huffman table are not supported", i);
-        const bool scaled = (flag & (1u << 30)) != 0;
-        if (h < 0 || w < 0) return set_err(ctx, TIC_E_STREAM, "frame %d: bad geometry in header", i);
-        if (scaled && (quality < 0 || quality > 62)) return set_err(ctx, TIC_E_QUALITY, "frame %d: scaled_dct exponent %d in header outside 0..62", i, quality);
-        if (!scaled && (quality < 1 || quality > 99)) return set_err(ctx, TIC_E_QUALITY, "frame %d: quality %d in header outside 1..99", i, quality);
-        const size_t nb = num_blocks(h, w);
-        if (nb && (!outs[i] || (size_t)h * (size_t)w > caps[i])) return set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small", i);
-        if (hs) hs[i] = h;
-        if (ws) ws[i] = w;
-        fr[(size_t)i] = {h, w, quality, nb, nb != 0 && !scaled && device_decoder_takes(nb, lens[i]) && !test_hook("TIC_DECODE_HOST") && !test_hook("TIC_DECODE_SERIAL")};
+        StreamHead sh;
+        const int rc = check_header(ctx, streams[i], lens[i], &sh, i);
+        if (rc) return rc;
+        const size_t nb = num_blocks(sh.h, sh.w);
+        if (nb && (!outs[i] || (size_t)sh.h * (size_t)sh.w > caps[i])) return set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small", i);
+        if (hs) hs[i] = sh.h;
+        if (ws) ws[i] = sh.w;
+        fr[(size_t)i] = {sh.h, sh.w, sh.quality, nb,
+                         nb != 0 && sh.scaled_exp < 0 && device_decoder_takes(nb, lens[i]) && !test_hook("TIC_DECODE_HOST") && !test_hook("TIC_DECODE_SERIAL")};
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_dec_luts) { // (as decode_on_device: the tables go up with the context's first device decode)
-        std::unique_ptr<DecLutsDev> l(new DecLutsDev());
-        dec_luts_fill(l->dc11, l->ac11, l->ac16);
-        dec_chain_luts_fill(l->mdc, l->mac, l->mlong);
-        dec_pair_luts_fill(l->ac2, l->long32);
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_dec_luts, sizeof(DecLutsDev)));
-        HIPCHK(ctx, hipMemcpy(ctx->d_dec_luts, l.get(), sizeof(DecLutsDev), hipMemcpyHostToDevice));
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_dec_status, 64, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(ctx, hipHostGetDevicePointer((void **)&ctx->d_dec_status, ctx->h_dec_status, 0));
-    }
+    int rc = ensure_dec_tables(ctx);
+    if (rc) return rc;
     tic_ctx::DecBatch &B = ctx->dbat;
-    auto grow_dev = [&](void **p, size_t *cap, size_t need) -> int {
-        if (need <= *cap) return TIC_OK;
-        if (*p) HIPCHK(ctx, hipFree(*p));
-        *p = nullptr, *cap = 0;
-        HIPCHK(ctx, hipMalloc(p, need + need / 4));
-        *cap = need + need / 4;
-        return TIC_OK;
-    };
-    auto grow_pin = [&](uint8_t **p, size_t *cap, size_t need) -> int {
-        if (need <= *cap) return TIC_OK;
-        if (*p) HIPCHK(ctx, hipHostFree(*p));
-        *p = nullptr, *cap = 0;
-        HIPCHK(ctx, hipHostMalloc((void **)p, need + need / 4, hipHostMallocDefault));
-        *cap = need + need / 4;
-        return TIC_OK;
-    };
     // chunks: frames in order, while the chunk's streams, pixels and frame count stay inside the limits (one 512 x 512 benchmark set - 49
     // frames, 12.8 MB of pixels - is one chunk; sixteen 4096^2 frames are one)
     constexpr size_t kMaxIn = 96u << 20, kMaxPix = 288u << 20;
@@ -2454,15 +2450,7 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
             d.pad_ = 0;
             pitches[k] = (size_t)(f.w % 8 == 0 ? f.w : (f.w + 7) / 8 * 8);
             pix_off[k] = poff;
-            d.idct.out = nullptr; // (set below, when the pixel buffer exists)
-            d.idct.h = f.h, d.idct.w = f.w;
-            d.idct.stride = (long)pitches[k];
-            d.idct.bw = (f.w + 7) / 8;
-            d.idct.aligned8 = 1;
-            d.idct.consts = ctx->d_consts + f.q;
-            d.idct.scaled = 0;
-            d.idct.pow2 = 1.0;
-            memcpy(d.idct.head, streams[i], 16);
+            d.idct = dec_idct_args(ctx, f.h, f.w, f.q, -1, nullptr /* set below, when the pixel buffer exists */, (long)pitches[k], streams[i]);
             words += (align_up(len, 16) + 16) / 4;
             ranges += d.nranges, tiles += d.ntiles, wgs += d.nwgs, blk += f.nblk;
             poff += align_up(pitches[k] * (size_t)f.h, 256);
@@ -2471,39 +2459,19 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
         const size_t o_frames = 0, o_tiles = align_up(o_frames + F * sizeof(DecFrame), 256), o_wgs = align_up(o_tiles + (size_t)tiles * 4, 256),
                      o_streams = align_up(o_wgs + (size_t)wgs * 4, 256), up_bytes = o_streams + words * 4;
         if (up_bytes > B.in_cap) { // the pinned upload buffer and its device mirror grow together
-            if (B.h_in) HIPCHK(ctx, hipHostFree(B.h_in));
-            if (B.d_in) HIPCHK(ctx, hipFree(B.d_in));
-            B.h_in = B.d_in = nullptr, B.in_cap = 0;
-            const size_t cap = up_bytes + up_bytes / 4;
-            HIPCHK(ctx, hipHostMalloc((void **)&B.h_in, cap, hipHostMallocDefault));
-            HIPCHK(ctx, hipMalloc((void **)&B.d_in, cap));
-            B.in_cap = cap;
+            size_t hcap = B.in_cap, dcap = B.in_cap;
+            B.in_cap = 0;
+            rc = grow_pinned(ctx, B.h_in, hcap, up_bytes, up_bytes + up_bytes / 4);
+            if (rc) return rc;
+            rc = grow_dev(ctx, B.d_in, dcap, up_bytes, up_bytes + up_bytes / 4);
+            if (rc) return rc;
+            B.in_cap = dcap;
         }
-        int rc = TIC_OK;
-        rc = grow_dev((void **)&B.d_pix, &B.pix_cap, poff);
+        rc = grow_dev(ctx, B.d_pix, B.pix_cap, poff, poff + poff / 4);
         if (rc) return rc;
-        rc = grow_dev(&B.d_work, &B.work_bytes, entropy_decode_batch_work_bytes(ranges288, blocks, F));
+        const size_t wb = entropy_decode_batch_work_bytes(ranges288, blocks, F);
+        rc = B.ws.grow(ctx, wb, wb + wb / 4, 4 * (size_t)((tiles > wgs ? tiles : wgs) + 2), F, F < 256 ? 256 : 2 * (size_t)F);
         if (rc) return rc;
-        {
-            size_t dw = 4 * (size_t)((tiles > wgs ? tiles : wgs) + 2);
-            if (dw > B.desc_words) {
-                dw = dw < 8192 ? 8192 : 2 * dw;
-                if (B.d_desc) HIPCHK(ctx, hipFree(B.d_desc));
-                B.d_desc = nullptr, B.desc_words = 0;
-                HIPCHK(ctx, hipMalloc((void **)&B.d_desc, dw * 8));
-                HIPCHK(ctx, hipMemset(B.d_desc, 0, dw * 8));
-                B.desc_words = dw;
-                B.epoch = 0;
-            }
-            if (F > B.status_cap) {
-                if (B.h_status) HIPCHK(ctx, hipHostFree(B.h_status));
-                B.h_status = nullptr, B.status_cap = 0;
-                const size_t cap = F < 256 ? 256 : 2 * (size_t)F;
-                HIPCHK(ctx, hipHostMalloc((void **)&B.h_status, cap * sizeof(DecStatus), hipHostMallocMapped | hipHostMallocCoherent));
-                HIPCHK(ctx, hipHostGetDevicePointer((void **)&B.d_status, B.h_status, 0));
-                B.status_cap = cap;
-            }
-        }
         BT_START();
         for (uint32_t k = 0; k < F; k++) frames[k].idct.out = B.d_pix + pix_off[k];
         memcpy(B.h_in + o_frames, frames.data(), F * sizeof(DecFrame));
@@ -2517,17 +2485,14 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
                 memcpy(B.h_in + o_streams + (size_t)frames[k].word0 * 4, streams[ids[k]], lens[ids[k]]);
             }
         }
-        memset(B.h_status, 0, F * sizeof(DecStatus));
+        rc = B.ws.begin(ctx, ctx->stream, F);
+        if (rc) return rc;
         BT_STOP(0);
         BT_START();
-        if (++B.epoch >= (1u << 22)) {
-            HIPCHK(ctx, hipMemsetAsync(B.d_desc, 0, B.desc_words * 8, ctx->stream));
-            B.epoch = 1;
-        }
         HIPCHK(ctx, hipMemcpyAsync(B.d_in, B.h_in, up_bytes, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, entropy_decode_idct_gpu_batch(B.d_in + o_streams, (const DecFrame *)(B.d_in + o_frames), (const uint32_t *)(B.d_in + o_tiles), (const uint32_t *)(B.d_in + o_wgs), F, tiles,
-                                                  wgs, ranges, blk, small_win, ctx->d_dec_luts, B.d_work, B.work_bytes, B.d_desc, B.desc_words, B.epoch, B.d_status, range_bits,
-                                                  ctx->stream));
+                                                  wgs, ranges, blk, small_win, ctx->d_dec_luts, B.ws.work, B.ws.work_bytes, B.ws.desc, B.ws.desc_words, B.ws.epoch, B.ws.d_status,
+                                                  range_bits, ctx->stream));
         BT_STOP(1);
         BT_START();
         // ---- the pixels come down: one copy into the caller's memory where the frames are dense and follow each other there, else one copy
@@ -2557,7 +2522,7 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
             if (reg && hipHostUnregister(reg) != hipSuccess) (void)hipGetLastError();
         }
         if (!direct) {
-            rc = grow_pin(&B.h_pix, &B.hpix_cap, poff);
+            rc = grow_pinned(ctx, B.h_pix, B.hpix_cap, poff, poff + poff / 4);
             if (rc) return rc;
             HIPCHK(ctx, hipMemcpyAsync(B.h_pix, B.d_pix, poff, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2568,7 +2533,7 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
         // ---- what the kernels report, frame by frame: the header they saw, nothing flagged, every block produced
         std::vector<char> good(F);
         for (uint32_t k = 0; k < F; k++) {
-            const DecStatus &st = B.h_status[k];
+            const DecStatus &st = B.ws.h_status[k];
             good[k] = memcmp(st.head, streams[ids[k]], 16) == 0 && st.giveup == 0 && st.m == (unsigned long long)frames[k].nblocks;
             if (good[k]) ctx->last_dbatch_frames++;
             else later.push_back(ids[k]);
@@ -2655,14 +2620,10 @@ int tic_decompress_dev(tic_ctx *ctx, const void *d_stream, size_t len, void *d_o
             memcpy(head, ctx->dec_head, 16);
         else
             HIPCHK(ctx, hipMemcpy(head, d_stream, 16, hipMemcpyDeviceToHost));
-        int h, w, quality;
-        uint32_t flag;
-        if (parse_header(head, 16, &h, &w, &quality, &flag) != TIC_OK) return set_err(ctx, TIC_E_STREAM, "stream shorter than the 16-byte header");
-        if (flag & (1u << 31)) return set_err(ctx, TIC_E_STREAM, "streams with an embedded Huffman table are not supported"); // (a cached header passed these checks when it was cached)
-        const bool scaled = (flag & (1u << 30)) != 0;
-        if (h < 0 || w < 0) return set_err(ctx, TIC_E_STREAM, "bad geometry in header");
-        if (scaled && (quality < 0 || quality > 62)) return set_err(ctx, TIC_E_QUALITY, "scaled_dct exponent %d in header outside 0..62", quality);
-        if (!scaled && (quality < 1 || quality > 99)) return set_err(ctx, TIC_E_QUALITY, "quality %d in header outside 1..99", quality);
+        StreamHead sh;
+        int rc = check_header(ctx, head, 16, &sh); // (a cached header passed these checks when it was cached)
+        if (rc) return rc;
+        const int h = sh.h, w = sh.w;
         const size_t n = num_blocks(h, w);
         if (guess && (n == 0 || out_stride < (ptrdiff_t)w || !d_out || (size_t)(h - 1) * (size_t)out_stride + (size_t)w > out_cap)) { // the guess does not fit this call
             ctx->last_decode_guess = -1;
@@ -2676,8 +2637,8 @@ int tic_decompress_dev(tic_ctx *ctx, const void *d_stream, size_t len, void *d_o
             if (!d_out || (size_t)(h - 1) * (size_t)out_stride + (size_t)w > out_cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
         }
         bool done = false, held = false;
-        int rc = decode_on_device(ctx, (const uint8_t *)d_stream, len, h, w, scaled ? 50 : quality, scaled ? quality : -1, (uint8_t *)d_out, true,
-                                  (size_t)out_stride, &done, head, true, guess, guess ? &held : nullptr);
+        rc = decode_on_device(ctx, (const uint8_t *)d_stream, len, sh, (uint8_t *)d_out, true, (size_t)out_stride, &done, head, true, guess,
+                              guess ? &held : nullptr);
         if (rc) return rc;
         if (guess) {
             ctx->last_decode_guess = held ? 1 : -1;
@@ -2694,19 +2655,7 @@ int tic_decompress_dev(tic_ctx *ctx, const void *d_stream, size_t len, void *d_o
         }
         std::vector<uint8_t> host(len);
         HIPCHK(ctx, hipMemcpy(host.data(), d_stream, len, hipMemcpyDeviceToHost));
-        if (n * 128 > ctx->h_zz_bytes) {
-            if (ctx->h_zz) (void)hipHostFree(ctx->h_zz);
-            ctx->h_zz = nullptr;
-            ctx->h_zz_bytes = 0;
-            HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_zz, n * 128, hipHostMallocDefault));
-            ctx->h_zz_bytes = n * 128;
-        }
-        entropy_decode(host.data(), len, h, w, ctx->h_zz);
-        ctx->last_decode_path = 2;
-        rc = ensure_scratch(ctx, align_up((size_t)w, 256) * (size_t)h, n * 128);
-        if (rc) return rc;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, ctx->h_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
-        return idct_from_device(ctx, h, w, scaled ? 50 : quality, scaled ? quality : -1, (uint8_t *)d_out, true, (size_t)out_stride);
+        return decode_on_host(ctx, host.data(), len, sh, (uint8_t *)d_out, true, (size_t)out_stride);
     }
     return set_err(ctx, TIC_E_ARG, "tic_decompress_dev: unreachable");
 }
@@ -2730,62 +2679,29 @@ int tic_decompress_dev_async(tic_ctx *ctx, const void *d_stream, size_t len, voi
     sl.d_out = d_out;
     sl.out_stride = out_stride;
     sl.out_cap = out_cap;
-    int h = 0, w = 0, quality = 0;
-    uint32_t flag = 0;
+    StreamHead sh = {0, 0, 0, -1};
     bool launch = ctx->dec_guess_on && ctx->dec_head_valid && ctx->dec_head_streak >= 1 && d_stream && d_out && ((uintptr_t)d_stream & 3u) == 0 &&
                   out_stride % 8 == 0 && (uintptr_t)d_out % 8 == 0 && ctx->d_dec_luts && !test_hook("TIC_DECODE_NO_GUESS") && !test_hook("TIC_DECODE_HOST") &&
-                  !test_hook("TIC_DECODE_SERIAL") && parse_header(ctx->dec_head, 16, &h, &w, &quality, &flag) == TIC_OK;
+                  !test_hook("TIC_DECODE_SERIAL") && check_header(ctx, ctx->dec_head, 16, &sh) == TIC_OK; // (it passed when it was cached)
+    const int h = sh.h, w = sh.w;
     const size_t n = launch ? num_blocks(h, w) : 0;
     launch = launch && device_decoder_takes(n, len) && out_stride >= (ptrdiff_t)w && (size_t)(h - 1) * (size_t)out_stride + (size_t)w <= out_cap;
     if (launch) {
         if (!sl.stream) HIPCHK(ctx, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
         if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
         if (!ctx->dec_order) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->dec_order, hipEventDisableTiming));
-        if (!sl.h_status) {
-            HIPCHK(ctx, hipHostMalloc((void **)&sl.h_status, 64, hipHostMallocMapped | hipHostMallocCoherent));
-            HIPCHK(ctx, hipHostGetDevicePointer((void **)&sl.d_status, sl.h_status, 0));
-        }
         const size_t wb = entropy_decode_gpu_work_bytes(len, n);
-        if (wb > sl.work_bytes) { // (nothing of this slot is in flight: its ticket is closed)
-            if (sl.work) HIPCHK(ctx, hipFree(sl.work));
-            sl.work = nullptr;
-            sl.work_bytes = 0;
-            HIPCHK(ctx, hipMalloc(&sl.work, wb));
-            sl.work_bytes = wb;
-        }
-        size_t dw = entropy_decode_gpu_desc_words(len, n);
-        if (dw > sl.desc_words) {
-            dw = dw < 8192 ? 8192 : 2 * dw;
-            if (sl.desc) HIPCHK(ctx, hipFree(sl.desc));
-            sl.desc = nullptr;
-            sl.desc_words = 0;
-            HIPCHK(ctx, hipMalloc((void **)&sl.desc, dw * 8));
-            HIPCHK(ctx, hipMemset(sl.desc, 0, dw * 8));
-            sl.desc_words = dw;
-            sl.epoch = 0;
-        }
-        if (++sl.epoch >= (1u << 22)) {
-            HIPCHK(ctx, hipMemsetAsync(sl.desc, 0, sl.desc_words * 8, sl.stream));
-            sl.epoch = 1;
-        }
-        const bool scaled = (flag & (1u << 30)) != 0;
-        DecIdctArgs ia;
-        ia.out = (uint8_t *)d_out;
-        ia.h = h;
-        ia.w = w;
-        ia.stride = (long)out_stride;
-        ia.bw = (w + 7) / 8;
-        ia.aligned8 = 1;
-        ia.consts = ctx->d_consts + (scaled ? 50 : quality);
-        ia.scaled = scaled;
-        ia.pow2 = scaled ? ldexp(1.0, quality) : 1.0;
-        memcpy(ia.head, ctx->dec_head, 16); // (the guess: pixels are written only if the stream really starts with it)
-        memset(sl.h_status, 0, sizeof(DecStatus));
+        int rc = sl.ws.grow(ctx, wb, wb, entropy_decode_gpu_desc_words(len, n), 1, 1); // (nothing of this slot is in flight: its ticket is closed)
+        if (rc) return rc;
+        rc = sl.ws.begin(ctx, sl.stream, 1);
+        if (rc) return rc;
+        // (the guess: pixels are written only if the stream really starts with it)
+        const DecIdctArgs ia = dec_idct_args(ctx, h, w, sh.quality, sh.scaled_exp, (uint8_t *)d_out, (long)out_stride, ctx->dec_head);
         // behind everything queued on the context's stream so far (the stream may just have been written there: tic_compress_dev_async)
         HIPCHK(ctx, hipEventRecord(ctx->dec_order, ctx->stream));
         HIPCHK(ctx, hipStreamWaitEvent(sl.stream, ctx->dec_order, 0));
-        HIPCHK(ctx, entropy_decode_idct_gpu(d_stream, len, n, ctx->d_dec_luts, sl.work, sl.work_bytes, sl.desc, sl.desc_words, sl.epoch, ia, sl.d_status,
-                                            decode_range_bits(len, n), 0, sl.stream));
+        HIPCHK(ctx, entropy_decode_idct_gpu(d_stream, len, n, ctx->d_dec_luts, sl.ws.work, sl.ws.work_bytes, sl.ws.desc, sl.ws.desc_words, sl.ws.epoch, ia,
+                                            sl.ws.d_status, decode_range_bits(len, n), 0, sl.stream));
         HIPCHK(ctx, hipEventRecord(sl.done, sl.stream));
         memcpy(sl.head, ctx->dec_head, 16);
         sl.n = n;
@@ -2817,7 +2733,7 @@ int tic_decompress_async_result(tic_ctx *ctx, long long ticket, int wait, int *h
             HIPCHK(ctx, q);
         }
         DecStatus st;
-        memcpy(&st, sl.h_status, sizeof st); // (host-mapped: the slot's stream has drained)
+        memcpy(&st, sl.ws.h_status, sizeof st); // (host-mapped: the slot's stream has drained)
         if (memcmp(st.head, sl.head, 16) == 0 && st.giveup == 0 && st.m == sl.n) {
             ctx->last_decode_path = 1;
             ctx->last_decode_giveup = 0;
@@ -2886,14 +2802,8 @@ static int adaptive_encode_dev(tic_ctx *ctx, size_t n, int h, int w, int quality
         ctx->d_adapt_tab = (HuffWide *)(p + a);
         ctx->d_adapt_err = (uint32_t *)(p + a + b);
     }
-    const size_t wb = adaptive_work_bytes(n);
-    if (wb > ctx->adapt_work_bytes) {
-        if (ctx->d_adapt_work) HIPCHK(ctx, hipFree(ctx->d_adapt_work));
-        ctx->d_adapt_work = nullptr;
-        ctx->adapt_work_bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->d_adapt_work, wb));
-        ctx->adapt_work_bytes = wb;
-    }
+    int rc = grow_dev(ctx, ctx->d_adapt_work, ctx->adapt_work_bytes, adaptive_work_bytes(n));
+    if (rc) return rc;
     AdaptStats *st = ctx->d_adapt_stats;
     HIPCHK(ctx, hipMemsetAsync(st, 0, sizeof(AdaptStats), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(st->first, 0xff, sizeof(st->first), ctx->stream));
@@ -2908,7 +2818,7 @@ static int adaptive_encode_dev(tic_ctx *ctx, size_t n, int h, int w, int quality
     unsigned long long dc_code[16], ac_code[256];
     uint8_t dc_len[16], ac_len[256];
     size_t tbits = 0;
-    int rc = huffman_table_build(hs.count + kAdaptDcBin, hs.first + kAdaptDcBin, hs.count, hs.first, dc_code, dc_len, ac_code, ac_len,
+    rc = huffman_table_build(hs.count + kAdaptDcBin, hs.first + kAdaptDcBin, hs.count, hs.first, dc_code, dc_len, ac_code, ac_len,
                                  head.data() + 16, kAdaptMaxTableBytes, &tbits);
     if (rc == TIC_E_RANGE)
         return set_err(ctx, rc, "a Huffman code of this frame and its value bits exceed %d bits", kAdaptMaxSymbolBits);
@@ -2927,13 +2837,8 @@ static int adaptive_encode_dev(tic_ctx *ctx, size_t n, int h, int w, int quality
         *out_len = bytes;
         return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", bytes, cap);
     }
-    if (words * 4 > ctx->adapt_out_bytes) {
-        if (ctx->d_adapt_out) HIPCHK(ctx, hipFree(ctx->d_adapt_out));
-        ctx->d_adapt_out = nullptr;
-        ctx->adapt_out_bytes = 0;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_adapt_out, words * 4));
-        ctx->adapt_out_bytes = words * 4;
-    }
+    rc = grow_dev(ctx, ctx->d_adapt_out, ctx->adapt_out_bytes, words * 4);
+    if (rc) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_adapt_out, 0, words * 4, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_adapt_out, head.data(), (size_t)((base + 7) / 8), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_adapt_tab, &tab, sizeof tab, hipMemcpyHostToDevice, ctx->stream));
