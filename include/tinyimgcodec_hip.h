@@ -325,11 +325,24 @@ int tic_entropy_encode_adaptive(tic_ctx *ctx, const int16_t *coeffs_zz, int h, i
 int tic_huffman_table_build(const uint64_t *dc_count /*16*/, const uint64_t *dc_first /*16*/, const uint64_t *ac_count /*256*/,
                             const uint64_t *ac_first /*256*/, uint64_t *dc_code /*16*/, uint8_t *dc_len /*16*/, uint64_t *ac_code /*256*/,
                             uint8_t *ac_len /*256*/, uint8_t *table, size_t table_cap, size_t *table_bits);
-/* decompress() codec.py:167-189 for streams with an embedded table, read as written: host Huffman decode (codes up to 64 bits), GPU
+/* decompress() codec.py:167-189 for streams with an embedded table, read as written: Huffman decode (codes up to 64 bits), GPU
  * dequantise + inverse DCT as tic_decompress.  Strict where the reference is not: a malformed table (not a prefix code, counts out of
  * range, a code the payload meets without a symbol), a truncated stream, a block of more than 63 AC coefficients or a DC outside int16
- * give TIC_E_STREAM.  out: uint8[h*w]. */
+ * give TIC_E_STREAM.  out: uint8[h*w].
+ * The Huffman decode runs on the device (the table is parsed on the host and goes up as look-up tables; the coefficients never cross
+ * PCIe) for every stream of >= 16,384 blocks, and for shorter ones from 1,024 blocks and 262,144 payload bits on, unless a code of its
+ * tables has length zero (a flat frame's one-symbol tree).  All other streams, and any stream in which the device decoder meets
+ * something unusual, take the host's bit-serial decoder, which alone decides between pixels and TIC_E_STREAM.  tic_last_decode_path
+ * (1 device, 2 host) and tic_last_decode_giveup (bits: 4 the chain did not settle, 8 a window without a code or a block of more than
+ * 63 AC entries, 16 the stream ends before the last block, 32 a DC outside int16) tell which. */
 int tic_decompress_adaptive(tic_ctx *ctx, const uint8_t *data, size_t len, uint8_t *out, size_t cap);
+/* The same with stream and pixels both resident in device memory, arguments as tic_decompress_dev: only the stream's first 2.6 KB
+ * (header and table) come down; d_out receives h rows of w pixels, out_stride bytes apart, and no other byte of it is written;
+ * *h / *w (may be null) receive the header's geometry.  TIC_E_SPACE (nothing written) when out_cap is short.  A stream the host decoder
+ * takes makes the round trip through host memory.  A stream at a 4-byte aligned address is decoded where it lies and read in 32-bit
+ * words: up to 3 bytes behind `len`, to the next 4-byte boundary, are read (and masked); any other address is copied first. */
+int tic_decompress_adaptive_dev(tic_ctx *ctx, const void *d_stream, size_t len, void *d_out, ptrdiff_t out_stride, size_t out_cap, int *h,
+                                int *w);
 
 /* ---- multi-GPU (the reference has no counterpart: it is single-process, codec.py:133-164 runs one image
  *      at a time).  One process per GPU; a batch shards by independent frames (frame i -> rank i / ceil(B/G)) with no

@@ -326,9 +326,10 @@ def entropy_encode_adaptive(coeffs_zz, height, width, quality, ctx=None):
 
 
 def decompress_adaptive(data, ctx=None):
-    """Reads a stream of compress_adaptive() (or of the reference's compress(..., auto_generate_huffman_table=True)) as written: host
-    Huffman decode with the embedded table, inverse transform on the GPU.  Strict: ValueError for a malformed table, a truncated or
-    damaged stream - the reference has no working counterpart, and decompress() keeps the reference's reading (garbage)."""
+    """Reads a stream of compress_adaptive() (or of the reference's compress(..., auto_generate_huffman_table=True)) as written:
+    Huffman decode with the embedded table (on the GPU for streams of 16,384 blocks, or 1,024 blocks and 32 KB of payload, and more;
+    else and for anything unusual on the host), inverse transform on the GPU.  Strict: ValueError for a malformed table, a truncated
+    or damaged stream - the reference has no working counterpart, and decompress() keeps the reference's reading (garbage)."""
     ctx = _ctx(ctx)
     buf = _as_bytes_view(data)
     if buf.size < 16:

@@ -225,10 +225,9 @@ int huffman_table_build(const unsigned long long *dc_count, const unsigned long 
     return TIC_OK;
 }
 
-int adaptive_decode(const uint8_t *data, size_t len, int h, int w, int16_t *zz, const char **why) {
-    const char *dummy;
-    if (!why) why = &dummy;
-    *why = "";
+// The header's flag and read_huffman_table (codec.py:87-99): the tries of the host decoder, the entries for the device decoder's
+// tables (t may be null); r is left at the payload's first bit.
+static int parse_table(const uint8_t *data, size_t len, BitIn &r, Trie &dc, Trie &ac, AdaptTable *t, const char **why) {
     if (!data || len < 16) {
         *why = "stream shorter than its 16-byte header";
         return TIC_E_STREAM;
@@ -237,10 +236,8 @@ int adaptive_decode(const uint8_t *data, size_t len, int h, int w, int16_t *zz, 
         *why = "the header carries no embedded Huffman table";
         return TIC_E_STREAM;
     }
-    BitIn r{data, len * 8, 128};
-    Trie dc, ac;
-    unsigned long long v, cnt;
-    // read_huffman_table (codec.py:87-99)
+    r = BitIn{data, len * 8, 128};
+    unsigned long long cnt;
     if (!r.get(16, cnt) || cnt == 0 || cnt > 16) {
         *why = "DC table: entry count missing or outside 1..16";
         return TIC_E_STREAM;
@@ -255,7 +252,9 @@ int adaptive_decode(const uint8_t *data, size_t len, int h, int w, int16_t *zz, 
             *why = "DC table is not a prefix code";
             return TIC_E_STREAM;
         }
+        if (t) t->dc_sym[i] = (uint8_t)cat, t->dc_len[i] = (uint8_t)n, t->dc_code[i] = code;
     }
+    if (t) t->ndc = (int)cnt;
     if (!r.get(16, cnt) || cnt == 0 || cnt > 256) {
         *why = "AC table: entry count missing or outside 1..256";
         return TIC_E_STREAM;
@@ -270,7 +269,55 @@ int adaptive_decode(const uint8_t *data, size_t len, int h, int w, int16_t *zz, 
             *why = "AC table is not a prefix code";
             return TIC_E_STREAM;
         }
+        if (t) t->ac_sym[i] = (uint8_t)rs, t->ac_len[i] = (uint8_t)n, t->ac_code[i] = code;
     }
+    if (t) t->nac = (int)cnt, t->payload_bit = r.pos;
+    return TIC_OK;
+}
+
+int adaptive_parse_table(const uint8_t *data, size_t len, AdaptTable *t, const char **why) {
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    BitIn r{nullptr, 0};
+    Trie dc, ac;
+    return parse_table(data, len, r, dc, ac, t, why);
+}
+
+bool adaptive_dec_tab_build(const AdaptTable &t, AdaptDecTab *out) {
+    memset(out, 0, sizeof *out);
+    for (int k = 0; k < 2; k++) {
+        const int n = k ? t.nac : t.ndc;
+        struct Long { unsigned long long code; uint16_t ls; };
+        std::vector<Long> longs;
+        for (int i = 0; i < n; i++) {
+            const int len = k ? t.ac_len[i] : t.dc_len[i];
+            const unsigned long long code = k ? t.ac_code[i] : t.dc_code[i];
+            const uint16_t ls = (uint16_t)((len << 8) | (k ? t.ac_sym[i] : t.dc_sym[i]));
+            if (len == 0) return false;
+            if (len <= kAdaptDecK) {
+                const unsigned first = (unsigned)(code << (kAdaptDecK - len));
+                for (unsigned j = 0; j < (1u << (kAdaptDecK - len)); j++) out->prim[k][first + j] = ls;
+            } else {
+                longs.push_back({code << (64 - len), ls});
+            }
+        }
+        std::sort(longs.begin(), longs.end(), [](const Long &a, const Long &b) { return a.code < b.code; });
+        out->nlong[k] = (uint32_t)longs.size();
+        for (size_t i = 0; i < longs.size(); i++) out->long_code[k][i] = longs[i].code, out->long_ls[k][i] = longs[i].ls;
+    }
+    return true;
+}
+
+int adaptive_decode(const uint8_t *data, size_t len, int h, int w, int16_t *zz, const char **why) {
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    BitIn r{nullptr, 0};
+    Trie dc, ac;
+    unsigned long long v;
+    const int rc = parse_table(data, len, r, dc, ac, nullptr, why);
+    if (rc) return rc;
     const size_t nb = num_blocks(h, w);
     long long dc_run = 0;
     for (size_t b = 0; b < nb; b++) {

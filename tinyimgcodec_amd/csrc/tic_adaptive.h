@@ -1,5 +1,6 @@
 // tic_adaptive.h - per-image Huffman tables (compress(..., auto_generate_huffman_table=True) of the reference, codec.py:133-164,
-// huffman.py:101-194): host table builder and decoder (tic_adaptive.cpp), device statistics and packing (tic_adaptive_gpu.hip).
+// huffman.py:101-194): host table builder, table parser and decoder (tic_adaptive.cpp), device statistics and packing
+// (tic_adaptive_gpu.hip), device decoder (tic_adaptive_dec_gpu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -42,7 +43,57 @@ int huffman_table_build(const unsigned long long *dc_count, const unsigned long 
 // a block of more than 63 AC entries or a DC outside int16.
 int adaptive_decode(const uint8_t *data, size_t len, int h, int w, int16_t *zz, const char **why);
 
-// Device part (tic_adaptive_gpu.hip).  d_stats: statistics of the n blocks of d_zz (zero the counts and the error, set the
+// The embedded table of such a stream as read_huffman_table (codec.py:87-99) reads it, entries in stream order: symbol (DC: size
+// category; AC: (run << 4) | size), code length and codeword (right-aligned), and the payload's first bit (128 + table bits, not
+// byte-aligned).
+struct AdaptTable {
+    int ndc, nac;
+    uint8_t dc_sym[16], dc_len[16], ac_sym[256], ac_len[256];
+    unsigned long long dc_code[16], ac_code[256];
+    size_t payload_bit;
+};
+// The one table parser of both decoders, with adaptive_decode's strict checks (and its messages): the flag of the header, counts in
+// range, a prefix code, code + value bits <= kAdaptMaxSymbolBits.  `len` bytes of `data` are readable: the whole stream, or its first
+// 16 + kAdaptMaxTableBytes bytes (no table reaches further).
+int adaptive_parse_table(const uint8_t *data, size_t len, AdaptTable *t, const char **why);
+
+// Look-up tables of the device decoder (tic_adaptive_dec_gpu.hip), DC at [0] and AC at [1]: a primary table indexed by the next
+// kAdaptDecK stream bits - (length << 8) | symbol for codes of at most kAdaptDecK bits, 0 (an escape) where the window starts a longer
+// code or no code - and the longer codes left-aligned in 64 bits in ascending order with (length << 8) | symbol beside them: a lane
+// takes the last one not above its window and confirms the prefix.  13.3 KB: the kernels stage it in LDS.
+constexpr int kAdaptDecK = 11;
+struct AdaptDecTab {
+    uint16_t prim[2][1 << kAdaptDecK];
+    unsigned long long long_code[2][256];
+    uint16_t long_ls[2][256];
+    uint32_t nlong[2];
+};
+// False when a code has length zero (the one-symbol tree of a flat frame: its symbols take no bits, so there is nothing to
+// synchronise on): such a stream is the host decoder's.
+bool adaptive_dec_tab_build(const AdaptTable &t, AdaptDecTab *out);
+
+// Device decoder (tic_adaptive_dec_gpu.hip): the payload of `len` stream bytes at d_stream (4-byte aligned; the bytes of its last word
+// behind `len` are masked) from bit `payload_bit` -> d_zz = int16 [nblocks][64] zig-zag with the DC integrated.  d_work:
+// adaptive_dec_work_bytes(len, payload_bit, nblocks, range_bits) bytes.  Nothing is synchronised: the caller reads *d_status behind the
+// stream.  Rounds [round0, round0 + nrounds) of the stitch are launched (round0 = 0 starts a decode and zeroes the status) and, with
+// `finish`, the passes behind them: block positions, decode and the DC sum (nrounds may be 0 then).  What the passes leave counts only
+// when the last round launched before them moved no exit.
+constexpr int kAdaptDecMaxRounds = 512;
+struct AdaptDecStatus {
+    uint32_t giveup;                      // kAdaptGiveup* bits
+    uint32_t blocks;                      // blocks on the chain up to the stream's end
+    uint32_t changed[kAdaptDecMaxRounds]; // exits round r moved: the chain is known only when the last round launched moved none
+};
+constexpr uint32_t kAdaptGiveupNoSync = 4,    // (set by the caller) no fixed point within kAdaptDecMaxRounds rounds
+                   kAdaptGiveupIncident = 8,  // a window without a code or a block of more than 63 AC entries on the chain before block N
+                   kAdaptGiveupShort = 16,    // the chain reaches the stream's end before block N
+                   kAdaptGiveupDc = 32;       // a running DC outside int16
+int adaptive_dec_range_bits(size_t len, size_t payload_bit, size_t nblocks);
+size_t adaptive_dec_work_bytes(size_t len, size_t payload_bit, size_t nblocks, int range_bits);
+hipError_t adaptive_decode_gpu(const void *d_stream, size_t len, size_t payload_bit, size_t nblocks, int range_bits, const AdaptDecTab *d_tab,
+                               void *d_work, AdaptDecStatus *d_status, int16_t *d_zz, int round0, int nrounds, bool finish, hipStream_t stream);
+
+// Device part of the encoder (tic_adaptive_gpu.hip).  d_stats: statistics of the n blocks of d_zz (zero the counts and the error, set the
 // first keys to ~0 before).  The packing: d_out (32-bit words, zeroed, the header and table bits already in place) receives the
 // payload from bit `base_bits`; nothing at or past word `out_words` is written (*d_err = 1 instead).  d_work:
 // adaptive_work_bytes(n).

@@ -240,6 +240,12 @@ struct tic_ctx {
     size_t adapt_work_bytes = 0;
     uint32_t *d_adapt_out = nullptr;
     size_t adapt_out_bytes = 0;
+    // ... and their device decoder (tic_decompress_adaptive): look-up tables and status words in one allocation, the workspace
+    AdaptDecTab adec_tab; // the host copy, built per call
+    AdaptDecTab *d_adec_tab = nullptr;
+    AdaptDecStatus *d_adec_status = nullptr;
+    void *d_adec_work = nullptr;
+    size_t adec_work_bytes = 0;
 };
 
 // NUMA node of a device (its PCI function's numa_node in sysfs) and the CPUs of that node within this process's affinity mask.
@@ -472,6 +478,8 @@ void tic_destroy(tic_ctx *ctx) {
     if (ctx->d_adapt_stats) (void)hipFree(ctx->d_adapt_stats); // table and error word live in the same block
     if (ctx->d_adapt_work) (void)hipFree(ctx->d_adapt_work);
     if (ctx->d_adapt_out) (void)hipFree(ctx->d_adapt_out);
+    if (ctx->d_adec_tab) (void)hipFree(ctx->d_adec_tab); // the status words live in the same block
+    if (ctx->d_adec_work) (void)hipFree(ctx->d_adec_work);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -2890,27 +2898,169 @@ int tic_entropy_encode_adaptive(tic_ctx *ctx, const int16_t *coeffs_zz, int h, i
     return adaptive_encode_dev(ctx, n, h, w, quality, out, cap, out_len);
 }
 
+// Streams with an embedded table the DEVICE decoder takes (tic_adaptive_dec_gpu.hip): every stream of at least 16,384 blocks, and
+// shorter ones from kAdaptDevMinBlocks blocks and kAdaptDevMinBits payload bits (32 KB) on - the crossover against the host's
+// bit-serial decoder measured in profiles/adaptive_decode.txt: a device decode of a small stream costs 0.45-0.65 ms whatever its
+// length, the host 25-30 us per KB; 512^2 at q = 5 (4 KB) stays on the host, at q = 90 (72 KB) goes to the device - provided no code
+// of its tables has length zero (a one-symbol tree: nothing to synchronise on) and the stream's bit positions fit 32 bits.  The hooks build moves the lines with TIC_DECODE_MIN_BLOCKS /
+// TIC_DECODE_MIN_BITS and sends everything to the host with TIC_DECODE_HOST, as for default-table streams.
+constexpr size_t kAdaptDevMinBlocks = 1024, kAdaptDevMinBits = 1u << 18;
+static bool adaptive_device_takes(size_t n, size_t len, size_t payload_bit) {
+    size_t min_blocks = kAdaptDevMinBlocks, min_bits = kAdaptDevMinBits;
+    if (const char *e = test_hook("TIC_DECODE_MIN_BLOCKS")) min_blocks = (size_t)atol(e);
+    if (const char *e = test_hook("TIC_DECODE_MIN_BITS")) min_bits = (size_t)atol(e);
+    if (test_hook("TIC_DECODE_HOST")) return false;
+    const size_t bits = len * 8;
+    if (n == 0 || n >= (1ull << 31) || bits <= payload_bit || bits + 8192 >= (1ull << 32)) return false;
+    return n >= 16384 || (n >= min_blocks && bits - payload_bit >= min_bits);
+}
+
+// The device decoder on a stream it takes, with the tables in ctx->adec_tab: coefficients into ctx->d_coef.  *done = false (and TIC_OK) after a give-up
+// (ctx->last_decode_giveup says why): the caller runs the host decoder.
+static int adaptive_decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, bool src_on_device, const AdaptTable &t, size_t n, bool *done) {
+    *done = false;
+    // decoded where it lies when it is in device memory at a 4-byte aligned address, else through the context's stream buffer
+    const bool in_place = src_on_device && ((uintptr_t)data & 3u) == 0;
+    int rc = TIC_OK;
+    if (!in_place) {
+        rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, align_up(len, 4) + 16);
+        if (rc) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_stream_buf, data, len, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    }
+    const void *d_stream = in_place ? (const void *)data : (const void *)ctx->d_stream_buf;
+    if (!ctx->d_adec_tab) { // tables and status words in one allocation
+        char *p = nullptr;
+        const size_t a = align_up(sizeof(AdaptDecTab), 256);
+        HIPCHK(ctx, hipMalloc((void **)&p, a + align_up(sizeof(AdaptDecStatus), 256)));
+        ctx->d_adec_tab = (AdaptDecTab *)p;
+        ctx->d_adec_status = (AdaptDecStatus *)(p + a);
+    }
+    const int range = adaptive_dec_range_bits(len, t.payload_bit, n);
+    const size_t wb = adaptive_dec_work_bytes(len, t.payload_bit, n, range);
+    rc = grow_dev(ctx, ctx->d_adec_work, ctx->adec_work_bytes, wb, wb + wb / 8); // (room for a longer stream of the same geometry)
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_adec_tab, &ctx->adec_tab, sizeof ctx->adec_tab, hipMemcpyHostToDevice, ctx->stream));
+    // Three launches of the stitch settle nearly every stream (the last one only proves it), so the passes behind them are launched
+    // right away and one synchronisation shows both.  A stream with stretches in which no walk falls in step gets more rounds, 16 at a
+    // time and nothing else, until the chain has crossed them a workgroup per launch; then the passes run once.
+    AdaptDecStatus st{};
+    const auto run = [&](int round0, int nrounds, bool finish) -> int {
+        HIPCHK(ctx, adaptive_decode_gpu(d_stream, len, t.payload_bit, n, range, ctx->d_adec_tab, ctx->d_adec_work, ctx->d_adec_status,
+                                        (int16_t *)ctx->d_coef, round0, nrounds, finish, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(&st, ctx->d_adec_status, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, wait_stream(ctx));
+        if (test_hook("TIC_DECODE_TRACE")) {
+            fprintf(stderr, "adaptive decode: %zu blocks, range %d, rounds %d..%d%s, exits moved:", n, range, round0, round0 + nrounds - 1,
+                    finish ? " and the passes" : "");
+            for (int r = round0; r < round0 + nrounds; r++) fprintf(stderr, " %u", st.changed[r]);
+            fprintf(stderr, ", give-up %u, blocks on the chain %u\n", st.giveup, st.blocks);
+        }
+        return TIC_OK;
+    };
+    int rounds = 3;
+    rc = run(0, rounds, true);
+    if (rc) return rc;
+    if (st.changed[rounds - 1]) {
+        while (st.changed[rounds - 1] && rounds < kAdaptDecMaxRounds) {
+            const int more = kAdaptDecMaxRounds - rounds < 16 ? kAdaptDecMaxRounds - rounds : 16;
+            rc = run(rounds, more, false);
+            if (rc) return rc;
+            rounds += more;
+        }
+        if (st.changed[rounds - 1]) {
+            st.giveup = kAdaptGiveupNoSync; // (whatever the passes of the first launches reported is void)
+        } else {
+            rc = run(rounds, 0, true);
+            if (rc) return rc;
+        }
+    }
+    ctx->last_decode_giveup = (int)st.giveup;
+    *done = st.giveup == 0;
+    return TIC_OK;
+}
+
+// tic_decompress_adaptive / _dev behind their argument checks.  The stream: `len` bytes at `data`, in host or device memory; `head`:
+// its first `head_len` bytes in host memory (all of it, or 16 + kAdaptMaxTableBytes: header and table).  Pixels as idct_from_device.
+// The host decoder runs for the streams the device decoder does not take, after a give-up, and whenever the table does not parse:
+// it alone decides between pixels and TIC_E_STREAM and words the message.
+static int decompress_adaptive_impl(tic_ctx *ctx, const uint8_t *data, size_t len, bool src_on_device, const uint8_t *head, size_t head_len, int h, int w,
+                                    int q, uint8_t *out, bool out_on_device, size_t out_stride) {
+    const size_t n = num_blocks(h, w);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = n ? ensure_scratch(ctx, align_up((size_t)w, 256) * (size_t)h, n * 128) : TIC_OK;
+    if (rc) return rc;
+    {
+        AdaptTable t;
+        if (adaptive_parse_table(head, head_len, &t, nullptr) == TIC_OK && adaptive_device_takes(n, len, t.payload_bit) &&
+            adaptive_dec_tab_build(t, &ctx->adec_tab)) {
+            bool done = false;
+            rc = adaptive_decode_on_device(ctx, data, len, src_on_device, t, n, &done);
+            if (rc) return rc;
+            if (done) {
+                ctx->last_decode_path = 1;
+                return idct_from_device(ctx, h, w, q, -1, out, out_on_device, out_stride);
+            }
+        }
+    }
+    ctx->last_decode_path = 2;
+    std::vector<uint8_t> host;
+    if (src_on_device && len > head_len) {
+        try {
+            host.resize(len);
+        } catch (...) {
+            return set_err(ctx, TIC_E_ARG, "out of host memory for a stream of %zu bytes", len);
+        }
+        HIPCHK(ctx, hipMemcpy(host.data(), data, len, hipMemcpyDeviceToHost));
+        head = host.data();
+    } else if (!src_on_device) {
+        head = data;
+    }
+    rc = grow_pinned(ctx, ctx->h_zz, ctx->h_zz_bytes, n * 128); // (the landing buffer of decode_on_host)
+    if (rc) return rc;
+    const char *why = "";
+    rc = adaptive_decode(head, len, h, w, ctx->h_zz, &why);
+    if (rc) return set_err(ctx, rc, "adaptive stream: %s", why);
+    if (n == 0) return TIC_OK;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, ctx->h_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
+    return idct_from_device(ctx, h, w, q, -1, out, out_on_device, out_stride);
+}
+
 int tic_decompress_adaptive(tic_ctx *ctx, const uint8_t *data, size_t len, uint8_t *out, size_t cap) {
     TIC_LOCK(ctx);
     if (!ctx) return TIC_E_ARG;
+    ctx->last_decode_giveup = 0;
     int h = 0, w = 0, q = 0;
     uint32_t flag = 0;
     if (parse_header(data, len, &h, &w, &q, &flag) != TIC_OK) return set_err(ctx, TIC_E_STREAM, "stream shorter than its 16-byte header");
     if (h < 0 || w < 0) return set_err(ctx, TIC_E_STREAM, "negative image size in the header");
     if (q < 1 || q > 99) return set_err(ctx, TIC_E_STREAM, "quality %d in the header outside 1..99", q);
     if ((size_t)h * (size_t)w > cap || (!out && h && w)) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
-    const size_t n = num_blocks(h, w);
-    std::vector<int16_t> zz;
-    try {
-        zz.resize(n * 64);
-    } catch (...) {
-        return set_err(ctx, TIC_E_ARG, "out of host memory for %zu blocks", n);
+    return decompress_adaptive_impl(ctx, data, len, false, data, len, h, w, q, out, false, 0);
+}
+
+int tic_decompress_adaptive_dev(tic_ctx *ctx, const void *d_stream, size_t len, void *d_out, ptrdiff_t out_stride, size_t out_cap, int *h_out, int *w_out) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    ctx->last_decode_giveup = 0;
+    if (!d_stream && len) return set_err(ctx, TIC_E_ARG, "null stream pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (len < 16) return set_err(ctx, TIC_E_STREAM, "stream shorter than its 16-byte header");
+    // header and table come down (2.6 KB at most); the payload stays where it is
+    uint8_t head[16 + kAdaptMaxTableBytes];
+    const size_t head_len = len < sizeof head ? len : sizeof head;
+    HIPCHK(ctx, hipMemcpy(head, d_stream, head_len, hipMemcpyDeviceToHost));
+    int h = 0, w = 0, q = 0;
+    uint32_t flag = 0;
+    (void)parse_header(head, head_len, &h, &w, &q, &flag);
+    if (h < 0 || w < 0) return set_err(ctx, TIC_E_STREAM, "negative image size in the header");
+    if (q < 1 || q > 99) return set_err(ctx, TIC_E_STREAM, "quality %d in the header outside 1..99", q);
+    if (h_out) *h_out = h;
+    if (w_out) *w_out = w;
+    if (num_blocks(h, w) != 0) {
+        if (out_stride < (ptrdiff_t)w) return set_err(ctx, TIC_E_ARG, "row stride %td smaller than the width %d", out_stride, w);
+        if (!d_out || (size_t)(h - 1) * (size_t)out_stride + (size_t)w > out_cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
     }
-    const char *why = "";
-    const int rc = adaptive_decode(data, len, h, w, zz.data(), &why);
-    if (rc) return set_err(ctx, rc, "adaptive stream: %s", why);
-    if (n == 0) return TIC_OK;
-    return idctq_impl(ctx, zz.data(), h, w, q, -1, out, cap);
+    return decompress_adaptive_impl(ctx, (const uint8_t *)d_stream, len, true, head, head_len, h, w, q, (uint8_t *)d_out, true, (size_t)out_stride);
 }
 
 } // extern "C"

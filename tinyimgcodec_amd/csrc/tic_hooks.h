@@ -15,9 +15,11 @@
 //   TIC_DECODE_NO_GUESS     tic_decompress_dev always reads the header first (no launch on a guess of it)
 //   TIC_NO_SMALL_PATH       tic_compress of small frames through the device stream buffer and a DMA copy, as large ones (not through host-mapped memory)
 //   TIC_DECODE_MIN_BLOCKS, TIC_DECODE_MIN_BITS, TIC_DECODE_MIN_DENSITY   the shortest stream the device Huffman decoder takes (defaults 1024 blocks, 8192 bits, any density)
+//                           (tic_decompress_adaptive honours _MIN_BLOCKS, _MIN_BITS - payload bits there - and TIC_DECODE_HOST: defaults 1024 blocks, 262144 bits)
 //   TIC_DECODE_FLAT_GRID    device Huffman decoder: launches of up to this many workgroups sum all words in front (default 4096; 0: inclusive sums always)
 //   TIC_DECODE_MARGIN       device Huffman decoder: first run with the 2,048-bit margin and the host's tail (rounds 2-3's only mode; now the second run's)
-//   TIC_DECODE_TRACE        device Huffman decoder: one line per run on stderr (range, margin, give-up bits, blocks produced)
+//   TIC_DECODE_TRACE        device Huffman decoder: one line per run on stderr (range, margin, give-up bits, blocks produced); tic_decompress_adaptive:
+//                           one line per batch of stitch rounds (range, exits moved per round, give-up bits, blocks on the chain)
 //   TIC_DECODE_HOST         Huffman decoder: never the device decoder (host parallel / serial as the stream's length says)
 //   TIC_DECODE_THREADS      host Huffman decoder: threads of the parallel decoder
 //   TIC_COMM_FORCE_RCCL     a single rank goes through RCCL too (the only way to exercise tic_comm.hip on a one-GPU box)
