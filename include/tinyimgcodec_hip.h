@@ -344,6 +344,50 @@ int tic_decompress_adaptive(tic_ctx *ctx, const uint8_t *data, size_t len, uint8
 int tic_decompress_adaptive_dev(tic_ctx *ctx, const void *d_stream, size_t len, void *d_out, ptrdiff_t out_stride, size_t out_cap, int *h,
                                 int *w);
 
+/* ---- the reference's integer encoder: c/img.c + c/encode.c, the standalone C program ("scaled DCT" streams) ------------------------
+ *      The stream is what the library calls IMG_init -> IMG_encodeHeader -> IMG_encodeBlock per block in raster order ->
+ *      IMG_encodeComplete produce (img.c:157-253), NOT what the command-line program writes: encode.c:47 loops on feof and appends the
+ *      code of w/8 blocks of uninitialised stack behind the last strip, and its 8 KiB FIFO overwrites itself on wide frames.
+ *      Header (img.c:183-192): height, width, setting qf (0 best .. 3 low), flag 1 << 30, four little-endian u32.  Per block
+ *      (img.c:207-249): pixel ^ 0x80 as int8, IMG_fdct (img.c:47-125: AAN butterflies with the 8-bit constants 181, 98, 139, 334, every
+ *      output of either pass truncated to int16; the AAN scale factors stay in the coefficients), IMG_quantize (img.c:194-205:
+ *      sign(d) * (((QUANT >> 1) + |d|) * (65536 / (QUANT << qf)) >> 16)), DC difference, zig-zag, run lengths, the default tables, EOB after
+ *      every block.  End (BB_flushBits, img.h:36-40): one byte with the 0..7 pending bits behind the last whole byte - a zero byte when the
+ *      payload ends on a byte boundary: 16 + floor(P / 8) + 1 bytes for P payload bits; an image without blocks is 17 bytes.
+ *      Heights and widths must be multiples of 8 (encode.c:37): anything else is TIC_E_ARG.  qf outside 0..3 is TIC_E_QUALITY.  An AC
+ *      magnitude above 1,023 (possible at best only: the reference reads past AC_HUFF_TABLE[run][10] there, undefined behaviour) or a DC
+ *      difference above category 11 is TIC_E_RANGE.  tic_decompress and its siblings read these streams (flag 1 << 30). */
+#define TIC_SCALED_BEST 0
+#define TIC_SCALED_HIGH 1
+#define TIC_SCALED_MED 2
+#define TIC_SCALED_LOW 3
+/* Upper bound of a scaled-DCT stream's size: tic_compress_bound + the flush byte. */
+size_t tic_compress_scaled_bound(int h, int w);
+/* IMG_fdct + IMG_quantize (img.c:47-125, 194-205) + zig-zag of every block on the GPU, host buffers: coeffs_zz int16[N*64] in the zz16
+ * layout (absolute DC), as tic_dctq. */
+int tic_dctq_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int qf, int16_t *coeffs_zz);
+/* The same between device buffers, asynchronous on the context's stream (as tic_dctq_dev).  Writes exactly N * 128 bytes. */
+int tic_dctq_scaled_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, int qf, void *d_coeffs_zz);
+/* ... for `nframes` equally sized frames in one launch (grid row per frame), strides as tic_dctq_dev_frames; coeff_frame_stride a
+ * multiple of 16. */
+int tic_dctq_scaled_dev_frames(tic_ctx *ctx, const void *d_images, int nframes, int h, int w, ptrdiff_t row_stride, ptrdiff_t frame_stride,
+                               int qf, void *d_coeffs_zz, ptrdiff_t coeff_frame_stride);
+/* tic_dctq_dev_timed_warm for this kernel: `warm` untimed launches, an event, `iters` timed launches, an event, one submission;
+ * per_launch_ms as there (NULL, or 2 * iters floats). */
+int tic_dctq_scaled_dev_timed_warm(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, int qf, void *d_coeffs_zz, int warm,
+                                   int iters, float *ms_total, float *per_launch_ms);
+/* IMG_encodeHeader + the entropy half of IMG_encodeBlock (img.c:217-248) + IMG_encodeComplete from zz16 coefficients, on the host (no
+ * GPU): the twin of tic_entropy_encode. */
+int tic_entropy_encode_scaled(const int16_t *coeffs_zz, int h, int w, int qf, uint8_t *out, size_t cap, size_t *out_len);
+/* The whole encoder (what `encode <width> <height> <setting>` of c/encode.c is meant to write), host buffers, every stage on the GPU. */
+int tic_compress_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int qf, uint8_t *out, size_t cap,
+                        size_t *out_len);
+/* ... with image and stream both resident in device memory.  cap >= tic_compress_scaled_bound(): d_out must be 16-byte aligned and
+ * receives the stream straight from the placing kernel (bytes behind the stream, up to the next 16-byte unit, may be written).  A smaller
+ * buffer gets exactly the stream's bytes, and nothing at all when the stream does not fit (TIC_E_SPACE). */
+int tic_compress_scaled_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, int qf, void *d_out, size_t cap,
+                            size_t *out_len);
+
 /* ---- multi-GPU (the reference has no counterpart: it is single-process, codec.py:133-164 runs one image
  *      at a time).  One process per GPU; a batch shards by independent frames (frame i -> rank i / ceil(B/G)) with no
  *      data-path collective.  The one exchange is an all-gather of per-frame compressed sizes, so that every rank knows every

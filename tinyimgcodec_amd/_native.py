@@ -20,6 +20,7 @@ def _lib_path():
 TIC_OK = 0
 TIC_E_ARG, TIC_E_QUALITY, TIC_E_RANGE, TIC_E_SPACE, TIC_E_STREAM, TIC_E_HIP, TIC_E_NODEVICE, TIC_E_BUSY = -1, -2, -3, -4, -5, -6, -7, -8
 KERNEL_AUTO, KERNEL_EXACT, KERNEL_HYBRID = 0, 1, 2
+SCALED_BEST, SCALED_HIGH, SCALED_MED, SCALED_LOW = 0, 1, 2, 3  # TIC_SCALED_*: the settings of the reference's integer encoder
 QUALITY_CUSTOM = 0  # TIC_QUALITY_CUSTOM: the quality installed with tic_set_custom_quality
 
 
@@ -156,6 +157,26 @@ SIGNATURES = {
     ),
     "tic_decompress_adaptive": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "tic_decompress_adaptive_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_ssize_t, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tic_compress_scaled_bound": (C.c_size_t, [C.c_int, C.c_int]),
+    "tic_dctq_scaled": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p]),
+    "tic_dctq_scaled_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p]),
+    "tic_dctq_scaled_dev_frames": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_ssize_t, C.c_int, C.c_void_p, C.c_ssize_t],
+    ),
+    "tic_dctq_scaled_dev_timed_warm": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)],
+    ),
+    "tic_entropy_encode_scaled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tic_compress_scaled": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    ),
+    "tic_compress_scaled_dev": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    ),
     "tic_selftest_transpose": (C.c_int, [_ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "tic_comm_create": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]),
     "tic_comm_create_ex": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]),

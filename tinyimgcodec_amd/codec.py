@@ -14,6 +14,13 @@ huffman.py:101-194), under names of their own because compress() keeps raising f
     entropy_encode_adaptive(coeffs_zz, height, width, quality) -> bytes   the same from int16 [N, 64] zig-zag coefficients
     decompress_adaptive(data) -> np.ndarray[uint8]  reads such a stream as written
 
+and, for the reference's standalone integer encoder (c/img.c, c/encode.c: 8-bit-constant AAN DCT, reciprocal quantiser with four
+settings, header flag 1 << 30 - the streams decompress() reads through its scaled_dct branch):
+
+    compress_scaled(image, quality="med") -> bytes        what `encode <width> <height> <setting>` is meant to write (img.c:157-253)
+    dctq_scaled(image, quality="med") -> int16 [N, 64]    its coefficients in the device layout (zig-zag, absolute DC)
+    entropy_encode_scaled(coeffs_zz, height, width, quality) -> bytes   its entropy stage alone (no GPU needed)
+
 The transform stage (pad, level shift, DCT, quantise, zig-zag) and the entropy stage (DPCM, run lengths, Huffman codes, bit
 packing; the Huffman decode and the inverse transform of decompress()) run in hand-written gfx950 kernels; the library's host
 entropy coder (C++) serves encode()-style callers that hold coefficients on the host, and streams the device decoder hands back
@@ -273,6 +280,85 @@ def entropy_encode(coeffs_zz, height, width, quality):
         raise KeyError("coefficient magnitude has no Huffman code")
     if rc != N.TIC_OK:
         raise N.NativeError(rc, "tic_entropy_encode failed")
+    return out[: n.value].tobytes()
+
+
+SCALED_SETTINGS = ("best", "high", "med", "low")  # encode.c:20-34; the header's quality field holds the index
+
+
+def _scaled_setting(quality):
+    """"best" | "high" | "med" | "low" or 0..3 -> 0..3 (ValueError for anything else; the reference program prints "Invalid quality factor")."""
+    if isinstance(quality, str):
+        if quality in SCALED_SETTINGS:
+            return SCALED_SETTINGS.index(quality)
+    elif isinstance(quality, (int, np.integer)) and not isinstance(quality, (bool, np.bool_)) and 0 <= int(quality) <= 3:
+        return int(quality)
+    raise ValueError("scaled-DCT quality must be one of %r or 0..3, not %r" % (SCALED_SETTINGS, quality))
+
+
+def _scaled_image(image):
+    img, h, w = _as_u8_image(image)  # 8-bit pixels only (ValueError otherwise), as compress_batch
+    if h % 8 or w % 8:
+        raise ValueError("Width and height must be multiples of 8")  # encode.c:37-39
+    return img, h, w
+
+
+def dctq_scaled(image, quality="med", ctx=None):
+    """Transform stage of the reference's integer encoder (IMG_fdct + IMG_quantize, img.c:47-125, 194-205) on the GPU, in the device
+    layout: int16 [N, 64], zig-zag order, DC not differenced."""
+    img, h, w = _scaled_image(image)
+    qf = _scaled_setting(quality)
+    L = N.load()
+    n = L.tic_num_blocks(h, w)
+    zz = np.zeros((n, 64), dtype=np.int16)
+    if n:
+        ctx = _ctx(ctx)
+        with ctx.lock:
+            ctx.check(L.tic_dctq_scaled(ctx.handle, img.ctypes.data, h, w, img.strides[0], qf, zz.ctypes.data))
+    return zz
+
+
+def compress_scaled(image, quality="med", ctx=None):
+    """The stream of the reference's integer encoder (c/img.c: IMG_init, IMG_encodeHeader, IMG_encodeBlock per block,
+    IMG_encodeComplete), byte for byte; every stage on the GPU.  quality: "best" | "high" | "med" | "low" or 0..3 (default as
+    encode.c:33).  KeyError when a coefficient has no Huffman code (|AC| > 1023, possible at "best" only: the C encoder reads past its
+    table there)."""
+    img, h, w = _scaled_image(image)
+    qf = _scaled_setting(quality)
+    ctx = _ctx(ctx)
+    L = N.load()
+    cap = L.tic_compress_scaled_bound(h, w)
+    with ctx.lock:
+        out = getattr(ctx, "_out_buf", None)  # compress()'s landing buffer
+        if out is None or out.size < cap:
+            out = ctx._out_buf = np.empty(cap, dtype=np.uint8)
+        n = C.c_size_t(0)
+        rc = L.tic_compress_scaled(ctx.handle, img.ctypes.data, h, w, img.strides[0] if img.size else max(w, 1), qf, out.ctypes.data, cap, C.byref(n))
+        if rc == N.TIC_E_RANGE:
+            raise KeyError("coefficient magnitude has no Huffman code")
+        ctx.check(rc)
+        return out[: n.value].tobytes()
+
+
+def entropy_encode_scaled(coeffs_zz, height, width, quality):
+    """Host entropy stage of the integer encoder alone (no GPU needed): int16 [N, 64] zig-zag coefficients -> stream bytes."""
+    L = N.load()
+    height, width = int(height), int(width)
+    qf = _scaled_setting(quality)
+    if height < 0 or width < 0 or height % 8 or width % 8:
+        raise ValueError("Width and height must be multiples of 8")
+    zz = np.ascontiguousarray(coeffs_zz, dtype=np.int16)
+    nb = L.tic_num_blocks(height, width)
+    if zz.size != nb * 64:
+        raise ValueError("coefficients of shape %r do not match %d blocks of 64" % (zz.shape, nb))
+    cap = L.tic_compress_scaled_bound(height, width)
+    out = np.empty(cap, dtype=np.uint8)
+    n = C.c_size_t(0)
+    rc = L.tic_entropy_encode_scaled(zz.ctypes.data, height, width, qf, out.ctypes.data, cap, C.byref(n))
+    if rc == N.TIC_E_RANGE:
+        raise KeyError("coefficient magnitude has no Huffman code")
+    if rc != N.TIC_OK:
+        raise N.NativeError(rc, "tic_entropy_encode_scaled failed")
     return out[: n.value].tobytes()
 
 

@@ -27,6 +27,7 @@
 #include "tic_hooks.h"
 #include "tic_kernels.h"
 #include "tic_math.h"
+#include "tic_scaled.h"
 
 using namespace tic;
 
@@ -1067,22 +1068,29 @@ int tic_parse_header(const uint8_t *data, size_t len, int *h, int *w, int *quali
 
 // Device entropy stage: coefficients in HBM -> finished stream in HBM.  Synchronous (the stream length is needed
 // on the host between the counting and the packing step).
-int tic_entropy_encode_dev(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, int quality, void *d_out, size_t cap,
-                           size_t *out_len) {
+// scaled: the stream of the reference's integer encoder (tic_entropy_gpu.h: flag 1 << 30, setting 0..3 in the quality field, flush byte).
+static int entropy_encode_dev_impl(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, int quality, void *d_out, size_t cap,
+                                   size_t *out_len, bool scaled) {
     TIC_LOCK(ctx);
     if (!ctx || !out_len) return TIC_E_ARG;
     if (h < 0 || w < 0) return set_err(ctx, TIC_E_ARG, "negative image size");
-    if (quality < 1 || quality > 99) return set_err(ctx, TIC_E_QUALITY, "quality %d outside 1..99", quality);
-    if (!d_out || cap < 16) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
+    if (scaled) {
+        if (quality < 0 || quality > 3) return set_err(ctx, TIC_E_QUALITY, "scaled-DCT setting %d outside 0..3", quality);
+    } else if (quality < 1 || quality > 99)
+        return set_err(ctx, TIC_E_QUALITY, "quality %d outside 1..99", quality);
+    if (!d_out || cap < (scaled ? 17u : 16u)) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
     if (((uintptr_t)d_out & 15u) != 0) return set_err(ctx, TIC_E_ARG, "device output buffer must be 16-byte aligned");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t n = num_blocks(h, w);
     if (n == 0) {
-        uint8_t hdr[16];
-        write_header(hdr, h, w, quality);
-        HIPCHK(ctx, hipMemcpyAsync(d_out, hdr, 16, hipMemcpyHostToDevice, ctx->stream));
+        uint8_t hdr[17] = {0};
+        if (scaled)
+            write_header_scaled(hdr, h, w, quality); // ... and BB_flushBits with nothing pending: hdr[16] = 0
+        else
+            write_header(hdr, h, w, quality);
+        HIPCHK(ctx, hipMemcpyAsync(d_out, hdr, scaled ? 17 : 16, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        *out_len = 16;
+        *out_len = scaled ? 17 : 16;
         return TIC_OK;
     }
     if (!d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "null coefficient pointer");
@@ -1095,11 +1103,13 @@ int tic_entropy_encode_dev(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, 
     unsigned long long total_bits = 0;
     int err = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
-        const int mode = (attempt == 0 && quality <= ctx->ent_lane_max_quality) ? kEntropyLanePerBlock : kEntropyEightLanes;
+        // (a scaled-DCT stream always takes the 8-lane kernel, which has no limit per block: the lane kernel's limit is learnt per quality)
+        const int mode = (attempt == 0 && !scaled && quality <= ctx->ent_lane_max_quality) ? kEntropyLanePerBlock : kEntropyEightLanes;
         const int par = ctx->ent_parity;
         ctx->ent_parity ^= 1;
         HIPCHK(ctx, entropy_gpu_fused((const int16_t *)d_coeffs_zz, n, 1, ctx->d_huff, ctx->d_ent_work, ctx->ent_work_bytes, d_out, 0,
-                                      cap_words, h, w, quality, nullptr, ctx->d_stat, ctx->d_err + par, ctx->d_err + (par ^ 1), mode, ctx->stream));
+                                      cap_words, h, w, quality, nullptr, ctx->d_stat, ctx->d_err + par, ctx->d_err + (par ^ 1), mode, ctx->stream,
+                                      nullptr, nullptr, scaled ? kFlagScaled : 0u));
         HIPCHK(ctx, wait_stream(ctx));
         total_bits = ((volatile unsigned long long *)ctx->h_stat)[0];
         err = (int)(((volatile unsigned long long *)ctx->h_stat)[1] & 0xffffffffull);
@@ -1107,11 +1117,16 @@ int tic_entropy_encode_dev(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, 
         ctx->ent_lane_max_quality = quality - 1; // a block of this frame needs more than a lane string holds: 8-lane kernel from here on
     }
     if (err == 1) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code (reference raises KeyError)");
-    const size_t payload = (size_t)((total_bits + 7) / 8);
+    const size_t payload = scaled ? (size_t)(total_bits / 8) + 1 : (size_t)((total_bits + 7) / 8); // (scaled: BB_flushBits' byte)
     if (err == 2 || 16 + payload > cap)
-        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed)", 16 + (size_t)((total_bits + 31) / 32) * 4);
+        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed)", 16 + (size_t)((payload + 3) / 4) * 4);
     *out_len = 16 + payload;
     return TIC_OK;
+}
+
+int tic_entropy_encode_dev(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, int quality, void *d_out, size_t cap,
+                           size_t *out_len) {
+    return entropy_encode_dev_impl(ctx, d_coeffs_zz, h, w, quality, d_out, cap, out_len, false);
 }
 
 // compress() with every stage on the device: transform kernels + device entropy stage; image and stream in HBM.
@@ -1284,6 +1299,183 @@ int tic_compress(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row
         HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_stream_buf, len, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
+    *out_len = len;
+    return TIC_OK;
+}
+
+// ---- the reference's integer encoder (c/img.c, c/encode.c): scaled-DCT streams ------------------------------------------------
+// Transform stage: fdctq_scaled_kernel (tic_scaled.hip).  Entropy stage: the packers and the host coder above with the stream's own
+// header and end (flag 1 << 30, setting 0..3, BB_flushBits' byte).
+static int check_scaled_geometry(tic_ctx *ctx, int h, int w, ptrdiff_t stride, int qf) {
+    if (!ctx) return TIC_E_ARG;
+    if (h < 0 || w < 0) return set_err(ctx, TIC_E_ARG, "negative image size %dx%d", h, w);
+    if ((h & 7) != 0 || (w & 7) != 0) return set_err(ctx, TIC_E_ARG, "the scaled-DCT encoder takes heights and widths that are multiples of 8 (encode.c:37), not %dx%d", h, w);
+    if (qf < 0 || qf > 3) return set_err(ctx, TIC_E_QUALITY, "scaled-DCT setting %d outside 0..3 (best, high, med, low)", qf);
+    if (h > 0 && w > 0 && stride < (ptrdiff_t)w) return set_err(ctx, TIC_E_ARG, "row stride %td < width %d", stride, w);
+    return TIC_OK;
+}
+
+static ScaledArgs make_scaled_args(const void *d_image, int h, int w, ptrdiff_t stride, int qf, void *d_out) {
+    ScaledArgs a;
+    a.img = (const uint8_t *)d_image;
+    a.out = (int16_t *)d_out;
+    a.stride = (long)stride;
+    a.bw = w / 8;
+    a.tiles_x = (a.bw + 7) / 8;
+    a.ntiles = (h / 8) * a.tiles_x;
+    a.qf = qf;
+    a.aligned8 = ((((uintptr_t)d_image) | (uintptr_t)stride) & 7) == 0;
+    a.nframes = 1;
+    a.frame_stride_in = 0;
+    a.frame_stride_out = 0;
+    return a;
+}
+
+size_t tic_compress_scaled_bound(int h, int w) { return compress_bound(h, w) + 1; }
+
+int tic_dctq_scaled_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, int qf, void *d_coeffs_zz) {
+    TIC_LOCK(ctx);
+    int rc = check_scaled_geometry(ctx, h, w, row_stride, qf);
+    if (rc) return rc;
+    if (h == 0 || w == 0) return TIC_OK;
+    if (!d_image || !d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "null device pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, launch_fdctq_scaled(make_scaled_args(d_image, h, w, row_stride, qf, d_coeffs_zz), ctx->stream));
+    return TIC_OK;
+}
+
+int tic_dctq_scaled_dev_frames(tic_ctx *ctx, const void *d_images, int nframes, int h, int w, ptrdiff_t row_stride, ptrdiff_t frame_stride,
+                               int qf, void *d_coeffs_zz, ptrdiff_t coeff_frame_stride) {
+    TIC_LOCK(ctx);
+    int rc = check_scaled_geometry(ctx, h, w, row_stride, qf);
+    if (rc) return rc;
+    if (nframes < 0) return set_err(ctx, TIC_E_ARG, "negative frame count");
+    if (h == 0 || w == 0 || nframes == 0) return TIC_OK;
+    if (!d_images || !d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "null device pointer");
+    if (nframes > 65535) return set_err(ctx, TIC_E_ARG, "at most 65535 frames per launch");
+    if (frame_stride < (ptrdiff_t)h * row_stride || coeff_frame_stride < (ptrdiff_t)(num_blocks(h, w) * 128))
+        return set_err(ctx, TIC_E_ARG, "frame strides smaller than one frame");
+    if ((coeff_frame_stride & 15) != 0) return set_err(ctx, TIC_E_ARG, "coefficient frame stride must be a multiple of 16");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ScaledArgs a = make_scaled_args(d_images, h, w, row_stride, qf, d_coeffs_zz);
+    a.aligned8 = a.aligned8 && ((frame_stride & 7) == 0);
+    a.nframes = nframes;
+    a.frame_stride_in = (long)frame_stride;
+    a.frame_stride_out = (long)coeff_frame_stride;
+    HIPCHK(ctx, launch_fdctq_scaled(a, ctx->stream));
+    return TIC_OK;
+}
+
+// tic_dctq_dev_timed_warm for the integer kernel: the same single submission (warm launches, event, timed launches, event) and the same
+// per-launch stamps, so that the two figures compare.
+int tic_dctq_scaled_dev_timed_warm(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, int qf, void *d_coeffs_zz, int warm,
+                                   int iters, float *ms_total, float *per_launch_ms) {
+    TIC_LOCK(ctx);
+    int rc = check_scaled_geometry(ctx, h, w, row_stride, qf);
+    if (rc) return rc;
+    if (!ms_total || iters < 1 || warm < 0 || !d_image || !d_coeffs_zz || h == 0 || w == 0) return set_err(ctx, TIC_E_ARG, "bad argument");
+    if (per_launch_ms && iters > 32768) return set_err(ctx, TIC_E_ARG, "per-launch times for at most 32768 launches");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const ScaledArgs a = make_scaled_args(d_image, h, w, row_stride, qf, d_coeffs_zz);
+    if (per_launch_ms)
+        while ((int)ctx->ev_steps.size() < 2 * iters) {
+            hipEvent_t e = nullptr;
+            HIPCHK(ctx, hipEventCreate(&e));
+            ctx->ev_steps.push_back(e);
+        }
+    for (int i = 0; i < warm; i++) HIPCHK(ctx, launch_fdctq_scaled(a, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    for (int i = 0; i < iters; i++) {
+        if (per_launch_ms)
+            HIPCHK(ctx, launch_fdctq_scaled(a, ctx->stream, ctx->ev_steps[2 * i], ctx->ev_steps[2 * i + 1]));
+        else
+            HIPCHK(ctx, launch_fdctq_scaled(a, ctx->stream));
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev1));
+    HIPCHK(ctx, hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));
+    if (per_launch_ms)
+        for (int i = 0; i < iters; i++) {
+            HIPCHK(ctx, hipEventElapsedTime(per_launch_ms + 2 * i, ctx->ev_steps[2 * i], ctx->ev_steps[2 * i + 1]));
+            HIPCHK(ctx, hipEventElapsedTime(per_launch_ms + 2 * i + 1, ctx->ev_steps[0], ctx->ev_steps[2 * i + 1]));
+        }
+    return TIC_OK;
+}
+
+int tic_dctq_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int qf, int16_t *coeffs_zz) {
+    TIC_LOCK(ctx);
+    int rc = check_scaled_geometry(ctx, h, w, row_stride, qf);
+    if (rc) return rc;
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return TIC_OK;
+    if (!image || !coeffs_zz) return set_err(ctx, TIC_E_ARG, "null host pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t pitch = align_up((size_t)w, 256);
+    rc = ensure_scratch(ctx, pitch * (size_t)h, n * 128);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_img, pitch, image, (size_t)row_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, launch_fdctq_scaled(make_scaled_args(ctx->d_img, h, w, (ptrdiff_t)pitch, qf, ctx->d_coef), ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(coeffs_zz, ctx->d_coef, n * 128, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TIC_OK;
+}
+
+int tic_entropy_encode_scaled(const int16_t *coeffs_zz, int h, int w, int qf, uint8_t *out, size_t cap, size_t *out_len) {
+    return entropy_encode_scaled(coeffs_zz, h, w, qf, out, cap, out_len);
+}
+
+// A buffer of at least tic_compress_scaled_bound() bytes receives the stream from the placing kernel itself.  A smaller one is never
+// handed to that kernel: the stream is placed in the context's own buffer and copied over only when it fits, so that TIC_E_SPACE leaves
+// the caller's buffer untouched and a stream that fits is written to its last byte and no further.
+int tic_compress_scaled_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, int qf, void *d_out, size_t cap,
+                            size_t *out_len) {
+    TIC_LOCK(ctx);
+    int rc = check_scaled_geometry(ctx, h, w, row_stride, qf);
+    if (rc) return rc;
+    if (!out_len) return set_err(ctx, TIC_E_ARG, "null length pointer");
+    if (!d_out || cap < 17) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
+    const size_t n = num_blocks(h, w);
+    if (n && !d_image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    rc = ensure_scratch(ctx, 0, n * 128 + 16);
+    if (rc) return rc;
+    rc = tic_dctq_scaled_dev(ctx, d_image, h, w, row_stride, qf, ctx->d_coef);
+    if (rc) return rc;
+    const size_t bound = tic_compress_scaled_bound(h, w);
+    if (cap >= bound || n == 0) return entropy_encode_dev_impl(ctx, ctx->d_coef, h, w, qf, d_out, cap, out_len, true);
+    rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, bound);
+    if (rc) return rc;
+    size_t len = 0;
+    rc = entropy_encode_dev_impl(ctx, ctx->d_coef, h, w, qf, ctx->d_stream_buf, ctx->d_stream_cap, &len, true);
+    if (rc) return rc;
+    if (len > cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", len, cap);
+    HIPCHK(ctx, hipMemcpyAsync(d_out, ctx->d_stream_buf, len, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *out_len = len;
+    return TIC_OK;
+}
+
+int tic_compress_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int qf, uint8_t *out, size_t cap,
+                        size_t *out_len) {
+    TIC_LOCK(ctx);
+    int rc = check_scaled_geometry(ctx, h, w, row_stride, qf);
+    if (rc) return rc;
+    if (!out || !out_len) return set_err(ctx, TIC_E_ARG, "null output pointer");
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return entropy_encode_scaled(nullptr, h, w, qf, out, cap, out_len);
+    if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t pitch = align_up((size_t)w, 256);
+    rc = ensure_scratch(ctx, pitch * (size_t)h, n * 128 + 16);
+    if (rc) return rc;
+    rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, tic_compress_scaled_bound(h, w));
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_img, pitch, image, (size_t)row_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    size_t len = 0;
+    rc = tic_compress_scaled_dev(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, qf, ctx->d_stream_buf, ctx->d_stream_cap, &len);
+    if (rc) return rc;
+    if (len > cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", len, cap);
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_stream_buf, len, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     *out_len = len;
     return TIC_OK;
 }

@@ -155,13 +155,24 @@ void write_header(uint8_t *out, int h, int w, int quality) {
     memset(out + 12, 0, 4);                                                         // flag 0: default tables
 }
 
-int entropy_encode(const int16_t *zz, int h, int w, int quality, uint8_t *out, size_t cap, size_t *out_len) {
+namespace {
+// scaled: a stream of the reference's integer encoder (c/img.c) - same symbols, same tables; the header carries the setting 0..3 and
+// flag 1 << 30 (IMG_encodeHeader, img.c:183-192), and the stream ends as BB_flushBits ends it (img.h:36-40): one byte with the pending
+// bits behind the last whole byte, written also when nothing is pending.
+int entropy_encode_impl(const int16_t *zz, int h, int w, int quality, uint8_t *out, size_t cap, size_t *out_len, bool scaled) {
     if (!out || !out_len || (!zz && num_blocks(h, w))) return TIC_E_ARG;
     if (h < 0 || w < 0) return TIC_E_ARG;
-    if (quality < 1 || quality > 99) return TIC_E_QUALITY;
-    if (cap < 16) return TIC_E_SPACE;
+    if (scaled) {
+        if ((h & 7) != 0 || (w & 7) != 0) return TIC_E_ARG; // encode.c:37
+        if (quality < 0 || quality > 3) return TIC_E_QUALITY;
+        if (cap < 17) return TIC_E_SPACE;
+    } else {
+        if (quality < 1 || quality > 99) return TIC_E_QUALITY;
+        if (cap < 16) return TIC_E_SPACE;
+    }
     const EncTables &T = tables();
     write_header(out, h, w, quality);
+    if (scaled) out[15] = 0x40; // little-endian 1 << 30
     BitWriter bw(out + 16, out + cap);
     const size_t n = num_blocks(h, w);
     int prev_dc = 0;
@@ -203,10 +214,29 @@ int entropy_encode(const int16_t *zz, int h, int w, int quality, uint8_t *out, s
         bw.put(T.ac_code[0], T.ac_len[0]); // EOB
         if (bw.overflow) return TIC_E_SPACE;
     }
+    const bool pending = (bw.nacc & 7) != 0;
     bw.finish();
+    if (scaled && !pending && !bw.overflow) { // BB_flushBits with nothing pending: a zero byte
+        if (bw.p >= bw.end) return TIC_E_SPACE;
+        *bw.p++ = 0;
+    }
     if (bw.overflow) return TIC_E_SPACE;
     *out_len = (size_t)(bw.p - out);
     return TIC_OK;
+}
+} // namespace
+
+int entropy_encode(const int16_t *zz, int h, int w, int quality, uint8_t *out, size_t cap, size_t *out_len) {
+    return entropy_encode_impl(zz, h, w, quality, out, cap, out_len, false);
+}
+
+int entropy_encode_scaled(const int16_t *zz, int h, int w, int qf, uint8_t *out, size_t cap, size_t *out_len) {
+    return entropy_encode_impl(zz, h, w, qf, out, cap, out_len, true);
+}
+
+void write_header_scaled(uint8_t *out, int h, int w, int qf) {
+    write_header(out, h, w, qf);
+    out[15] = 0x40; // little-endian 1 << 30 (img.c:185)
 }
 
 int parse_header(const uint8_t *data, size_t len, int *h, int *w, int *quality, uint32_t *flag) {

@@ -8,6 +8,10 @@ size_t num_blocks(int h, int w);
 size_t compress_bound(int h, int w);
 void write_header(uint8_t *out, int h, int w, int quality);
 int entropy_encode(const int16_t *zz, int h, int w, int quality, uint8_t *out, size_t cap, size_t *out_len);
+// The same for a stream of the reference's integer encoder (c/img.c): quality field = setting 0..3, flag 1 << 30, one flush byte more
+// (BB_flushBits); h and w multiples of 8.
+void write_header_scaled(uint8_t *out, int h, int w, int qf);
+int entropy_encode_scaled(const int16_t *zz, int h, int w, int qf, uint8_t *out, size_t cap, size_t *out_len);
 int parse_header(const uint8_t *data, size_t len, int *h, int *w, int *quality, uint32_t *flag);
 // Huffman + run-length decode into int16 [N][64] zig-zag with the DC already integrated (np.cumsum).
 int entropy_decode(const uint8_t *data, size_t len, int h, int w, int16_t *zz);

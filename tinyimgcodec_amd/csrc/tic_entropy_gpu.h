@@ -31,8 +31,11 @@ size_t entropy_fused_work_bytes(size_t nblocks_total);
 hipError_t entropy_gpu_fused(const int16_t *d_zz, size_t blocks_per_frame, int nframes, const HuffDev *d_tab, void *d_work,
                              size_t work_bytes, void *d_out, size_t out_frame_stride, size_t cap_words, int h, int w, int quality,
                              unsigned long long *d_lens, unsigned long long *d_status, int *d_err, int *d_err_next, int mode,
-                             hipStream_t stream, hipStream_t place_stream = nullptr, hipEvent_t pack_done = nullptr);
+                             hipStream_t stream, hipStream_t place_stream = nullptr, hipEvent_t pack_done = nullptr, uint32_t flag = 0);
 // place_stream (with pack_done, an event of the caller's): the placing kernel - the stage's only writer of d_out, d_lens, d_status and
 // *d_err_next - is queued on place_stream behind the packing on `stream`; the packing of the NEXT frame may then run on `stream` beside it.
+// flag: the header's fourth word.  0 = a default-table stream (payload zero-padded to a byte, codec.py:102-114).  1 << 30 = a stream of the
+// reference's integer encoder (img.c:183-192): `quality` is its setting 0..3 and the payload ends as BB_flushBits ends it (img.h:36-40) -
+// floor(bits / 8) whole bytes and ONE more byte with the pending bits, a zero byte when there are none; lengths and the fit test count it.
 
 } // namespace tic

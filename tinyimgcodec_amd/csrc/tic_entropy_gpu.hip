@@ -710,7 +710,7 @@ __global__ __launch_bounds__(256) void entropy_place_kernel(const uint32_t *__re
                                                             unsigned char *__restrict__ out, unsigned long long out_frame_stride,
                                                             unsigned long long cap_words, int h, int w, int quality,
                                                             unsigned long long *__restrict__ lens, int *__restrict__ err_flag,
-                                                            int *__restrict__ err_next, unsigned long long *__restrict__ status) {
+                                                            int *__restrict__ err_next, unsigned long long *__restrict__ status, uint32_t flag) {
     constexpr int kN = kPlace + 3;             // its own partitions and the three behind them (the last word may run into those)
     constexpr int kPer = (kN + 3) / 4;         // slots a wave fetches
     __shared__ uint32_t roff[kN + 1]; // first bit of partition p0 + i, counted from bit 0 of word base_word (empty past the frame's end)
@@ -854,9 +854,15 @@ __global__ __launch_bounds__(256) void entropy_place_kernel(const uint32_t *__re
         hdr[0] = (uint32_t)h; // struct.pack("III") little-endian == native order here
         hdr[1] = (uint32_t)w;
         hdr[2] = (uint32_t)quality;
-        hdr[3] = 0u;
-        if (lens) lens[frame] = 16ull + (frame_bits + 7ull) / 8ull;
-        const bool over = ((frame_bits + 31ull) >> 5) > cap_words;
+        hdr[3] = flag; // 0: default tables (codec.py:111); 1 << 30: a scaled-DCT stream (img.c:185)
+        // a scaled-DCT stream ends as BB_flushBits ends it (img.h:36-40): ONE more byte behind the last whole byte, the pending bits
+        // zero-padded - a zero byte when the payload ends on a byte boundary.  The words the partitions wrote are zero-padded already;
+        // only a payload of whole words has its flush byte in a word nobody wrote.
+        const bool flush = flag == (1u << 30);
+        const unsigned long long bytes = flush ? (frame_bits >> 3) + 1ull : (frame_bits + 7ull) >> 3;
+        if (lens) lens[frame] = 16ull + bytes;
+        const bool over = ((bytes + 3ull) >> 2) > cap_words;
+        if (flush && !over && (frame_bits & 31ull) == 0ull) store_u32_wt(reinterpret_cast<uint32_t *>(out + frame * out_frame_stride + 16) + (frame_bits >> 5), 0u);
         if (over) atomicMax(err_flag, 2);
         if (frame == 0ull) {
             *err_next = 0; // the flag the NEXT call uses (two flags in turn: no memset between calls)
@@ -887,7 +893,7 @@ size_t entropy_fused_work_bytes(size_t nblocks_total) {
 hipError_t entropy_gpu_fused(const int16_t *d_zz, size_t blocks_per_frame, int nframes, const HuffDev *d_tab, void *d_work,
                              size_t work_bytes, void *d_out, size_t out_frame_stride, size_t cap_words, int h, int w, int quality,
                              unsigned long long *d_lens, unsigned long long *d_status, int *d_err, int *d_err_next, int mode,
-                             hipStream_t stream, hipStream_t place_stream, hipEvent_t pack_done) {
+                             hipStream_t stream, hipStream_t place_stream, hipEvent_t pack_done, uint32_t flag) {
     if (blocks_per_frame == 0 || nframes <= 0) return hipSuccess;
     const bool lane_form = mode == kEntropyLanePerBlock;
     const size_t part_blocks = lane_form ? (size_t)kPB : 8, grp = lane_form ? (size_t)kGroupL : (size_t)kGroup;
@@ -971,7 +977,7 @@ hipError_t entropy_gpu_fused(const int16_t *d_zz, size_t blocks_per_frame, int n
 #define TIC_PLACE_ARGS                                                                                                                     \
     dim3((unsigned)(places_per_frame * (size_t)nframes)), dim3(256), 0, stream, stage, nbits, gsum, tile_sum, (unsigned long long)parts_per_frame, \
         (unsigned long long)groups_per_frame, (unsigned long long)places_per_frame, (unsigned long long)tiles_per_frame, (unsigned char *)d_out,   \
-        (unsigned long long)out_frame_stride, (unsigned long long)cap_words, h, w, quality, d_lens, d_err, d_err_next, d_status
+        (unsigned long long)out_frame_stride, (unsigned long long)cap_words, h, w, quality, d_lens, d_err, d_err_next, d_status, flag
     if (lane_form) {
         hipLaunchKernelGGL((entropy_place_kernel<0, 8, kGroupL, PackL<kLaneW>::kStageWords, false>), TIC_PLACE_ARGS);
     } else {
