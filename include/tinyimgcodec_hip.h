@@ -192,6 +192,50 @@ int tic_async_result(tic_ctx *ctx, long long ticket, int wait, size_t *out_len);
 int tic_compress(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int quality, uint8_t *out,
                  size_t cap, size_t *out_len);
 
+/* ---- rate control: how large a stream would be, and the best quality within a byte budget ------------------------------
+ *      No counterpart in the reference, where a size is len(compress(image, q)) (codec.py:133-164; tests/benchmark.py tabulates
+ *      six of them per image).  The length of a default-table stream (flag 0) is a function of the coefficients alone: the code
+ *      lengths of encode_huffman (huffman.py:41-63) summed - DC category code + category bits, ZRLs, (run, size) code + size bits,
+ *      the EOB that closes every block (huffman.py:12-33) - rounded up to a byte (bitbuffer.py:17-18), plus the 16-byte header. */
+/* The length tic_entropy_encode would write for these coefficients (same layout: int16 [N][64] zig-zag, absolute DC), from a walk
+ * that only sums lengths; TIC_E_RANGE exactly where tic_entropy_encode returns it.  Host, no GPU. */
+int tic_entropy_size(const int16_t *coeffs_zz, int h, int w, size_t *bytes);
+/* The same for coefficients resident in device memory, by the size kernel: one read of the coefficients, no workspace, nothing
+ * written but the result.  Synchronous.  Equals the out_len of tic_entropy_encode_dev for the same buffer. */
+int tic_entropy_size_dev(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, size_t *bytes);
+/* Times the size kernel alone: `warm` untimed launches, an event, `iters` timed launches, an event, one submission (as
+ * tic_dctq_dev_timed_warm); *ms_total = elapsed milliseconds for the `iters` launches. */
+int tic_entropy_size_dev_timed(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, int warm, int iters, float *ms_total);
+/* sizes[i] = the length tic_compress_dev would report at qualities[i], or -1 where it would return TIC_E_RANGE - without writing a
+ * stream: per quality the transform into a workspace of the context and the size kernel, all queued on the context's stream with
+ * no host wait in between, then one read-back of the nq results.  A quality outside 1..99 gives TIC_E_QUALITY before anything is
+ * queued. */
+int tic_stream_sizes_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq,
+                         long long *sizes);
+/* ... for an image in host memory: one upload, then the above. */
+int tic_stream_sizes(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq,
+                     long long *sizes);
+/* The stream of the quality this bisection ends at, where fits(q) means "tic_compress_dev at q succeeds with a length <= max_bytes":
+ *     if not fits(qmin): fail
+ *     lo, hi = qmin, qmax
+ *     while lo < hi: mid = (lo + hi + 1) / 2;  if fits(mid): lo = mid  else: hi = mid - 1
+ *     *quality = lo
+ * Where sizes do not decrease with the quality (every image measured so far; no theorem) that is the largest fitting quality of the
+ * range; a quality without a code (TIC_E_RANGE) counts as not fitting.  On success d_out holds exactly the *out_len bytes
+ * tic_compress_dev(..., lo, ...) produces, and no byte behind them is written.  Failures write nothing to d_out: qmin fits no code
+ * TIC_E_RANGE; qmin is too large TIC_E_SPACE with *out_len = its length; the stream does not fit cap TIC_E_SPACE with *out_len = its
+ * length (cap < 16: TIC_E_SPACE at once); qmin > qmax or either outside 1..99 TIC_E_QUALITY.  The search probes with
+ * tic_stream_sizes_dev's machinery and may probe ahead - the middles of the next two or three steps in one submission - so the host
+ * waits a few times, not once per step; the result is the bisection's. */
+int tic_compress_to_size_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, size_t max_bytes, int qmin, int qmax,
+                             void *d_out, size_t cap, size_t *out_len, int *quality);
+/* ... with image and stream in host memory. */
+int tic_compress_to_size(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, size_t max_bytes, int qmin, int qmax,
+                         uint8_t *out, size_t cap, size_t *out_len, int *quality);
+/* What the context's last tic_compress_to_size[_dev] did (either pointer may be null): qualities probed, and times the host waited
+ * for the device (the probe submissions plus the one for the final stream). */
+int tic_last_rate_search(tic_ctx *ctx, int *probes, int *host_waits);
+
 /* Batch of n independent frames of identical geometry (BASELINE config 3): pinned staging buffers, two HIP
  * streams (the H2D copy of chunk c+1 overlaps the kernels of chunk c and the read-back of chunk c-1).
  * threads <= 0: entropy stage on the device (only finished streams cross PCIe); threads > 0: coefficients are

@@ -112,6 +112,22 @@ SIGNATURES = {
         C.c_int,
         [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
     ),
+    "tic_entropy_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "tic_entropy_size_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "tic_entropy_size_dev_timed": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "tic_stream_sizes_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "tic_stream_sizes": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "tic_compress_to_size_dev": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+         C.POINTER(C.c_int)],
+    ),
+    "tic_compress_to_size": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+         C.POINTER(C.c_int)],
+    ),
+    "tic_last_rate_search": (C.c_int, [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tic_compress_batch": (
         C.c_int,
         [_ctxp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.POINTER(C.c_void_p),

@@ -283,6 +283,89 @@ def entropy_encode(coeffs_zz, height, width, quality):
     return out[: n.value].tobytes()
 
 
+def entropy_size(coeffs_zz, height, width):
+    """len(entropy_encode(coeffs_zz, height, width, q)) for any quality, from a walk that only sums code lengths (no GPU needed).
+    KeyError where entropy_encode raises it."""
+    L = N.load()
+    height, width = int(height), int(width)
+    zz = np.ascontiguousarray(coeffs_zz, dtype=np.int16)
+    if height < 0 or width < 0:
+        raise ValueError("negative image size")
+    nb = L.tic_num_blocks(height, width)
+    if zz.size != nb * 64:
+        raise ValueError("coefficients of shape %r do not match %d blocks of 64" % (zz.shape, nb))
+    n = C.c_size_t(0)
+    rc = L.tic_entropy_size(zz.ctypes.data, height, width, C.byref(n))
+    if rc == N.TIC_E_RANGE:
+        raise KeyError("coefficient magnitude has no Huffman code")
+    if rc != N.TIC_OK:
+        raise N.NativeError(rc, "tic_entropy_size failed")
+    return int(n.value)
+
+
+def compressed_sizes(image, qualities, ctx=None):
+    """len(compress(image, q)) for every q of `qualities` -> int64 array, -1 where compress() would raise KeyError for a coefficient
+    without a Huffman code.  No stream is produced: per quality the transform and a size kernel that reads the coefficients once, all
+    queued without a host wait in between, one read-back.  8-bit images only (ValueError otherwise, as compress_batch); an invalid
+    quality raises what compress() raises for it, before any GPU work."""
+    img, h, w = _as_u8_image(image)
+    qs = [_check_quality(q, packs_header=True) for q in qualities]
+    sizes = np.zeros(len(qs), dtype=np.int64)
+    if not qs:
+        return sizes
+    ctx = _ctx(ctx)
+    qarr = np.asarray(qs, dtype=np.intc)
+    with ctx.lock:
+        ctx.check(N.load().tic_stream_sizes(ctx.handle, img.ctypes.data, h, w, img.strides[0] if img.size else max(w, 1), qarr.ctypes.data, len(qs),
+                                            sizes.ctypes.data))
+    return sizes
+
+
+def compressed_size(image, quality=50, ctx=None):
+    """len(compress(image, quality)) without producing the stream; the same exceptions for the same arguments."""
+    size = int(compressed_sizes(image, [quality], ctx=ctx)[0])
+    if size < 0:
+        raise KeyError("coefficient magnitude has no Huffman code")  # as the reference's dict lookup
+    return size
+
+
+def compress_to_size(image, max_bytes, min_quality=1, max_quality=99, ctx=None):
+    """The best stream within a byte budget -> (bytes, quality): compress(image, quality) of the quality at which a bisection over
+    min_quality..max_quality ends, with "compress() succeeds and len(...) <= max_bytes" as its test -
+
+        lo, hi = min_quality, max_quality
+        while lo < hi: mid = (lo + hi + 1) // 2;  lo = mid if fits(mid) else hi = mid - 1
+
+    which is the largest fitting quality wherever sizes do not decrease with the quality (observed on every image tried; a quality at
+    which a coefficient has no Huffman code counts as not fitting).  The probes run on the GPU without producing streams
+    (compressed_sizes) and several steps ahead per submission.  ValueError naming the size at min_quality when even that exceeds the
+    budget, KeyError when min_quality has a coefficient without a code; 8-bit images only."""
+    img, h, w = _as_u8_image(image)
+    qmin = _check_quality(min_quality, packs_header=True)
+    qmax = _check_quality(max_quality, packs_header=True)
+    if qmin > qmax:
+        raise ValueError("min_quality %d above max_quality %d" % (qmin, qmax))
+    max_bytes = int(max_bytes)
+    if max_bytes < 0:
+        raise ValueError("max_bytes must not be negative")
+    ctx = _ctx(ctx)
+    L = N.load()
+    cap = L.tic_compress_bound(h, w)
+    with ctx.lock:
+        out = getattr(ctx, "_out_buf", None)  # compress()'s landing buffer
+        if out is None or out.size < cap:
+            out = ctx._out_buf = np.empty(cap, dtype=np.uint8)
+        n, q = C.c_size_t(0), C.c_int(0)
+        rc = L.tic_compress_to_size(ctx.handle, img.ctypes.data, h, w, img.strides[0] if img.size else max(w, 1), max_bytes, qmin, qmax,
+                                    out.ctypes.data, cap, C.byref(n), C.byref(q))
+        if rc == N.TIC_E_RANGE:
+            raise KeyError("coefficient magnitude has no Huffman code")
+        if rc == N.TIC_E_SPACE:
+            raise ValueError("%d bytes at quality %d exceed max_bytes = %d" % (n.value, qmin, max_bytes))
+        ctx.check(rc)
+        return out[: n.value].tobytes(), int(q.value)
+
+
 SCALED_SETTINGS = ("best", "high", "med", "low")  # encode.c:20-34; the header's quality field holds the index
 
 

@@ -28,6 +28,7 @@
 #include "tic_kernels.h"
 #include "tic_math.h"
 #include "tic_scaled.h"
+#include "tic_size_gpu.h"
 
 using namespace tic;
 
@@ -247,6 +248,12 @@ struct tic_ctx {
     AdaptDecStatus *d_adec_status = nullptr;
     void *d_adec_work = nullptr;
     size_t adec_work_bytes = 0;
+    // rate control (tic_stream_sizes_dev, tic_compress_to_size_dev): the size kernel's table, a result per probe on the device and its
+    // pinned landing buffer, and what the last search did
+    SizeTabDev *d_size_tab = nullptr;
+    SizeResult *d_rate = nullptr, *h_rate = nullptr;
+    size_t rate_dev_bytes = 0, rate_host_bytes = 0;
+    int last_rate_probes = 0, last_rate_waits = 0;
 };
 
 // NUMA node of a device (its PCI function's numa_node in sysfs) and the CPUs of that node within this process's affinity mask.
@@ -481,6 +488,9 @@ void tic_destroy(tic_ctx *ctx) {
     if (ctx->d_adapt_out) (void)hipFree(ctx->d_adapt_out);
     if (ctx->d_adec_tab) (void)hipFree(ctx->d_adec_tab); // the status words live in the same block
     if (ctx->d_adec_work) (void)hipFree(ctx->d_adec_work);
+    if (ctx->d_size_tab) (void)hipFree(ctx->d_size_tab);
+    if (ctx->d_rate) (void)hipFree(ctx->d_rate);
+    if (ctx->h_rate) (void)hipHostFree(ctx->h_rate);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1062,6 +1072,8 @@ int tic_entropy_encode(const int16_t *coeffs_zz, int h, int w, int quality, uint
     return entropy_encode(coeffs_zz, h, w, quality, out, cap, out_len);
 }
 
+int tic_entropy_size(const int16_t *coeffs_zz, int h, int w, size_t *bytes) { return entropy_size(coeffs_zz, h, w, bytes); }
+
 int tic_parse_header(const uint8_t *data, size_t len, int *h, int *w, int *quality, uint32_t *flag) {
     return parse_header(data, len, h, w, quality, flag);
 }
@@ -1300,6 +1312,281 @@ int tic_compress(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     *out_len = len;
+    return TIC_OK;
+}
+
+// ---- rate control: the size of a stream without the stream, and the best quality within a byte budget -----------------------------
+// (No counterpart in the reference, whose only way to a size is len(compress(image, q)), codec.py:133-164; its benchmark is a table of
+// such sizes, tests/benchmark.py.)  A PROBE of quality q is the transform into the context's coefficient workspace followed by the
+// size kernel (tic_size_gpu.hip) adding into the probe's SizeResult: two launches, nothing staged, nothing placed, no stream byte
+// written.  Any number of probes are queued back to back on the context's stream - they share the workspace, the stream orders them -
+// and come back in ONE copy.
+static int ensure_rate(tic_ctx *ctx, size_t nres) {
+    if (!ctx->d_size_tab) {
+        SizeTabDev t, *d = nullptr;
+        build_size_tab(&t);
+        HIPCHK(ctx, hipMalloc((void **)&d, sizeof t));
+        const hipError_t e = hipMemcpy(d, &t, sizeof t, hipMemcpyHostToDevice);
+        if (e != hipSuccess) (void)hipFree(d);
+        HIPCHK(ctx, e);
+        ctx->d_size_tab = d;
+    }
+    const size_t need = nres * sizeof(SizeResult), alloc = align_up(need, 4096);
+    const int rc = grow_dev(ctx, ctx->d_rate, ctx->rate_dev_bytes, need, alloc);
+    return rc ? rc : grow_pinned(ctx, ctx->h_rate, ctx->rate_host_bytes, need, alloc);
+}
+
+// Queues the probes of q[0 .. nq) and the copy of their results into ctx->h_rate; the caller waits for the stream.
+static int queue_probes(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, size_t n, const int *q, int nq) {
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_rate, 0, (size_t)nq * sizeof(SizeResult), ctx->stream));
+    for (int i = 0; i < nq; i++) {
+        DctqArgs a = make_args(ctx, d_image, h, w, row_stride, q[i], ctx->d_coef);
+        HIPCHK(ctx, launch_dctq(a, dctq_kernel_id(TIC_KERNEL_AUTO), ctx->stream));
+        HIPCHK(ctx, stream_size_gpu((const int16_t *)ctx->d_coef, n, 1, ctx->d_size_tab, ctx->d_rate + i, ctx->stream));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_rate, ctx->d_rate, (size_t)nq * sizeof(SizeResult), hipMemcpyDeviceToHost, ctx->stream));
+    return TIC_OK;
+}
+
+// Stream length of a probe: 16-byte header + the payload rounded up to a byte (bitbuffer.py:17-18); -1: a coefficient without a code.
+static inline long long probe_size(const SizeResult &r) { return r.nocode ? -1ll : (long long)(16ull + ((r.bits + 7ull) >> 3)); }
+
+int tic_entropy_size_dev(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, size_t *bytes) {
+    TIC_LOCK(ctx);
+    if (!ctx || !bytes) return TIC_E_ARG;
+    if (h < 0 || w < 0) return set_err(ctx, TIC_E_ARG, "negative image size");
+    const size_t n = num_blocks(h, w);
+    if (n == 0) {
+        *bytes = 16;
+        return TIC_OK;
+    }
+    if (!d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "null coefficient pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int rc = ensure_rate(ctx, 1);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_rate, 0, sizeof(SizeResult), ctx->stream));
+    HIPCHK(ctx, stream_size_gpu((const int16_t *)d_coeffs_zz, n, 1, ctx->d_size_tab, ctx->d_rate, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_rate, ctx->d_rate, sizeof(SizeResult), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream(ctx));
+    const long long s = probe_size(ctx->h_rate[0]);
+    if (s < 0) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code (reference raises KeyError)");
+    *bytes = (size_t)s;
+    return TIC_OK;
+}
+
+// Times `iters` back-to-back launches of the size kernel on resident coefficients, behind `warm` untimed ones, with HIP events on the
+// context's stream, all in one submission (as tic_dctq_dev_timed_warm).  *ms_total = elapsed milliseconds for the `iters` launches.
+int tic_entropy_size_dev_timed(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, int warm, int iters, float *ms_total) {
+    TIC_LOCK(ctx);
+    if (!ctx || !ms_total || warm < 0 || iters <= 0) return TIC_E_ARG;
+    if (h < 0 || w < 0) return set_err(ctx, TIC_E_ARG, "negative image size");
+    const size_t n = num_blocks(h, w);
+    if (n && !d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "null coefficient pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int rc = ensure_rate(ctx, 1);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_rate, 0, sizeof(SizeResult), ctx->stream));
+    for (int i = 0; i < warm; i++) HIPCHK(ctx, stream_size_gpu((const int16_t *)d_coeffs_zz, n, 1, ctx->d_size_tab, ctx->d_rate, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    for (int i = 0; i < iters; i++) HIPCHK(ctx, stream_size_gpu((const int16_t *)d_coeffs_zz, n, 1, ctx->d_size_tab, ctx->d_rate, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev1));
+    HIPCHK(ctx, hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));
+    return TIC_OK;
+}
+
+static int check_size_args(tic_ctx *ctx, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq, long long *sizes) {
+    if (!ctx) return TIC_E_ARG;
+    if (nq < 0 || (nq > 0 && (!qualities || !sizes))) return set_err(ctx, TIC_E_ARG, "bad quality list");
+    for (int i = 0; i < nq; i++) {
+        const int rc = check_stream_geometry(ctx, h, w, row_stride, qualities[i]);
+        if (rc) return rc;
+    }
+    return TIC_OK;
+}
+
+int tic_stream_sizes_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq,
+                         long long *sizes) {
+    TIC_LOCK(ctx);
+    int rc = check_size_args(ctx, h, w, row_stride, qualities, nq, sizes); // (a bad quality fails here: nothing has been queued)
+    if (rc || nq == 0) return rc;
+    const size_t n = num_blocks(h, w);
+    if (n == 0) { // header only (codec.py:151)
+        for (int i = 0; i < nq; i++) sizes[i] = 16;
+        return TIC_OK;
+    }
+    if (!d_image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    rc = ensure_scratch(ctx, 0, n * 128 + 16);
+    if (rc) return rc;
+    rc = ensure_rate(ctx, (size_t)nq);
+    if (rc) return rc;
+    rc = queue_probes(ctx, d_image, h, w, row_stride, n, qualities, nq);
+    if (rc) return rc;
+    HIPCHK(ctx, wait_stream(ctx));
+    for (int i = 0; i < nq; i++) sizes[i] = probe_size(ctx->h_rate[i]);
+    return TIC_OK;
+}
+
+// The host-image forms upload the frame into the context's scratch image as tic_compress does (rows padded to 256 bytes).
+static int upload_image(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, size_t n, size_t *pitch) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    *pitch = align_up((size_t)w, 256);
+    const int rc = ensure_scratch(ctx, *pitch * (size_t)h, n * 128 + 16);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_img, *pitch, image, (size_t)row_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    return TIC_OK;
+}
+
+int tic_stream_sizes(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq, long long *sizes) {
+    TIC_LOCK(ctx);
+    int rc = check_size_args(ctx, h, w, row_stride, qualities, nq, sizes);
+    if (rc || nq == 0) return rc;
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return tic_stream_sizes_dev(ctx, nullptr, h, w, row_stride, qualities, nq, sizes);
+    if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    size_t pitch = 0;
+    rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
+    if (rc) return rc;
+    return tic_stream_sizes_dev(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, qualities, nq, sizes);
+}
+
+// The search.  Its contract is the bisection of the header (tic_compress_to_size_dev); what is free is WHEN a quality is probed.  One
+// submission probes every middle the bisection can reach within `depth` further steps from where it stands (2^depth - 1 probes, the
+// first one qmin as well), then the bisection is replayed over the known sizes as far as they carry.  A wait costs about what a probe
+// of a 4096^2 frame does (some 15 us), a probe of a small frame a fraction of that: deep look-ahead for small frames, none for
+// frames beyond 4096^2.  Sizes: -1 = no code, kRateUnknown = not probed.
+constexpr long long kRateUnknown = -2;
+static void rate_candidates(int lo, int hi, int depth, const long long *known, int *out, int *nout) {
+    if (lo >= hi || depth == 0) return;
+    const int mid = (lo + hi + 1) / 2;
+    if (known[mid] == kRateUnknown) out[(*nout)++] = mid;
+    rate_candidates(mid, hi, depth - 1, known, out, nout);
+    rate_candidates(lo, mid - 1, depth - 1, known, out, nout);
+}
+
+static int compress_to_size_impl(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, size_t max_bytes, int qmin, int qmax,
+                                 void *out, bool out_on_host, size_t cap, size_t *out_len, int *quality) {
+    const size_t n = num_blocks(h, w);
+    ctx->last_rate_probes = ctx->last_rate_waits = 0;
+    if (n == 0) { // a header at every quality: the bisection ends at qmax
+        if (max_bytes < 16) {
+            *out_len = 16;
+            return set_err(ctx, TIC_E_SPACE, "16 bytes at quality %d exceed the budget of %zu", qmin, max_bytes);
+        }
+        uint8_t hdr[16];
+        write_header(hdr, h, w, qmax);
+        if (out_on_host) {
+            memcpy(out, hdr, 16);
+        } else {
+            HIPCHK(ctx, hipMemcpyAsync(out, hdr, 16, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        *out_len = 16;
+        *quality = qmax;
+        return TIC_OK;
+    }
+    int rc = ensure_rate(ctx, 8);
+    if (rc) return rc;
+    const int depth = n <= 16384 ? 3 : (n <= 262144 ? 2 : 1);
+    long long known[100];
+    for (auto &k : known) k = kRateUnknown;
+    auto fits = [&](int q) { return known[q] >= 0 && (unsigned long long)known[q] <= (unsigned long long)max_bytes; };
+    int lo = qmin, hi = qmax;
+    for (bool first = true;; first = false) {
+        int cand[8], nc = 0;
+        if (first) cand[nc++] = qmin;
+        rate_candidates(lo, hi, depth, known, cand, &nc);
+        if (nc == 0) break;
+        rc = queue_probes(ctx, d_image, h, w, row_stride, n, cand, nc);
+        if (rc) return rc;
+        HIPCHK(ctx, wait_stream(ctx));
+        ctx->last_rate_probes += nc;
+        ctx->last_rate_waits++;
+        for (int i = 0; i < nc; i++) known[cand[i]] = probe_size(ctx->h_rate[i]);
+        if (first && !fits(qmin)) {
+            if (known[qmin] < 0) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code at quality %d (reference raises KeyError)", qmin);
+            *out_len = (size_t)known[qmin];
+            return set_err(ctx, TIC_E_SPACE, "%lld bytes at quality %d exceed the budget of %zu", known[qmin], qmin, max_bytes);
+        }
+        while (lo < hi) { // the bisection, as far as the known sizes carry it
+            const int mid = (lo + hi + 1) / 2;
+            if (known[mid] == kRateUnknown) break;
+            if (fits(mid)) lo = mid; else hi = mid - 1;
+        }
+    }
+    // the stream of quality lo: transform, pack and place into the context's own buffer, then exactly its bytes into the caller's - the
+    // length is known from the probe, so the copy is queued behind the placing kernel and the whole stream costs one wait
+    const size_t len = (size_t)known[lo];
+    if (len > cap) {
+        *out_len = len;
+        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", len, cap);
+    }
+    rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, compress_bound(h, w));
+    if (rc) return rc;
+    rc = grow_dev(ctx, ctx->d_ent_work, ctx->ent_work_bytes, entropy_fused_work_bytes(n));
+    if (rc) return rc;
+    DctqArgs a = make_args(ctx, d_image, h, w, row_stride, lo, ctx->d_coef);
+    HIPCHK(ctx, launch_dctq(a, dctq_kernel_id(TIC_KERNEL_HYBRID), ctx->stream));
+    const int par = ctx->ent_parity;
+    ctx->ent_parity ^= 1;
+    HIPCHK(ctx, entropy_gpu_fused((const int16_t *)ctx->d_coef, n, 1, ctx->d_huff, ctx->d_ent_work, ctx->ent_work_bytes, ctx->d_stream_buf, 0,
+                                  ((ctx->d_stream_cap - 16) / 16) * 4, h, w, lo, nullptr, ctx->d_stat, ctx->d_err + par, ctx->d_err + (par ^ 1),
+                                  kEntropyEightLanes, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_stream_buf, len, out_on_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, out_on_host ? hipStreamSynchronize(ctx->stream) : wait_stream(ctx));
+    ctx->last_rate_waits++;
+    const unsigned long long total_bits = ((volatile unsigned long long *)ctx->h_stat)[0];
+    const int err = (int)(((volatile unsigned long long *)ctx->h_stat)[1] & 0xffffffffull);
+    if (err || 16 + (size_t)((total_bits + 7) / 8) != len) // (two independent walks over the same coefficients: cannot differ)
+        return set_err(ctx, TIC_E_HIP, "the packed stream (%llu bits, error %d) contradicts its probe (%zu bytes)", total_bits, err, len);
+    *out_len = len;
+    *quality = lo;
+    return TIC_OK;
+}
+
+static int check_search_args(tic_ctx *ctx, int h, int w, ptrdiff_t row_stride, int qmin, int qmax, const void *out, size_t cap, size_t *out_len,
+                             int *quality) {
+    if (!ctx || !out_len || !quality) return TIC_E_ARG;
+    if (qmin < 1 || qmax > 99 || qmin > qmax) return set_err(ctx, TIC_E_QUALITY, "quality range %d..%d is not inside 1..99", qmin, qmax);
+    const int rc = check_geometry(ctx, h, w, row_stride, qmin);
+    if (rc) return rc;
+    if (!out || cap < 16) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
+    return TIC_OK;
+}
+
+int tic_compress_to_size_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, size_t max_bytes, int qmin, int qmax,
+                             void *d_out, size_t cap, size_t *out_len, int *quality) {
+    TIC_LOCK(ctx);
+    int rc = check_search_args(ctx, h, w, row_stride, qmin, qmax, d_out, cap, out_len, quality);
+    if (rc) return rc;
+    const size_t n = num_blocks(h, w);
+    if (n && !d_image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    rc = ensure_scratch(ctx, 0, n * 128 + 16);
+    if (rc) return rc;
+    return compress_to_size_impl(ctx, d_image, h, w, row_stride, max_bytes, qmin, qmax, d_out, false, cap, out_len, quality);
+}
+
+int tic_compress_to_size(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, size_t max_bytes, int qmin, int qmax,
+                         uint8_t *out, size_t cap, size_t *out_len, int *quality) {
+    TIC_LOCK(ctx);
+    int rc = check_search_args(ctx, h, w, row_stride, qmin, qmax, out, cap, out_len, quality);
+    if (rc) return rc;
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return compress_to_size_impl(ctx, nullptr, h, w, row_stride, max_bytes, qmin, qmax, out, true, cap, out_len, quality);
+    if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    size_t pitch = 0;
+    rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
+    if (rc) return rc;
+    return compress_to_size_impl(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, max_bytes, qmin, qmax, out, true, cap, out_len, quality);
+}
+
+int tic_last_rate_search(tic_ctx *ctx, int *probes, int *host_waits) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (probes) *probes = ctx->last_rate_probes;
+    if (host_waits) *host_waits = ctx->last_rate_waits;
     return TIC_OK;
 }
 

@@ -234,6 +234,41 @@ int entropy_encode_scaled(const int16_t *zz, int h, int w, int qf, uint8_t *out,
     return entropy_encode_impl(zz, h, w, qf, out, cap, out_len, true);
 }
 
+// The length of the default-table stream entropy_encode would write, from a walk that only sums code lengths: per block the DC
+// category code + category bits, per non-zero AC entry the ZRLs of its zero run + the (run, size) code + size bits, and the EOB that
+// closes every block (huffman.py:33).  16-byte header + the payload rounded up to a byte (bitbuffer.py:17-18).
+int entropy_size(const int16_t *zz, int h, int w, size_t *bytes) {
+    if (!bytes || h < 0 || w < 0) return TIC_E_ARG;
+    const size_t n = num_blocks(h, w);
+    if (!zz && n) return TIC_E_ARG;
+    const EncTables &T = tables();
+    uint64_t bits = 0;
+    int prev_dc = 0;
+    for (size_t b = 0; b < n; b++) {
+        const int16_t *c = zz + b * 64;
+        const int diff = b ? (int)c[0] - prev_dc : (int)c[0];
+        prev_dc = c[0];
+        const int dsize = bit_length((uint32_t)(diff < 0 ? -diff : diff));
+        if (dsize > 11) return TIC_E_RANGE;
+        unsigned blk = (unsigned)T.dc_len[dsize] + (unsigned)dsize;
+        int run = 0;
+        for (int k = 1; k < 64; k++) {
+            const int v = c[k];
+            if (v == 0) {
+                run++;
+                continue;
+            }
+            const int size = bit_length((uint32_t)(v < 0 ? -v : v));
+            if (size > 10) return TIC_E_RANGE;
+            blk += (unsigned)(run >> 4) * T.ac_len[0xF0] + T.ac_len[((run & 15) << 4) | size] + (unsigned)size;
+            run = 0;
+        }
+        bits += blk + T.ac_len[0]; // EOB; a trailing zero run emits nothing else
+    }
+    *bytes = 16 + (size_t)((bits + 7) / 8);
+    return TIC_OK;
+}
+
 void write_header_scaled(uint8_t *out, int h, int w, int qf) {
     write_header(out, h, w, qf);
     out[15] = 0x40; // little-endian 1 << 30 (img.c:185)

@@ -8,6 +8,9 @@ size_t num_blocks(int h, int w);
 size_t compress_bound(int h, int w);
 void write_header(uint8_t *out, int h, int w, int quality);
 int entropy_encode(const int16_t *zz, int h, int w, int quality, uint8_t *out, size_t cap, size_t *out_len);
+// The length of the stream entropy_encode would write (any quality: the header's fields do not change it), from a walk of its own that
+// only sums code lengths; TIC_E_RANGE exactly where entropy_encode returns it.
+int entropy_size(const int16_t *zz, int h, int w, size_t *bytes);
 // The same for a stream of the reference's integer encoder (c/img.c): quality field = setting 0..3, flag 1 << 30, one flush byte more
 // (BB_flushBits); h and w multiples of 8.
 void write_header_scaled(uint8_t *out, int h, int w, int qf);
