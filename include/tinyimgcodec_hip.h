@@ -299,6 +299,14 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
 /* How the last tic_decompress_batch went (any pointer may be null): frames decoded by the batch kernels, frames that took the
  * single-frame call, chunks, frames whose pixels were copied straight into the caller's memory. */
 int tic_last_decompress_batch(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks, int *direct_frames);
+/* ... and the work buffer of the last chunk it handed to the batch kernels' launcher (any pointer may be null): the chunk's range - the
+ * stream bits one lane walks, the largest of its frames' choices -, the bytes the launcher carves out for the chunk, the bytes the
+ * context held.  All zero when the call formed no chunk. */
+int tic_last_decompress_batch_work(tic_ctx *ctx, int *range_bits, size_t *work_used, size_t *work_held);
+/* Diagnostics: the bytes of work buffer the device decoder's launchers carve out for nframes streams with total_ranges ranges of
+ * range_bits stream bits (an odd number of 32-bit words, 288 ... 2016; a stream of b bits has ceil((b - 128) / range_bits) ranges) and
+ * total_blocks blocks in all.  0 for a range the decoder does not take. */
+size_t tic_decode_work_bytes(size_t nframes, size_t total_ranges, size_t total_blocks, int range_bits);
 /* decompress() with stream and pixels both resident in device memory - the counterpart of tic_compress_dev (decompress()
  * codec.py:167-189 between two device buffers).  d_out receives h rows of w pixels, out_stride bytes apart (out_cap: bytes of
  * the buffer); *h / *w (may be null) receive the geometry of the header.  Long streams never leave the device; short ones and

@@ -1657,16 +1657,9 @@ def test_the_references_own_benchmark_set(ctx, monkeypatch):
             L.tic_dev_free(ctx.handle, d)
 
 
-def test_decompress_batch_mixed_streams(ctx, oracle, golden):
-    """decompress_batch() == [decompress(s) for s in streams] on a batch of everything: unequal geometries and qualities, dense and sparse
-    content, ragged shapes (row pitch != width in the device buffer), an empty image, a stream too short for the device decoder, a
-    C-encoder stream (scaled_dct), a cut stream and one with a flipped bit (both end on the host decoder), a 2048^2 frame of noise at
-    q = 90 (the fused kernel's large window).  Through the C-ABI with scattered destinations too (the pinned route instead of the direct copy);
-    and the exceptions of decompress() for a stream shorter than its header and for one flagged as carrying a table."""
-    import struct
-
-    L = N.load()
-    rs = np.random.RandomState(5)
+def mixed_batch_streams(ctx, golden):
+    """The 14 streams of test_decompress_batch_mixed_streams (its docstring says what they are); tests/test_decompress_batch_edges_gpu.py
+    decodes the same mix."""
     imgs = [(rand_frame(31, 512, 512), 50), (rand_frame(32, 520, 776), 80), (np.full((512, 640), 77, np.uint8), 50), (rand_frame(33, 1080, 1920), 20),
             ((rand_frame(34, 600, 1000) // 64 * 64).astype(np.uint8), 10), (rand_frame(35, 203, 517), 90), (rand_frame(36, 64, 64), 50), (np.zeros((0, 8), np.uint8), 50),
             (rand_frame(37, 2048, 2048), 90), (np.tile(golden("lenna")["img"], (2, 2)), 5), (rand_frame(38, 512, 512), 50)]
@@ -1676,6 +1669,19 @@ def test_decompress_batch_mixed_streams(ctx, oracle, golden):
     cut = streams[0][: len(streams[0]) * 2 // 3]
     flip = bytearray(streams[3]); flip[len(flip) // 2] ^= 0x10
     streams += [cut, bytes(flip)]
+    return streams
+
+
+def test_decompress_batch_mixed_streams(ctx, oracle, golden):
+    """decompress_batch() == [decompress(s) for s in streams] on a batch of everything: unequal geometries and qualities, dense and sparse
+    content, ragged shapes (row pitch != width in the device buffer), an empty image, a stream too short for the device decoder, a
+    C-encoder stream (scaled_dct), a cut stream and one with a flipped bit (both end on the host decoder), a 2048^2 frame of noise at
+    q = 90 (the fused kernel's large window).  Through the C-ABI with scattered destinations too (the pinned route instead of the direct copy);
+    and the exceptions of decompress() for a stream shorter than its header and for one flagged as carrying a table."""
+    import struct
+
+    L = N.load()
+    streams = mixed_batch_streams(ctx, golden)
     want = [oracle.decompress(s) for s in streams]
     got = T.decompress_batch(streams, ctx=ctx)
     assert len(got) == len(want)

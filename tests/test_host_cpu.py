@@ -32,7 +32,7 @@ def test_library_loads_and_exports_every_declared_symbol():
         # variable name; the test-hooks build of the same sources says what it is
         assert lib.tic_build_has_test_hooks() == hooks
         blob = open(path, "rb").read()
-        for var in (b"TIC_SCHED", b"TIC_SPLIT", b"TIC_DECODE_HOST", b"TIC_DECODE_SERIAL", b"TIC_COMM_FORCE_RCCL", b"TIC_BAND_BYTES", b"TIC_TEST_HOOKS"):
+        for var in (b"TIC_SCHED", b"TIC_SPLIT", b"TIC_DECODE_HOST", b"TIC_DECODE_SERIAL", b"TIC_COMM_FORCE_RCCL", b"TIC_BAND_BYTES", b"TIC_DBATCH_WORK_CAP", b"TIC_TEST_HOOKS"):
             assert (var in blob) == bool(hooks) or var == b"TIC_TEST_HOOKS", (os.path.basename(path), var)
         assert b"TIC_TEST_HOOKS" not in blob  # (neither build reads that one: _native.py picks the build by it)
     assert declared == set(N.SIGNATURES), declared ^ set(N.SIGNATURES)
@@ -252,6 +252,34 @@ def test_division_of_the_tie_path_is_the_ieee_division(tmp_path):
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", str(exe), os.path.join(root, "tests", "native", "div_selftest.cpp")], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith(": ok"), r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_decoder_work_buffer_provision_bounds_the_carve_up(tmp_path):
+    """The device Huffman decoder's work buffer is sized from the stream lengths before the range (stream bits per lane) is known, and carved up
+    by the launchers at the range the call ends up with - a chunk's largest, 2,016 bits on a second run, a hook's.  Both sides are functions of
+    csrc/tic_entropy_dec_gpu.h (dec_work_provision_bytes / dec_work_carve_bytes, the launchers call the latter), and tests/native/decws_selftest.cpp
+    compiles that header for the host: for all 28 legal ranges the provision covers the carve-up - every stream length from the decoder's floor to
+    64 KiB and a seeded sample up to 64 MiB, from the sparsest stream a length can hold (6 bits per block) to the densest the tables allow,
+    batches of 1, 2, 79, 200 and 1,024 equal frames, 4,000 seeded mixed batches of 1..1,024 frames, the single-frame pair with and without its
+    margin, and by construction the flat 192 x 472 frame (1,416 blocks, 1,078 bytes, range 1,056) in batches of 1..1,024.
+    With --parent the same sweep runs on the two expressions the provision replaced, and must find their counterexamples (that frame from 76
+    copies on): the sweep can fail."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no host compiler")
+    exe = tmp_path / "decws_selftest"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-o", str(exe), os.path.join(ROOT, "tests", "native", "decws_selftest.cpp")], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("decws_selftest ok") and ", 0 counterexamples" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    assert r.stdout.count(", 0 counterexamples") == 4, r.stdout
+    p = subprocess.run([str(exe), "--parent"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 1 and "decws_selftest FAILED (parent formulas)" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
+    assert "the flat 192 x 472 frame: 1024 cases, 949 counterexamples" in p.stdout and "smallest: 76 frame(s) of 1078 bytes and 1416 blocks" in p.stdout, p.stdout
+    assert "single-frame sweep" in p.stdout and p.stdout.count(", 0 counterexamples") == 1, p.stdout  # (the single-frame pair's 16 KiB always sufficed: at most 1,352 bytes are missing)
+    # the library's diagnostic is the same carve-up
+    L = N.load()
+    assert L.tic_decode_work_bytes(76, 76 * 9, 76 * 1416, 1056) == 918784 and L.tic_decode_work_bytes(1, 9, 1416, 1000) == 0
 
 
 def test_strip_kernel_binary_keeps_its_landing_registers_private():

@@ -210,6 +210,8 @@ struct tic_ctx {
         DecWorkspace ws;
     } dbat;
     int last_dbatch_frames = 0, last_dbatch_fallback = 0, last_dbatch_chunks = 0, last_dbatch_direct = 0;
+    int last_dbatch_range = 0;                                 // tic_last_decompress_batch_work: the last chunk handed to the batch launcher -
+    size_t last_dbatch_work_used = 0, last_dbatch_work_held = 0; // its range, the bytes of work buffer it carves, the bytes the context held
     // batch pipeline buffers, kept across calls (pinned allocations are expensive)
     std::vector<Slot> bslots;
     size_t bslot_img_bytes = 0, bslot_coef_bytes = 0;
@@ -2612,10 +2614,7 @@ static int decode_range_bits(size_t len, size_t n, size_t mult = 2, size_t floor
     // (nearly flat content - below 7 stream bits per block: DC code + end-of-block and little else - is periodic bit patterns in which a walk can stay
     //  out of step for tens of ranges: ranges twice as long there.  tools/stress_decoder.py 600: second runs on valid streams of 4-7 bits per block 1 in
     //  24 instead of 4; everywhere else the longer range only costs - the benchmark loop's decompress() +10-17 us, profiles/r06_decoder.txt)
-    if (floor_words == 9 && len * 8 < 7 * n) floor_words = 33;
-    size_t k = (mult * (len * 8) / n + 31) / 32;
-    k |= 1;
-    return (int)(k < floor_words ? floor_words : (k > 63 ? 63 : k)) * 32;
+    return dec_range_rule(len, n, mult, floor_words); // (tic_entropy_dec_gpu.h: the work buffer's self-test asks it too)
 }
 
 static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const StreamHead &sh, uint8_t *out, bool out_on_device, size_t out_stride,
@@ -2855,13 +2854,17 @@ int tic_decompress(tic_ctx *ctx, const uint8_t *data, size_t len, uint8_t *out, 
 // memory (pinned for the call by one hipHostRegister), else through the context's pinned buffer and a few copy threads.
 // Frame i: what tic_decompress(ctx, streams[i], lens[i], outs[i], caps[i]) gives, geometry in hs[i] / ws[i] (either may be null).  A frame the
 // batch kernels do not take (a short or damaged stream, a C-encoder stream, anything the device decoder flags) is decoded by that very
-// call afterwards.  Errors: headers are checked before any work (the first bad frame's error, nothing decoded); an error while decoding is
-// the first failing frame's, the other frames are complete.
+// call afterwards - and so is every frame of a chunk the batch launcher refuses (its host-side checks, before any kernel: a work buffer
+// too small for the chunk) or that fails on the way.  Errors: headers are checked before any work (the first bad frame's error, nothing
+// decoded); an error while decoding is the first one met, and every frame that did not fail itself is complete: an error inside a chunk
+// ends the chunks, not the call - the frames it leaves still go to the single-frame call.
 int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size_t *lens, int n, uint8_t *const *outs, const size_t *caps, int *hs, int *ws) {
     TIC_LOCK(ctx);
     if (!ctx) return TIC_E_ARG;
     if (n < 0 || (n > 0 && (!streams || !lens || !outs || !caps))) return set_err(ctx, TIC_E_ARG, "bad batch arguments");
     ctx->last_dbatch_frames = ctx->last_dbatch_fallback = ctx->last_dbatch_chunks = ctx->last_dbatch_direct = 0;
+    ctx->last_dbatch_range = 0;
+    ctx->last_dbatch_work_used = ctx->last_dbatch_work_held = 0;
     ctx->bt = BatchTrace(); // (tic_last_batch_phases: [0] packing the upload buffer, [1] enqueue, [2] wait + download, [4] hand-out, [5] single-frame calls)
     if (n == 0) return TIC_OK;
     struct Fr { int h, w, q; size_t nblk; bool batch; };
@@ -2886,6 +2889,7 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
     constexpr size_t kMaxIn = 96u << 20, kMaxPix = 288u << 20;
     constexpr int kMaxFrames = 1024;
     int result = TIC_OK;
+    std::string first_err; // (the text of an error inside a chunk: the single-frame calls behind it write their own)
     auto fail = [&](int rc) { if (result == TIC_OK) result = rc; };
     std::vector<int> later; // frames for the single-frame call
     for (int i = 0; i < n; i++)
@@ -2913,6 +2917,9 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
         i0 = i1;
         if (ids.empty()) break;
         const uint32_t F = (uint32_t)ids.size();
+        bool refused = false; // the launcher's host-side checks said no: nothing was launched
+        // (a function of its own: whatever ends it early - a failed allocation, copy or launch - comes back here, and the frames still go somewhere)
+        const int chunk_rc = [&]() -> int {
         std::vector<DecFrame> frames(F);
         std::vector<size_t> pix_off(F), pitches(F);
         uint32_t tiles = 0, wgs = 0, ranges = 0;
@@ -2976,17 +2983,35 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
         if (rc) return rc;
         BT_STOP(0);
         BT_START();
+        size_t work_held = B.ws.work_bytes;
+        if (const char *e = test_hook("TIC_DBATCH_WORK_CAP")) work_held = (size_t)atoll(e) < work_held ? (size_t)atoll(e) : work_held; // (tests: a launcher that refuses)
+        ctx->last_dbatch_range = range_bits;
+        ctx->last_dbatch_work_used = dec_work_carve_bytes(F, ranges, blk, range_bits);
+        ctx->last_dbatch_work_held = work_held;
         HIPCHK(ctx, hipMemcpyAsync(B.d_in, B.h_in, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, entropy_decode_idct_gpu_batch(B.d_in + o_streams, (const DecFrame *)(B.d_in + o_frames), (const uint32_t *)(B.d_in + o_tiles), (const uint32_t *)(B.d_in + o_wgs), F, tiles,
-                                                  wgs, ranges, blk, small_win, ctx->d_dec_luts, B.ws.work, B.ws.work_bytes, B.ws.desc, B.ws.desc_words, B.ws.epoch, B.ws.d_status,
-                                                  range_bits, ctx->stream));
+        const hipError_t le = entropy_decode_idct_gpu_batch(B.d_in + o_streams, (const DecFrame *)(B.d_in + o_frames), (const uint32_t *)(B.d_in + o_tiles), (const uint32_t *)(B.d_in + o_wgs), F,
+                                                            tiles, wgs, ranges, blk, small_win, ctx->d_dec_luts, B.ws.work, work_held, B.ws.desc, B.ws.desc_words, B.ws.epoch, B.ws.d_status,
+                                                            range_bits, ctx->stream);
+        if (le == hipErrorInvalidValue) { // refused: every check of the launcher that says so comes before its first launch
+            (void)hipGetLastError();
+            refused = true;
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (the upload still reads the pinned buffer the next chunk is packed into)
+            return TIC_OK;
+        }
+        HIPCHK(ctx, le);
         BT_STOP(1);
         BT_START();
         // ---- the pixels come down: one copy into the caller's memory where the frames are dense and follow each other there, else one copy
         // into pinned memory and a few threads
+        // (the copy is `total` bytes long, the device buffer's padding between two frames included: it may only cover bytes the caller gave away -
+        //  a frame of a whole number of 256 B has none behind it, elsewhere caps[] must reach to the next frame; an arena of frames at
+        //  256-byte aligned distances with caps[i] = h * w takes the pinned route, and the bytes between its frames stay the caller's)
         bool dense = true;
-        for (uint32_t k = 0; k < F && dense; k++)
-            dense = pitches[k] == (size_t)fr[(size_t)ids[k]].w && (k == 0 || (outs[ids[k]] == outs[ids[k - 1]] + (pix_off[k] - pix_off[k - 1])));
+        for (uint32_t k = 0; k < F && dense; k++) {
+            const size_t hw = (size_t)fr[(size_t)ids[k]].h * (size_t)fr[(size_t)ids[k]].w;
+            dense = pitches[k] == (size_t)fr[(size_t)ids[k]].w && (k == 0 || (outs[ids[k]] == outs[ids[k - 1]] + (pix_off[k] - pix_off[k - 1]))) &&
+                    (k + 1 == F || hw % 256 == 0 || caps[ids[k]] >= pix_off[k + 1] - pix_off[k]);
+        }
         bool direct = false;
         if (dense && ctx->auto_register) {
             const size_t total = pix_off[F - 1] + (size_t)fr[(size_t)ids[F - 1]].h * (size_t)fr[(size_t)ids[F - 1]].w;
@@ -3046,6 +3071,17 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
             }
         }
         BT_STOP(4);
+        return TIC_OK;
+        }();
+        if (chunk_rc != TIC_OK || refused) { // (every early way out lies in front of the status words: none of the chunk's frames is counted or queued yet)
+            later.insert(later.end(), ids.begin(), ids.end());
+            if (chunk_rc != TIC_OK) { // the first error stands (its text too: kept below); no further chunk is tried, what they would have held goes one by one
+                fail(chunk_rc);
+                first_err = ctx->err;
+                for (; i0 < n; i0++)
+                    if (fr[(size_t)i0].batch) later.push_back(i0);
+            }
+        }
     }
     // frames the batch did not take, or did not finish: the single-frame call, with everything it knows (second run, host decoders)
     std::sort(later.begin(), later.end());
@@ -3060,6 +3096,7 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
             fail(rc);
         }
     }
+    if (!first_err.empty()) ctx->err = first_err;
     return result;
 }
 
@@ -3073,6 +3110,23 @@ int tic_last_decompress_batch(tic_ctx *ctx, int *batch_frames, int *single_frame
     if (chunks) *chunks = ctx->last_dbatch_chunks;
     if (direct_frames) *direct_frames = ctx->last_dbatch_direct;
     return TIC_OK;
+}
+
+// ... and the work buffer of the last chunk it handed to the batch launcher: the chunk's range (stream bits per lane, the largest of its
+// frames' choices), the bytes the launcher carves for it and the bytes the context held for it (0 / 0 / 0: no chunk).  Any pointer may be null.
+int tic_last_decompress_batch_work(tic_ctx *ctx, int *range_bits, size_t *work_used, size_t *work_held) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (range_bits) *range_bits = ctx->last_dbatch_range;
+    if (work_used) *work_used = ctx->last_dbatch_work_used;
+    if (work_held) *work_held = ctx->last_dbatch_work_held;
+    return TIC_OK;
+}
+
+// The device decoder's work buffer for `nframes` streams of `total_ranges` ranges of `range_bits` bits and `total_blocks` blocks in all: the
+// launchers' own carve-up (tic_entropy_dec_gpu.h dec_work_carve_bytes); 0 for a range the decoder does not take.
+size_t tic_decode_work_bytes(size_t nframes, size_t total_ranges, size_t total_blocks, int range_bits) {
+    return dec_range_ok(range_bits) ? dec_work_carve_bytes(nframes, total_ranges, total_blocks, range_bits) : 0;
 }
 
 // decompress() with stream and pixels both resident in HBM (the counterpart of tic_compress_dev): only the 16-byte header, the

@@ -1,10 +1,65 @@
 // tic_entropy_dec_gpu.h - Huffman + run-length decode of a long stream on the device (see tic_entropy_dec_gpu.hip).
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+// TIC_DEC_WORKSPACE_ONLY: only the workspace arithmetic below, for a host compiler without the HIP headers (tests/native/decws_selftest.cpp)
+#ifndef TIC_DEC_WORKSPACE_ONLY
+#include <hip/hip_runtime.h>
+#define TIC_DEC_HD __host__ __device__
+#else
+#define TIC_DEC_HD
+#endif
 
 namespace tic {
+
+// ---- the device decoder's ranges and its work buffer.  A range is the stream bits one lane walks: an odd number of 32-bit words.
+constexpr int kDecRangeMin = 288, kDecRangeMax = 2016;
+TIC_DEC_HD constexpr uint32_t dec_cap_of(uint32_t range) { return range / 6u + 2u; } // block starts a range can hold (a block has at least 6 bits: 2-bit DC code + EOB)
+inline bool dec_range_ok(int range_bits) { return range_bits >= kDecRangeMin && range_bits <= kDecRangeMax && range_bits % 64 == 32; }
+// The rule for it: `mult` average blocks, at least `floor_words` 32-bit words - 33 for nearly flat content, below 7 stream bits per block -,
+// as an odd number of words up to 63 (why: tic_api.hip decode_range_bits).  stream_bytes with the header, as everywhere here.
+inline int dec_range_rule(size_t stream_bytes, size_t nblocks, size_t mult = 2, size_t floor_words = 9) {
+    if (floor_words == 9 && stream_bytes * 8 < 7 * nblocks) floor_words = 33;
+    size_t k = (mult * (stream_bytes * 8) / nblocks + 31) / 32;
+    k |= 1;
+    return (int)(k < floor_words ? floor_words : (k > 63 ? 63 : k)) * 32;
+}
+inline size_t dec_ranges_of(size_t stream_bits, int range_bits) { return (stream_bits - 128 + (size_t)range_bits - 1) / (size_t)range_bits; } // (behind the 16-byte header)
+
+// The carve-up of the work buffer, the only one: both launchers take their pieces through it, in this order, every piece rounded up to
+// 256 B - an 8-byte total per frame, two traces of dec_cap_of(range_bits) 2-byte entries per range, a 4-byte position per block.
+// `end` is what a launch uses.
+struct DecWorkCarve {
+    size_t totals, starts, hand, bpos, end;
+    static size_t up(size_t b) { return (b + 255) / 256 * 256; }
+    DecWorkCarve(size_t nframes, size_t total_ranges, size_t total_blocks, int range_bits) {
+        const size_t trace = total_ranges * dec_cap_of((uint32_t)range_bits) * 2;
+        totals = 0;
+        starts = totals + up(nframes * 8);
+        hand = starts + up(trace);
+        bpos = hand + up(trace);
+        end = bpos + up(total_blocks * 4);
+    }
+};
+inline size_t dec_work_carve_bytes(size_t nframes, size_t total_ranges, size_t total_blocks, int range_bits) {
+    return DecWorkCarve(nframes, total_ranges, total_blocks, range_bits).end;
+}
+
+// What is provided for it, before the range is known (a chunk's range is its frames' largest; the single-frame call may come back with
+// kDecRangeMax, a hook may name any): the carve-up at the SHORTEST range with b / 288 + 2 ranges for a frame of b stream bits
+// (`total_ranges_288`: their sum), plus one range of the LONGEST kind per frame and trace.  A bound for every legal range R, because a
+// frame's trace entries are
+//     ceil((b - 128) / R) * dec_cap_of(R) <= ((b - 129) / R + 1) * (R / 6 + 2) = (b - 129) / 6 + 2 (b - 129) / R + R / 6 + 2
+//                                         <  (b / 288 + 1) * 50 + dec_cap_of(kDecRangeMax)           [R >= 288: 2 / R <= 1 / 144; R / 6 + 2 <= 338]
+//                                         <  (floor(b / 288) + 2) * dec_cap_of(288) + dec_cap_of(kDecRangeMax),
+// the 2 x 2 bytes per entry of the added ranges are added outside the rounding (up(a + b) <= up(a) + b + 255: 2 x 256 B more), and the
+// other two pieces are the launch's own.  tests/native/decws_selftest.cpp sweeps it.
+inline size_t dec_work_provision_bytes(size_t nframes, size_t total_ranges_288, size_t total_blocks) {
+    return dec_work_carve_bytes(nframes, total_ranges_288, total_blocks, kDecRangeMin) + nframes * ((size_t)dec_cap_of(kDecRangeMax) * 2 * 2) + 2 * 256;
+}
+inline size_t dec_ranges_288(size_t stream_bytes) { return stream_bytes * 8 / kDecRangeMin + 2; } // a frame's share of total_ranges_288
+
+#ifndef TIC_DEC_WORKSPACE_ONLY
 
 // The host decoder's look-up tables (tic_entropy.cpp EncTables::Dec): the next 11 / 16 stream bits -> (code length << 8) | symbol,
 // 0 when no codeword (of at most 11 bits, for the short tables) is a prefix of them.
@@ -92,5 +147,7 @@ hipError_t entropy_decode_idct_gpu_batch(const void *d_words_all, const DecFrame
                                          uint32_t total_tiles, uint32_t total_wgs, uint32_t total_ranges, size_t total_blocks, bool small_win, const DecLutsDev *d_luts, void *d_work,
                                          size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, DecStatus *d_status, int range_bits, hipStream_t stream,
                                          int flat_grid = 4096);
+
+#endif // TIC_DEC_WORKSPACE_ONLY
 
 } // namespace tic

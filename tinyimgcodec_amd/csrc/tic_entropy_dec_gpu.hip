@@ -58,8 +58,8 @@ namespace {
 // profiles/r04_decoder.txt), so their time goes with the bits a lane walks - hence ranges as short as the stitch tolerates: it needs
 // every range to hold a block start of the true chain that the range's own walk recorded, and a range shorter than the stream's
 // long blocks makes it give up (the caller then tries the longest range).
-constexpr int kRangeMin = 288, kRangeMax = 2016;
-__host__ __device__ constexpr uint32_t cap_of(uint32_t range) { return range / 6u + 2u; } // block starts a range can hold (a block has at least 6 bits: 2-bit DC code + EOB)
+constexpr int kRangeMin = kDecRangeMin; // (tic_entropy_dec_gpu.h, with the work buffer's arithmetic: ranges of kDecRangeMin .. kDecRangeMax bits)
+__host__ __device__ constexpr uint32_t cap_of(uint32_t range) { return dec_cap_of(range); }
 
 // The stream bits a workgroup walks, staged in LDS.  A workgroup is one wave, its lanes own 64 consecutive ranges: one contiguous
 // window of 64 ranges plus the longest block a lane may run into behind its range (kOver words).  The kernels are one dependent chain
@@ -876,13 +876,11 @@ static uint32_t dec_shadows(int range_bits) {
 }
 
 bool entropy_decode_gpu_range_ok(int range_bits) {
-    return range_bits >= kRangeMin && range_bits <= kRangeMax && range_bits % 64 == 32; // an odd number of 32-bit words
+    return dec_range_ok(range_bits); // an odd number of 32-bit words
 }
 
 size_t entropy_decode_gpu_work_bytes(size_t stream_bytes, size_t nblocks) {
-    const size_t nbits = stream_bytes * 8;
-    const size_t nranges = nbits / kRangeMin + 2; // (the smallest range: most ranges, and the most room per stream bit)
-    return nranges * ((size_t)cap_of(kRangeMin) * 2 * 2) + nblocks * 4 + 16384; // (two traces per range, a 4-byte position per block; every piece is rounded up to 256 B)
+    return dec_work_provision_bytes(1, dec_ranges_288(stream_bytes), nblocks); // (a bound for every range a run may take: tic_entropy_dec_gpu.h)
 }
 
 size_t entropy_decode_gpu_desc_words(size_t stream_bytes, size_t nblocks) { // look-back words of the two sums (own and inclusive sums: a quarter of the array each)
@@ -897,7 +895,6 @@ hipError_t entropy_decode_idct_gpu(const void *d_stream_words, size_t stream_byt
     const size_t nbits = stream_bytes * 8;
     if (!entropy_decode_gpu_range_ok(range_bits)) return hipErrorInvalidValue;
     const uint32_t range = (uint32_t)range_bits;
-    const uint32_t kCap = cap_of(range);
     const int kRange = range_bits;
     if (nbits < 128 + 2048 + 2048 || nbits + 8192 >= (1ull << 32) || nblocks == 0) return hipErrorInvalidValue; // (a walk stands up to 1,827 bits behind the end)
     if (margin_bits != 0 && margin_bits != 2048) return hipErrorInvalidValue;
@@ -919,12 +916,12 @@ hipError_t entropy_decode_idct_gpu(const void *d_stream_words, size_t stream_byt
     const uint32_t desc_half = (uint32_t)(desc_words / 4); // per sum: own sums, then inclusive sums
     unsigned long long *desc_r = d_desc, *desc_b = d_desc + 2 * (size_t)desc_half;
     // workspace carve-up
-    char *w = (char *)d_work;
-    auto take = [&](size_t bytes) { char *p = w; w += (bytes + 255) / 256 * 256; return (void *)p; };
-    long long *totals = (long long *)take(16);
-    uint16_t *starts = (uint16_t *)take((size_t)nranges * kCap * 2), *hand = (uint16_t *)take((size_t)nranges * kCap * 2);
-    uint32_t *bpos = (uint32_t *)take(nblocks * 4);
-    if ((size_t)(w - (char *)d_work) > work_bytes) return hipErrorInvalidValue;
+    const DecWorkCarve cv(1, nranges, nblocks, range_bits);
+    if (cv.end > work_bytes) return hipErrorInvalidValue; // (before anything is launched)
+    char *const w = (char *)d_work;
+    long long *totals = (long long *)(w + cv.totals);
+    uint16_t *starts = (uint16_t *)(w + cv.starts), *hand = (uint16_t *)(w + cv.hand);
+    uint32_t *bpos = (uint32_t *)(w + cv.bpos);
     const uint32_t *words = (const uint32_t *)d_stream_words;
     const uint32_t nwords = (uint32_t)((stream_bytes + 3) / 4);
     const uint32_t last_mask = (stream_bytes & 3) ? 0xffffffffu << (8u * (4u - (uint32_t)(stream_bytes & 3))) : 0xffffffffu; // (big-endian: the stream's bytes are the word's high bytes)
@@ -951,27 +948,29 @@ hipError_t entropy_decode_idct_gpu(const void *d_stream_words, size_t stream_byt
 
 
 size_t entropy_decode_batch_work_bytes(size_t total_ranges_288, size_t total_blocks, size_t nframes) {
-    return total_ranges_288 * ((size_t)cap_of(kRangeMin) * 2 * 2) + total_blocks * 4 + nframes * 8 + 16384;
+    return dec_work_provision_bytes(nframes, total_ranges_288, total_blocks);
 }
 uint32_t entropy_decode_batch_tiles(uint32_t nranges, int range_bits) { const uint32_t owned = 64u - dec_shadows(range_bits); return (nranges + owned - 1u) / owned; }
 uint32_t entropy_decode_batch_wgs(size_t nblocks) { return (uint32_t)((nblocks + kDecodeWG - 1) / kDecodeWG); }
-uint32_t entropy_decode_batch_ranges(size_t stream_bytes, int range_bits) { return (uint32_t)((stream_bytes * 8 - 128 + (size_t)range_bits - 1) / (size_t)range_bits); }
+uint32_t entropy_decode_batch_ranges(size_t stream_bytes, int range_bits) { return (uint32_t)dec_ranges_of(stream_bytes * 8, range_bits); }
 
 hipError_t entropy_decode_idct_gpu_batch(const void *d_words_all, const DecFrame *d_frames, const uint32_t *d_tile_frame, const uint32_t *d_wg_frame, uint32_t nframes,
                                          uint32_t total_tiles, uint32_t total_wgs, uint32_t total_ranges, size_t total_blocks, bool small_win, const DecLutsDev *d_luts, void *d_work,
                                          size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, DecStatus *d_status, int range_bits, hipStream_t stream,
                                          int flat_grid) {
     if (!entropy_decode_gpu_range_ok(range_bits) || nframes == 0 || total_tiles == 0 || total_wgs == 0) return hipErrorInvalidValue;
-    const uint32_t range = (uint32_t)range_bits, kCap = cap_of(range);
+    const uint32_t range = (uint32_t)range_bits;
     if (!d_desc || desc_words < 4 * (size_t)(total_tiles > total_wgs ? total_tiles : total_wgs) || epoch == 0 || epoch >= (1u << 22) || flat_grid < 0) return hipErrorInvalidValue;
     const uint32_t desc_half = (uint32_t)(desc_words / 4);
     unsigned long long *desc_r = d_desc, *desc_b = d_desc + 2 * (size_t)desc_half;
-    char *w = (char *)d_work;
-    auto take = [&](size_t bytes) { char *p = w; w += (bytes + 255) / 256 * 256; return (void *)p; };
-    long long *totals = (long long *)take((size_t)nframes * 8);
-    uint16_t *starts = (uint16_t *)take((size_t)total_ranges * kCap * 2), *hand = (uint16_t *)take((size_t)total_ranges * kCap * 2);
-    uint32_t *bpos = (uint32_t *)take(total_blocks * 4);
-    if ((size_t)(w - (char *)d_work) > work_bytes) return hipErrorInvalidValue;
+    // The host-side size check: a work buffer too small for this chunk at this range is refused HERE, before either kernel is launched
+    // (the caller decodes the chunk's frames one by one).
+    const DecWorkCarve cv(nframes, total_ranges, total_blocks, range_bits);
+    if (cv.end > work_bytes) return hipErrorInvalidValue;
+    char *const w = (char *)d_work;
+    long long *totals = (long long *)(w + cv.totals);
+    uint16_t *starts = (uint16_t *)(w + cv.starts), *hand = (uint16_t *)(w + cv.hand);
+    uint32_t *bpos = (uint32_t *)(w + cv.bpos);
     const unsigned win_lds = stage_lds_words(range) * 4u;
     const unsigned wpw = (unsigned)kChainLds + 4u * win_lds <= 60000u ? 4u : ((unsigned)kChainLds + 2u * win_lds <= 60000u ? 2u : 1u);
     auto measure = [&](auto kern) {

@@ -12,6 +12,7 @@
 //   TIC_DECODE_ROUNDS       device Huffman decoder: hand-over rounds of the stitch (default 8)
 //   TIC_DECODE_NO_HOSTPIX   tic_decompress of small images through the device image buffer and a DMA copy, as large ones (not through host-mapped memory)
 //   TIC_BATCH_CHUNK         tic_compress_batch: frames per chunk instead of the choice by frame size
+//   TIC_DBATCH_WORK_CAP     tic_decompress_batch: at most this many bytes of work buffer are handed to the batch launcher (it refuses a chunk that needs more)
 //   TIC_DECODE_NO_GUESS     tic_decompress_dev always reads the header first (no launch on a guess of it)
 //   TIC_NO_SMALL_PATH       tic_compress of small frames through the device stream buffer and a DMA copy, as large ones (not through host-mapped memory)
 //   TIC_DECODE_MIN_BLOCKS, TIC_DECODE_MIN_BITS, TIC_DECODE_MIN_DENSITY   the shortest stream the device Huffman decoder takes (defaults 1024 blocks, 8192 bits, any density)
