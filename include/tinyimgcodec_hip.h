@@ -319,7 +319,14 @@ int tic_decompress_dev(tic_ctx *ctx, const void *d_stream, size_t len, void *d_o
 int tic_last_decode_path(tic_ctx *ctx);
 /* ... and, when the device decoder handed a long stream to the host decoder, why (0: it did not; bit 1 an incident in the stream's
  * first range, 4 a range without a synchronisation point, 8 / 16 / 32 an incident on the true chain, 2 trace overflow, 64 no block
- * produced). */
+ * produced, 128 a look-back that timed out, 256 a block that reaches behind the stream's end, 512 a running DC outside int16).
+ * Bit 512: the reference integrates the DC differences as int32 (np.cumsum, codec.py:53) and transforms whatever the sum holds, so a
+ * well-formed default-table or scaled_dct stream may carry a DC the int16 coefficient layout cannot (differences of +-2047 leave
+ * int16 within 17 blocks; no encoder of this library or of the reference writes such a stream).  The device decoder hands the stream
+ * over, and the host route gives the inverse stage the true DC in an int32 side array: tic_decompress, tic_decompress_batch (behind
+ * the batch) and tic_decompress_dev decode such a stream to the reference's pixels.  The int16 layout of tic_idctq / tic_idctq_scaled
+ * is unchanged and cannot express it.  Out of scope: a running DC beyond int32 (np.cumsum wraps there), and adaptive streams with a
+ * DC outside int16, which stay TIC_E_STREAM (tic_decompress_adaptive). */
 int tic_last_decode_giveup(tic_ctx *ctx);
 /* ... and the stream bits per lane the device decoder's last run worked with (2 average blocks, 288 ... 2,016; 1,056 at least for nearly flat streams), and how many runs the
  * last long stream took: 2 = the first choice met a range without a synchronisation point and the longest range was tried.

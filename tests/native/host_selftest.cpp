@@ -148,6 +148,94 @@ int main() {
             cases++;
         }
     }
+    // ---- a running DC that leaves int16 (np.cumsum keeps int32, codec.py:53): differences of +-2047 in a triangle walk beyond +-60,000,
+    //      every AC 300 against the DC's sign.  The int16 layout holds the saturated DC; the DC the decoder hands on to the inverse stage
+    //      - the layout's value, replaced by the side list's where there is an entry - must be the int32 running sum, block for block:
+    //      serial decoder, parallel decoder (24,576 blocks) and the tail form the device decoder calls
+    for (int big = 0; big < 2; big++) {
+        const int h = big ? 1024 : 8, w = big ? 1536 : 8 * 1100;
+        const size_t n = tic::num_blocks(h, w);
+        std::vector<int32_t> dc(n), ac(n * 63), run(n);
+        int32_t acc = 0;
+        for (size_t b = 0; b < n; b++) {
+            const size_t ph = b % 120;
+            dc[b] = (ph < 30 || ph >= 90) ? 2047 : -2047;
+            acc += dc[b];
+            run[b] = acc;
+            for (int k = 0; k < 63; k++) ac[b * 63 + (size_t)k] = acc > 0 ? -300 : 300;
+        }
+        if (*std::max_element(run.begin(), run.end()) <= 60000 || *std::min_element(run.begin(), run.end()) >= -60000) return fail("wide DC: the walk stays small", h, w, big);
+        std::vector<uint8_t> bs(tic::compress_bound(h, w));
+        size_t len = 0;
+        if (tico_entropy_encode(dc.data(), ac.data(), h, w, 50, bs.data(), bs.size(), &len) != 0) return fail("wide DC: encode", h, w, big);
+        bs.resize(len); // (exact size: ASan guards its end)
+        auto handed_on = [&](const std::vector<int16_t> &zz, const std::vector<tic::DcWide> &wide, size_t first) {
+            std::vector<int32_t> d(n - first);
+            for (size_t b = first; b < n; b++) d[b - first] = zz[(b - first) * 64];
+            size_t prev = 0;
+            for (size_t i = 0; i < wide.size(); i++) {
+                if (wide[i].block < first || wide[i].block >= n || (i && wide[i].block <= prev)) return std::vector<int32_t>();
+                prev = wide[i].block;
+                d[wide[i].block - first] = wide[i].dc;
+            }
+            return d;
+        };
+        for (int serial = 0; serial < 2; serial++) {
+            if (serial) setenv("TIC_DECODE_SERIAL", "1", 1);
+            std::vector<int16_t> back(n * 64, (int16_t)0x5A5A);
+            std::vector<tic::DcWide> wide(3, tic::DcWide{7, 7}); // (stale entries: the call clears them)
+            const int rc = tic::entropy_decode(bs.data(), bs.size(), h, w, back.data(), &wide);
+            unsetenv("TIC_DECODE_SERIAL");
+            if (rc != 0) return fail("wide DC: decode failed", h, w, big * 10 + serial);
+            size_t outside = 0;
+            for (size_t b = 0; b < n; b++) {
+                const int32_t s = run[b] < -32768 ? -32768 : (run[b] > 32767 ? 32767 : run[b]);
+                outside += s != run[b];
+                if (back[b * 64] != (int16_t)s) return fail("wide DC: the int16 layout does not hold the saturated DC", h, (int)b, big * 10 + serial);
+                for (int k = 1; k < 64; k++)
+                    if (back[b * 64 + (size_t)k] != ac[b * 63 + (size_t)k - 1]) return fail("wide DC: an AC coefficient differs", h, (int)b, big * 10 + serial);
+            }
+            if (wide.size() != outside || outside < n / 4) return fail("wide DC: the side list does not name every block outside int16", (int)wide.size(), (int)outside, big * 10 + serial);
+            if (handed_on(back, wide, 0) != run) return fail("wide DC: the DC handed on is not the int32 running sum", h, w, big * 10 + serial);
+            // without a list the call is what it was
+            std::vector<int16_t> plain(n * 64);
+            if (tic::entropy_decode(bs.data(), bs.size(), h, w, plain.data()) != 0 || plain != back) return fail("wide DC: decode without a list differs", h, w, big * 10 + serial);
+            cases++;
+        }
+        if (!big) { // the tail form: from a block boundary in the middle (found by encoding the first blocks alone: same bits), with the sum so far
+            const size_t first = 517;
+            const int hf = 8, wf = 8 * (int)first;
+            std::vector<uint8_t> head(tic::compress_bound(hf, wf));
+            size_t hlen = 0;
+            if (tico_entropy_encode(dc.data(), ac.data(), hf, wf, 50, head.data(), head.size(), &hlen) != 0) return fail("wide DC: encode (head)", hf, wf, 0);
+            // (every block of this stream has the same length: one DC code of category 11 and 63 coefficients of one size)
+            const size_t block_bits = ((len - 16) * 8) / n, pos = 128 + first * block_bits;
+            if ((hlen - 16) * 8 < first * block_bits || (hlen - 16) * 8 >= first * block_bits + 8) return fail("wide DC: blocks of unequal length", (int)hlen, (int)block_bits, 0);
+            std::vector<int16_t> tail((n - first) * 64, (int16_t)0x5A5A);
+            std::vector<tic::DcWide> wide;
+            if (tic::entropy_decode_tail(bs.data(), bs.size(), h, w, first, pos, run[first - 1], tail.data(), &wide) != 0) return fail("wide DC: tail decode failed", h, w, 0);
+            if (handed_on(tail, wide, first) != std::vector<int32_t>(run.begin() + (long)first, run.end())) return fail("wide DC: the tail's DC is not the running sum", h, w, 0);
+            cases++;
+        }
+    }
+    { // ... and a stream whose DC stays inside int16 reports nothing (-32768 and 32767 themselves are inside)
+        const int h = 8, w = 8 * 64;
+        const size_t n = 64;
+        std::vector<int32_t> dc(n, 0), ac(n * 63, 0);
+        for (size_t b = 0; b < 16; b++) dc[b] = 2047;
+        dc[16] = 15;                                   // 32767
+        for (size_t b = 17; b < 49; b++) dc[b] = -2047;
+        dc[49] = -31;                                  // -32768
+        std::vector<uint8_t> bs(tic::compress_bound(h, w));
+        size_t len = 0;
+        if (tico_entropy_encode(dc.data(), ac.data(), h, w, 50, bs.data(), bs.size(), &len) != 0) return fail("edge DC: encode", h, w, 0);
+        bs.resize(len);
+        std::vector<int16_t> back(n * 64);
+        std::vector<tic::DcWide> wide;
+        if (tic::entropy_decode(bs.data(), bs.size(), h, w, back.data(), &wide) != 0 || !wide.empty() || back[16 * 64] != 32767 || back[63 * 64] != -32768)
+            return fail("edge DC: +32767 / -32768 are inside int16", (int)wide.size(), back[16 * 64], back[63 * 64]);
+        cases++;
+    }
     // ---- the device decoder's chain tables (dec_chain_luts_fill): a walk that consumes a chain of symbols per look-up must stand on the
     //      same bits at every EOB as the walk that takes one symbol per look-up (dec_luts_fill's tables: what the device decoder's
     //      fused kernel and rounds 2-3's measure kernel use), from any bit of any stream, in step with the true symbols or not

@@ -161,6 +161,8 @@ struct tic_ctx {
     int ent_lane_max_quality = -1;
     void *d_stream_buf = nullptr;
     size_t d_stream_cap = 0;
+    int32_t *d_dc32 = nullptr;                   // int32 DC of every block of a frame whose running DC left int16 (decode_on_host; idct_kernel's wide-DC form)
+    size_t d_dc32_cap = 0;
     // device Huffman decoder (tic_decompress of long streams): tables, workspace, status
     DecLutsDev *d_dec_luts = nullptr;
     DecWorkspace dec_ws;
@@ -469,6 +471,7 @@ void tic_destroy(tic_ctx *ctx) {
     if (ctx->h_stat) (void)hipHostFree(ctx->h_stat);
     if (ctx->h_zz) (void)hipHostFree(ctx->h_zz);
     if (ctx->d_stream_buf) (void)hipFree(ctx->d_stream_buf);
+    if (ctx->d_dc32) (void)hipFree(ctx->d_dc32);
     if (ctx->d_dec_luts) (void)hipFree(ctx->d_dec_luts);
     ctx->dec_ws.release();
     if (ctx->h_dec_tail) (void)hipHostFree(ctx->h_dec_tail);
@@ -2544,14 +2547,16 @@ static IdctArgs idct_args(const DecIdctArgs &d, const int16_t *coeffs) {
 
 // Inverse stage on coefficients that already sit in ctx->d_coef (int16 [N][64] zig-zag, DC integrated) -> pixels in `out`.
 // quality and scaled_exp as StreamHead.
+// d_dc32 (may be null): the blocks' DC as int32 [N], for a frame whose running DC left int16 (IdctArgs::dc32).
 static int idct_from_device(tic_ctx *ctx, int h, int w, int quality, int scaled_exp, uint8_t *out, bool out_on_device = false,
-                            size_t out_stride = 0) {
+                            size_t out_stride = 0, const int32_t *d_dc32 = nullptr) {
     const size_t pitch = align_up((size_t)w, 256);
     // a device destination whose rows are 8-byte aligned takes the pixels straight from the kernel (its row stores are cropped to w)
     const bool direct = out_on_device && out_stride % 8 == 0 && (uintptr_t)out % 8 == 0;
-    const IdctArgs a = idct_args(dec_idct_args(ctx, h, w, quality, scaled_exp, direct ? out : (uint8_t *)ctx->d_img,
-                                               direct ? (long)out_stride : (long)pitch, nullptr),
-                                 (const int16_t *)ctx->d_coef);
+    IdctArgs a = idct_args(dec_idct_args(ctx, h, w, quality, scaled_exp, direct ? out : (uint8_t *)ctx->d_img,
+                                         direct ? (long)out_stride : (long)pitch, nullptr),
+                           (const int16_t *)ctx->d_coef);
+    a.dc32 = d_dc32;
     HIPCHK(ctx, launch_idct(a, ctx->stream));
     if (!direct)
         HIPCHK(ctx, hipMemcpy2DAsync(out, out_on_device ? out_stride : (size_t)w, ctx->d_img, pitch, (size_t)w, (size_t)h,
@@ -2711,6 +2716,9 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
         if (test_hook("TIC_DECODE_TRACE"))
             fprintf(stderr, "device decoder run %d: range %d margin %d -> giveup %d, m %llu of %zu, pos_out %llu of %zu bits\n", ctx->last_decode_tries, range_bits,
                     margin_bits, st.giveup, st.m, n, st.pos_out, len * 8);
+        // (a whole stream, walked cleanly, whose running DC left int16: no other run decodes it, the host route does.  Beside another bit the DC
+        //  sums are those of a broken chain and say nothing: the tries go on as ever)
+        if (st.giveup == kDecGiveupWideDc) break;
         if ((st.giveup & 4) && range_bits < 2016) { // (a range without a synchronisation point breaks the chain: whatever else was flagged follows from it)
             range_bits = 2016; // (one retry, with the longest range: a stream that trips the first choice has blocks far above its average)
             continue;
@@ -2732,15 +2740,20 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
             tail = big.data();
         }
         const size_t off = len - end_bytes; // the piece of the stream that came down in front of the kernels starts here
+        std::vector<DcWide> wide;
         if (src_on_device && tail_prefetched && (size_t)st.pos_out / 8 >= off) { // (pos_out >= 8 len - 2048: always inside that piece)
-            entropy_decode_tail(ctx->h_dec_tail, end_bytes, h, w, (size_t)st.m, (size_t)st.pos_out - off * 8, st.dc_out, tail);
+            entropy_decode_tail(ctx->h_dec_tail, end_bytes, h, w, (size_t)st.m, (size_t)st.pos_out - off * 8, st.dc_out, tail, &wide);
         } else if (src_on_device) {
             const size_t o2 = (size_t)st.pos_out / 8;
             std::vector<uint8_t> end(len - o2);
             HIPCHK(ctx, hipMemcpy(end.data(), (const char *)data + o2, len - o2, hipMemcpyDeviceToHost));
-            entropy_decode_tail(end.data(), len - o2, h, w, (size_t)st.m, (size_t)st.pos_out - o2 * 8, st.dc_out, tail);
+            entropy_decode_tail(end.data(), len - o2, h, w, (size_t)st.m, (size_t)st.pos_out - o2 * 8, st.dc_out, tail, &wide);
         } else {
-            entropy_decode_tail(data, len, h, w, (size_t)st.m, (size_t)st.pos_out, st.dc_out, tail);
+            entropy_decode_tail(data, len, h, w, (size_t)st.m, (size_t)st.pos_out, st.dc_out, tail, &wide);
+        }
+        if (!wide.empty()) { // the running DC leaves int16 in the tail only: the host route, as if the kernel had met it
+            ctx->last_decode_giveup = kDecGiveupWideDc;
+            return TIC_OK;
         }
         HIPCHK(ctx, hipMemcpyAsync((char *)ctx->d_coef + (size_t)st.m * 128, tail, tail_bytes, hipMemcpyHostToDevice, ctx->stream));
         IdctArgs a = idct_args(ia, (const int16_t *)ctx->d_coef);
@@ -2819,12 +2832,26 @@ static int decode_on_host(tic_ctx *ctx, const uint8_t *data, size_t len, const S
     // runs at PCIe speed instead of through the runtime's staging of pageable memory
     int rc = grow_pinned(ctx, ctx->h_zz, ctx->h_zz_bytes, n * 128);
     if (rc) return rc;
-    entropy_decode(data, len, sh.h, sh.w, ctx->h_zz);
+    std::vector<DcWide> wide;
+    entropy_decode(data, len, sh.h, sh.w, ctx->h_zz, &wide);
     ctx->last_decode_path = 2;
     rc = ensure_scratch(ctx, align_up((size_t)sh.w, 256) * (size_t)sh.h, n * 128);
     if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, ctx->h_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
-    return idct_from_device(ctx, sh.h, sh.w, sh.quality, sh.scaled_exp, out, out_on_device, out_stride);
+    // The running DC left int16 somewhere (np.cumsum keeps int32, codec.py:53, and the reference transforms what it holds): the int16
+    // layout holds the saturated value, so every block's DC goes up once more as int32 and the wide-DC form of idct_kernel reads it
+    // from there.  No stream of our encoders comes here (their DC is an int16 coefficient).
+    const int32_t *d_dc32 = nullptr;
+    if (!wide.empty()) {
+        std::vector<int32_t> dc32(n);
+        for (size_t b = 0; b < n; b++) dc32[b] = ctx->h_zz[b * 64];
+        for (const DcWide &x : wide) dc32[x.block] = x.dc;
+        rc = grow_dev(ctx, ctx->d_dc32, ctx->d_dc32_cap, n * sizeof(int32_t));
+        if (rc) return rc;
+        HIPCHK(ctx, hipMemcpy(ctx->d_dc32, dc32.data(), n * sizeof(int32_t), hipMemcpyHostToDevice)); // (pageable, synchronous: dc32 dies with this scope)
+        d_dc32 = ctx->d_dc32;
+    }
+    return idct_from_device(ctx, sh.h, sh.w, sh.quality, sh.scaled_exp, out, out_on_device, out_stride, d_dc32);
 }
 
 int tic_decompress(tic_ctx *ctx, const uint8_t *data, size_t len, uint8_t *out, size_t cap) {

@@ -367,6 +367,12 @@ inline bool read_int(BitReader &r, int size, int &out) {
 }
 
 inline int16_t sat16(int v) { return (int16_t)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
+// the integrated DC of block b: saturated into the int16 layout, and noted with its true value where that changed it
+inline int16_t dc16(int running_dc, size_t b, std::vector<DcWide> *wide) {
+    const int16_t s = sat16(running_dc);
+    if (wide && (int)s != running_dc) wide->push_back({b, (int32_t)running_dc});
+    return s;
+}
 
 // One symbol and its value bits (huffman.py:77-98).  While 64 bits remain, a single 32-bit peek covers the codeword
 // (<= 16 bits) and the value (<= 15 bits); otherwise, and for prefixes that are no codeword, the bit-serial readers
@@ -464,7 +470,7 @@ inline bool block_fast(const EncTables &T, const uint8_t *p, size_t pos0, int16_
 // a block of more than 63 coefficients) makes the function give up, and the caller decodes serially as before: malformed
 // streams keep the reference's quirks.  Returns the number of blocks decoded (0: not attempted / given up) and the read
 // position and running DC behind them.
-size_t decode_parallel(const EncTables &T, const uint8_t *data, size_t nbits, size_t n, int16_t *zz, size_t &pos_out, int &dc_out) {
+size_t decode_parallel(const EncTables &T, const uint8_t *data, size_t nbits, size_t n, int16_t *zz, size_t &pos_out, int &dc_out, std::vector<DcWide> *wide) {
     const size_t first_bit = 128;
     if (n < 16384 || nbits < first_bit + (1u << 21) || test_hook("TIC_DECODE_SERIAL")) return 0; // (tic_hooks.h: off unless TIC_TEST_HOOKS=1)
     unsigned hw = std::thread::hardware_concurrency();
@@ -581,6 +587,7 @@ size_t decode_parallel(const EncTables &T, const uint8_t *data, size_t nbits, si
         for (size_t b = 0; b < m; b++) {
             acc += dcd[b];
             run[b] = acc;
+            if (wide && acc != (int)sat16(acc)) wide->push_back({b, (int32_t)acc}); // (the threads below store the saturated value)
         }
     }
     // (C)
@@ -618,7 +625,7 @@ size_t decode_parallel(const EncTables &T, const uint8_t *data, size_t nbits, si
 namespace {
 // The serial decoder from block b_first at read position r.pos with running DC `running_dc`: blocks [b_first, n) into zz (zeroed
 // here), zz indexed from block b_first (zz points at block b_first).
-void decode_serial_from(const EncTables &T, BitReader &r, int running_dc, size_t b_first, size_t n, int16_t *zz) {
+void decode_serial_from(const EncTables &T, BitReader &r, int running_dc, size_t b_first, size_t n, int16_t *zz, std::vector<DcWide> *wide) {
     memset(zz, 0, (n - b_first) * 64 * sizeof(int16_t));
     for (size_t b = b_first; b < n; b++) {
         int16_t *c = zz + (b - b_first) * 64;
@@ -632,7 +639,7 @@ void decode_serial_from(const EncTables &T, BitReader &r, int running_dc, size_t
             size_t used;
             if (block_fast<true>(T, r.p, r.pos, c, d, used)) {
                 running_dc += d;
-                c[0] = sat16(running_dc);
+                c[0] = dc16(running_dc, b, wide);
                 r.pos += used;
                 continue;
             }
@@ -640,7 +647,7 @@ void decode_serial_from(const EncTables &T, BitReader &r, int running_dc, size_t
         }
         bool have_dc = read_symbol(r, T.dcd, sym, v);
         if (have_dc) running_dc += v;
-        c[0] = sat16(running_dc);
+        c[0] = dc16(running_dc, b, wide);
         if (!have_dc) continue; // exception before the AC loop: block stays zero (codec.py:185-186)
         int16_t tmp[1100];
         int m = 0;
@@ -668,33 +675,38 @@ void decode_serial_from(const EncTables &T, BitReader &r, int running_dc, size_t
 }
 } // namespace
 
-int entropy_decode(const uint8_t *data, size_t len, int h, int w, int16_t *zz) {
+int entropy_decode(const uint8_t *data, size_t len, int h, int w, int16_t *zz, std::vector<DcWide> *wide) {
     const EncTables &T = tables();
     const size_t n = num_blocks(h, w);
     BitReader r{data, len * 8, 128};
     int running_dc = 0; // np.cumsum(dc), codec.py:53
     size_t b_first = 0;
+    if (wide) wide->clear();
     {
         size_t pos = 0;
         int dc = 0;
-        const size_t done = decode_parallel(T, data, len * 8, n, zz, pos, dc); // zeroes and fills blocks [0, done)
+        const size_t done = decode_parallel(T, data, len * 8, n, zz, pos, dc, wide); // zeroes and fills blocks [0, done)
         if (done) {
             b_first = done;
             r.pos = pos;
             running_dc = dc;
+        } else if (wide) {
+            wide->clear(); // (an attempt that gave up behind its DC sum)
         }
     }
-    decode_serial_from(T, r, running_dc, b_first, n, zz + b_first * 64); // (everything, if the parallel attempt gave up)
+    decode_serial_from(T, r, running_dc, b_first, n, zz + b_first * 64, wide); // (everything, if the parallel attempt gave up)
     return TIC_OK;
 }
 
 // Blocks [first_block, n) from read position pos_bits with running DC `running_dc` (what the device decoder leaves to the host:
 // the blocks that start in the last 2048 bits of the stream) into zz_tail, which holds n - first_block blocks.
-int entropy_decode_tail(const uint8_t *data, size_t len, int h, int w, size_t first_block, size_t pos_bits, int running_dc, int16_t *zz_tail) {
+int entropy_decode_tail(const uint8_t *data, size_t len, int h, int w, size_t first_block, size_t pos_bits, int running_dc, int16_t *zz_tail,
+                        std::vector<DcWide> *wide) {
     const size_t n = num_blocks(h, w);
+    if (wide) wide->clear();
     if (first_block >= n) return TIC_OK;
     BitReader r{data, len * 8, pos_bits};
-    decode_serial_from(tables(), r, running_dc, first_block, n, zz_tail);
+    decode_serial_from(tables(), r, running_dc, first_block, n, zz_tail, wide);
     return TIC_OK;
 }
 

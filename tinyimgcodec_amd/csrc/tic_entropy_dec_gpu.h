@@ -79,6 +79,11 @@ struct DecLutsDev {
     uint32_t long32[192 + 4];
 };
 
+// DecStatus::giveup bit: the integrated DC of a block does not fit int16.  np.cumsum keeps the running DC as int32 (codec.py:53) and
+// the reference transforms what it holds; the fused kernel's LDS image and the int16 layout hold the saturated value, so the whole
+// stream goes to the host route, whose inverse stage takes the true DC from an int32 side array (tic_entropy.h DcWide).
+constexpr int kDecGiveupWideDc = 512;
+
 struct DecStatus {
     int giveup;                 // != 0: something unusual on the true chain - the caller decodes the whole stream on the host
     int dc_out;                 // running DC behind the last block produced here

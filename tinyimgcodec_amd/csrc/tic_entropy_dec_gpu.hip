@@ -751,6 +751,9 @@ __device__ __forceinline__ void decode_idct_body(const uint32_t *__restrict__ gw
             const long long dc = part + dc_inc; // sum of the differences of blocks 0..b
             const int32_t dc32 = (int32_t)dc;   // (the host decoder's long long, narrowed where it is used)
             c[0] = (int16_t)(dc32 < -32768 ? -32768 : (dc32 > 32767 ? 32767 : dc32)); // the host decoder's sat16
+            // ... which is NOT what the reference transforms: np.cumsum keeps int32 (codec.py:53).  The image holds int16, so such a stream
+            // (no encoder of ours writes one) goes to the host route, whose inverse stage takes the int32 DC from a side array
+            if ((int32_t)c[0] != dc32) atomicOr(&st->giveup, kDecGiveupWideDc);
             if (b == m - 1) st->dc_out = (int)dc32; // running DC behind the last block produced here (the host's tail continues from it)
         }
     }

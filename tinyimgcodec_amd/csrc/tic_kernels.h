@@ -77,6 +77,10 @@ struct IdctArgs {
     // sit at their places in `coeffs`; every other block's pixels come from the fused decode kernel).
     long first_block = -1;
     long nblocks_sel = 0;
+    // Wide-DC form (dc32 != null): block b's DC is dc32[b], not coeffs[b * 64] - the integrated DC of a stream whose running sum left
+    // int16 (np.cumsum keeps int32, codec.py:53; the int16 layout holds the saturated value).  A kernel of its own, launched for such
+    // frames only: idct_kernel itself is unchanged.
+    const int32_t *dc32 = nullptr;
 };
 
 // C-ABI kernel selector (TIC_KERNEL_AUTO / _EXACT / _HYBRID) -> launch_dctq's variant (1 exact, 2 strip kernel), -1 for anything else.

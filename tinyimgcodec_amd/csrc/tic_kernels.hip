@@ -886,7 +886,9 @@ __constant__ int kAnnScalesInt[64] = {
     16384, 22725, 21407, 19266, 16384, 12873, 8867,  4520,  12873, 17855, 16819, 15137, 12873, 10114, 6967,  3552,
     8867,  12299, 11585, 10426, 8867,  6967,  4799,  2446,  4520,  6270,  5906,  5315,  4520,  3552,  2446,  1247};
 
-__global__ __launch_bounds__(kWavesPerWG * 64) void idct_kernel(IdctArgs a) {
+// kWideDc: the DC comes from a.dc32 (IdctArgs: a stream whose running DC left int16), everything else as ever
+template <bool kWideDc>
+__device__ __forceinline__ void idct_body(const IdctArgs &a) {
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[kWavesPerWG][kLdsWaveBytes / 4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = lane >> 3, i = lane & 7;
@@ -926,6 +928,10 @@ __global__ __launch_bounds__(kWavesPerWG * 64) void idct_kernel(IdctArgs a) {
         else
             c[u] = (double)cv * C->div[u * 8 + i]; // coeffs * (Q*factor/100)
     }
+    if (kWideDc && i == 0 && s.valid) { // the same expressions on the int32 value (exact in float64, like the int16 one)
+        const double dcv = (double)a.dc32[s.oblk];
+        c[0] = a.scaled ? ((dcv / ((double)kAnnScalesInt[0] / 2048.0)) * a.pow2) * C->div[0] : dcv * C->div[0];
+    }
     wave_lds_fence();
     idct8_exact(c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]); // axis -2
     uint32_t w[8], wh[8];
@@ -962,6 +968,8 @@ __global__ __launch_bounds__(kWavesPerWG * 64) void idct_kernel(IdctArgs a) {
             if (x0 + k < a.w) p[k] = (uint8_t)px[k];
     }
 }
+__global__ __launch_bounds__(kWavesPerWG * 64) void idct_kernel(IdctArgs a) { idct_body<false>(a); }
+__global__ __launch_bounds__(kWavesPerWG * 64) void idct_wide_dc_kernel(IdctArgs a) { idct_body<true>(a); }
 
 // ---------------------------------------------------------------------------------------------------------
 // Self-test kernel: checks the DPP byte transpose against the shuffle formulation on arbitrary data.
@@ -1186,7 +1194,8 @@ hipError_t launch_dctq_wide(const WideArgs &a, hipStream_t stream) {
 hipError_t launch_idct(const IdctArgs &a, hipStream_t stream) {
     if (a.ntiles <= 0) return hipSuccess;
     dim3 grid(grid_for(a.ntiles)), block(kWavesPerWG * 64);
-    hipLaunchKernelGGL(idct_kernel, grid, block, 0, stream, a);
+    if (a.dc32) hipLaunchKernelGGL(idct_wide_dc_kernel, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(idct_kernel, grid, block, 0, stream, a);
     return hipGetLastError();
 }
 
