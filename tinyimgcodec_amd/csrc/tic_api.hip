@@ -112,8 +112,7 @@ struct tic_ctx {
     double custom_quality = 0.0;      // what slot 0 holds (0: nothing yet)
     unsigned long long *d_fallback = nullptr;
     bool stats = false; // count guard-band fallbacks with a global atomic (diagnostic; serialises at ~12 ns per wave)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<hipEvent_t> ev_steps; // tic_dctq_dev_timed_warm with per-launch times: one event behind every timed launch
+    hipEvent_t ev0 = nullptr, ev1 = nullptr; // the interval of the timed entry points (timed_launches)
     // scratch for the host-buffer entry points
     void *d_img = nullptr;
     size_t d_img_cap = 0;
@@ -445,8 +444,6 @@ void tic_destroy(tic_ctx *ctx) {
     }
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    for (auto &e : ctx->ev_steps)
-        if (e) (void)hipEventDestroy(e);
     if (ctx->d_img) (void)hipFree(ctx->d_img);
     if (ctx->d_coef) (void)hipFree(ctx->d_coef);
     if (ctx->d_consts) (void)hipFree(ctx->d_consts);
@@ -789,6 +786,22 @@ int tic_dctq_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_
     return TIC_OK;
 }
 
+// Multi-frame form of a launch (DctqArgs and ScaledArgs alike): frame f's pixels lie f * frame_stride bytes behind the first frame's, its
+// coefficients f * coeff_frame_stride bytes behind the first frame's.
+extern "C++" { // (a template inside the C-ABI block)
+template <class Args>
+static int set_frames(tic_ctx *ctx, Args &a, int nframes, int h, int w, ptrdiff_t row_stride, ptrdiff_t frame_stride, ptrdiff_t coeff_frame_stride) {
+    if (nframes > 65535) return set_err(ctx, TIC_E_ARG, "at most 65535 frames per launch");
+    if (frame_stride < (ptrdiff_t)h * row_stride || coeff_frame_stride < (ptrdiff_t)(num_blocks(h, w) * 128))
+        return set_err(ctx, TIC_E_ARG, "frame strides smaller than one frame");
+    a.aligned8 = a.aligned8 && ((frame_stride & 7) == 0);
+    a.nframes = nframes;
+    a.frame_stride_in = (long)frame_stride;
+    a.frame_stride_out = (long)coeff_frame_stride;
+    return TIC_OK;
+}
+}
+
 int tic_dctq_dev_frames(tic_ctx *ctx, const void *d_images, int nframes, int h, int w, ptrdiff_t row_stride,
                         ptrdiff_t frame_stride, int quality, void *d_coeffs_zz, ptrdiff_t coeff_frame_stride, int variant) {
     TIC_LOCK(ctx);
@@ -797,20 +810,55 @@ int tic_dctq_dev_frames(tic_ctx *ctx, const void *d_images, int nframes, int h, 
     if (nframes < 0) return set_err(ctx, TIC_E_ARG, "negative frame count");
     if (h == 0 || w == 0 || nframes == 0) return TIC_OK;
     if (!d_images || !d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "null device pointer");
-    if (nframes > 65535) return set_err(ctx, TIC_E_ARG, "at most 65535 frames per launch");
-    if (frame_stride < (ptrdiff_t)h * row_stride || coeff_frame_stride < (ptrdiff_t)(num_blocks(h, w) * 128))
-        return set_err(ctx, TIC_E_ARG, "frame strides smaller than one frame");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     DctqArgs a = make_args(ctx, d_images, h, w, row_stride, quality, d_coeffs_zz);
-    a.aligned8 = a.aligned8 && ((frame_stride & 7) == 0);
-    a.nframes = nframes;
-    a.frame_stride_in = (long)frame_stride;
-    a.frame_stride_out = (long)coeff_frame_stride;
+    rc = set_frames(ctx, a, nframes, h, w, row_stride, frame_stride, coeff_frame_stride);
+    if (rc) return rc;
     merge_frames(a);
     const int v = dctq_kernel_id(variant);
     if (v < 0) return set_err(ctx, TIC_E_ARG, "unknown kernel variant %d", variant);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, launch_dctq(a, v, ctx->stream));
     return TIC_OK;
+}
+
+// The timed entry points' submission: `warm` untimed launches, an event, `iters` timed launches, an event - ONE submission, nothing
+// between the warm-up and the first event that the host waits for.  The first event is therefore stamped when the last warm-up launch
+// retires, with the timed launches already in the queue behind it; recorded on an IDLE stream (warm = 0 after a synchronisation) it is
+// stamped at once and the interval opens with whatever the host needs to get the first launch to the device - 28 us on the driver's box
+// in round 5, 1.4 us per step at K = 20 (profiles/r06_driver_flags.txt).  *ms_total = the time between the two events.
+// launch(i, ev_start, ev_stop) queues launch i of its phase (warm-up or timed) on the context's stream and returns a hipError_t.
+// per_launch_ms: NULL, or room for 2 * iters floats.  Then every timed launch is handed a start and a stop event for its OWN dispatch
+// packet (hipExtLaunchKernelGGL: the packet's time stamps, no marker packet between the launches - an event recorded behind every
+// launch costs 3 us per launch) and per_launch_ms[2 i] = duration of launch i, per_launch_ms[2 i + 1] = the time between the start
+// of the first timed launch and the end of launch i.  These events live for this call alone - created before the warm-up, destroyed
+// on every way out - so a launch that does not bind them (the exact kernel, a banded frame) leaves them never recorded and the call
+// reports TIC_E_ARG, whatever an earlier call on the context measured.
+extern "C++" {
+template <class Launch>
+static int timed_launches(tic_ctx *ctx, int warm, int iters, float *ms_total, float *per_launch_ms, Launch launch) {
+    struct Events {
+        std::vector<hipEvent_t> v;
+        ~Events() {
+            for (hipEvent_t e : v)
+                if (e) (void)hipEventDestroy(e);
+        }
+    } ev;
+    ev.v.assign(per_launch_ms ? 2 * (size_t)iters : 0, nullptr);
+    for (hipEvent_t &e : ev.v) HIPCHK(ctx, hipEventCreate(&e));
+    for (int i = 0; i < warm; i++) HIPCHK(ctx, launch(i, nullptr, nullptr));
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    for (int i = 0; i < iters; i++) HIPCHK(ctx, launch(i, per_launch_ms ? ev.v[2 * i] : nullptr, per_launch_ms ? ev.v[2 * i + 1] : nullptr));
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev1));
+    HIPCHK(ctx, hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));
+    for (int i = 0; per_launch_ms && i < iters; i++)
+        if (hipEventElapsedTime(per_launch_ms + 2 * i, ev.v[2 * i], ev.v[2 * i + 1]) != hipSuccess ||
+            hipEventElapsedTime(per_launch_ms + 2 * i + 1, ev.v[0], ev.v[2 * i + 1]) != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(ctx, TIC_E_ARG, "per-launch times need a frame that takes the strip kernel in one launch");
+        }
+    return TIC_OK;
+}
 }
 
 int tic_dctq_dev_timed(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, int quality,
@@ -820,26 +868,13 @@ int tic_dctq_dev_timed(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_
     if (rc) return rc;
     if (!ms_total || iters < 1 || !d_image || !d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "bad argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    DctqArgs a = make_args(ctx, d_image, h, w, row_stride, quality, d_coeffs_zz);
+    const DctqArgs a = make_args(ctx, d_image, h, w, row_stride, quality, d_coeffs_zz);
     const int v = dctq_kernel_id(variant);
     if (v < 0) return set_err(ctx, TIC_E_ARG, "unknown kernel variant %d", variant);
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int i = 0; i < iters; i++) HIPCHK(ctx, launch_dctq(a, v, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev1));
-    HIPCHK(ctx, hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));
-    return TIC_OK;
+    return timed_launches(ctx, 0, iters, ms_total, nullptr, [&](int, hipEvent_t e0, hipEvent_t e1) { return launch_dctq(a, v, ctx->stream, e0, e1); });
 }
 
-// The benchmark's form of the timed entry: `warm` untimed launches, an event, `iters` timed launches, an event - ONE submission,
-// nothing between the warm-up and the first event that the host waits for.  The first event is therefore stamped when the last
-// warm-up launch retires, with the timed launches already in the queue behind it; recorded on an IDLE stream (tic_dctq_dev_timed
-// after a synchronisation) it is stamped at once and the interval opens with whatever the host needs to get the first launch to
-// the device - 28 us on the driver's box in round 5, 1.4 us per step at K = 20 (profiles/r06_driver_flags.txt).
-// per_launch_ms: NULL, or room for 2 * iters floats.  Then every timed launch carries a start and a stop event on its OWN dispatch
-// packet (hipExtLaunchKernelGGL: the packet's time stamps, no marker packet between the launches - an event recorded behind every
-// launch costs 3 us per launch) and per_launch_ms[2 i] = duration of launch i, per_launch_ms[2 i + 1] = the time between the start
-// of the first timed launch and the end of launch i.
+// The benchmark's form of the timed entry: warm-up launches in front of the interval and, on request, per-launch times (timed_launches).
 int tic_dctq_dev_timed_warm(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, int quality, void *d_coeffs_zz,
                             int variant, int warm, int iters, float *ms_total, float *per_launch_ms) {
     TIC_LOCK(ctx);
@@ -848,36 +883,11 @@ int tic_dctq_dev_timed_warm(tic_ctx *ctx, const void *d_image, int h, int w, ptr
     if (!ms_total || iters < 1 || warm < 0 || !d_image || !d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "bad argument");
     if (per_launch_ms && iters > 32768) return set_err(ctx, TIC_E_ARG, "per-launch times for at most 32768 launches");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    DctqArgs a = make_args(ctx, d_image, h, w, row_stride, quality, d_coeffs_zz);
+    const DctqArgs a = make_args(ctx, d_image, h, w, row_stride, quality, d_coeffs_zz);
     const int v = dctq_kernel_id(variant);
     if (v < 0) return set_err(ctx, TIC_E_ARG, "unknown kernel variant %d", variant);
-    if (per_launch_ms)
-        while ((int)ctx->ev_steps.size() < 2 * iters) {
-            hipEvent_t e = nullptr;
-            HIPCHK(ctx, hipEventCreate(&e));
-            ctx->ev_steps.push_back(e);
-        }
-    for (int i = 0; i < warm; i++) HIPCHK(ctx, launch_dctq(a, v, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int i = 0; i < iters; i++) {
-        if (per_launch_ms)
-            HIPCHK(ctx, launch_dctq(a, v, ctx->stream, ctx->ev_steps[2 * i], ctx->ev_steps[2 * i + 1]));
-        else
-            HIPCHK(ctx, launch_dctq(a, v, ctx->stream));
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev1));
-    HIPCHK(ctx, hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));
-    if (per_launch_ms)
-        for (int i = 0; i < iters; i++) {
-            // (a frame that does not take the strip kernel - padded strips only, bands - leaves its events unrecorded: reported as such)
-            if (hipEventElapsedTime(per_launch_ms + 2 * i, ctx->ev_steps[2 * i], ctx->ev_steps[2 * i + 1]) != hipSuccess ||
-                hipEventElapsedTime(per_launch_ms + 2 * i + 1, ctx->ev_steps[0], ctx->ev_steps[2 * i + 1]) != hipSuccess) {
-                (void)hipGetLastError();
-                return set_err(ctx, TIC_E_ARG, "per-launch times need a frame that takes the strip kernel in one launch");
-            }
-        }
-    return TIC_OK;
+    return timed_launches(ctx, warm, iters, ms_total, per_launch_ms,
+                          [&](int, hipEvent_t e0, hipEvent_t e1) { return launch_dctq(a, v, ctx->stream, e0, e1); });
 }
 
 // Batch form of the timed entry: `iters` back-to-back launches of the batched transform (nframes frames per launch).
@@ -890,21 +900,12 @@ int tic_dctq_dev_frames_timed(tic_ctx *ctx, const void *d_images, int nframes, i
     if (!ms_total || iters < 1 || nframes < 1 || nframes > 65535 || !d_images || !d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "bad argument");
     const int v = dctq_kernel_id(variant);
     if (v < 0) return set_err(ctx, TIC_E_ARG, "unknown kernel variant %d", variant);
-    if (frame_stride < (ptrdiff_t)h * row_stride || coeff_frame_stride < (ptrdiff_t)(num_blocks(h, w) * 128))
-        return set_err(ctx, TIC_E_ARG, "frame strides smaller than one frame");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     DctqArgs a = make_args(ctx, d_images, h, w, row_stride, quality, d_coeffs_zz);
-    a.aligned8 = a.aligned8 && ((frame_stride & 7) == 0);
-    a.nframes = nframes;
-    a.frame_stride_in = (long)frame_stride;
-    a.frame_stride_out = (long)coeff_frame_stride;
+    rc = set_frames(ctx, a, nframes, h, w, row_stride, frame_stride, coeff_frame_stride);
+    if (rc) return rc;
     merge_frames(a);
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int i = 0; i < iters; i++) HIPCHK(ctx, launch_dctq(a, v, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev1));
-    HIPCHK(ctx, hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));
-    return TIC_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return timed_launches(ctx, 0, iters, ms_total, nullptr, [&](int, hipEvent_t e0, hipEvent_t e1) { return launch_dctq(a, v, ctx->stream, e0, e1); });
 }
 
 // Cold-cache form of the timed entry: launch i works on pair i % npairs of (image, coefficient buffer).  With enough
@@ -921,15 +922,9 @@ int tic_dctq_dev_timed_rotating(tic_ctx *ctx, const void *const *d_images, void 
     for (int k = 0; k < npairs; k++)
         if (!d_images[k] || !d_coeffs_zz[k]) return set_err(ctx, TIC_E_ARG, "null device pointer in pair %d", k);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int i = 0; i < iters; i++) {
-        DctqArgs a = make_args(ctx, d_images[i % npairs], h, w, row_stride, quality, d_coeffs_zz[i % npairs]);
-        HIPCHK(ctx, launch_dctq(a, v, ctx->stream));
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev1));
-    HIPCHK(ctx, hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));
-    return TIC_OK;
+    return timed_launches(ctx, 0, iters, ms_total, nullptr, [&](int i, hipEvent_t e0, hipEvent_t e1) {
+        return launch_dctq(make_args(ctx, d_images[i % npairs], h, w, row_stride, quality, d_coeffs_zz[i % npairs]), v, ctx->stream, e0, e1);
+    });
 }
 
 // Device entropy stage: pack with a lane per block (max_quality >= 1: for qualities up to it, with the automatic fall-back to the
@@ -992,6 +987,18 @@ static int ensure_scratch(tic_ctx *ctx, size_t img_bytes, size_t coef_bytes) {
     return rc ? rc : grow_dev(ctx, ctx->d_coef, ctx->d_coef_cap, coef_bytes);
 }
 
+// Every host-image entry point brings its frame to the device here: the n blocks' uint8 pixels into the context's scratch image, rows
+// padded to *pitch (a multiple of 256 bytes), queued on the context's stream; the coefficient workspace is provisioned beside it (with
+// the 16 bytes of slack that the stream entry points provision for it).
+static int upload_image(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, size_t n, size_t *pitch) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    *pitch = align_up((size_t)w, 256);
+    const int rc = ensure_scratch(ctx, *pitch * (size_t)h, n * 128 + 16);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_img, *pitch, image, (size_t)row_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    return TIC_OK;
+}
+
 int tic_dctq(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int quality, int16_t *coeffs_zz) {
     TIC_LOCK(ctx);
     int rc = check_geometry(ctx, h, w, row_stride, quality);
@@ -999,12 +1006,9 @@ int tic_dctq(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_str
     const size_t n = num_blocks(h, w);
     if (n == 0) return TIC_OK;
     if (!image || !coeffs_zz) return set_err(ctx, TIC_E_ARG, "null host pointer");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t pitch = align_up((size_t)w, 256);
-    rc = ensure_scratch(ctx, pitch * (size_t)h, n * 128);
+    size_t pitch = 0;
+    rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
     if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_img, pitch, image, (size_t)row_stride, (size_t)w, (size_t)h,
-                                 hipMemcpyHostToDevice, ctx->stream));
     DctqArgs a = make_args(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, quality, ctx->d_coef);
     HIPCHK(ctx, launch_dctq(a, 2, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(coeffs_zz, ctx->d_coef, n * 128, hipMemcpyDeviceToHost, ctx->stream));
@@ -1083,8 +1087,59 @@ int tic_parse_header(const uint8_t *data, size_t len, int *h, int *w, int *quali
     return parse_header(data, len, h, w, quality, flag);
 }
 
-// Device entropy stage: coefficients in HBM -> finished stream in HBM.  Synchronous (the stream length is needed
-// on the host between the counting and the packing step).
+// ---- device entropy stage: what its entry points share ------------------------------------------------------------------------------
+// A stream's destination in device memory: room for a header (and the scaled form's flush byte), 16-byte aligned for the placing kernel.
+static int check_dev_out(tic_ctx *ctx, const void *d_out, size_t cap, size_t min_cap) {
+    if (!d_out || cap < min_cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
+    if (((uintptr_t)d_out & 15u) != 0) return set_err(ctx, TIC_E_ARG, "device output buffer must be 16-byte aligned");
+    return TIC_OK;
+}
+
+// The stream of an image without blocks, queued on the context's stream: 16 bytes of header (codec.py:151) and, for a scaled-DCT stream,
+// the byte BB_flushBits writes with nothing pending (17 bytes).
+static int put_header_only(tic_ctx *ctx, void *d_out, int h, int w, int quality, bool scaled) {
+    uint8_t hdr[17] = {0};
+    if (scaled)
+        write_header_scaled(hdr, h, w, quality);
+    else
+        write_header(hdr, h, w, quality);
+    HIPCHK(ctx, hipMemcpyAsync(d_out, hdr, scaled ? 17 : 16, hipMemcpyHostToDevice, ctx->stream));
+    return TIC_OK;
+}
+
+// Pack and place on the context's own workspace and stream: the n blocks at d_zz -> the stream at d_out, which holds `cap` bytes; the
+// placing kernel writes the header and puts {payload bits, error} into the host-mapped status block; nothing is written past the
+// caller's buffer.  The context's two error flags are used in turn (tic_entropy_gpu.h).
+static hipError_t pack_and_place(tic_ctx *ctx, const void *d_zz, size_t n, int h, int w, int quality, void *d_out, size_t cap, int mode,
+                                 uint32_t flag) {
+    const int par = ctx->ent_parity;
+    ctx->ent_parity ^= 1;
+    const size_t cap_words = ((cap - 16) / 16) * 4; // whole 16-byte units behind the header
+    return entropy_gpu_fused((const int16_t *)d_zz, n, 1, ctx->d_huff, ctx->d_ent_work, ctx->ent_work_bytes, d_out, 0, cap_words, h, w, quality,
+                             nullptr, ctx->d_stat, ctx->d_err + par, ctx->d_err + (par ^ 1), mode, ctx->stream, nullptr, nullptr, flag);
+}
+
+// What a placing kernel left in a {payload bits, error} pair of the host-mapped status block (read behind the kernel's completion), and
+// what that means for a caller whose buffer holds `cap` bytes: TIC_OK and the stream's length, TIC_E_RANGE, or TIC_E_SPACE.
+struct StreamStatus {
+    unsigned long long bits;
+    int err;
+};
+static StreamStatus read_status(const unsigned long long *h_pair) {
+    const volatile unsigned long long *p = h_pair;
+    return {p[0], (int)(p[1] & 0xffffffffull)};
+}
+static int stream_result(tic_ctx *ctx, StreamStatus st, size_t cap, bool scaled, size_t *out_len) {
+    if (st.err == 1) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code (reference raises KeyError)");
+    const size_t payload = scaled ? (size_t)(st.bits / 8) + 1 : (size_t)((st.bits + 7) / 8); // (scaled: BB_flushBits' byte)
+    if (st.err == 2 || 16 + payload > cap)
+        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed)", 16 + (size_t)((payload + 3) / 4) * 4);
+    *out_len = 16 + payload;
+    return TIC_OK;
+}
+
+// Device entropy stage: coefficients in HBM -> finished stream in HBM, three launches (pack: one walk over the symbols, tile sums,
+// place), no host round trip and no copy.  Synchronous: the call returns the stream's length.
 // scaled: the stream of the reference's integer encoder (tic_entropy_gpu.h: flag 1 << 30, setting 0..3 in the quality field, flush byte).
 static int entropy_encode_dev_impl(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, int quality, void *d_out, size_t cap,
                                    size_t *out_len, bool scaled) {
@@ -1095,50 +1150,31 @@ static int entropy_encode_dev_impl(tic_ctx *ctx, const void *d_coeffs_zz, int h,
         if (quality < 0 || quality > 3) return set_err(ctx, TIC_E_QUALITY, "scaled-DCT setting %d outside 0..3", quality);
     } else if (quality < 1 || quality > 99)
         return set_err(ctx, TIC_E_QUALITY, "quality %d outside 1..99", quality);
-    if (!d_out || cap < (scaled ? 17u : 16u)) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
-    if (((uintptr_t)d_out & 15u) != 0) return set_err(ctx, TIC_E_ARG, "device output buffer must be 16-byte aligned");
+    int rc = check_dev_out(ctx, d_out, cap, scaled ? 17 : 16);
+    if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t n = num_blocks(h, w);
     if (n == 0) {
-        uint8_t hdr[17] = {0};
-        if (scaled)
-            write_header_scaled(hdr, h, w, quality); // ... and BB_flushBits with nothing pending: hdr[16] = 0
-        else
-            write_header(hdr, h, w, quality);
-        HIPCHK(ctx, hipMemcpyAsync(d_out, hdr, scaled ? 17 : 16, hipMemcpyHostToDevice, ctx->stream));
+        rc = put_header_only(ctx, d_out, h, w, quality, scaled);
+        if (rc) return rc;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         *out_len = scaled ? 17 : 16;
         return TIC_OK;
     }
     if (!d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "null coefficient pointer");
-    const int rc = grow_dev(ctx, ctx->d_ent_work, ctx->ent_work_bytes, entropy_fused_work_bytes(n));
+    rc = grow_dev(ctx, ctx->d_ent_work, ctx->ent_work_bytes, entropy_fused_work_bytes(n));
     if (rc) return rc;
-    // three launches, no host round trip and no copy: pack (one walk over the symbols), tile sums, place; the placing kernel
-    // writes the header and puts {payload bits, error} into the host-mapped status block; nothing is written past the
-    // caller's buffer
-    const size_t cap_words = ((cap - 16) / 16) * 4; // whole 16-byte units behind the header
-    unsigned long long total_bits = 0;
-    int err = 0;
+    StreamStatus st = {0, 0};
     for (int attempt = 0; attempt < 2; attempt++) {
         // (a scaled-DCT stream always takes the 8-lane kernel, which has no limit per block: the lane kernel's limit is learnt per quality)
         const int mode = (attempt == 0 && !scaled && quality <= ctx->ent_lane_max_quality) ? kEntropyLanePerBlock : kEntropyEightLanes;
-        const int par = ctx->ent_parity;
-        ctx->ent_parity ^= 1;
-        HIPCHK(ctx, entropy_gpu_fused((const int16_t *)d_coeffs_zz, n, 1, ctx->d_huff, ctx->d_ent_work, ctx->ent_work_bytes, d_out, 0,
-                                      cap_words, h, w, quality, nullptr, ctx->d_stat, ctx->d_err + par, ctx->d_err + (par ^ 1), mode, ctx->stream,
-                                      nullptr, nullptr, scaled ? kFlagScaled : 0u));
+        HIPCHK(ctx, pack_and_place(ctx, d_coeffs_zz, n, h, w, quality, d_out, cap, mode, scaled ? kFlagScaled : 0u));
         HIPCHK(ctx, wait_stream(ctx));
-        total_bits = ((volatile unsigned long long *)ctx->h_stat)[0];
-        err = (int)(((volatile unsigned long long *)ctx->h_stat)[1] & 0xffffffffull);
-        if (err != 4 || mode == kEntropyEightLanes) break;
+        st = read_status(ctx->h_stat);
+        if (st.err != 4 || mode == kEntropyEightLanes) break;
         ctx->ent_lane_max_quality = quality - 1; // a block of this frame needs more than a lane string holds: 8-lane kernel from here on
     }
-    if (err == 1) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code (reference raises KeyError)");
-    const size_t payload = scaled ? (size_t)(total_bits / 8) + 1 : (size_t)((total_bits + 7) / 8); // (scaled: BB_flushBits' byte)
-    if (err == 2 || 16 + payload > cap)
-        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed)", 16 + (size_t)((payload + 3) / 4) * 4);
-    *out_len = 16 + payload;
-    return TIC_OK;
+    return stream_result(ctx, st, cap, scaled, out_len);
 }
 
 int tic_entropy_encode_dev(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, int quality, void *d_out, size_t cap,
@@ -1160,6 +1196,37 @@ int tic_compress_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t 
     return tic_entropy_encode_dev(ctx, ctx->d_coef, h, w, quality, d_out, cap, out_len);
 }
 
+// A lane's stream, events and error words (once), and its buffers for frames of n blocks.
+static int ensure_lane(tic_ctx *ctx, tic_ctx::AsyncLane &ln, size_t n) {
+    if (!ln.stream) {
+        HIPCHK(ctx, hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
+        HIPCHK(ctx, hipEventCreateWithFlags(&ln.packed, hipEventDisableTiming));
+        HIPCHK(ctx, hipEventCreateWithFlags(&ln.placed[0], hipEventDisableTiming));
+        HIPCHK(ctx, hipEventCreateWithFlags(&ln.placed[1], hipEventDisableTiming));
+        HIPCHK(ctx, hipMalloc((void **)&ln.d_err, 4 * sizeof(int)));
+        HIPCHK(ctx, hipMemset(ln.d_err, 0, 4 * sizeof(int)));
+    }
+    if (!ctx->lane_order) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->lane_order, hipEventDisableTiming));
+    const size_t coef_bytes = n * 128 + 16, wb = entropy_fused_work_bytes(n);
+    if (coef_bytes <= ln.coef_cap && wb <= ln.work_bytes) return TIC_OK;
+    // (grows only between bursts of one geometry: frames in flight still use the old buffers)
+    HIPCHK(ctx, hipStreamSynchronize(ln.stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const int rc = grow_dev(ctx, ln.d_coef, ln.coef_cap, coef_bytes);
+    if (rc) return rc;
+    if (wb > ln.work_bytes) {
+        for (int k = 0; k < 2; k++) {
+            if (ln.d_work[k]) HIPCHK(ctx, hipFree(ln.d_work[k]));
+            ln.d_work[k] = nullptr;
+        }
+        ln.work_bytes = 0;
+        HIPCHK(ctx, hipMalloc(&ln.d_work[0], wb));
+        HIPCHK(ctx, hipMalloc(&ln.d_work[1], wb));
+        ln.work_bytes = wb;
+    }
+    return TIC_OK;
+}
+
 // Asynchronous form of tic_compress_dev: the frame's launches (transform, pack, tile sums, place) are queued and the call returns; a
 // caller that compresses resident frames back to back pays the submission ramp and the completion wake-up once per burst instead of once
 // per frame.  Round 6: ONE context, TWO lanes.  Transform and packing of ticket t run on lane t & 1 - a stream, a coefficient buffer, an
@@ -1178,8 +1245,8 @@ int tic_compress_dev_async(tic_ctx *ctx, const void *d_image, int h, int w, ptrd
     if (!ctx || !ticket) return TIC_E_ARG;
     int rc = check_stream_geometry(ctx, h, w, row_stride, quality);
     if (rc) return rc;
-    if (!d_out || cap < 16) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
-    if (((uintptr_t)d_out & 15u) != 0) return set_err(ctx, TIC_E_ARG, "device output buffer must be 16-byte aligned");
+    rc = check_dev_out(ctx, d_out, cap, 16);
+    if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const long long t = ctx->async_next;
     tic_ctx::AsyncSlot &sl = ctx->async_slots[t % kAsyncSlots];
@@ -1190,39 +1257,14 @@ int tic_compress_dev_async(tic_ctx *ctx, const void *d_image, int h, int w, ptrd
     const size_t n = num_blocks(h, w);
     sl.cap = cap;
     sl.empty_image = n == 0;
-    if (n == 0) { // header only (codec.py:151: an empty image is a 16-byte stream)
-        uint8_t hdr[16];
-        write_header(hdr, h, w, quality);
-        HIPCHK(ctx, hipMemcpyAsync(d_out, hdr, 16, hipMemcpyHostToDevice, ctx->stream));
+    if (n == 0) {
+        rc = put_header_only(ctx, d_out, h, w, quality, false);
+        if (rc) return rc;
     } else {
         if (!d_image) return set_err(ctx, TIC_E_ARG, "null image pointer");
         tic_ctx::AsyncLane &ln = ctx->lanes[t & 1];
-        if (!ln.stream) {
-            HIPCHK(ctx, hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
-            HIPCHK(ctx, hipEventCreateWithFlags(&ln.packed, hipEventDisableTiming));
-            HIPCHK(ctx, hipEventCreateWithFlags(&ln.placed[0], hipEventDisableTiming));
-            HIPCHK(ctx, hipEventCreateWithFlags(&ln.placed[1], hipEventDisableTiming));
-            HIPCHK(ctx, hipMalloc((void **)&ln.d_err, 4 * sizeof(int)));
-            HIPCHK(ctx, hipMemset(ln.d_err, 0, 4 * sizeof(int)));
-        }
-        if (!ctx->lane_order) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->lane_order, hipEventDisableTiming));
-        const size_t coef_bytes = n * 128 + 16, wb = entropy_fused_work_bytes(n);
-        if (coef_bytes > ln.coef_cap || wb > ln.work_bytes) { // (grows only between bursts of one geometry: frames in flight still use the old buffers)
-            HIPCHK(ctx, hipStreamSynchronize(ln.stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            const int rc = grow_dev(ctx, ln.d_coef, ln.coef_cap, coef_bytes);
-            if (rc) return rc;
-            if (wb > ln.work_bytes) {
-                for (int k = 0; k < 2; k++) {
-                    if (ln.d_work[k]) HIPCHK(ctx, hipFree(ln.d_work[k]));
-                    ln.d_work[k] = nullptr;
-                }
-                ln.work_bytes = 0;
-                HIPCHK(ctx, hipMalloc(&ln.d_work[0], wb));
-                HIPCHK(ctx, hipMalloc(&ln.d_work[1], wb));
-                ln.work_bytes = wb;
-            }
-        }
+        rc = ensure_lane(ctx, ln, n);
+        if (rc) return rc;
         hs[0] = 0;
         hs[1] = 0;
         if (ctx->async_open == 0) { // a burst begins: its lanes start behind whatever the context's stream holds now
@@ -1274,15 +1316,7 @@ int tic_async_result(tic_ctx *ctx, long long ticket, int wait, size_t *out_len) 
         *out_len = 16;
         return TIC_OK;
     }
-    volatile unsigned long long *hs = ctx->h_stat + 8 + 2 * (ticket % kAsyncSlots);
-    const unsigned long long total_bits = hs[0];
-    const int err = (int)(hs[1] & 0xffffffffull);
-    if (err == 1) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code (reference raises KeyError)");
-    const size_t payload = (size_t)((total_bits + 7) / 8);
-    if (err == 2 || 16 + payload > sl.cap)
-        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed)", 16 + (size_t)((total_bits + 31) / 32) * 4);
-    *out_len = 16 + payload;
-    return TIC_OK;
+    return stream_result(ctx, read_status(ctx->h_stat + 8 + 2 * (ticket % kAsyncSlots)), sl.cap, false, out_len);
 }
 
 int tic_compress(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int quality, uint8_t *out,
@@ -1296,16 +1330,13 @@ int tic_compress(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row
     if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // image -> HBM, transform stage, entropy stage, all on the device; only the finished stream returns
-    const size_t pitch = align_up((size_t)w, 256);
-    rc = ensure_scratch(ctx, pitch * (size_t)h, n * 128 + 16);
-    if (rc) return rc;
     const size_t need = compress_bound(h, w);
     const bool small = need <= kSmallHostBytes && !test_hook("TIC_NO_SMALL_PATH"); // the placing kernel writes the stream into host memory itself
     rc = small ? ensure_small(ctx, kSmallHostBytes) : grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, need);
     if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_img, pitch, image, (size_t)row_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice,
-                                 ctx->stream));
-    size_t len = 0;
+    size_t pitch = 0, len = 0;
+    rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
+    if (rc) return rc;
     rc = tic_compress_dev(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, quality, small ? (void *)ctx->d_small : ctx->d_stream_buf,
                           small ? ctx->small_cap : ctx->d_stream_cap, &len);
     if (rc) return rc;
@@ -1379,8 +1410,7 @@ int tic_entropy_size_dev(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, si
     return TIC_OK;
 }
 
-// Times `iters` back-to-back launches of the size kernel on resident coefficients, behind `warm` untimed ones, with HIP events on the
-// context's stream, all in one submission (as tic_dctq_dev_timed_warm).  *ms_total = elapsed milliseconds for the `iters` launches.
+// Times `iters` back-to-back launches of the size kernel on resident coefficients, behind `warm` untimed ones (timed_launches).
 int tic_entropy_size_dev_timed(tic_ctx *ctx, const void *d_coeffs_zz, int h, int w, int warm, int iters, float *ms_total) {
     TIC_LOCK(ctx);
     if (!ctx || !ms_total || warm < 0 || iters <= 0) return TIC_E_ARG;
@@ -1391,13 +1421,9 @@ int tic_entropy_size_dev_timed(tic_ctx *ctx, const void *d_coeffs_zz, int h, int
     const int rc = ensure_rate(ctx, 1);
     if (rc) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_rate, 0, sizeof(SizeResult), ctx->stream));
-    for (int i = 0; i < warm; i++) HIPCHK(ctx, stream_size_gpu((const int16_t *)d_coeffs_zz, n, 1, ctx->d_size_tab, ctx->d_rate, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int i = 0; i < iters; i++) HIPCHK(ctx, stream_size_gpu((const int16_t *)d_coeffs_zz, n, 1, ctx->d_size_tab, ctx->d_rate, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev1));
-    HIPCHK(ctx, hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));
-    return TIC_OK;
+    return timed_launches(ctx, warm, iters, ms_total, nullptr, [&](int, hipEvent_t, hipEvent_t) {
+        return stream_size_gpu((const int16_t *)d_coeffs_zz, n, 1, ctx->d_size_tab, ctx->d_rate, ctx->stream);
+    });
 }
 
 static int check_size_args(tic_ctx *ctx, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq, long long *sizes) {
@@ -1430,16 +1456,6 @@ int tic_stream_sizes_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdif
     if (rc) return rc;
     HIPCHK(ctx, wait_stream(ctx));
     for (int i = 0; i < nq; i++) sizes[i] = probe_size(ctx->h_rate[i]);
-    return TIC_OK;
-}
-
-// The host-image forms upload the frame into the context's scratch image as tic_compress does (rows padded to 256 bytes).
-static int upload_image(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, size_t n, size_t *pitch) {
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    *pitch = align_up((size_t)w, 256);
-    const int rc = ensure_scratch(ctx, *pitch * (size_t)h, n * 128 + 16);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_img, *pitch, image, (size_t)row_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
     return TIC_OK;
 }
 
@@ -1479,12 +1495,11 @@ static int compress_to_size_impl(tic_ctx *ctx, const void *d_image, int h, int w
             *out_len = 16;
             return set_err(ctx, TIC_E_SPACE, "16 bytes at quality %d exceed the budget of %zu", qmin, max_bytes);
         }
-        uint8_t hdr[16];
-        write_header(hdr, h, w, qmax);
         if (out_on_host) {
-            memcpy(out, hdr, 16);
+            write_header((uint8_t *)out, h, w, qmax);
         } else {
-            HIPCHK(ctx, hipMemcpyAsync(out, hdr, 16, hipMemcpyHostToDevice, ctx->stream));
+            const int rc = put_header_only(ctx, out, h, w, qmax, false);
+            if (rc) return rc;
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         }
         *out_len = 16;
@@ -1533,18 +1548,14 @@ static int compress_to_size_impl(tic_ctx *ctx, const void *d_image, int h, int w
     if (rc) return rc;
     DctqArgs a = make_args(ctx, d_image, h, w, row_stride, lo, ctx->d_coef);
     HIPCHK(ctx, launch_dctq(a, dctq_kernel_id(TIC_KERNEL_HYBRID), ctx->stream));
-    const int par = ctx->ent_parity;
-    ctx->ent_parity ^= 1;
-    HIPCHK(ctx, entropy_gpu_fused((const int16_t *)ctx->d_coef, n, 1, ctx->d_huff, ctx->d_ent_work, ctx->ent_work_bytes, ctx->d_stream_buf, 0,
-                                  ((ctx->d_stream_cap - 16) / 16) * 4, h, w, lo, nullptr, ctx->d_stat, ctx->d_err + par, ctx->d_err + (par ^ 1),
-                                  kEntropyEightLanes, ctx->stream));
+    HIPCHK(ctx, pack_and_place(ctx, ctx->d_coef, n, h, w, lo, ctx->d_stream_buf, ctx->d_stream_cap, kEntropyEightLanes, 0u));
     HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_stream_buf, len, out_on_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(ctx, out_on_host ? hipStreamSynchronize(ctx->stream) : wait_stream(ctx));
     ctx->last_rate_waits++;
-    const unsigned long long total_bits = ((volatile unsigned long long *)ctx->h_stat)[0];
-    const int err = (int)(((volatile unsigned long long *)ctx->h_stat)[1] & 0xffffffffull);
-    if (err || 16 + (size_t)((total_bits + 7) / 8) != len) // (two independent walks over the same coefficients: cannot differ)
-        return set_err(ctx, TIC_E_HIP, "the packed stream (%llu bits, error %d) contradicts its probe (%zu bytes)", total_bits, err, len);
+    const StreamStatus st = read_status(ctx->h_stat);
+    size_t packed = 0; // (two independent walks over the same coefficients: cannot differ, in error or length)
+    if (st.err || stream_result(ctx, st, len, false, &packed) != TIC_OK || packed != len)
+        return set_err(ctx, TIC_E_HIP, "the packed stream (%llu bits, error %d) contradicts its probe (%zu bytes)", st.bits, st.err, len);
     *out_len = len;
     *quality = lo;
     return TIC_OK;
@@ -1644,22 +1655,17 @@ int tic_dctq_scaled_dev_frames(tic_ctx *ctx, const void *d_images, int nframes, 
     if (nframes < 0) return set_err(ctx, TIC_E_ARG, "negative frame count");
     if (h == 0 || w == 0 || nframes == 0) return TIC_OK;
     if (!d_images || !d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "null device pointer");
-    if (nframes > 65535) return set_err(ctx, TIC_E_ARG, "at most 65535 frames per launch");
-    if (frame_stride < (ptrdiff_t)h * row_stride || coeff_frame_stride < (ptrdiff_t)(num_blocks(h, w) * 128))
-        return set_err(ctx, TIC_E_ARG, "frame strides smaller than one frame");
+    ScaledArgs a = make_scaled_args(d_images, h, w, row_stride, qf, d_coeffs_zz);
+    rc = set_frames(ctx, a, nframes, h, w, row_stride, frame_stride, coeff_frame_stride);
+    if (rc) return rc;
     if ((coeff_frame_stride & 15) != 0) return set_err(ctx, TIC_E_ARG, "coefficient frame stride must be a multiple of 16");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    ScaledArgs a = make_scaled_args(d_images, h, w, row_stride, qf, d_coeffs_zz);
-    a.aligned8 = a.aligned8 && ((frame_stride & 7) == 0);
-    a.nframes = nframes;
-    a.frame_stride_in = (long)frame_stride;
-    a.frame_stride_out = (long)coeff_frame_stride;
     HIPCHK(ctx, launch_fdctq_scaled(a, ctx->stream));
     return TIC_OK;
 }
 
-// tic_dctq_dev_timed_warm for the integer kernel: the same single submission (warm launches, event, timed launches, event) and the same
-// per-launch stamps, so that the two figures compare.
+// tic_dctq_dev_timed_warm for the integer kernel: the same submission and the same per-launch stamps (timed_launches), so that the two
+// figures compare.
 int tic_dctq_scaled_dev_timed_warm(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, int qf, void *d_coeffs_zz, int warm,
                                    int iters, float *ms_total, float *per_launch_ms) {
     TIC_LOCK(ctx);
@@ -1669,29 +1675,8 @@ int tic_dctq_scaled_dev_timed_warm(tic_ctx *ctx, const void *d_image, int h, int
     if (per_launch_ms && iters > 32768) return set_err(ctx, TIC_E_ARG, "per-launch times for at most 32768 launches");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const ScaledArgs a = make_scaled_args(d_image, h, w, row_stride, qf, d_coeffs_zz);
-    if (per_launch_ms)
-        while ((int)ctx->ev_steps.size() < 2 * iters) {
-            hipEvent_t e = nullptr;
-            HIPCHK(ctx, hipEventCreate(&e));
-            ctx->ev_steps.push_back(e);
-        }
-    for (int i = 0; i < warm; i++) HIPCHK(ctx, launch_fdctq_scaled(a, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int i = 0; i < iters; i++) {
-        if (per_launch_ms)
-            HIPCHK(ctx, launch_fdctq_scaled(a, ctx->stream, ctx->ev_steps[2 * i], ctx->ev_steps[2 * i + 1]));
-        else
-            HIPCHK(ctx, launch_fdctq_scaled(a, ctx->stream));
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev1));
-    HIPCHK(ctx, hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));
-    if (per_launch_ms)
-        for (int i = 0; i < iters; i++) {
-            HIPCHK(ctx, hipEventElapsedTime(per_launch_ms + 2 * i, ctx->ev_steps[2 * i], ctx->ev_steps[2 * i + 1]));
-            HIPCHK(ctx, hipEventElapsedTime(per_launch_ms + 2 * i + 1, ctx->ev_steps[0], ctx->ev_steps[2 * i + 1]));
-        }
-    return TIC_OK;
+    return timed_launches(ctx, warm, iters, ms_total, per_launch_ms,
+                          [&](int, hipEvent_t e0, hipEvent_t e1) { return launch_fdctq_scaled(a, ctx->stream, e0, e1); });
 }
 
 int tic_dctq_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int qf, int16_t *coeffs_zz) {
@@ -1701,11 +1686,9 @@ int tic_dctq_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t 
     const size_t n = num_blocks(h, w);
     if (n == 0) return TIC_OK;
     if (!image || !coeffs_zz) return set_err(ctx, TIC_E_ARG, "null host pointer");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t pitch = align_up((size_t)w, 256);
-    rc = ensure_scratch(ctx, pitch * (size_t)h, n * 128);
+    size_t pitch = 0;
+    rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
     if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_img, pitch, image, (size_t)row_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, launch_fdctq_scaled(make_scaled_args(ctx->d_img, h, w, (ptrdiff_t)pitch, qf, ctx->d_coef), ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(coeffs_zz, ctx->d_coef, n * 128, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1756,13 +1739,11 @@ int tic_compress_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdif
     if (n == 0) return entropy_encode_scaled(nullptr, h, w, qf, out, cap, out_len);
     if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t pitch = align_up((size_t)w, 256);
-    rc = ensure_scratch(ctx, pitch * (size_t)h, n * 128 + 16);
-    if (rc) return rc;
     rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, tic_compress_scaled_bound(h, w));
     if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_img, pitch, image, (size_t)row_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
-    size_t len = 0;
+    size_t pitch = 0, len = 0;
+    rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
+    if (rc) return rc;
     rc = tic_compress_scaled_dev(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, qf, ctx->d_stream_buf, ctx->d_stream_cap, &len);
     if (rc) return rc;
     if (len > cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", len, cap);
@@ -3431,11 +3412,9 @@ int tic_compress_adaptive(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrd
     const size_t n = num_blocks(h, w);
     if (n == 0) return set_err(ctx, TIC_E_ARG, "an image without blocks has no symbols to build a table from (the reference raises IndexError)");
     if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t pitch = align_up((size_t)w, 256);
-    rc = ensure_scratch(ctx, pitch * (size_t)h, n * 128);
+    size_t pitch = 0;
+    rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
     if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_img, pitch, image, (size_t)row_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
     DctqArgs a = make_args(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, quality, ctx->d_coef);
     HIPCHK(ctx, launch_dctq(a, 2, ctx->stream));
     return adaptive_encode_dev(ctx, n, h, w, quality, out, cap, out_len);
