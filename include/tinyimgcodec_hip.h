@@ -236,6 +236,62 @@ int tic_compress_to_size(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdi
  * for the device (the probe submissions plus the one for the final stream). */
 int tic_last_rate_search(tic_ctx *ctx, int *probes, int *host_waits);
 
+/* ---- rate-distortion: the exact round-trip error, and the smallest stream at no more than a given error ----------------
+ *      The reference's benchmark is a loop of compress -> decompress -> psnr (tests/benchmark.py:12-23, tests/cbenchmark.py:20-31).
+ *      The decoder here reproduces the reference's pixels bit for bit, so the squared error between an image and
+ *      decompress(compress(image, q)) is an exact integer, a function of the quantised coefficients and the image alone: the measuring
+ *      kernel runs the inverse transform on resident coefficients and, instead of storing pixels, sums over the h x w pixels of the frame
+ *          sums[0] = sum of d * d            d = original - decoded             (the true squared error)
+ *          sums[1] = sum of (d * d) & 255    what the reference's tests/psnr.py sums: it subtracts and squares uint8 arrays
+ *      No stream, no entropy stage, no decoded frame.  PSNR = 20 log10(255 / sqrt(sum / (h * w))). */
+/* The kernel alone, synchronous: coefficients in the device layout (int16 [N][64] zig-zag, absolute DC), the original frame d_image
+ * with its own row stride (bytes of a row behind w are never read).  scaled_exponent < 0: the float codec at `quality` (1..99, or
+ * TIC_QUALITY_CUSTOM); scaled_exponent 0..62: a scaled-DCT frame as tic_idctq_scaled decodes it (`quality` is ignored; above 62
+ * TIC_E_QUALITY).  Neither buffer is written.  No blocks: both sums 0. */
+int tic_distortion_dev(tic_ctx *ctx, const void *d_coeffs_zz, const void *d_image, int h, int w, ptrdiff_t row_stride, int quality,
+                       int scaled_exponent, uint64_t sums[2]);
+/* Times the measuring kernel alone: `warm` untimed launches, an event, `iters` timed launches, an event, one submission (as
+ * tic_entropy_size_dev_timed); *ms_total = elapsed milliseconds for the `iters` launches. */
+int tic_distortion_dev_timed(tic_ctx *ctx, const void *d_coeffs_zz, const void *d_image, int h, int w, ptrdiff_t row_stride, int quality,
+                             int scaled_exponent, int warm, int iters, float *ms_total);
+/* Times idct_kernel alone the same way, on the same kind of coefficients, storing its pixels to d_out (uint8 [h][out_stride], device):
+ * the launch the measuring kernel stands beside (tools/distortion_timing.py). */
+int tic_idct_dev_timed(tic_ctx *ctx, const void *d_coeffs_zz, void *d_out, int h, int w, ptrdiff_t out_stride, int quality, int scaled_exponent,
+                       int warm, int iters, float *ms_total);
+/* Rate and distortion at every quality of a list: sizes[i] as tic_stream_sizes_dev (-1 where a coefficient has no Huffman code; the
+ * sums are reported there all the same - the coefficients exist, only the entropy coder has no code for one), sse[i] / sse_wrapped[i]
+ * the two sums of decompress(compress(image, qualities[i])) against the image.  One memset clears the nq results; per quality the
+ * transform into the context's coefficient workspace, the size kernel and the measuring kernel are queued back to back on the
+ * context's stream; one read-back.  Argument checks and their order: tic_stream_sizes_dev's (a null sse or sse_wrapped with nq > 0 is
+ * TIC_E_ARG). */
+int tic_rd_points_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq, long long *sizes,
+                      uint64_t *sse, uint64_t *sse_wrapped);
+/* ... for an image in host memory: one upload, then the above. */
+int tic_rd_points(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq, long long *sizes,
+                  uint64_t *sse, uint64_t *sse_wrapped);
+/* The mirror of tic_compress_to_size_dev: the stream of the quality this bisection ends at, where meets(q) means "tic_compress_dev at q
+ * succeeds and the squared error of its round trip is <= max_sse":
+ *     if not meets(qmax): fail
+ *     lo, hi = qmin, qmax
+ *     while lo < hi: mid = (lo + hi) / 2;  if meets(mid): hi = mid  else: lo = mid + 1
+ *     *quality = lo, *sse = its squared error
+ * Where the error does not grow with the quality that is the smallest quality of the range that meets the bound - the smallest stream
+ * at no less than the PSNR max_sse stands for.  On success d_out holds exactly the *out_len bytes tic_compress_dev(..., lo, ...)
+ * produces, and no byte behind them is written.  Failures write nothing to d_out: qmax has a coefficient without a code TIC_E_RANGE;
+ * qmax misses the bound TIC_E_SPACE (the target is out of reach) - both with *quality = qmax and *sse = its squared error, and the
+ * latter with *out_len = 0; the stream does not fit cap TIC_E_SPACE with *out_len = its length, at least 16 - so *out_len tells the two
+ * TIC_E_SPACE apart (cap < 16: TIC_E_SPACE at once, nothing written to any of the three); qmin > qmax or either outside 1..99
+ * TIC_E_QUALITY.  Probes (transform, size kernel, measuring kernel) are queued several bisection steps ahead per submission, to the
+ * depth per frame size of the size search; tic_last_rate_search reports this search too.  No blocks: the header at qmin, *sse = 0. */
+int tic_compress_to_psnr_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, uint64_t max_sse, int qmin, int qmax,
+                             void *d_out, size_t cap, size_t *out_len, int *quality, uint64_t *sse);
+/* ... with image and stream in host memory. */
+int tic_compress_to_psnr(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, uint64_t max_sse, int qmin, int qmax,
+                         uint8_t *out, size_t cap, size_t *out_len, int *quality, uint64_t *sse);
+/* The distortion column of the reference's tests/cbenchmark.py: the two sums of decompress(stream of the integer encoder at setting qf)
+ * against the image - tic_dctq_scaled's kernel followed by the measuring kernel at exponent qf.  Arguments as tic_dctq_scaled. */
+int tic_roundtrip_sse_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int qf, uint64_t sums[2]);
+
 /* Batch of n independent frames of identical geometry (BASELINE config 3): pinned staging buffers, two HIP
  * streams (the H2D copy of chunk c+1 overlaps the kernels of chunk c and the read-back of chunk c-1).
  * threads <= 0: entropy stage on the device (only finished streams cross PCIe); threads > 0: coefficients are

@@ -128,6 +128,28 @@ SIGNATURES = {
          C.POINTER(C.c_int)],
     ),
     "tic_last_rate_search": (C.c_int, [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tic_distortion_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_int, C.c_void_p]),
+    "tic_distortion_dev_timed": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)],
+    ),
+    "tic_idct_dev_timed": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)],
+    ),
+    "tic_rd_points_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tic_rd_points": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tic_compress_to_psnr_dev": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+         C.POINTER(C.c_int), C.POINTER(C.c_uint64)],
+    ),
+    "tic_compress_to_psnr": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+         C.POINTER(C.c_int), C.POINTER(C.c_uint64)],
+    ),
+    "tic_roundtrip_sse_scaled": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p]),
     "tic_compress_batch": (
         C.c_int,
         [_ctxp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.POINTER(C.c_void_p),

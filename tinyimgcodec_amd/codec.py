@@ -44,6 +44,7 @@ Documented differences from the reference (all outside its working domain):
     decoded for exponents 0..62 (the C encoder writes 0..3).
 """
 import ctypes as C
+import math
 import struct
 
 import numpy as np
@@ -366,6 +367,109 @@ def compress_to_size(image, max_bytes, min_quality=1, max_quality=99, ctx=None):
         return out[: n.value].tobytes(), int(q.value)
 
 
+def psnr_from_sse(sse, npixels, max_pixel=255):
+    """PSNR in dB from a sum of squared differences over `npixels` pixels, with the operations of the reference's tests/psnr.py (its
+    np.mean of the squares is the exact integer sum divided by the count): inf for a sum of 0.  The one place PSNR is defined for
+    roundtrip_psnr and compress_to_psnr.  Fed the wrapped sum (rd_points' third array) it returns the very float the reference's
+    psnr() returns for the two uint8 arrays - that function squares uint8 differences in uint8 arithmetic."""
+    sse, npixels = int(sse), int(npixels)
+    if sse < 0 or npixels < 0:
+        raise ValueError("negative sum or pixel count")
+    if sse == 0:
+        return math.inf
+    mse = sse / npixels
+    return 20 * math.log10(max_pixel / mse ** 0.5)
+
+
+def max_sse_for_psnr(min_psnr, npixels):
+    """The largest integer sum of squared differences over `npixels` pixels whose psnr_from_sse is still >= min_psnr (0 for inf: an
+    exact round trip), capped at 255^2 per pixel, which no 8-bit round trip exceeds.  Computed from the inverted formula, then corrected
+    against the predicate itself, so that `psnr_from_sse(s, n) >= min_psnr` and `s <= max_sse_for_psnr(min_psnr, n)` agree for every
+    reachable s."""
+    min_psnr, npixels = float(min_psnr), int(npixels)
+    if math.isnan(min_psnr):
+        raise ValueError("min_psnr is not a number")
+    top = npixels * 255 * 255
+    if min_psnr == math.inf or npixels == 0:
+        return 0
+    if psnr_from_sse(top, npixels) >= min_psnr:
+        return top
+    est = min(top, max(0, int(npixels * 255.0 * 255.0 / 10.0 ** (min_psnr / 10.0)))) if min_psnr < 3000 else 0
+    while est > 0 and not psnr_from_sse(est, npixels) >= min_psnr:
+        est -= 1
+    while est < top and psnr_from_sse(est + 1, npixels) >= min_psnr:
+        est += 1
+    return est
+
+
+def rd_points(image, qualities, ctx=None):
+    """Rate and distortion at every q of `qualities` from one submission -> (sizes int64, sse uint64, sse_wrapped uint64):
+    sizes as compressed_sizes (-1 where compress() would raise KeyError); sse[i] the exact sum of squared differences between the image
+    and decompress(compress(image, q)), sse_wrapped[i] the sum of those squares modulo 256, which is what the reference's tests/psnr.py
+    sums - both reported for the -1 entries too.  No stream is produced and no frame decoded into memory: per quality the transform, the
+    size kernel and a measuring instance of the inverse transform, one read-back.  Validation as compressed_sizes."""
+    img, h, w = _as_u8_image(image)
+    qs = [_check_quality(q, packs_header=True) for q in qualities]
+    sizes = np.zeros(len(qs), dtype=np.int64)
+    sse = np.zeros(len(qs), dtype=np.uint64)
+    wrapped = np.zeros(len(qs), dtype=np.uint64)
+    if not qs:
+        return sizes, sse, wrapped
+    ctx = _ctx(ctx)
+    qarr = np.asarray(qs, dtype=np.intc)
+    with ctx.lock:
+        ctx.check(N.load().tic_rd_points(ctx.handle, img.ctypes.data, h, w, img.strides[0] if img.size else max(w, 1), qarr.ctypes.data, len(qs),
+                                         sizes.ctypes.data, sse.ctypes.data, wrapped.ctypes.data))
+    return sizes, sse, wrapped
+
+
+def roundtrip_psnr(image, quality=50, reference_arithmetic=False, ctx=None):
+    """PSNR of decompress(compress(image, quality)) against the image, from the exact squared error (rd_points).  With
+    reference_arithmetic=True the float the reference's tests/psnr.py returns for that pair, which wraps every squared difference to
+    8 bits (Lenna at quality 50: 35.8 dB that way, 35.41 dB in truth).  KeyError where compress() raises it."""
+    img, h, w = _as_u8_image(image)
+    sizes, sse, wrapped = rd_points(img, [quality], ctx=ctx)
+    if sizes[0] < 0:
+        raise KeyError("coefficient magnitude has no Huffman code")  # as the reference's dict lookup
+    return psnr_from_sse(int(wrapped[0] if reference_arithmetic else sse[0]), h * w)
+
+
+def compress_to_psnr(image, min_psnr, min_quality=1, max_quality=99, ctx=None):
+    """The smallest stream at no less than `min_psnr` dB -> (bytes, quality, psnr): compress(image, quality) of the quality at which a
+    bisection over min_quality..max_quality ends, with "compress() succeeds and the PSNR of its round trip is >= min_psnr" as its test -
+
+        lo, hi = min_quality, max_quality
+        while lo < hi: mid = (lo + hi) // 2;  hi = mid if meets(mid) else lo = mid + 1
+
+    which is the smallest quality that meets the target wherever the error does not grow with the quality.  The PSNR is the true one
+    (psnr_from_sse of the exact squared error); min_psnr = inf asks for an exact round trip.  The probes run on the GPU without streams
+    or decoded frames (rd_points) and several steps ahead per submission.  ValueError naming the PSNR at max_quality when even that
+    falls short; KeyError when max_quality has a coefficient without a Huffman code (on photographs 98 and 99 usually have one: pass a
+    lower max_quality); 8-bit images only."""
+    img, h, w = _as_u8_image(image)
+    qmin = _check_quality(min_quality, packs_header=True)
+    qmax = _check_quality(max_quality, packs_header=True)
+    if qmin > qmax:
+        raise ValueError("min_quality %d above max_quality %d" % (qmin, qmax))
+    max_sse = max_sse_for_psnr(min_psnr, h * w)
+    ctx = _ctx(ctx)
+    L = N.load()
+    cap = L.tic_compress_bound(h, w)
+    with ctx.lock:
+        out = getattr(ctx, "_out_buf", None)  # compress()'s landing buffer
+        if out is None or out.size < cap:
+            out = ctx._out_buf = np.empty(cap, dtype=np.uint8)
+        n, q, sse = C.c_size_t(0), C.c_int(0), C.c_uint64(0)
+        rc = L.tic_compress_to_psnr(ctx.handle, img.ctypes.data, h, w, img.strides[0] if img.size else max(w, 1), max_sse, qmin, qmax,
+                                    out.ctypes.data, cap, C.byref(n), C.byref(q), C.byref(sse))
+        if rc == N.TIC_E_RANGE:
+            raise KeyError("coefficient magnitude has no Huffman code")
+        if rc == N.TIC_E_SPACE and n.value == 0:  # (a stream that does not fit cap reports its length; cap is the bound here)
+            raise ValueError("%r dB at quality %d fall short of min_psnr = %r" % (psnr_from_sse(sse.value, h * w), qmax, float(min_psnr)))
+        ctx.check(rc)
+        return out[: n.value].tobytes(), int(q.value), psnr_from_sse(sse.value, h * w)
+
+
 SCALED_SETTINGS = ("best", "high", "med", "low")  # encode.c:20-34; the header's quality field holds the index
 
 
@@ -399,6 +503,20 @@ def dctq_scaled(image, quality="med", ctx=None):
         with ctx.lock:
             ctx.check(L.tic_dctq_scaled(ctx.handle, img.ctypes.data, h, w, img.strides[0], qf, zz.ctypes.data))
     return zz
+
+
+def roundtrip_sse_scaled(image, quality="med", ctx=None):
+    """(sse, sse_wrapped) of decompress(compress_scaled(image, quality)) against the image - the distortion column of the reference's
+    tests/cbenchmark.py - as exact integers, from the integer encoder's coefficients and a measuring instance of the inverse transform:
+    no stream, no decoded frame.  psnr_from_sse turns either into dB (the wrapped sum into the reference's own figure)."""
+    img, h, w = _scaled_image(image)
+    qf = _scaled_setting(quality)
+    sums = (C.c_uint64 * 2)(0, 0)
+    if N.load().tic_num_blocks(h, w):
+        ctx = _ctx(ctx)
+        with ctx.lock:
+            ctx.check(N.load().tic_roundtrip_sse_scaled(ctx.handle, img.ctypes.data, h, w, img.strides[0], qf, sums))
+    return int(sums[0]), int(sums[1])
 
 
 def compress_scaled(image, quality="med", ctx=None):

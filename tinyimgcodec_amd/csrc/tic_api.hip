@@ -1367,20 +1367,55 @@ static int ensure_rate(tic_ctx *ctx, size_t nres) {
         HIPCHK(ctx, e);
         ctx->d_size_tab = d;
     }
-    const size_t need = nres * sizeof(SizeResult), alloc = align_up(need, 4096);
+    // (a DistortionResult per probe as well, behind the nres SizeResults: dist_of)
+    const size_t need = nres * (sizeof(SizeResult) + sizeof(DistortionResult)), alloc = align_up(need, 4096);
     const int rc = grow_dev(ctx, ctx->d_rate, ctx->rate_dev_bytes, need, alloc);
     return rc ? rc : grow_pinned(ctx, ctx->h_rate, ctx->rate_host_bytes, need, alloc);
 }
 
+// The distortion results of a submission of nq probes lie behind its nq size results, in the device buffer and in its landing buffer alike:
+// one memset clears both, one copy brings both back.
+static inline DistortionResult *dist_of(SizeResult *rate, int nq) { return reinterpret_cast<DistortionResult *>(rate + nq); }
+
+// Launch arguments of the measuring kernel: coefficients as idct_kernel takes them (quality / scaled_exp as StreamHead), the original frame.
+static void measure_args(const tic_ctx *ctx, const void *d_coeffs, const void *d_image, int h, int w, ptrdiff_t stride, int quality, int scaled_exp,
+                         DistortionResult *d_res, IdctArgs *a, SseArgs *m) {
+    a->coeffs = (const int16_t *)d_coeffs;
+    a->out = nullptr;
+    a->h = h;
+    a->w = w;
+    a->stride = 0;
+    a->bw = (w + 7) / 8;
+    a->tiles_x = (a->bw + 7) / 8;
+    a->ntiles = (h > 0 && w > 0) ? ((h + 7) / 8) * a->tiles_x : 0;
+    a->aligned8 = 0;
+    a->consts = ctx->d_consts + (scaled_exp >= 0 ? 50 : quality); // codec.py:62: quality = 50 on the scaled branch
+    a->scaled = scaled_exp >= 0;
+    a->pow2 = scaled_exp >= 0 ? ldexp(1.0, scaled_exp) : 1.0;
+    m->img = (const uint8_t *)d_image;
+    m->stride = (long)stride;
+    m->aligned8 = ((((uintptr_t)d_image) | (uintptr_t)stride) & 7) == 0;
+    m->res = d_res;
+}
+
 // Queues the probes of q[0 .. nq) and the copy of their results into ctx->h_rate; the caller waits for the stream.
-static int queue_probes(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, size_t n, const int *q, int nq) {
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_rate, 0, (size_t)nq * sizeof(SizeResult), ctx->stream));
+// distortion: every probe also runs the measuring kernel on its coefficients against the frame (a rate-distortion probe: three launches);
+// its sums come back in the same copy (dist_of(ctx->h_rate, nq)).
+static int queue_probes(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, size_t n, const int *q, int nq, bool distortion = false) {
+    const size_t res_bytes = (size_t)nq * (sizeof(SizeResult) + (distortion ? sizeof(DistortionResult) : 0));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_rate, 0, res_bytes, ctx->stream));
     for (int i = 0; i < nq; i++) {
         DctqArgs a = make_args(ctx, d_image, h, w, row_stride, q[i], ctx->d_coef);
         HIPCHK(ctx, launch_dctq(a, dctq_kernel_id(TIC_KERNEL_AUTO), ctx->stream));
         HIPCHK(ctx, stream_size_gpu((const int16_t *)ctx->d_coef, n, 1, ctx->d_size_tab, ctx->d_rate + i, ctx->stream));
+        if (distortion) {
+            IdctArgs ia;
+            SseArgs m;
+            measure_args(ctx, ctx->d_coef, d_image, h, w, row_stride, q[i], -1, dist_of(ctx->d_rate, nq) + i, &ia, &m);
+            HIPCHK(ctx, launch_idct_sse(ia, m, ctx->stream));
+        }
     }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_rate, ctx->d_rate, (size_t)nq * sizeof(SizeResult), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_rate, ctx->d_rate, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
     return TIC_OK;
 }
 
@@ -1486,6 +1521,34 @@ static void rate_candidates(int lo, int hi, int depth, const long long *known, i
     rate_candidates(lo, mid - 1, depth - 1, known, out, nout);
 }
 
+// The last step of a search (by size or by distortion) that ended at quality q, whose probe said `len` bytes: transform, pack and place
+// into the context's own buffer, then exactly its bytes into the caller's - the length is known from the probe, so the copy is queued
+// behind the placing kernel and the whole stream costs one wait.
+static int chosen_stream(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, size_t n, int q, size_t len, void *out,
+                         bool out_on_host, size_t cap, size_t *out_len, int *quality) {
+    if (len > cap) {
+        *out_len = len;
+        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", len, cap);
+    }
+    int rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, compress_bound(h, w));
+    if (rc) return rc;
+    rc = grow_dev(ctx, ctx->d_ent_work, ctx->ent_work_bytes, entropy_fused_work_bytes(n));
+    if (rc) return rc;
+    DctqArgs a = make_args(ctx, d_image, h, w, row_stride, q, ctx->d_coef);
+    HIPCHK(ctx, launch_dctq(a, dctq_kernel_id(TIC_KERNEL_HYBRID), ctx->stream));
+    HIPCHK(ctx, pack_and_place(ctx, ctx->d_coef, n, h, w, q, ctx->d_stream_buf, ctx->d_stream_cap, kEntropyEightLanes, 0u));
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_stream_buf, len, out_on_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, out_on_host ? hipStreamSynchronize(ctx->stream) : wait_stream(ctx));
+    ctx->last_rate_waits++;
+    const StreamStatus st = read_status(ctx->h_stat);
+    size_t packed = 0; // (two independent walks over the same coefficients: cannot differ, in error or length)
+    if (st.err || stream_result(ctx, st, len, false, &packed) != TIC_OK || packed != len)
+        return set_err(ctx, TIC_E_HIP, "the packed stream (%llu bits, error %d) contradicts its probe (%zu bytes)", st.bits, st.err, len);
+    *out_len = len;
+    *quality = q;
+    return TIC_OK;
+}
+
 static int compress_to_size_impl(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, size_t max_bytes, int qmin, int qmax,
                                  void *out, bool out_on_host, size_t cap, size_t *out_len, int *quality) {
     const size_t n = num_blocks(h, w);
@@ -1535,30 +1598,7 @@ static int compress_to_size_impl(tic_ctx *ctx, const void *d_image, int h, int w
             if (fits(mid)) lo = mid; else hi = mid - 1;
         }
     }
-    // the stream of quality lo: transform, pack and place into the context's own buffer, then exactly its bytes into the caller's - the
-    // length is known from the probe, so the copy is queued behind the placing kernel and the whole stream costs one wait
-    const size_t len = (size_t)known[lo];
-    if (len > cap) {
-        *out_len = len;
-        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", len, cap);
-    }
-    rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, compress_bound(h, w));
-    if (rc) return rc;
-    rc = grow_dev(ctx, ctx->d_ent_work, ctx->ent_work_bytes, entropy_fused_work_bytes(n));
-    if (rc) return rc;
-    DctqArgs a = make_args(ctx, d_image, h, w, row_stride, lo, ctx->d_coef);
-    HIPCHK(ctx, launch_dctq(a, dctq_kernel_id(TIC_KERNEL_HYBRID), ctx->stream));
-    HIPCHK(ctx, pack_and_place(ctx, ctx->d_coef, n, h, w, lo, ctx->d_stream_buf, ctx->d_stream_cap, kEntropyEightLanes, 0u));
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_stream_buf, len, out_on_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, out_on_host ? hipStreamSynchronize(ctx->stream) : wait_stream(ctx));
-    ctx->last_rate_waits++;
-    const StreamStatus st = read_status(ctx->h_stat);
-    size_t packed = 0; // (two independent walks over the same coefficients: cannot differ, in error or length)
-    if (st.err || stream_result(ctx, st, len, false, &packed) != TIC_OK || packed != len)
-        return set_err(ctx, TIC_E_HIP, "the packed stream (%llu bits, error %d) contradicts its probe (%zu bytes)", st.bits, st.err, len);
-    *out_len = len;
-    *quality = lo;
-    return TIC_OK;
+    return chosen_stream(ctx, d_image, h, w, row_stride, n, lo, (size_t)known[lo], out, out_on_host, cap, out_len, quality);
 }
 
 static int check_search_args(tic_ctx *ctx, int h, int w, ptrdiff_t row_stride, int qmin, int qmax, const void *out, size_t cap, size_t *out_len,
@@ -1604,6 +1644,239 @@ int tic_last_rate_search(tic_ctx *ctx, int *probes, int *host_waits) {
     if (probes) *probes = ctx->last_rate_probes;
     if (host_waits) *host_waits = ctx->last_rate_waits;
     return TIC_OK;
+}
+
+// ---- rate-distortion: the exact round-trip error without a stream or a decoded frame ------------------------------------------
+// The decoder reproduces the reference's pixels bit for bit, so the squared error between a frame and decompress(compress(frame, q)) is
+// an integer that depends on the quantised coefficients and the frame alone.  The measuring kernel (idct_sse_kernel: idct_kernel's
+// arithmetic, an epilogue that compares instead of storing) sums it from what a rate probe leaves resident.
+static int check_distortion_args(tic_ctx *ctx, int h, int w, ptrdiff_t row_stride, int quality, int scaled_exp, const void *sums) {
+    if (!ctx || !sums) return TIC_E_ARG;
+    if (h < 0 || w < 0) return set_err(ctx, TIC_E_ARG, "negative image size %dx%d", h, w);
+    if (scaled_exp < 0 && (quality < 1 || quality > 99) && !(quality == TIC_QUALITY_CUSTOM && ctx->custom_quality != 0.0))
+        return set_err(ctx, TIC_E_QUALITY, "quality %d outside 1..99", quality);
+    if (scaled_exp > 62) return set_err(ctx, TIC_E_QUALITY, "scaled_dct exponent %d outside 0..62", scaled_exp);
+    if (h > 0 && w > 0 && row_stride < (ptrdiff_t)w) return set_err(ctx, TIC_E_ARG, "row stride %td < width %d", row_stride, w);
+    return TIC_OK;
+}
+
+// Clears result 0 of the context's rate buffer and queues the measuring kernel adding into it; read_distortion brings it back.
+static int queue_distortion(tic_ctx *ctx, const void *d_coeffs_zz, const void *d_image, int h, int w, ptrdiff_t row_stride, int quality,
+                            int scaled_exp, IdctArgs *ia, SseArgs *m) {
+    const int rc = ensure_rate(ctx, 1);
+    if (rc) return rc;
+    measure_args(ctx, d_coeffs_zz, d_image, h, w, row_stride, quality, scaled_exp, dist_of(ctx->d_rate, 1), ia, m);
+    HIPCHK(ctx, hipMemsetAsync(m->res, 0, sizeof(DistortionResult), ctx->stream));
+    return TIC_OK;
+}
+
+static int read_distortion(tic_ctx *ctx, uint64_t sums[2]) {
+    DistortionResult *h_res = dist_of(ctx->h_rate, 1);
+    HIPCHK(ctx, hipMemcpyAsync(h_res, dist_of(ctx->d_rate, 1), sizeof(DistortionResult), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream(ctx));
+    sums[0] = h_res->sse;
+    sums[1] = h_res->sse_wrapped;
+    return TIC_OK;
+}
+
+int tic_distortion_dev(tic_ctx *ctx, const void *d_coeffs_zz, const void *d_image, int h, int w, ptrdiff_t row_stride, int quality,
+                       int scaled_exponent, uint64_t sums[2]) {
+    TIC_LOCK(ctx);
+    int rc = check_distortion_args(ctx, h, w, row_stride, quality, scaled_exponent, sums);
+    if (rc) return rc;
+    sums[0] = sums[1] = 0;
+    if (num_blocks(h, w) == 0) return TIC_OK;
+    if (!d_coeffs_zz || !d_image) return set_err(ctx, TIC_E_ARG, "null device pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    IdctArgs ia;
+    SseArgs m;
+    rc = queue_distortion(ctx, d_coeffs_zz, d_image, h, w, row_stride, quality, scaled_exponent, &ia, &m);
+    if (rc) return rc;
+    HIPCHK(ctx, launch_idct_sse(ia, m, ctx->stream));
+    return read_distortion(ctx, sums);
+}
+
+// Times `iters` back-to-back launches of the measuring kernel on resident coefficients, behind `warm` untimed ones (timed_launches).
+int tic_distortion_dev_timed(tic_ctx *ctx, const void *d_coeffs_zz, const void *d_image, int h, int w, ptrdiff_t row_stride, int quality,
+                             int scaled_exponent, int warm, int iters, float *ms_total) {
+    TIC_LOCK(ctx);
+    int rc = check_distortion_args(ctx, h, w, row_stride, quality, scaled_exponent, ms_total);
+    if (rc) return rc;
+    if (warm < 0 || iters <= 0) return set_err(ctx, TIC_E_ARG, "bad argument");
+    if (num_blocks(h, w) && (!d_coeffs_zz || !d_image)) return set_err(ctx, TIC_E_ARG, "null device pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    IdctArgs ia;
+    SseArgs m;
+    rc = queue_distortion(ctx, d_coeffs_zz, d_image, h, w, row_stride, quality, scaled_exponent, &ia, &m);
+    if (rc) return rc;
+    return timed_launches(ctx, warm, iters, ms_total, nullptr, [&](int, hipEvent_t, hipEvent_t) { return launch_idct_sse(ia, m, ctx->stream); });
+}
+
+// Times idct_kernel alone on resident coefficients, writing pixels to d_out: the launch the measuring kernel is to be compared with.
+int tic_idct_dev_timed(tic_ctx *ctx, const void *d_coeffs_zz, void *d_out, int h, int w, ptrdiff_t out_stride, int quality, int scaled_exponent,
+                       int warm, int iters, float *ms_total) {
+    TIC_LOCK(ctx);
+    int rc = check_distortion_args(ctx, h, w, out_stride, quality, scaled_exponent, ms_total);
+    if (rc) return rc;
+    if (warm < 0 || iters <= 0) return set_err(ctx, TIC_E_ARG, "bad argument");
+    if (num_blocks(h, w) && (!d_coeffs_zz || !d_out)) return set_err(ctx, TIC_E_ARG, "null device pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    IdctArgs ia;
+    SseArgs m;
+    measure_args(ctx, d_coeffs_zz, d_out, h, w, out_stride, quality, scaled_exponent, nullptr, &ia, &m);
+    ia.out = (uint8_t *)d_out;
+    ia.stride = (long)out_stride;
+    ia.aligned8 = m.aligned8;
+    return timed_launches(ctx, warm, iters, ms_total, nullptr, [&](int, hipEvent_t, hipEvent_t) { return launch_idct(ia, ctx->stream); });
+}
+
+static int check_rd_args(tic_ctx *ctx, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq, long long *sizes, const uint64_t *sse,
+                         const uint64_t *sse_wrapped) {
+    if (ctx && nq > 0 && (!sse || !sse_wrapped)) return set_err(ctx, TIC_E_ARG, "null result pointer");
+    return check_size_args(ctx, h, w, row_stride, qualities, nq, sizes);
+}
+
+int tic_rd_points_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq, long long *sizes,
+                      uint64_t *sse, uint64_t *sse_wrapped) {
+    TIC_LOCK(ctx);
+    int rc = check_rd_args(ctx, h, w, row_stride, qualities, nq, sizes, sse, sse_wrapped); // (a bad quality fails here: nothing has been queued)
+    if (rc || nq == 0) return rc;
+    const size_t n = num_blocks(h, w);
+    if (n == 0) { // header only (codec.py:151): no pixel, no error
+        for (int i = 0; i < nq; i++) {
+            sizes[i] = 16;
+            sse[i] = sse_wrapped[i] = 0;
+        }
+        return TIC_OK;
+    }
+    if (!d_image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    rc = ensure_scratch(ctx, 0, n * 128 + 16);
+    if (rc) return rc;
+    rc = ensure_rate(ctx, (size_t)nq);
+    if (rc) return rc;
+    rc = queue_probes(ctx, d_image, h, w, row_stride, n, qualities, nq, true);
+    if (rc) return rc;
+    HIPCHK(ctx, wait_stream(ctx));
+    const DistortionResult *d = dist_of(ctx->h_rate, nq);
+    for (int i = 0; i < nq; i++) {
+        sizes[i] = probe_size(ctx->h_rate[i]);
+        sse[i] = d[i].sse;
+        sse_wrapped[i] = d[i].sse_wrapped;
+    }
+    return TIC_OK;
+}
+
+int tic_rd_points(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq, long long *sizes,
+                  uint64_t *sse, uint64_t *sse_wrapped) {
+    TIC_LOCK(ctx);
+    int rc = check_rd_args(ctx, h, w, row_stride, qualities, nq, sizes, sse, sse_wrapped);
+    if (rc || nq == 0) return rc;
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return tic_rd_points_dev(ctx, nullptr, h, w, row_stride, qualities, nq, sizes, sse, sse_wrapped);
+    if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    size_t pitch = 0;
+    rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
+    if (rc) return rc;
+    return tic_rd_points_dev(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, qualities, nq, sizes, sse, sse_wrapped);
+}
+
+// The search by distortion: the mirror of compress_to_size_impl.  Contract (header, tic_compress_to_psnr_dev): lo, hi = qmin, qmax;
+// while lo < hi: mid = (lo + hi) / 2; meets(mid) ? hi = mid : lo = mid + 1 - the first probe is qmax as well, the look-ahead and its depth
+// per frame size are the size search's.
+static void psnr_candidates(int lo, int hi, int depth, const long long *known, int *out, int *nout) {
+    if (lo >= hi || depth == 0) return;
+    const int mid = (lo + hi) / 2;
+    if (known[mid] == kRateUnknown) out[(*nout)++] = mid;
+    psnr_candidates(lo, mid, depth - 1, known, out, nout);
+    psnr_candidates(mid + 1, hi, depth - 1, known, out, nout);
+}
+
+static int compress_to_psnr_impl(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, uint64_t max_sse, int qmin, int qmax,
+                                 void *out, bool out_on_host, size_t cap, size_t *out_len, int *quality, uint64_t *sse) {
+    const size_t n = num_blocks(h, w);
+    ctx->last_rate_probes = ctx->last_rate_waits = 0;
+    if (n == 0) { // a header and no error at every quality: the bisection ends at qmin
+        if (out_on_host) {
+            write_header((uint8_t *)out, h, w, qmin);
+        } else {
+            const int rc = put_header_only(ctx, out, h, w, qmin, false);
+            if (rc) return rc;
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        *out_len = 16;
+        *quality = qmin;
+        *sse = 0;
+        return TIC_OK;
+    }
+    int rc = ensure_rate(ctx, 8);
+    if (rc) return rc;
+    const int depth = n <= 16384 ? 3 : (n <= 262144 ? 2 : 1);
+    long long known[100];
+    uint64_t known_sse[100];
+    for (auto &k : known) k = kRateUnknown;
+    auto meets = [&](int q) { return known[q] >= 0 && known_sse[q] <= max_sse; };
+    int lo = qmin, hi = qmax;
+    for (bool first = true;; first = false) {
+        int cand[8], nc = 0;
+        if (first) cand[nc++] = qmax; // (never a middle: mid < hi <= qmax)
+        psnr_candidates(lo, hi, depth, known, cand, &nc);
+        if (nc == 0) break;
+        rc = queue_probes(ctx, d_image, h, w, row_stride, n, cand, nc, true);
+        if (rc) return rc;
+        HIPCHK(ctx, wait_stream(ctx));
+        ctx->last_rate_probes += nc;
+        ctx->last_rate_waits++;
+        const DistortionResult *d = dist_of(ctx->h_rate, nc);
+        for (int i = 0; i < nc; i++) {
+            known[cand[i]] = probe_size(ctx->h_rate[i]);
+            known_sse[cand[i]] = d[i].sse;
+        }
+        if (first && !meets(qmax)) {
+            *quality = qmax;
+            *sse = known_sse[qmax];
+            *out_len = 0; // (tells this TIC_E_SPACE from the one of a stream that does not fit cap, which reports its length)
+            if (known[qmax] < 0) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code at quality %d (reference raises KeyError)", qmax);
+            return set_err(ctx, TIC_E_SPACE, "squared error %llu at quality %d exceeds the bound of %llu", (unsigned long long)known_sse[qmax], qmax,
+                           (unsigned long long)max_sse);
+        }
+        while (lo < hi) { // the bisection, as far as the known results carry it
+            const int mid = (lo + hi) / 2;
+            if (known[mid] == kRateUnknown) break;
+            if (meets(mid)) hi = mid; else lo = mid + 1;
+        }
+    }
+    *sse = known_sse[lo];
+    return chosen_stream(ctx, d_image, h, w, row_stride, n, lo, (size_t)known[lo], out, out_on_host, cap, out_len, quality);
+}
+
+int tic_compress_to_psnr_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, uint64_t max_sse, int qmin, int qmax,
+                             void *d_out, size_t cap, size_t *out_len, int *quality, uint64_t *sse) {
+    TIC_LOCK(ctx);
+    if (ctx && !sse) return TIC_E_ARG;
+    int rc = check_search_args(ctx, h, w, row_stride, qmin, qmax, d_out, cap, out_len, quality);
+    if (rc) return rc;
+    const size_t n = num_blocks(h, w);
+    if (n && !d_image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    rc = ensure_scratch(ctx, 0, n * 128 + 16);
+    if (rc) return rc;
+    return compress_to_psnr_impl(ctx, d_image, h, w, row_stride, max_sse, qmin, qmax, d_out, false, cap, out_len, quality, sse);
+}
+
+int tic_compress_to_psnr(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, uint64_t max_sse, int qmin, int qmax,
+                         uint8_t *out, size_t cap, size_t *out_len, int *quality, uint64_t *sse) {
+    TIC_LOCK(ctx);
+    if (ctx && !sse) return TIC_E_ARG;
+    int rc = check_search_args(ctx, h, w, row_stride, qmin, qmax, out, cap, out_len, quality);
+    if (rc) return rc;
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return compress_to_psnr_impl(ctx, nullptr, h, w, row_stride, max_sse, qmin, qmax, out, true, cap, out_len, quality, sse);
+    if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    size_t pitch = 0;
+    rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
+    if (rc) return rc;
+    return compress_to_psnr_impl(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, max_sse, qmin, qmax, out, true, cap, out_len, quality, sse);
 }
 
 // ---- the reference's integer encoder (c/img.c, c/encode.c): scaled-DCT streams ------------------------------------------------
@@ -1693,6 +1966,29 @@ int tic_dctq_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t 
     HIPCHK(ctx, hipMemcpyAsync(coeffs_zz, ctx->d_coef, n * 128, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TIC_OK;
+}
+
+// The distortion column of the reference's tests/cbenchmark.py: the integer encoder's coefficients through the measuring kernel at the
+// exponent the stream's header would carry (the setting's index).
+int tic_roundtrip_sse_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, int qf, uint64_t sums[2]) {
+    TIC_LOCK(ctx);
+    int rc = check_scaled_geometry(ctx, h, w, row_stride, qf);
+    if (rc) return rc;
+    if (!sums) return set_err(ctx, TIC_E_ARG, "null result pointer");
+    sums[0] = sums[1] = 0;
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return TIC_OK;
+    if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    size_t pitch = 0;
+    rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
+    if (rc) return rc;
+    HIPCHK(ctx, launch_fdctq_scaled(make_scaled_args(ctx->d_img, h, w, (ptrdiff_t)pitch, qf, ctx->d_coef), ctx->stream));
+    IdctArgs ia;
+    SseArgs m;
+    rc = queue_distortion(ctx, ctx->d_coef, ctx->d_img, h, w, (ptrdiff_t)pitch, 50, qf, &ia, &m);
+    if (rc) return rc;
+    HIPCHK(ctx, launch_idct_sse(ia, m, ctx->stream));
+    return read_distortion(ctx, sums);
 }
 
 int tic_entropy_encode_scaled(const int16_t *coeffs_zz, int h, int w, int qf, uint8_t *out, size_t cap, size_t *out_len) {

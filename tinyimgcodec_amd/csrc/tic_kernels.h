@@ -83,6 +83,19 @@ struct IdctArgs {
     const int32_t *dc32 = nullptr;
 };
 
+// Round-trip error of a frame (idct_sse_kernel): the sum of d * d and of (d * d) & 255 over its pixels, d = original - decoded.  The
+// second is what squaring a difference of uint8 arrays in uint8 arithmetic sums (the reference's tests/psnr.py).
+struct DistortionResult {
+    unsigned long long sse, sse_wrapped;
+};
+
+struct SseArgs {           // idct_sse_kernel, beside its IdctArgs (whose out / stride / aligned8 / dc32 it does not use)
+    const uint8_t *img;    // device, the original: uint8 [h][stride]; bytes of a row behind w are never read
+    long stride;
+    int aligned8;          // img and stride are multiples of 8 -> 8-byte row loads
+    DistortionResult *res; // device; the kernel ADDS to it (one 64-bit atomic per sum and workgroup)
+};
+
 // C-ABI kernel selector (TIC_KERNEL_AUTO / _EXACT / _HYBRID) -> launch_dctq's variant (1 exact, 2 strip kernel), -1 for anything else.
 int dctq_kernel_id(int abi_variant);
 // ev_start / ev_stop (both or neither): bound to the strip kernel's own dispatch packet (hipExtLaunchKernelGGL) - its start and end
@@ -90,6 +103,7 @@ int dctq_kernel_id(int abi_variant);
 hipError_t launch_dctq(DctqArgs a, int variant, hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 hipError_t launch_dctq_wide(const WideArgs &a, hipStream_t stream);
 hipError_t launch_idct(const IdctArgs &a, hipStream_t stream);
+hipError_t launch_idct_sse(const IdctArgs &a, const SseArgs &m, hipStream_t stream);
 hipError_t launch_selftest_transpose(const void *in, void *out_dpp, void *out_ref, int nthreads, hipStream_t stream);
 
 } // namespace tic

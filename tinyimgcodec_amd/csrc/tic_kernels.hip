@@ -887,8 +887,9 @@ __constant__ int kAnnScalesInt[64] = {
     8867,  12299, 11585, 10426, 8867,  6967,  4799,  2446,  4520,  6270,  5906,  5315,  4520,  3552,  2446,  1247};
 
 // kWideDc: the DC comes from a.dc32 (IdctArgs: a stream whose running DC left int16), everything else as ever
-template <bool kWideDc>
-__device__ __forceinline__ void idct_body(const IdctArgs &a) {
+// kMeasure: the measuring epilogue (idct_sse_kernel): the decoded pixels are compared with the frame `m` describes instead of being stored
+template <bool kWideDc, bool kMeasure = false>
+__device__ __forceinline__ void idct_body(const IdctArgs &a, const SseArgs *m = nullptr) {
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[kWavesPerWG][kLdsWaveBytes / 4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = lane >> 3, i = lane & 7;
@@ -952,6 +953,61 @@ __device__ __forceinline__ void idct_body(const IdctArgs &a) {
         v = v > 255.0 ? 255.0 : v;
         px[k] = (uint32_t)(int)v; // truncation toward zero, as astype(np.uint8) on a clipped value
     }
+    if constexpr (kMeasure) {
+        // Round-trip error instead of pixels: lane i of block b holds decoded row y = 8 by + i, pixels x0 .. x0 + 7; it reads the same eight
+        // pixels of the original (one 8-byte load where that is aligned and whole, byte loads otherwise: the store path's split below) and
+        // sums d * d and (d * d) & 255 over the pixels INSIDE the frame - what lies beyond h or w (the decoder's cropped padding; in the
+        // original whatever the row pitch leaves there) is neither read nor counted.  Eight pixels are at most 8 * 255^2 per lane, a
+        // workgroup's 2,048 at most 2^27: 32 bits up to the one 64-bit atomic per sum and workgroup.  Integer sums: the order of arrival
+        // does not change the result.
+        __shared__ uint32_t wsum[kWavesPerWG][2];
+        uint32_t sq = 0, sw = 0;
+        const int y = s.by * 8 + i, x0 = s.bx * 8;
+        if (s.valid && y < a.h) {
+            const uint8_t *p = m->img + (long)y * m->stride + x0;
+            uint32_t lo = 0, hi = 0;
+            if (m->aligned8 && x0 + 8 <= a.w) {
+                const uint2 v = *reinterpret_cast<const uint2 *>(p);
+                lo = v.x;
+                hi = v.y;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; k++)
+                    if (x0 + k < a.w) {
+                        const uint32_t bt = p[k];
+                        if (k < 4) lo |= bt << (8 * k); else hi |= bt << (8 * (k - 4));
+                    }
+            }
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const int d = (int)px[k] - (int)(((k < 4 ? lo : hi) >> (8 * (k & 3))) & 0xffu);
+                const uint32_t e = x0 + k < a.w ? (uint32_t)(d * d) : 0u;
+                sq += e;
+                sw += e & 255u;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            sq += (uint32_t)__shfl_xor((int)sq, off, 64);
+            sw += (uint32_t)__shfl_xor((int)sw, off, 64);
+        }
+        if (lane == 0) {
+            wsum[wave][0] = sq;
+            wsum[wave][1] = sw;
+        }
+        __syncthreads(); // (every lane of the workgroup arrives: nothing above returns)
+        if (threadIdx.x == 0) {
+            unsigned long long tq = 0, tw = 0;
+#pragma unroll
+            for (int k = 0; k < kWavesPerWG; k++) {
+                tq += wsum[k][0];
+                tw += wsum[k][1];
+            }
+            if (tq) atomicAdd(&m->res->sse, tq); // (tw != 0 implies tq != 0)
+            if (tw) atomicAdd(&m->res->sse_wrapped, tw);
+        }
+        return;
+    }
     if (!s.valid) return;
     int y = s.by * 8 + i;
     if (y >= a.h) return;
@@ -970,6 +1026,8 @@ __device__ __forceinline__ void idct_body(const IdctArgs &a) {
 }
 __global__ __launch_bounds__(kWavesPerWG * 64) void idct_kernel(IdctArgs a) { idct_body<false>(a); }
 __global__ __launch_bounds__(kWavesPerWG * 64) void idct_wide_dc_kernel(IdctArgs a) { idct_body<true>(a); }
+// The measuring instantiation: decode and compare, no pixel written (tic_distortion_dev, tic_rd_points_dev, tic_compress_to_psnr_dev).
+__global__ __launch_bounds__(kWavesPerWG * 64) void idct_sse_kernel(IdctArgs a, SseArgs m) { idct_body<false, true>(a, &m); }
 
 // ---------------------------------------------------------------------------------------------------------
 // Self-test kernel: checks the DPP byte transpose against the shuffle formulation on arbitrary data.
@@ -1196,6 +1254,12 @@ hipError_t launch_idct(const IdctArgs &a, hipStream_t stream) {
     dim3 grid(grid_for(a.ntiles)), block(kWavesPerWG * 64);
     if (a.dc32) hipLaunchKernelGGL(idct_wide_dc_kernel, grid, block, 0, stream, a);
     else hipLaunchKernelGGL(idct_kernel, grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_idct_sse(const IdctArgs &a, const SseArgs &m, hipStream_t stream) {
+    if (a.ntiles <= 0) return hipSuccess;
+    hipLaunchKernelGGL(idct_sse_kernel, dim3(grid_for(a.ntiles)), dim3(kWavesPerWG * 64), 0, stream, a, m);
     return hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
 """Command-line counterpart of the reference's encode.py (encode.py:1-19): image in, .img stream out.
 
     python -m tinyimgcodec_amd.encode_cli input.(gif|png|jpg|npy|raw) output.img [--quality 50] [--shape H W] [--scaled {best,high,med,low}]
-                                         [--max-bytes N [--min-quality 1] [--max-quality 99]]
+                                         [--max-bytes N | --min-psnr DB [--min-quality 1] [--max-quality 99]]
 
 Prints "<n> bytes" and "Compression Ratio: <w*h/n>:1" exactly as the reference does.  Inputs: anything Pillow
 opens (converted to "L" as the reference does), a .npy array, or headerless 8-bit gray (.raw with --shape) so that
@@ -12,7 +12,10 @@ a box without Pillow can still feed it.  Runs on the MI355X path (no CPU fallbac
 reading raw pixels; header flag 1 << 30); --quality is then ignored, and height and width must be multiples of 8.
 
 --max-bytes N writes the stream of the best quality in --min-quality .. --max-quality that fits N bytes (compress_to_size) and prints
-"Quality: <q>" as a third line; it cannot be combined with --scaled or an explicit --quality."""
+"Quality: <q>" as a third line; it cannot be combined with --scaled or an explicit --quality.
+
+--min-psnr DB writes the smallest stream of that range whose round trip reaches DB decibels (compress_to_psnr) and prints "Quality: <q>"
+and "PSNR: <dB>" as third and fourth lines; the same restrictions, and not together with --max-bytes."""
 import argparse
 import sys
 
@@ -38,21 +41,26 @@ def main(argv=None):
     ap.add_argument("--quality", type=int, default=None, help="default 50")
     ap.add_argument("--shape", type=int, nargs=2, metavar=("H", "W"))
     ap.add_argument("--scaled", choices=("best", "high", "med", "low"), help="write the integer encoder's stream (c/encode.c) at this setting")
-    ap.add_argument("--max-bytes", type=int, metavar="N", help="write the best quality whose stream fits N bytes")
-    ap.add_argument("--min-quality", type=int, default=None, help="with --max-bytes: lowest quality tried (default 1)")
-    ap.add_argument("--max-quality", type=int, default=None, help="with --max-bytes: highest quality tried (default 99)")
+    target = ap.add_mutually_exclusive_group()
+    target.add_argument("--max-bytes", type=int, metavar="N", help="write the best quality whose stream fits N bytes")
+    target.add_argument("--min-psnr", type=float, metavar="DB", help="write the smallest stream whose round trip reaches DB decibels")
+    ap.add_argument("--min-quality", type=int, default=None, help="with --max-bytes / --min-psnr: lowest quality tried (default 1)")
+    ap.add_argument("--max-quality", type=int, default=None, help="with --max-bytes / --min-psnr: highest quality tried (default 99)")
     args = ap.parse_args(argv)
-    if args.max_bytes is not None and (args.scaled or args.quality is not None):
-        ap.error("--max-bytes cannot be combined with --scaled or --quality")
-    if args.max_bytes is None and (args.min_quality is not None or args.max_quality is not None):
-        ap.error("--min-quality / --max-quality need --max-bytes")
-    from . import compress, compress_scaled, compress_to_size
+    searching = args.max_bytes is not None or args.min_psnr is not None
+    if searching and (args.scaled or args.quality is not None):
+        ap.error("--max-bytes / --min-psnr cannot be combined with --scaled or --quality")
+    if not searching and (args.min_quality is not None or args.max_quality is not None):
+        ap.error("--min-quality / --max-quality need --max-bytes or --min-psnr")
+    from . import compress, compress_scaled, compress_to_psnr, compress_to_size
 
     im = load_gray(args.input, args.shape)
-    chosen = None
+    chosen = reached = None
+    qrange = (1 if args.min_quality is None else args.min_quality, 99 if args.max_quality is None else args.max_quality)
     if args.max_bytes is not None:
-        out, chosen = compress_to_size(im, args.max_bytes, 1 if args.min_quality is None else args.min_quality,
-                                       99 if args.max_quality is None else args.max_quality)
+        out, chosen = compress_to_size(im, args.max_bytes, *qrange)
+    elif args.min_psnr is not None:
+        out, chosen, reached = compress_to_psnr(im, args.min_psnr, *qrange)
     elif args.scaled:
         out = compress_scaled(im, args.scaled)
     else:
@@ -62,6 +70,8 @@ def main(argv=None):
     print(f"Compression Ratio: {im.shape[1] * im.shape[0] / byte_size}:1")
     if chosen is not None:
         print(f"Quality: {chosen}")
+    if reached is not None:
+        print(f"PSNR: {reached}")
     with open(args.output, "wb") as f:
         f.write(out)
     return 0
