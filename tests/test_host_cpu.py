@@ -346,3 +346,24 @@ def test_rendezvous_file_is_created_exclusively_and_stale_files_are_ignored(tmp_
     # communicators of one job get distinct names
     from tinyimgcodec_amd import distributed as D
     assert D.default_rendezvous_path() != D.default_rendezvous_path()
+
+
+def test_host_pipeline_header_under_the_sanitizers(tmp_path):
+    """The batch pipeline's host-side pieces that need neither HIP nor a context live in csrc/tic_host_pipeline.h, and tests/native/pipeline_selftest.cpp
+    runs them on the CPU: the closable queue (one producer, three consumers, 10,000 items popped exactly once each; close() wakes every waiting
+    consumer; what was pushed before close() is still delivered, then pop() returns false), the strided copy-thread loop (cnt 0..9 on 1..9
+    threads: every index exactly once, inline on one thread), and the three decisions about a caller's buffers - the density rule of the in-place
+    registration, the rows-of-one-block test of the zero-copy read-back, the dense-arena test of tic_decompress_batch - with hand-derived
+    accepting cases and a rejecting case per clause.  Built and run twice as a stand-alone program: under the thread sanitizer, and under the
+    address and undefined-behaviour sanitizers."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no host compiler")
+    src = os.path.join(ROOT, "tests", "native", "pipeline_selftest.cpp")
+    for name, san in (("tsan", "-fsanitize=thread"), ("asan", "-fsanitize=address,undefined")):
+        exe = tmp_path / ("pipeline_selftest_" + name)
+        subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", san, "-pthread", "-o", str(exe), src], check=True)
+        r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and r.stdout.strip().endswith("pipeline_selftest ok") and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, \
+            name + ": " + r.stdout[-2000:] + r.stderr[-2000:]

@@ -7,12 +7,10 @@
 #include <sched.h>
 
 #include <algorithm>
-#include <atomic>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <deque>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -25,6 +23,7 @@
 #include "tic_entropy_dec_gpu.h"
 #include "tic_entropy_gpu.h"
 #include "tic_hooks.h"
+#include "tic_host_pipeline.h"
 #include "tic_kernels.h"
 #include "tic_math.h"
 #include "tic_scaled.h"
@@ -76,8 +75,9 @@ struct Slot {
     int *d_err = nullptr, *h_err = nullptr;
     void *d_streams = nullptr;                                // finished streams, one compress_bound() apart
     int first = 0, count = 0; // frames [first, first+count) are in flight in this slot
-    int remaining = 0;        // frames of the chunk not yet consumed; 0 = slot free
+    int pending = 0;          // pieces of the chunk's work not yet finished (SlotGate); 0 = the slot is free
     size_t rb_row = 0;        // row pitch of the streams read back into pin_out (0: they went straight to the caller)
+    void release();           // frees everything the slot owns
 };
 // Workspace of the device Huffman decoder (tic_entropy_dec_gpu.hip), one per user: the single-frame calls, every asynchronous decode slot
 // and the batch.  Nothing of an earlier run may be in flight when it grows or a run begins.
@@ -215,7 +215,6 @@ struct tic_ctx {
     size_t last_dbatch_work_used = 0, last_dbatch_work_held = 0; // its range, the bytes of work buffer it carves, the bytes the context held
     // batch pipeline buffers, kept across calls (pinned allocations are expensive)
     std::vector<Slot> bslots;
-    size_t bslot_img_bytes = 0, bslot_coef_bytes = 0;
     int bslot_h = -1, bslot_w = -1, bslot_chunk = 0;
     // host side of the batch pipeline: the device's NUMA node and the CPUs of that node this process may run on
     int numa_node = -1;
@@ -399,6 +398,16 @@ void DecWorkspace::release() {
     *this = DecWorkspace();
 }
 
+void Slot::release() {
+    for (void *p : {(void *)pin_in, (void *)pin_out, (void *)h_lens, (void *)h_err})
+        if (p) (void)hipHostFree(p);
+    for (void *p : {d_img, d_coef, d_work, (void *)d_lens, (void *)d_err, d_streams})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t e : {done, rb_done})
+        if (e) (void)hipEventDestroy(e);
+    *this = Slot();
+}
+
 extern "C" {
 
 const char *tic_version(void) { return "tinyimgcodec_amd 0.1.0 (gfx950)"; }
@@ -429,19 +438,7 @@ void tic_destroy(tic_ctx *ctx) {
             (void)hipStreamSynchronize(s);
             (void)hipStreamDestroy(s);
         }
-    for (auto &sl : ctx->bslots) {
-        if (sl.pin_in) (void)hipHostFree(sl.pin_in);
-        if (sl.pin_out) (void)hipHostFree(sl.pin_out);
-        if (sl.d_img) (void)hipFree(sl.d_img);
-        if (sl.d_coef) (void)hipFree(sl.d_coef);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        if (sl.d_work) (void)hipFree(sl.d_work);
-        if (sl.d_lens) (void)hipFree(sl.d_lens);
-        if (sl.h_lens) (void)hipHostFree(sl.h_lens);
-        if (sl.d_err) (void)hipFree(sl.d_err);
-        if (sl.h_err) (void)hipHostFree(sl.h_err);
-        if (sl.d_streams) (void)hipFree(sl.d_streams);
-    }
+    for (auto &sl : ctx->bslots) sl.release();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->d_img) (void)hipFree(ctx->d_img);
@@ -2050,13 +2047,31 @@ int tic_compress_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdif
 }
 
 // ---- batch pipeline (BASELINE config 3) -------------------------------------------------------------------
-// Frames travel in chunks of up to kChunk frames: one pinned staging buffer, one H2D copy, ONE kernel launch
-// (grid row per frame) and one D2H copy per chunk, alternating between two streams so that the copy of chunk
-// c+1 overlaps the kernel of chunk c and the read-back of chunk c-1.  Worker threads entropy-code frame by frame.
+// Frames travel in chunks (chunk_frames): per chunk one H2D copy - from where the caller's frames lie when they are pinned, else out of the
+// slot's pinned staging buffer - and ONE transform launch, on two streams in turn so that the copy of chunk c + 1 overlaps the kernels of
+// chunk c.  Two pipelines share that front: tic_compress_batch with threads > 0 and tic_dctq_batch bring the coefficients back and code
+// them on host worker threads (batch_host_coder); tic_compress_batch with threads <= 0 runs the entropy stage on the device and brings
+// back finished streams (batch_device_entropy).  What they share is written once:
+//   batch_begin     checks, frames without blocks, the plan (BatchPlan), the slots, the call's figures, the batch-wide registration
+//   enqueue_chunk   upload + transform + what the pipeline adds on the chunk's stream + the chunk's `done` event
+//   batch_end       joins the pipeline's threads, drains the streams, releases the call's registrations and the slots
+//   SlotGate        which slot is free (Slot::pending), and the first error a pipeline thread met
+//   ClosableQueue, run_strided, the decisions about the caller's memory: tic_host_pipeline.h
+
+// The slots a context keeps, a chunk in each: one is being staged and uploaded, one is on the device, one has its results read back, one
+// is handed out to the caller (the host coder's pipeline: coded by the workers).  Chunk c takes slot c % kBatchSlots once that is free.
+constexpr int kBatchSlots = 4;
 
 // Row pitch of staged frames: rows that are already a multiple of 8 bytes are staged back to back (one memcpy per
 // frame when the caller's rows are contiguous too); other widths are padded so that 8-byte row loads stay aligned.
 static inline size_t batch_pitch(int w) { return (w % 8 == 0) ? (size_t)w : align_up((size_t)w, 256); }
+
+// What a batch call works out once: blocks per frame, the staged row pitch, bytes of a frame's pixels and coefficients, the distance of two
+// streams in a slot, frames per chunk (0: the call had nothing to put through the pipeline).
+struct BatchPlan {
+    size_t nblk = 0, pitch = 0, img_bytes = 0, coef_bytes = 0, bound = 0;
+    int chunk = 0;
+};
 
 static void stage_frame(uint8_t *dst, size_t pitch, const uint8_t *src, ptrdiff_t row_stride, int h, int w) {
     if ((size_t)row_stride == pitch && pitch == (size_t)w) {
@@ -2074,23 +2089,11 @@ static void stage_chunk(const tic_ctx *ctx, uint8_t *pin, size_t img_bytes, size
     int T = ctx->stage_threads > 0 ? ctx->stage_threads : (int)(hw ? hw / 2 : 4);
     T = T < 1 ? 1 : (T > 8 ? 8 : T);
     if (T > cnt) T = cnt;
-    if (T <= 1 || img_bytes * (size_t)cnt < (4u << 20)) {
-        for (int k = 0; k < cnt; k++) stage_frame(pin + (size_t)k * img_bytes, pitch, images[first + k], row_stride, h, w);
-        return;
-    }
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; t++)
-        th.emplace_back([=]() {
-            bind_pipeline_thread(ctx);
-            for (int k = t; k < cnt; k += T) stage_frame(pin + (size_t)k * img_bytes, pitch, images[first + k], row_stride, h, w);
-        });
-    for (auto &x : th) x.join();
+    if (img_bytes * (size_t)cnt < (4u << 20)) T = 1;
+    run_strided(cnt, T, [ctx]() { bind_pipeline_thread(ctx); },
+                [=](int k) { stage_frame(pin + (size_t)k * img_bytes, pitch, images[first + k], row_stride, h, w); });
 }
 
-// Host -> device copy of a chunk.  Frames the caller holds in pinned or registered memory, rows back to back, go to the device from
-// where they lie (one copy for the chunk when the frames follow each other in memory, else one per frame); anything else is staged
-// into the slot's pinned buffer first (pageable memory: the runtime would stage it too, synchronously and through a small bounce
-// buffer).  Returns the number of frames that took the direct path.
 static bool host_pointer_is_pinned(const void *p) {
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, p) != hipSuccess) {
@@ -2099,16 +2102,25 @@ static bool host_pointer_is_pinned(const void *p) {
     }
     return at.type == hipMemoryTypeHost;
 }
+// Pins [p, p + bytes), widened to whole pages, where it lies.  Returns the registered base for hipHostUnregister, or null when the runtime
+// refuses (memory of another kind, part of the range registered already): not an error of ours, the caller takes its other route.
+static void *pin_range(const void *p, size_t bytes) {
+    const uintptr_t lo = page_floor((uintptr_t)p), hi = page_ceil((uintptr_t)p + bytes);
+    if (hipHostRegister((void *)lo, hi - lo, hipHostRegisterDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return (void *)lo;
+}
 // Pageable input.  Copying 2 MB frames into the pinned slots costs the host 2 x the batch in DRAM traffic and eight copy threads,
 // and it is what makes the host -> host rate depend on the box: 12.3 ms for 256 x 1080p on a quiet host, 18-22 ms when the copy
 // threads compete with other tenants or sit on the wrong side of the socket link (profiles/r04_numa_probe.txt), while frames the
 // DMA engine reads where they lie take 12.7-13.5 ms everywhere.  hipHostRegister is cheap PER CALL, not per byte - 0.03 ms for a
 // chunk's 36 MB, 0.18 ms for 510 MB, the pages are validated when the copy engine first touches them - but 77 us per call: one by
 // one, 256 frames cost 19.7 ms.  So the frames [first, first + cnt) are registered as ONE range, from the lowest to the highest
-// address, when that range is dense enough to be mostly frames (arrays allocated one after the other are 16 bytes to a few pages
-// apart) - for the whole batch if possible, else chunk by chunk.  Anything that cannot be registered this way (a range with a
-// hole, memory of another kind, part of it registered by the caller already) is staged as before.  Returns true if the frames
-// are now pinned.
+// address, when that range is dense enough to be mostly frames (range_is_mostly_frames) - for the whole batch if possible, else chunk
+// by chunk.  Anything that cannot be registered this way (a range with a hole, memory of another kind, part of it registered by the
+// caller already) is staged.  Returns true if the frames are now pinned.
 static bool auto_register_frames(tic_ctx *ctx, const uint8_t *const *images, int first, int cnt, size_t img_bytes) {
     if (!ctx->auto_register || cnt < 1 || img_bytes < (256u << 10)) return false;
     // (a range over frames of which some are pinned already would overlap the caller's own registration: such a set is left alone)
@@ -2121,15 +2133,10 @@ static bool auto_register_frames(tic_ctx *ctx, const uint8_t *const *images, int
         lo = p < lo ? p : lo;
         hi = p + img_bytes > hi ? p + img_bytes : hi;
     }
-    lo &= ~(uintptr_t)4095;
-    hi = (hi + 4095) & ~(uintptr_t)4095;
-    const size_t span = hi - lo, frames = img_bytes * (size_t)cnt;
-    if (span > frames + frames / 4 + (1u << 20)) return false; // the frames lie scattered: a range over them would pin memory that is not theirs
-    if (hipHostRegister((void *)lo, span, hipHostRegisterDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    ctx->autoregs.push_back((void *)lo);
+    if (!range_is_mostly_frames(lo, hi, img_bytes, (size_t)cnt)) return false;
+    void *reg = pin_range((const void *)lo, hi - lo);
+    if (!reg) return false;
+    ctx->autoregs.push_back(reg);
     ctx->last_batch_autoreg_frames += cnt;
     return true;
 }
@@ -2140,6 +2147,10 @@ static void auto_unregister_all(tic_ctx *ctx) { // (after the call's last copy h
     ctx->autoregs.clear();
 }
 
+// Host -> device copy of a chunk.  Frames the caller holds in pinned or registered memory, rows back to back, go to the device from
+// where they lie (one copy for the chunk when the frames follow each other in memory, else one per frame); anything else is staged
+// into the slot's pinned buffer first (pageable memory: the runtime would stage it too, synchronously and through a small bounce
+// buffer).  *direct: the number of frames that took the direct path.
 static hipError_t upload_chunk(tic_ctx *ctx, Slot &s, size_t img_bytes, size_t pitch, const uint8_t *const *images, int first, int cnt,
                                ptrdiff_t row_stride, int h, int w, hipStream_t st, int *direct) {
     *direct = 0;
@@ -2179,507 +2190,159 @@ static hipError_t upload_chunk(tic_ctx *ctx, Slot &s, size_t img_bytes, size_t p
 }
 
 static int ensure_batch_slots(tic_ctx *ctx, int h, int w, int chunk) {
-    const int S = 4; // staging, device, read-back, hand-out: one chunk each
+    if ((int)ctx->bslots.size() == kBatchSlots && ctx->bslot_h == h && ctx->bslot_w == w && ctx->bslot_chunk >= chunk) return TIC_OK;
     const size_t nblk = num_blocks(h, w);
-    const size_t pitch = batch_pitch(w);
-    const size_t img_bytes = pitch * (size_t)h, coef_bytes = nblk * 128;
-    const size_t need_img = img_bytes * chunk, need_coef = coef_bytes * chunk;
-    if ((int)ctx->bslots.size() != S || ctx->bslot_h != h || ctx->bslot_w != w || ctx->bslot_chunk < chunk) {
-        for (auto &sl : ctx->bslots) {
-            if (sl.pin_in) (void)hipHostFree(sl.pin_in);
-            if (sl.pin_out) (void)hipHostFree(sl.pin_out);
-            if (sl.d_img) (void)hipFree(sl.d_img);
-            if (sl.d_coef) (void)hipFree(sl.d_coef);
-            if (sl.done) (void)hipEventDestroy(sl.done);
-            if (sl.rb_done) (void)hipEventDestroy(sl.rb_done);
-            if (sl.d_work) (void)hipFree(sl.d_work);
-            if (sl.d_lens) (void)hipFree(sl.d_lens);
-            if (sl.h_lens) (void)hipHostFree(sl.h_lens);
-            if (sl.d_err) (void)hipFree(sl.d_err);
-            if (sl.h_err) (void)hipHostFree(sl.h_err);
-            if (sl.d_streams) (void)hipFree(sl.d_streams);
-        }
-        ctx->bslots.assign(S, Slot());
-        ctx->bslot_img_bytes = ctx->bslot_coef_bytes = 0;
-        ctx->bslot_h = ctx->bslot_w = -1;
-        ctx->bslot_chunk = 0;
-        for (auto &sl : ctx->bslots) {
-            hipError_t e;
-            if ((e = hipHostMalloc((void **)&sl.pin_in, need_img, hipHostMallocDefault)) != hipSuccess ||
-                (e = hipHostMalloc((void **)&sl.pin_out, need_coef, hipHostMallocDefault)) != hipSuccess ||
-                (e = hipMalloc(&sl.d_img, need_img)) != hipSuccess || (e = hipMalloc(&sl.d_coef, need_coef)) != hipSuccess ||
-                (e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)) != hipSuccess ||
-                (e = hipEventCreateWithFlags(&sl.rb_done, hipEventDisableTiming)) != hipSuccess)
-                return set_err(ctx, TIC_E_HIP, "batch buffer allocation failed: %s", hipGetErrorString(e));
-            sl.work_bytes = entropy_fused_work_bytes((nblk + 8) * (size_t)chunk); // (every frame's partitions are rounded up)
-            sl.parity = 0;
-            if ((e = hipMalloc(&sl.d_work, sl.work_bytes)) != hipSuccess ||
-                (e = hipMalloc((void **)&sl.d_lens, chunk * sizeof(unsigned long long))) != hipSuccess ||
-                (e = hipHostMalloc((void **)&sl.h_lens, chunk * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess ||
-                (e = hipMalloc((void **)&sl.d_err, 2 * sizeof(int))) != hipSuccess || (e = hipMemset(sl.d_err, 0, 2 * sizeof(int))) != hipSuccess ||
-                (e = hipHostMalloc((void **)&sl.h_err, sizeof(int), hipHostMallocDefault)) != hipSuccess ||
-                (e = hipMalloc(&sl.d_streams, align_up(compress_bound(h, w), 16) * (size_t)chunk)) != hipSuccess)
-                return set_err(ctx, TIC_E_HIP, "batch entropy workspace allocation failed: %s", hipGetErrorString(e));
-        }
-        ctx->bslot_img_bytes = need_img;
-        ctx->bslot_coef_bytes = need_coef;
-        ctx->bslot_h = h;
-        ctx->bslot_w = w;
-        ctx->bslot_chunk = chunk;
+    const size_t need_img = batch_pitch(w) * (size_t)h * chunk, need_coef = nblk * 128 * chunk;
+    for (auto &sl : ctx->bslots) sl.release();
+    ctx->bslots.assign(kBatchSlots, Slot());
+    ctx->bslot_h = ctx->bslot_w = -1;
+    ctx->bslot_chunk = 0;
+    for (auto &sl : ctx->bslots) {
+        hipError_t e;
+        if ((e = hipHostMalloc((void **)&sl.pin_in, need_img, hipHostMallocDefault)) != hipSuccess ||
+            (e = hipHostMalloc((void **)&sl.pin_out, need_coef, hipHostMallocDefault)) != hipSuccess ||
+            (e = hipMalloc(&sl.d_img, need_img)) != hipSuccess || (e = hipMalloc(&sl.d_coef, need_coef)) != hipSuccess ||
+            (e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)) != hipSuccess ||
+            (e = hipEventCreateWithFlags(&sl.rb_done, hipEventDisableTiming)) != hipSuccess)
+            return set_err(ctx, TIC_E_HIP, "batch buffer allocation failed: %s", hipGetErrorString(e));
+        sl.work_bytes = entropy_fused_work_bytes((nblk + 8) * (size_t)chunk); // (every frame's partitions are rounded up)
+        if ((e = hipMalloc(&sl.d_work, sl.work_bytes)) != hipSuccess ||
+            (e = hipMalloc((void **)&sl.d_lens, chunk * sizeof(unsigned long long))) != hipSuccess ||
+            (e = hipHostMalloc((void **)&sl.h_lens, chunk * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess ||
+            (e = hipMalloc((void **)&sl.d_err, 2 * sizeof(int))) != hipSuccess || (e = hipMemset(sl.d_err, 0, 2 * sizeof(int))) != hipSuccess ||
+            (e = hipHostMalloc((void **)&sl.h_err, sizeof(int), hipHostMallocDefault)) != hipSuccess ||
+            (e = hipMalloc(&sl.d_streams, align_up(compress_bound(h, w), 16) * (size_t)chunk)) != hipSuccess)
+            return set_err(ctx, TIC_E_HIP, "batch entropy workspace allocation failed: %s", hipGetErrorString(e));
     }
+    ctx->bslot_h = h;
+    ctx->bslot_w = w;
+    ctx->bslot_chunk = chunk;
     return TIC_OK;
 }
 
-static int batch_impl(tic_ctx *ctx, const uint8_t *const *images, int n, int h, int w, ptrdiff_t row_stride, int quality,
-                      int16_t *const *coeffs, uint8_t *const *outs, const size_t *caps, size_t *out_lens, int threads,
-                      bool want_entropy) {
-    int rc = check_geometry(ctx, h, w, row_stride, quality);
+// The front end of both pipelines: argument checks (`device_entropy`: the stricter ones of the calls whose streams the device writes),
+// frames without blocks (a header each, where streams are wanted), the plan, the slots, the call's figures, and the registration of the whole
+// batch as one range, if it is one.  p->chunk == 0 on return: nothing is left to do - an error, n == 0, or frames without blocks.
+static int batch_begin(tic_ctx *ctx, const uint8_t *const *images, int n, int h, int w, ptrdiff_t row_stride, int quality, bool want_streams,
+                       bool device_entropy, uint8_t *const *outs, const size_t *caps, size_t *out_lens, BatchPlan *p) {
+    *p = BatchPlan();
+    int rc = device_entropy ? check_stream_geometry(ctx, h, w, row_stride, quality) : check_geometry(ctx, h, w, row_stride, quality);
     if (rc) return rc;
     if (n < 0 || (n > 0 && !images)) return set_err(ctx, TIC_E_ARG, "bad batch arguments");
-    if (want_entropy && n > 0 && (!outs || !caps || !out_lens)) return set_err(ctx, TIC_E_ARG, "null output arrays");
+    if (want_streams && n > 0 && (!outs || !caps || !out_lens)) return set_err(ctx, TIC_E_ARG, "null output arrays");
     if (n == 0) return TIC_OK;
     const size_t nblk = num_blocks(h, w);
     if (nblk == 0) {
-        for (int i = 0; i < n && want_entropy; i++) {
+        for (int i = 0; i < n && want_streams; i++) {
             int r = entropy_encode(nullptr, h, w, quality, outs[i], caps[i], &out_lens[i]);
             if (r) return r;
         }
         return TIC_OK;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const bool need_d2h = want_entropy || coeffs != nullptr;
-    const size_t pitch = batch_pitch(w);
-    const size_t img_bytes = pitch * (size_t)h, coef_bytes = nblk * 128;
+    const size_t pitch = batch_pitch(w), img_bytes = pitch * (size_t)h;
     const int chunk = chunk_frames(n, img_bytes);
-    const int S = 3;
-    int result = TIC_OK;
     rc = ensure_batch_slots(ctx, h, w, chunk);
     if (rc) return rc;
-    std::vector<Slot> &slots = ctx->bslots;
-    for (auto &sl : slots) sl.remaining = 0;
-    auto cleanup = [&]() {};
-
-    std::mutex mu;
-    std::condition_variable cv_job, cv_free;
-    std::deque<std::pair<int, int>> jobs; // (slot, frame index inside the chunk)
-    bool closing = false;
-    std::atomic<int> first_err{TIC_OK};
-
-    ctx->last_batch_direct_frames = ctx->last_batch_staged_frames = ctx->last_batch_autoreg_frames = 0;
+    for (auto &sl : ctx->bslots) sl.pending = 0;
+    ctx->last_batch_direct_frames = ctx->last_batch_staged_frames = ctx->last_batch_autoreg_frames = ctx->last_batch_zero_copy = 0;
     ctx->bt = BatchTrace();
     if ((size_t)row_stride == pitch && pitch == (size_t)w) { // the whole batch as one range, if it is one
         BT_START();
         (void)auto_register_frames(ctx, images, 0, n, img_bytes);
         BT_STOP(0);
     }
-    auto consumer = [&]() {
-        bind_pipeline_thread(ctx);
-        (void)hipSetDevice(ctx->device);
-        for (;;) {
-            std::pair<int, int> job;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv_job.wait(lk, [&] { return !jobs.empty() || closing; });
-                if (jobs.empty()) return;
-                job = jobs.front();
-                jobs.pop_front();
-            }
-            Slot &s = slots[job.first];
-            const int f = s.first + job.second;
-            int r = hipEventSynchronize(s.done) == hipSuccess ? TIC_OK : TIC_E_HIP;
-            const int16_t *zz = need_d2h ? s.pin_out + (size_t)job.second * nblk * 64 : nullptr;
-            if (r == TIC_OK && want_entropy) r = entropy_encode(zz, h, w, quality, outs[f], caps[f], &out_lens[f]);
-            if (r == TIC_OK && coeffs && coeffs[f]) memcpy(coeffs[f], zz, coef_bytes);
-            if (r != TIC_OK) {
-                int exp = TIC_OK;
-                first_err.compare_exchange_strong(exp, r);
-            }
-            bool freed;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                freed = --s.remaining == 0;
-            }
-            if (freed) cv_free.notify_all();
-        }
-    };
-    int nthreads = threads < 1 ? 1 : (threads > 64 ? 64 : threads);
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nthreads; t++) pool.emplace_back(consumer);
-
-    int c = 0;
-    for (int first = 0; first < n && result == TIC_OK; first += chunk, c++) {
-        const int cnt = n - first < chunk ? n - first : chunk;
-        const int si = c % S;
-        Slot &s = slots[si];
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv_free.wait(lk, [&] { return s.remaining == 0; });
-            s.first = first;
-            s.count = cnt;
-            s.remaining = cnt;
-        }
-        hipStream_t st = ctx->bstream[c & 1];
-        int direct = 0;
-        hipError_t e = upload_chunk(ctx, s, img_bytes, pitch, images, first, cnt, row_stride, h, w, st, &direct);
-        ctx->last_batch_direct_frames += direct;
-        ctx->last_batch_staged_frames += cnt - direct;
-        BT_START();
-        if (e == hipSuccess) {
-            DctqArgs a = make_args(ctx, s.d_img, h, w, (ptrdiff_t)pitch, quality, s.d_coef);
-            a.fallback_count = nullptr;
-            a.nframes = cnt;
-            a.frame_stride_in = (long)img_bytes;
-            a.frame_stride_out = (long)coef_bytes;
-            merge_frames(a);
-            e = launch_dctq(a, 2, st);
-        }
-        if (e == hipSuccess && need_d2h) e = hipMemcpyAsync(s.pin_out, s.d_coef, coef_bytes * cnt, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipEventRecord(s.done, st);
-        BT_STOP(1);
-        if (e != hipSuccess) {
-            result = set_err(ctx, TIC_E_HIP, "batch enqueue failed at frame %d: %s", first, hipGetErrorString(e));
-            std::lock_guard<std::mutex> lk(mu);
-            s.remaining = 0;
-            break;
-        }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            for (int k = 0; k < cnt; k++) jobs.emplace_back(si, k);
-        }
-        cv_job.notify_all();
-    }
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        closing = true;
-    }
-    cv_job.notify_all();
-    for (auto &t : pool) t.join();
-    (void)hipStreamSynchronize(ctx->bstream[0]);
-    (void)hipStreamSynchronize(ctx->bstream[1]);
-    auto_unregister_all(ctx);
-    cleanup();
-    if (result == TIC_OK && first_err.load() != TIC_OK)
-        result = set_err(ctx, first_err.load(), "batch consumer failed with code %d", first_err.load());
-    return result;
+    p->nblk = nblk, p->pitch = pitch, p->img_bytes = img_bytes, p->coef_bytes = nblk * 128, p->bound = align_up(compress_bound(h, w), 16);
+    p->chunk = chunk;
+    return TIC_OK;
 }
 
-// Batch compress with the entropy stage on the device: per chunk one H2D copy, one transform launch, the three
-// entropy steps, then only the finished streams (and 8 bytes of length per frame) come back.
-constexpr int kRetryEightLanes = -1000; // internal: compress_batch_gpu asks tic_compress_batch for another run with the 8-lane packing kernel
+// Which slot is free, and the first error one of a pipeline's threads met.  A chunk claims its slot for `units` pieces of work (the
+// device entropy pipeline: 1, the chunk; the host coder's: its frames, one per worker job); whoever finishes the last piece frees it.
+struct SlotGate {
+    std::mutex mu;
+    std::condition_variable cv;
+    int err = TIC_OK;
+    void claim(tic_ctx *ctx, Slot &s, int units) { // (tic_last_batch_phases [5]: the submitting thread's wait for a free slot)
+        BT_START();
+        std::unique_lock<std::mutex> l(mu);
+        cv.wait(l, [&] { return s.pending == 0; });
+        s.pending = units;
+        BT_STOP(5);
+    }
+    void finish(Slot &s) {
+        bool freed;
+        {
+            std::lock_guard<std::mutex> l(mu);
+            freed = --s.pending == 0;
+        }
+        if (freed) cv.notify_all();
+    }
+    void fail(int rc) {
+        std::lock_guard<std::mutex> l(mu);
+        if (err == TIC_OK) err = rc;
+    }
+    int error() {
+        std::lock_guard<std::mutex> l(mu);
+        return err;
+    }
+};
 
-// Read-back of a chunk's streams by the SHADER, not by a DMA engine: rows of `row16` 16-byte pieces from device memory into the slot's
-// pinned host buffer (device-accessible).  The runtime spreads the batch's uploads over both SDMA engines and queues every later copy
+// Enqueues frames [first, first + cnt) in slot `s` on stream `st`: the upload, ONE transform launch (a grid plane per frame, or one tall
+// frame where merge_frames sees one), then `rest(s, st)` - what the pipeline wants on the stream behind the transform - and the slot's
+// `done` event.
+extern "C++" { // (templates inside the C-ABI block)
+template <class Rest>
+static int enqueue_chunk(tic_ctx *ctx, const BatchPlan &p, Slot &s, hipStream_t st, const uint8_t *const *images, int first, int cnt,
+                         ptrdiff_t row_stride, int h, int w, int quality, Rest rest) {
+    s.first = first;
+    s.count = cnt;
+    DctqArgs a = make_args(ctx, s.d_img, h, w, (ptrdiff_t)p.pitch, quality, s.d_coef);
+    a.fallback_count = nullptr;
+    const int rc = set_frames(ctx, a, cnt, h, w, (ptrdiff_t)p.pitch, (ptrdiff_t)p.img_bytes, (ptrdiff_t)p.coef_bytes);
+    if (rc) return rc;
+    merge_frames(a);
+    int direct = 0;
+    hipError_t e = upload_chunk(ctx, s, p.img_bytes, p.pitch, images, first, cnt, row_stride, h, w, st, &direct);
+    ctx->last_batch_direct_frames += direct;
+    ctx->last_batch_staged_frames += cnt - direct;
+    BT_START();
+    if (e == hipSuccess) e = launch_dctq(a, 2, st);
+    if (e == hipSuccess) e = rest(s, st);
+    if (e == hipSuccess) e = hipEventRecord(s.done, st);
+    BT_STOP(1);
+    if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "batch enqueue failed at frame %d: %s", first, hipGetErrorString(e));
+    return TIC_OK;
+}
+
+// Read-back of a chunk's streams by the SHADER, not by a DMA engine: `row` pieces of V (16 or 8 bytes) of every row from device memory into
+// device-accessible host memory.  The runtime spreads the batch's uploads over both SDMA engines and queues every later copy
 // behind the uploads already submitted - with four chunks of uploads in the queue a chunk's read-back started 2 ms after its kernels
 // had finished, the read-backs came in bursts of four, and the uploads stalled 0.5-0.7 ms behind every burst for want of a free slot
 // (rocprofv3 --memory-copy-trace, profiles/r04_batch_timeline.txt).  Stores from a kernel cross the link in the other direction while
 // the engines upload.
-__global__ __launch_bounds__(256) void readback_rows_kernel(const uint4 *__restrict__ src, size_t src_pitch16, uint4 *__restrict__ dst, size_t dst_pitch16,
-                                                            size_t row16) {
-    const uint4 *s = src + (size_t)blockIdx.y * src_pitch16;
-    uint4 *d = dst + (size_t)blockIdx.y * dst_pitch16;
-    typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < row16; i += (size_t)gridDim.x * 256u)
-        __builtin_nontemporal_store(reinterpret_cast<const u32x4v *>(s)[i], reinterpret_cast<u32x4v *>(d) + i);
+template <class V>
+__global__ __launch_bounds__(256) void readback_rows_kernel(const V *__restrict__ src, size_t src_pitch, V *__restrict__ dst, size_t dst_pitch, size_t row) {
+    const V *s = src + (size_t)blockIdx.y * src_pitch;
+    V *d = dst + (size_t)blockIdx.y * dst_pitch;
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < row; i += (size_t)gridDim.x * 256u) __builtin_nontemporal_store(s[i], d + i);
 }
-
-// ... and straight into the CALLER's buffers when those are rows of one block of memory (a pool of n x cap bytes: what compress_batch() of the
-// Python mirror and bench.py hold), pinned for the call: 8-byte pieces, because a row pitch of tic_compress_bound() bytes is a multiple of 8, not 16.
-__global__ __launch_bounds__(256) void readback_rows8_kernel(const uint2 *__restrict__ src, size_t src_pitch8, uint2 *__restrict__ dst, size_t dst_pitch8, size_t row8) {
-    const uint2 *s = src + (size_t)blockIdx.y * src_pitch8;
-    uint2 *d = dst + (size_t)blockIdx.y * dst_pitch8;
-    typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
-    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < row8; i += (size_t)gridDim.x * 256u)
-        __builtin_nontemporal_store(reinterpret_cast<const u32x2v *>(s)[i], reinterpret_cast<u32x2v *>(d) + i);
+// `rows` rows of `row_bytes` (rounded up to whole pieces), the pitches in bytes (multiples of the piece)
+template <class V>
+static hipError_t launch_readback(const void *src, size_t src_pitch, void *dst, size_t dst_pitch, size_t row_bytes, int rows, hipStream_t st) {
+    hipLaunchKernelGGL(readback_rows_kernel<V>, dim3(64, (unsigned)rows), dim3(256), 0, st, (const V *)src, src_pitch / sizeof(V), (V *)dst, dst_pitch / sizeof(V),
+                       (row_bytes + sizeof(V) - 1) / sizeof(V));
+    return hipGetLastError();
 }
+}
+typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
 
-static int compress_batch_gpu(tic_ctx *ctx, const uint8_t *const *images, int n, int h, int w, ptrdiff_t row_stride,
-                              int quality, uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
-    int rc = check_stream_geometry(ctx, h, w, row_stride, quality);
-    if (rc) return rc;
-    if (n < 0 || (n > 0 && (!images || !outs || !caps || !out_lens))) return set_err(ctx, TIC_E_ARG, "bad batch arguments");
-    if (n == 0) return TIC_OK;
-    const size_t nblk = num_blocks(h, w);
-    if (nblk == 0) {
-        for (int i = 0; i < n; i++) {
-            int r = entropy_encode(nullptr, h, w, quality, outs[i], caps[i], &out_lens[i]);
-            if (r) return r;
-        }
-        return TIC_OK;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t pitch = batch_pitch(w);
-    const size_t img_bytes = pitch * (size_t)h, coef_bytes = nblk * 128, bound = align_up(compress_bound(h, w), 16);
-    const int chunk = chunk_frames(n, img_bytes);
-    rc = ensure_batch_slots(ctx, h, w, chunk);
-    if (rc) return rc;
-    std::vector<Slot> &slots = ctx->bslots;
-    const int S = (int)slots.size();
-    int result = TIC_OK;
-    const bool inline_path = n <= chunk; // a batch of ONE chunk runs on the calling thread (below)
-    // finishing a chunk, part 1: wait for its lengths, then read its streams back into pinned memory
-    auto read_back = [&](Slot &s, hipStream_t st) -> int {
-        if (s.count == 0) return TIC_OK;
-        BT_START();
-        const hipError_t ev = hipEventSynchronize(s.done);
-        BT_STOP(2);
-        if (ev != hipSuccess) return set_err(ctx, TIC_E_HIP, "batch chunk failed");
-        if (*s.h_err == 1) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code (reference raises KeyError)");
-        if (*s.h_err == 4) return kRetryEightLanes; // a block exceeds the lane-per-block kernel's strings: the whole call is run again
-        if (*s.h_err) return set_err(ctx, TIC_E_SPACE, "device entropy stage: stream buffer too small");
-        // The streams come back into the slot's pinned buffer (asynchronous DMA; a copy straight into the caller's pageable
-        // buffers is staged by the runtime, ~0.15 ms each) and are handed out by a few threads.
-        size_t maxlen = 0;
-        for (int k = 0; k < s.count; k++) {
-            const size_t len = (size_t)s.h_lens[k];
-            const int f = s.first + k;
-            if (len > caps[f]) return set_err(ctx, TIC_E_SPACE, "output buffer of frame %d too small (%zu bytes needed)", f, len);
-            out_lens[f] = len;
-            if (len > maxlen) maxlen = len;
-        }
-        // ONE strided copy brings the head of every frame's stream buffer - as many bytes as the longest stream has - into
-        // the slot's pinned buffer (16 separate copies of ~0.9 MB cost ~45 us each, 2.5 x their transfer time); frames of one
-        // batch compress to similar sizes, so little more than the streams themselves crosses PCIe.
-        // Zero copy (round 6; a batch of one chunk only - it runs on the calling thread, which owns the call's registrations): the caller's
-        // buffers are rows of ONE block of memory (equal distances, 8-byte aligned: a pool of n x cap bytes) -> the block is pinned for the
-        // call and the shader stores every stream where the caller wants it; the copy out of the pipeline's pinned buffer (0.12-0.28 ms for the
-        // 49 streams of the reference's benchmark set: a third of the call) does not happen.  The rows are written up to the chunk's longest
-        // stream rounded to 8 bytes (all within the frames' capacities, checked): bytes behind a stream's end are not preserved.
-        if (inline_path && ctx->auto_register && s.count >= 2 && maxlen >= 16) {
-            const uint8_t *base = outs[s.first];
-            const size_t P = (size_t)(outs[s.first + 1] - outs[s.first]), row8 = (maxlen + 7) / 8;
-            bool ok = outs[s.first + 1] > outs[s.first] && P % 8 == 0 && (uintptr_t)base % 8 == 0 && P >= row8 * 8;
-            for (int k = 0; k < s.count && ok; k++) ok = outs[s.first + k] == base + (size_t)k * P && caps[s.first + k] >= row8 * 8;
-            const size_t span = ok ? (size_t)(s.count - 1) * P + row8 * 8 : 0;
-            void *reg = nullptr;
-            if (ok && !(host_pointer_is_pinned(base) && host_pointer_is_pinned(base + span - 1))) {
-                const uintptr_t lo = (uintptr_t)base & ~(uintptr_t)4095, hi = ((uintptr_t)base + span + 4095) & ~(uintptr_t)4095;
-                if (hipHostRegister((void *)lo, hi - lo, hipHostRegisterDefault) == hipSuccess) {
-                    reg = (void *)lo;
-                    ctx->autoregs.push_back(reg); // (released with the call's other registrations, behind its last synchronisation)
-                } else {
-                    (void)hipGetLastError();
-                    ok = false;
-                }
-            }
-            void *d_dst = nullptr;
-            if (ok && hipHostGetDevicePointer(&d_dst, (void *)base, 0) != hipSuccess) {
-                (void)hipGetLastError();
-                ok = false;
-            }
-            if (ok) {
-                BT_START();
-                hipLaunchKernelGGL(readback_rows8_kernel, dim3(64, (unsigned)s.count), dim3(256), 0, st, (const uint2 *)s.d_streams, bound / 8, (uint2 *)d_dst, P / 8, row8);
-                hipError_t e = hipGetLastError();
-                if (e == hipSuccess) e = hipEventRecord(s.rb_done, st);
-                BT_STOP(3);
-                if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "stream read-back failed: %s", hipGetErrorString(e));
-                s.rb_row = 0; // (nothing to hand out)
-                ctx->last_batch_zero_copy += s.count;
-                return TIC_OK;
-            }
-        }
-        const size_t pin_cap = coef_bytes * (size_t)chunk; // size of pin_out (ensure_batch_slots)
-        const size_t row = align_up(maxlen, 256);
-        const bool packed = row * (size_t)s.count <= pin_cap;
-        BT_START();
-        if (packed) {
-            // (round 3: ONE strided hipMemcpy2DAsync per chunk - 16 separate copies of ~0.9 MB cost ~45 us each; now the kernel above)
-            const size_t row16 = (maxlen + 15) / 16; // (row and bound are multiples of 16; the bytes behind a stream are never handed out)
-            hipLaunchKernelGGL(readback_rows_kernel, dim3(64, (unsigned)s.count), dim3(256), 0, st, (const uint4 *)s.d_streams, bound / 16, (uint4 *)s.pin_out, row / 16,
-                               row16);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "stream read-back failed: %s", hipGetErrorString(e));
-        } else {
-            for (int k = 0; k < s.count; k++) {
-                hipError_t e = hipMemcpyAsync(outs[s.first + k], (char *)s.d_streams + (size_t)k * bound, (size_t)s.h_lens[k],
-                                              hipMemcpyDeviceToHost, st);
-                if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "stream read-back failed: %s", hipGetErrorString(e));
-            }
-        }
-        // (the reading thread does not wait for the copy: it records an event behind it and turns to the next chunk, so that the
-        // read-backs follow each other on their stream without a host round trip in between; the hand-out thread waits for the event)
-        const hipError_t rb = hipEventRecord(s.rb_done, st);
-        BT_STOP(3);
-        if (rb != hipSuccess) return set_err(ctx, TIC_E_HIP, "stream read-back failed");
-        s.rb_row = packed ? row : 0;
-        return TIC_OK;
-    };
-    // part 2: out of pinned memory into the caller's buffers, by a few threads
-    auto hand_out_chunk = [&](Slot &s) -> int {
-        if (s.count == 0) return TIC_OK;
-        const size_t row = s.rb_row;
-        const bool packed = row != 0;
-        BT_START();
-        if (hipEventSynchronize(s.rb_done) != hipSuccess) return set_err(ctx, TIC_E_HIP, "stream read-back failed");
-        if (packed) {
-            const int cnt = s.count, first = s.first;
-            const char *src = (const char *)s.pin_out;
-            const unsigned long long *lens = s.h_lens;
-            auto hand_out = [=](int t, int T) {
-                if (T > 1) bind_pipeline_thread(ctx);
-                for (int k = t; k < cnt; k += T) memcpy(outs[first + k], src + (size_t)k * row, (size_t)lens[k]);
-            };
-            size_t total = 0;
-            for (int k = 0; k < cnt; k++) total += (size_t)lens[k];
-            const int T = cnt < 4 || total < (4u << 20) ? 1 : 4; // (starting and joining four threads costs 0.15-0.2 ms: more than copying 4 MB)
-            if (T == 1) {
-                hand_out(0, 1);
-            } else {
-                std::vector<std::thread> th;
-                for (int t = 0; t < T; t++) th.emplace_back(hand_out, t, T);
-                for (auto &x : th) x.join();
-            }
-        }
-        BT_STOP(4);
-        s.count = 0;
-        return TIC_OK;
-    };
-    for (auto &sl : slots) sl.count = 0;
-    // Three host threads, four slots: this thread stages chunk c into pinned memory and enqueues it (H2D, kernels, lengths),
-    // a second waits for each chunk in turn and reads its streams back into pinned memory, a third hands them out to the
-    // caller's buffers.  The device always has work queued while the threads copy, and a slot is staged into again only after
-    // the third thread has released it.
-    // (History, 256 x 1080p host -> host: one thread that finished chunk c - 3 on the stream already holding chunk c - 1,
-    // then staged chunk c: 28 ms, the device idle during the host copies; read-back on its own stream after enqueueing
-    // chunk c: 23.5 ms; one strided read-back copy per chunk instead of 16: 21.5 ms; read-back + hand-out on a second
-    // thread: 15 ms; this: see DESIGN.md section 6.)
-    std::mutex mu;
-    std::condition_variable cv_read, cv_hand, cv_free;
-    std::deque<int> q_read, q_hand; // slots to read back / to hand out, in submission order
-    std::vector<char> busy(S, 0);   // slot submitted and not yet released by the hand-out thread
-    bool stop_read = false, stop_hand = false;
-    int fin_result = TIC_OK;
-    ctx->last_batch_direct_frames = ctx->last_batch_staged_frames = ctx->last_batch_autoreg_frames = 0;
-    ctx->last_batch_zero_copy = 0;
-    ctx->bt = BatchTrace();
-    if ((size_t)row_stride == pitch && pitch == (size_t)w) { // the whole batch as one range, if it is one
-        BT_START();
-        (void)auto_register_frames(ctx, images, 0, n, img_bytes);
-        BT_STOP(0);
-    }
-    // A batch of ONE chunk (the reference's benchmark set: 49 frames of 512 x 512) runs on the calling thread: enqueue, wait, read back, hand out.
-    // Starting the two pipeline threads costs more than the chunk's work when the host is busy - their first wake-up came 3-10 ms late in
-    // one call in three on a shared box (tools/batch_small_probe.py: chunk_wait 0.008 ms, the reader found the chunk long finished).
-    std::thread reader, hander;
-    if (!inline_path) {
-    reader = std::thread([&]() {
-        bind_pipeline_thread(ctx);
-        (void)hipSetDevice(ctx->device);
-        for (;;) {
-            int k;
-            {
-                std::unique_lock<std::mutex> l(mu);
-                cv_read.wait(l, [&] { return stop_read || !q_read.empty(); });
-                if (q_read.empty()) break;
-                k = q_read.front();
-                q_read.pop_front();
-            }
-            const int r = read_back(slots[k], ctx->rstream);
-            {
-                std::lock_guard<std::mutex> l(mu);
-                if (r != TIC_OK) {
-                    if (fin_result == TIC_OK) fin_result = r;
-                    slots[k].count = 0; // nothing to hand out
-                }
-                q_hand.push_back(k);
-            }
-            cv_hand.notify_one();
-        }
-        {
-            std::lock_guard<std::mutex> l(mu);
-            stop_hand = true;
-        }
-        cv_hand.notify_one();
-    });
-    hander = std::thread([&]() {
-        bind_pipeline_thread(ctx);
-        for (;;) {
-            int k;
-            {
-                std::unique_lock<std::mutex> l(mu);
-                cv_hand.wait(l, [&] { return stop_hand || !q_hand.empty(); });
-                if (q_hand.empty()) return;
-                k = q_hand.front();
-                q_hand.pop_front();
-            }
-            const int r = hand_out_chunk(slots[k]);
-            {
-                std::lock_guard<std::mutex> l(mu);
-                if (r != TIC_OK && fin_result == TIC_OK) fin_result = r;
-                slots[k].count = 0;
-                busy[k] = 0;
-            }
-            cv_free.notify_all();
-        }
-    });
-    }
-    int c = 0;
-    for (int first = 0; first < n && result == TIC_OK; first += chunk, c++) {
-        const int cnt = n - first < chunk ? n - first : chunk;
-        const int si = c % S;
-        Slot &s = slots[si];
-        hipStream_t st = ctx->bstream[c & 1];
-        {
-            BT_START();
-            std::unique_lock<std::mutex> l(mu);
-            cv_free.wait(l, [&] { return !busy[si]; });
-            BT_STOP(5);
-            if (fin_result != TIC_OK) break;
-        }
-        s.first = first;
-        s.count = cnt;
-        int direct = 0;
-        hipError_t e = upload_chunk(ctx, s, img_bytes, pitch, images, first, cnt, row_stride, h, w, st, &direct);
-        ctx->last_batch_direct_frames += direct;
-        ctx->last_batch_staged_frames += cnt - direct;
-        BT_START();
-        if (e == hipSuccess) {
-            DctqArgs a = make_args(ctx, s.d_img, h, w, (ptrdiff_t)pitch, quality, s.d_coef);
-            a.fallback_count = nullptr;
-            a.nframes = cnt;
-            a.frame_stride_in = (long)img_bytes;
-            a.frame_stride_out = (long)coef_bytes;
-            merge_frames(a);
-            e = launch_dctq(a, 2, st);
-        }
-        const int par = s.parity;
-        s.parity ^= 1;
-        if (e == hipSuccess) // entropy stage of the whole chunk: pack + place (headers, lengths); no zero fill
-            e = entropy_gpu_fused((const int16_t *)s.d_coef, nblk, cnt, ctx->d_huff, s.d_work, s.work_bytes, s.d_streams, bound,
-                                  (bound - 16) / 4, h, w, quality, s.d_lens, nullptr, s.d_err + par, s.d_err + (par ^ 1),
-                                  quality <= ctx->ent_lane_max_quality ? kEntropyLanePerBlock : kEntropyEightLanes, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(s.h_lens, s.d_lens, cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(s.h_err, s.d_err + par, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipEventRecord(s.done, st);
-        BT_STOP(1);
-        if (e != hipSuccess) {
-            result = set_err(ctx, TIC_E_HIP, "batch enqueue failed at frame %d: %s", first, hipGetErrorString(e));
-            s.count = 0;
-            break;
-        }
-        if (inline_path) {
-            int r = read_back(s, ctx->rstream);
-            if (r == TIC_OK) r = hand_out_chunk(s);
-            s.count = 0;
-            if (r != TIC_OK) result = r;
-            continue;
-        }
-        {
-            std::lock_guard<std::mutex> l(mu);
-            busy[si] = 1;
-            q_read.push_back(si);
-        }
-        cv_read.notify_one();
-    }
-    {
-        std::lock_guard<std::mutex> l(mu);
-        stop_read = true;
-    }
-    cv_read.notify_one();
+// The end of a batch call: the pipeline's threads (their queues are closed: each drains its own first), the streams, the frames pinned for
+// the call - behind its last copy - and the slots.
+static void batch_end(tic_ctx *ctx, std::vector<std::thread> &threads) {
     BT_START();
-    if (reader.joinable()) reader.join(); // (each drains its queue first)
-    if (hander.joinable()) hander.join();
-    if (result == TIC_OK) result = fin_result;
+    for (auto &t : threads) t.join();
     (void)hipStreamSynchronize(ctx->bstream[0]);
     (void)hipStreamSynchronize(ctx->bstream[1]);
     (void)hipStreamSynchronize(ctx->rstream);
@@ -2687,22 +2350,243 @@ static int compress_batch_gpu(tic_ctx *ctx, const uint8_t *const *images, int n,
     BT_START();
     auto_unregister_all(ctx);
     BT_STOP(7);
-    for (auto &sl : slots) sl.count = 0;
+    for (auto &sl : ctx->bslots) sl.pending = 0;
+}
+
+// The host coder's pipeline (tic_compress_batch with threads > 0, tic_dctq_batch): the coefficients of a chunk come back into the slot's
+// pinned buffer, `threads` workers entropy-code them frame by frame (and copy them out, where the caller wants them).
+static int batch_host_coder(tic_ctx *ctx, const uint8_t *const *images, int n, int h, int w, ptrdiff_t row_stride, int quality,
+                            int16_t *const *coeffs, uint8_t *const *outs, const size_t *caps, size_t *out_lens, int threads, bool want_entropy) {
+    BatchPlan p;
+    const int rc = batch_begin(ctx, images, n, h, w, row_stride, quality, want_entropy, false, outs, caps, out_lens, &p);
+    if (rc || p.chunk == 0) return rc;
+    std::vector<Slot> &slots = ctx->bslots;
+    const bool need_d2h = want_entropy || coeffs != nullptr;
+    SlotGate gate;
+    ClosableQueue<std::pair<int, int>> jobs; // (slot, frame index inside the chunk)
+    auto worker = [&]() {
+        bind_pipeline_thread(ctx);
+        (void)hipSetDevice(ctx->device);
+        std::pair<int, int> job;
+        while (jobs.pop(job)) {
+            Slot &s = slots[job.first];
+            const int f = s.first + job.second;
+            int r = hipEventSynchronize(s.done) == hipSuccess ? TIC_OK : TIC_E_HIP;
+            const int16_t *zz = need_d2h ? s.pin_out + (size_t)job.second * p.nblk * 64 : nullptr;
+            if (r == TIC_OK && want_entropy) r = entropy_encode(zz, h, w, quality, outs[f], caps[f], &out_lens[f]);
+            if (r == TIC_OK && coeffs && coeffs[f]) memcpy(coeffs[f], zz, p.coef_bytes);
+            if (r != TIC_OK) gate.fail(r);
+            gate.finish(s);
+        }
+    };
+    const int nthreads = threads < 1 ? 1 : (threads > 64 ? 64 : threads);
+    std::vector<std::thread> pool;
+    for (int t = 0; t < nthreads; t++) pool.emplace_back(worker);
+
+    int result = TIC_OK, c = 0;
+    for (int first = 0; first < n; first += p.chunk, c++) {
+        const int cnt = n - first < p.chunk ? n - first : p.chunk, si = c % kBatchSlots;
+        Slot &s = slots[si];
+        gate.claim(ctx, s, cnt);
+        result = enqueue_chunk(ctx, p, s, ctx->bstream[c & 1], images, first, cnt, row_stride, h, w, quality, [&](Slot &sl, hipStream_t st) {
+            return need_d2h ? hipMemcpyAsync(sl.pin_out, sl.d_coef, p.coef_bytes * cnt, hipMemcpyDeviceToHost, st) : hipSuccess;
+        });
+        if (result != TIC_OK) break;
+        for (int k = 0; k < cnt; k++) jobs.push({si, k});
+    }
+    jobs.close();
+    batch_end(ctx, pool);
+    if (result == TIC_OK && gate.error() != TIC_OK) result = set_err(ctx, gate.error(), "batch consumer failed with code %d", gate.error());
     return result;
+}
+
+// The device entropy pipeline (tic_compress_batch with threads <= 0): per chunk one H2D copy, one transform launch, the entropy
+// stage, then only the finished streams (and 8 bytes of length per frame) come back.
+constexpr int kRetryEightLanes = -1000; // internal: batch_device_entropy asks tic_compress_batch for another run with the 8-lane packing kernel
+
+// Zero copy, for a batch of one chunk (it runs on the calling thread, which owns the call's registrations): where the caller's buffers are
+// rows of ONE block of memory (rows_of_one_block: a pool of n x cap bytes - what compress_batch() of the Python mirror and bench.py hold),
+// the block is pinned for the call and the shader stores every stream where the caller wants it, in 8-byte pieces (a row pitch of
+// tic_compress_bound() bytes is a multiple of 8, not 16); the copy out of the pipeline's pinned buffer (0.12-0.28 ms for the 49 streams of
+// the reference's benchmark set: a third of the call) does not happen.  The rows are written up to the chunk's longest stream rounded to 8
+// bytes (all within the frames' capacities): bytes behind a stream's end are not preserved.  *done = false: not applicable, nothing was
+// enqueued.
+static int read_back_zero_copy(tic_ctx *ctx, const BatchPlan &p, Slot &s, hipStream_t st, uint8_t *const *outs, const size_t *caps, size_t maxlen, bool *done) {
+    *done = false;
+    const size_t row = (maxlen + 7) / 8 * 8;
+    size_t P = 0;
+    if (!ctx->auto_register || maxlen < 16 || !rows_of_one_block(outs + s.first, caps + s.first, s.count, row, &P)) return TIC_OK;
+    uint8_t *base = outs[s.first];
+    const size_t span = (size_t)(s.count - 1) * P + row;
+    if (!(host_pointer_is_pinned(base) && host_pointer_is_pinned(base + span - 1))) {
+        void *reg = pin_range(base, span);
+        if (!reg) return TIC_OK;
+        ctx->autoregs.push_back(reg); // (released with the call's other registrations, behind its last synchronisation)
+    }
+    void *d_dst = nullptr;
+    if (hipHostGetDevicePointer(&d_dst, base, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return TIC_OK;
+    }
+    BT_START();
+    hipError_t e = launch_readback<u32x2v>(s.d_streams, p.bound, d_dst, P, row, s.count, st);
+    if (e == hipSuccess) e = hipEventRecord(s.rb_done, st);
+    BT_STOP(3);
+    if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "stream read-back failed: %s", hipGetErrorString(e));
+    s.rb_row = 0; // (nothing to hand out)
+    ctx->last_batch_zero_copy += s.count;
+    *done = true;
+    return TIC_OK;
+}
+
+// Finishing a chunk, part 1: wait for its lengths, then start the read-back of its streams on `st`.  The reading thread does not wait for
+// the copy: it records the slot's rb_done behind it and turns to the next chunk, so that the read-backs follow each other on their stream
+// without a host round trip in between; hand_out_chunk waits for the event.
+static int read_back(tic_ctx *ctx, const BatchPlan &p, Slot &s, hipStream_t st, uint8_t *const *outs, const size_t *caps, size_t *out_lens, bool zero_copy) {
+    BT_START();
+    const hipError_t ev = hipEventSynchronize(s.done);
+    BT_STOP(2);
+    if (ev != hipSuccess) return set_err(ctx, TIC_E_HIP, "batch chunk failed");
+    if (*s.h_err == 1) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code (reference raises KeyError)");
+    if (*s.h_err == 4) return kRetryEightLanes; // a block exceeds the lane-per-block kernel's strings: the whole call is run again
+    if (*s.h_err) return set_err(ctx, TIC_E_SPACE, "device entropy stage: stream buffer too small");
+    size_t maxlen = 0;
+    for (int k = 0; k < s.count; k++) {
+        const size_t len = (size_t)s.h_lens[k];
+        const int f = s.first + k;
+        if (len > caps[f]) return set_err(ctx, TIC_E_SPACE, "output buffer of frame %d too small (%zu bytes needed)", f, len);
+        out_lens[f] = len;
+        if (len > maxlen) maxlen = len;
+    }
+    if (zero_copy) {
+        bool done = false;
+        const int rc = read_back_zero_copy(ctx, p, s, st, outs, caps, maxlen, &done);
+        if (rc || done) return rc;
+    }
+    // Packed: ONE launch brings the head of every frame's stream buffer - as many bytes as the longest stream has - into the slot's pinned
+    // buffer, to be handed out by a few threads (a copy straight into the caller's pageable buffers is staged by the runtime, ~0.15 ms
+    // each; 16 separate copies of ~0.9 MB into pinned memory cost ~45 us each, 2.5 x their transfer time).  Frames of one batch compress
+    // to similar sizes, so little more than the streams themselves crosses PCIe.  Where the rows would not fit the pinned buffer: a copy
+    // per frame, straight to the caller.
+    const size_t pin_cap = p.coef_bytes * (size_t)p.chunk; // size of pin_out (ensure_batch_slots)
+    const size_t row = align_up(maxlen, 256);
+    const bool packed = row * (size_t)s.count <= pin_cap;
+    BT_START();
+    hipError_t e = hipSuccess;
+    if (packed) // (row and bound are multiples of 16; the bytes behind a stream are never handed out)
+        e = launch_readback<u32x4v>(s.d_streams, p.bound, s.pin_out, row, maxlen, s.count, st);
+    for (int k = 0; k < s.count && !packed && e == hipSuccess; k++)
+        e = hipMemcpyAsync(outs[s.first + k], (char *)s.d_streams + (size_t)k * p.bound, (size_t)s.h_lens[k], hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "stream read-back failed: %s", hipGetErrorString(e));
+    e = hipEventRecord(s.rb_done, st);
+    BT_STOP(3);
+    if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "stream read-back failed");
+    s.rb_row = packed ? row : 0;
+    return TIC_OK;
+}
+
+// ... part 2: once the read-back has arrived, out of the slot's pinned buffer into the caller's buffers, by a few threads
+static int hand_out_chunk(tic_ctx *ctx, Slot &s, uint8_t *const *outs) {
+    BT_START();
+    if (hipEventSynchronize(s.rb_done) != hipSuccess) return set_err(ctx, TIC_E_HIP, "stream read-back failed");
+    if (const size_t row = s.rb_row) {
+        const int cnt = s.count, first = s.first;
+        const char *src = (const char *)s.pin_out;
+        const unsigned long long *lens = s.h_lens;
+        size_t total = 0;
+        for (int k = 0; k < cnt; k++) total += (size_t)lens[k];
+        const int T = cnt < 4 || total < (4u << 20) ? 1 : 4; // (starting and joining four threads costs 0.15-0.2 ms: more than copying 4 MB)
+        run_strided(cnt, T, [ctx]() { bind_pipeline_thread(ctx); }, [=](int k) { memcpy(outs[first + k], src + (size_t)k * row, (size_t)lens[k]); });
+    }
+    BT_STOP(4);
+    return TIC_OK;
+}
+
+// Three host threads, kBatchSlots slots: the calling thread stages chunk c into pinned memory and enqueues it (H2D, kernels, lengths), a
+// second waits for each chunk in turn and starts the read-back of its streams, a third hands them out to the caller's buffers.  The
+// device always has work queued while the threads copy, and a slot is claimed again only after the third thread has freed it
+// (256 x 1080p host -> host: DESIGN.md section 6).
+// A batch of ONE chunk (the reference's benchmark set: 49 frames of 512 x 512) runs on the calling thread: enqueue, wait, read back, hand out.
+// Starting the two pipeline threads costs more than the chunk's work when the host is busy - their first wake-up came 3-10 ms late in
+// one call in three on a shared box (tools/batch_small_probe.py: chunk_wait 0.008 ms, the reader found the chunk long finished).
+static int batch_device_entropy(tic_ctx *ctx, const uint8_t *const *images, int n, int h, int w, ptrdiff_t row_stride, int quality,
+                                uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
+    BatchPlan p;
+    const int rc = batch_begin(ctx, images, n, h, w, row_stride, quality, true, true, outs, caps, out_lens, &p);
+    if (rc || p.chunk == 0) return rc;
+    std::vector<Slot> &slots = ctx->bslots;
+    const bool inline_path = n <= p.chunk;
+    SlotGate gate;
+    ClosableQueue<int> q_read, q_hand; // slots to read back / to hand out, in submission order
+    std::vector<std::thread> threads;
+    if (!inline_path) {
+        threads.emplace_back([&]() {
+            bind_pipeline_thread(ctx);
+            (void)hipSetDevice(ctx->device);
+            int k;
+            while (q_read.pop(k)) {
+                const int r = read_back(ctx, p, slots[k], ctx->rstream, outs, caps, out_lens, false);
+                if (r == TIC_OK) {
+                    q_hand.push(k);
+                } else { // nothing to hand out
+                    gate.fail(r);
+                    gate.finish(slots[k]);
+                }
+            }
+            q_hand.close();
+        });
+        threads.emplace_back([&]() {
+            bind_pipeline_thread(ctx);
+            int k;
+            while (q_hand.pop(k)) {
+                const int r = hand_out_chunk(ctx, slots[k], outs);
+                if (r != TIC_OK) gate.fail(r);
+                gate.finish(slots[k]);
+            }
+        });
+    }
+    int result = TIC_OK, c = 0;
+    for (int first = 0; first < n; first += p.chunk, c++) {
+        const int cnt = n - first < p.chunk ? n - first : p.chunk, si = c % kBatchSlots;
+        Slot &s = slots[si];
+        gate.claim(ctx, s, 1);
+        if (gate.error() != TIC_OK) break;
+        const int par = s.parity;
+        s.parity ^= 1;
+        result = enqueue_chunk(ctx, p, s, ctx->bstream[c & 1], images, first, cnt, row_stride, h, w, quality, [&](Slot &sl, hipStream_t st) {
+            // entropy stage of the whole chunk: pack + place (headers, lengths); no zero fill
+            hipError_t e = entropy_gpu_fused((const int16_t *)sl.d_coef, p.nblk, cnt, ctx->d_huff, sl.d_work, sl.work_bytes, sl.d_streams, p.bound,
+                                             (p.bound - 16) / 4, h, w, quality, sl.d_lens, nullptr, sl.d_err + par, sl.d_err + (par ^ 1),
+                                             quality <= ctx->ent_lane_max_quality ? kEntropyLanePerBlock : kEntropyEightLanes, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(sl.h_lens, sl.d_lens, cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(sl.h_err, sl.d_err + par, sizeof(int), hipMemcpyDeviceToHost, st);
+            return e;
+        });
+        if (result != TIC_OK) break;
+        if (inline_path) {
+            result = read_back(ctx, p, s, ctx->rstream, outs, caps, out_lens, true);
+            if (result == TIC_OK) result = hand_out_chunk(ctx, s, outs);
+            break;
+        }
+        q_read.push(si);
+    }
+    q_read.close();
+    batch_end(ctx, threads);
+    return result != TIC_OK ? result : gate.error();
 }
 
 int tic_compress_batch(tic_ctx *ctx, const uint8_t *const *images, int n, int h, int w, ptrdiff_t row_stride, int quality,
                        uint8_t *const *outs, const size_t *caps, size_t *out_lens, int threads) {
     TIC_LOCK(ctx);
     if (threads <= 0) {
-        int rc = compress_batch_gpu(ctx, images, n, h, w, row_stride, quality, outs, caps, out_lens);
+        int rc = batch_device_entropy(ctx, images, n, h, w, row_stride, quality, outs, caps, out_lens);
         if (rc == kRetryEightLanes) {
             ctx->ent_lane_max_quality = quality - 1;
-            rc = compress_batch_gpu(ctx, images, n, h, w, row_stride, quality, outs, caps, out_lens);
+            rc = batch_device_entropy(ctx, images, n, h, w, row_stride, quality, outs, caps, out_lens);
         }
         return rc;
     }
-    return batch_impl(ctx, images, n, h, w, row_stride, quality, nullptr, outs, caps, out_lens, threads, true);
+    return batch_host_coder(ctx, images, n, h, w, row_stride, quality, nullptr, outs, caps, out_lens, threads, true);
 }
 
 // One batch over several contexts - normally one per GPU of the node - from ONE process: a host thread per context, contiguous shards
@@ -2742,7 +2626,7 @@ int tic_compress_batch_multi(tic_ctx *const *ctxs, int nctx, const uint8_t *cons
 int tic_dctq_batch(tic_ctx *ctx, const uint8_t *const *images, int n, int h, int w, ptrdiff_t row_stride, int quality,
                    int16_t *const *coeffs) {
     TIC_LOCK(ctx);
-    return batch_impl(ctx, images, n, h, w, row_stride, quality, coeffs, nullptr, nullptr, nullptr, 4, false);
+    return batch_host_coder(ctx, images, n, h, w, row_stride, quality, coeffs, nullptr, nullptr, nullptr, 4, false);
 }
 
 // ---- decode ---------------------------------------------------------------------------------------------
@@ -3311,24 +3195,17 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
         //  a frame of a whole number of 256 B has none behind it, elsewhere caps[] must reach to the next frame; an arena of frames at
         //  256-byte aligned distances with caps[i] = h * w takes the pinned route, and the bytes between its frames stay the caller's)
         bool dense = true;
-        for (uint32_t k = 0; k < F && dense; k++) {
-            const size_t hw = (size_t)fr[(size_t)ids[k]].h * (size_t)fr[(size_t)ids[k]].w;
-            dense = pitches[k] == (size_t)fr[(size_t)ids[k]].w && (k == 0 || (outs[ids[k]] == outs[ids[k - 1]] + (pix_off[k] - pix_off[k - 1]))) &&
-                    (k + 1 == F || hw % 256 == 0 || caps[ids[k]] >= pix_off[k + 1] - pix_off[k]);
-        }
+        for (uint32_t k = 0; k < F && dense; k++) dense = pitches[k] == (size_t)fr[(size_t)ids[k]].w;
+        dense = dense && frames_are_one_arena(F, [&](size_t k) {
+                    const Fr &f = fr[(size_t)ids[k]];
+                    return ArenaFrame{outs[ids[k]], pix_off[k], (size_t)f.h * (size_t)f.w, caps[ids[k]]};
+                });
         bool direct = false;
         if (dense && ctx->auto_register) {
             const size_t total = pix_off[F - 1] + (size_t)fr[(size_t)ids[F - 1]].h * (size_t)fr[(size_t)ids[F - 1]].w;
             bool pinned = host_pointer_is_pinned(outs[ids[0]]) && host_pointer_is_pinned(outs[ids[0]] + total - 1);
             void *reg = nullptr;
-            if (!pinned && total >= (256u << 10)) {
-                const uintptr_t lo = (uintptr_t)outs[ids[0]] & ~(uintptr_t)4095, hi = ((uintptr_t)outs[ids[0]] + total + 4095) & ~(uintptr_t)4095;
-                if (hipHostRegister((void *)lo, hi - lo, hipHostRegisterDefault) == hipSuccess) {
-                    reg = (void *)lo;
-                    pinned = true;
-                } else
-                    (void)hipGetLastError();
-            }
+            if (!pinned && total >= (256u << 10)) pinned = (reg = pin_range(outs[ids[0]], total)) != nullptr;
             if (pinned) {
                 hipError_t e = hipMemcpyAsync(outs[ids[0]], B.d_pix, total, hipMemcpyDeviceToHost, ctx->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -3356,23 +3233,14 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
         }
         BT_START();
         if (!direct) {
-            auto hand_out = [&](int t, int T) {
-                if (T > 1) bind_pipeline_thread(ctx);
-                for (uint32_t k = (uint32_t)t; k < F; k += (uint32_t)T) {
-                    if (!good[k]) continue;
-                    const Fr &f = fr[(size_t)ids[k]];
-                    const uint8_t *src = B.h_pix + pix_off[k];
-                    if (pitches[k] == (size_t)f.w) memcpy(outs[ids[k]], src, (size_t)f.h * (size_t)f.w);
-                    else for (int y = 0; y < f.h; y++) memcpy(outs[ids[k]] + (size_t)y * (size_t)f.w, src + (size_t)y * pitches[k], (size_t)f.w);
-                }
-            };
             const int T = poff < (2u << 20) || F < 2 ? 1 : (F < 8 ? (int)F : 8);
-            if (T == 1) hand_out(0, 1);
-            else {
-                std::vector<std::thread> th;
-                for (int t = 0; t < T; t++) th.emplace_back(hand_out, t, T);
-                for (auto &x : th) x.join();
-            }
+            run_strided((int)F, T, [ctx]() { bind_pipeline_thread(ctx); }, [&](int k) {
+                if (!good[(size_t)k]) return;
+                const Fr &f = fr[(size_t)ids[(size_t)k]];
+                const uint8_t *src = B.h_pix + pix_off[(size_t)k];
+                if (pitches[(size_t)k] == (size_t)f.w) memcpy(outs[ids[(size_t)k]], src, (size_t)f.h * (size_t)f.w);
+                else for (int y = 0; y < f.h; y++) memcpy(outs[ids[(size_t)k]] + (size_t)y * (size_t)f.w, src + (size_t)y * pitches[(size_t)k], (size_t)f.w);
+            });
         }
         BT_STOP(4);
         return TIC_OK;
