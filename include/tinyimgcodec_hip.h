@@ -305,6 +305,21 @@ int tic_compress_batch(tic_ctx *ctx, const uint8_t *const *images, int n, int h,
  * *streams = how many streams of the last tic_compress_batch went that way. */
 int tic_last_batch_zero_copy(tic_ctx *ctx, int *streams);
 
+/* compress() (codec.py:133-164 of the reference) of n frames of ANY sizes and qualities in one call - the whole loop over image x quality of
+ * the reference's tests/benchmark.py:12-23 is one call, and so is a folder of photographs of different sizes.  Frame i is hs[i] x ws[i] with
+ * rows row_strides[i] bytes apart, coded at qualities[i] into outs[i] (caps[i] bytes; tic_compress_bound(hs[i], ws[i]) always suffices);
+ * out_lens[i] receives its size.  Every stream is byte for byte what tic_compress gives for that frame, whatever the order of the frames.
+ * Entropy stage on the device.  All arguments are checked before any work: a bad size, stride or quality, a null image or buffer is reported
+ * for the first offending frame ("frame i: ...") and nothing is written.  Frames without blocks get the header-only stream; frames the batch
+ * kernels do not take (more than 8,192^2 pixels, or more pixels than a chunk holds) are coded one by one behind the batch.  A coefficient
+ * without a Huffman code in any frame fails the call with TIC_E_RANGE; a stream longer than caps[i] fails it with TIC_E_SPACE naming frame i
+ * (other frames may have been written by then). */
+int tic_compress_batch_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                         const int *qualities, uint8_t *const *outs, const size_t *caps, size_t *out_lens);
+/* How the last tic_compress_batch_v went: frames through the batch kernels / frames coded one by one / chunks / transform launches (one per
+ * run of neighbouring frames of one width and quality whose heights are multiples of 8).  Any pointer may be NULL. */
+int tic_last_compress_batch_v(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks, int *transform_launches);
+
 /* The same batch spread over nctx contexts - one per GPU of the node - by ONE process: a host thread per context, contiguous
  * shards of ceil(n / nctx) frames in frame order, no exchange between the shards; out_lens in frame order.  What a caller that
  * loops over images (/root/reference/tests/benchmark.py:12-23) gets from a multi-GPU node without a launcher.  Returns the first

@@ -155,6 +155,12 @@ SIGNATURES = {
         [_ctxp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.POINTER(C.c_void_p),
          C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_int],
     ),
+    "tic_compress_batch_v": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ssize_t), C.POINTER(C.c_int),
+         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    ),
+    "tic_last_compress_batch_v": (C.c_int, [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tic_compress_batch_multi": (
         C.c_int,
         [C.POINTER(_ctxp), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.POINTER(C.c_void_p),

@@ -199,17 +199,32 @@ def compress(image, quality=50, auto_generate_huffman_table=False, ctx=None):
 
 
 def compress_batch(images, quality=50, threads=0, ctx=None, devices=None):
-    """Batch of equally sized frames through the stream-overlapped pipeline -> list of bytes (frame order).
+    """Batch of frames through the stream-overlapped pipeline -> list of bytes (frame order).
 
-    threads=0: entropy stage on the GPU; threads>0: host entropy coder on that many worker threads.
+    Frames of one shape at one quality (an int): threads=0: entropy stage on the GPU; threads>0: host entropy coder on that many worker threads.
     devices=[0, 1, ...]: the batch is cut into contiguous shards, one per listed device, and every shard runs its own pipeline on its
     own context and host thread inside this process (tic_compress_batch_multi; the GIL is released for the whole call) - the
     multi-GPU form of a loop over images (/root/reference/tests/benchmark.py:12-23) without a launcher.  A device may be listed
-    twice (two pipelines on one GPU)."""
+    twice (two pipelines on one GPU).
+
+    Frames of different shapes, or `quality` a sequence with one entry per frame: one call of tic_compress_batch_v, entropy stage on the GPU -
+    the reference's whole loop over image x quality, or a folder of photographs, in one call; every stream is what compress(image, q) gives.
+    Such a mixed call takes neither threads > 0 nor devices= (ValueError)."""
+    per_frame = not isinstance(quality, (int, float, np.integer, np.floating, bool, np.bool_, str, bytes)) and hasattr(quality, "__len__")
+    if per_frame:
+        frames = [_as_u8_image(im) for im in images]
+        if len(quality) != len(frames):
+            raise ValueError("quality has %d entries for %d frames" % (len(quality), len(frames)))
+        qs = [_check_quality(qi, packs_header=True) for qi in quality]
+        if not frames:
+            return []
+        return _compress_batch_mixed(frames, qs, threads, ctx, devices)
     q = _check_quality(quality, packs_header=True)
     frames = [_as_u8_image(im) for im in images]
     if not frames:
         return []
+    if any((f[1], f[2]) != (frames[0][1], frames[0][2]) for f in frames):
+        return _compress_batch_mixed(frames, [q] * len(frames), threads, ctx, devices)
     if devices is not None:
         return _compress_batch_multi(frames, q, int(threads), list(devices))
     ctx = _ctx(ctx)
@@ -235,6 +250,37 @@ def compress_batch(images, quality=50, threads=0, ctx=None, devices=None):
             raise KeyError("coefficient magnitude has no Huffman code")
         ctx.check(rc)
         return [outs[i][: lens[i]].tobytes() for i in range(n)]
+
+
+def _compress_batch_mixed(frames, qs, threads, ctx, devices):
+    """Frames of any shapes, a quality each: tic_compress_batch_v, with a pool of per-frame capacities kept on the context."""
+    if int(threads) > 0:
+        raise ValueError("a batch of mixed shapes or qualities is not supported with threads > 0 (device entropy stage only)")
+    if devices is not None:
+        raise ValueError("a batch of mixed shapes or qualities is not supported with devices= (one context only)")
+    ctx = _ctx(ctx)
+    L = N.load()
+    n = len(frames)
+    caps_l = [L.tic_compress_bound(f[1], f[2]) for f in frames]
+    offs = np.concatenate(([0], np.cumsum([(c + 63) // 64 * 64 for c in caps_l]))).astype(np.int64)
+    with ctx.lock:
+        pool = getattr(ctx, "_mixed_pool", None)
+        if pool is None or pool.size < offs[-1]:
+            pool = ctx._mixed_pool = np.empty(int(offs[-1]), dtype=np.uint8)
+        base = pool.ctypes.data
+        inp = (C.c_void_p * n)(*[f[0].ctypes.data if f[0].size else None for f in frames])
+        hs = (C.c_int * n)(*[f[1] for f in frames])
+        ws = (C.c_int * n)(*[f[2] for f in frames])
+        strides = (C.c_ssize_t * n)(*[max(f[2], 1) for f in frames])
+        qa = (C.c_int * n)(*qs)
+        outp = (C.c_void_p * n)(*[base + int(o) for o in offs[:-1]])
+        caps = (C.c_size_t * n)(*caps_l)
+        lens = (C.c_size_t * n)()
+        rc = L.tic_compress_batch_v(ctx.handle, inp, n, hs, ws, strides, qa, outp, caps, lens)
+        if rc == N.TIC_E_RANGE:
+            raise KeyError("coefficient magnitude has no Huffman code")
+        ctx.check(rc)
+        return [pool[int(offs[i]): int(offs[i]) + lens[i]].tobytes() for i in range(n)]
 
 
 def _compress_batch_multi(frames, q, threads, devices):

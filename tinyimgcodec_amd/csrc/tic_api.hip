@@ -74,6 +74,10 @@ struct Slot {
     unsigned long long *d_lens = nullptr, *h_lens = nullptr; // stream length per frame (device / pinned host)
     int *d_err = nullptr, *h_err = nullptr;
     void *d_streams = nullptr;                                // finished streams, one compress_bound() apart
+    // mixed batches (tic_compress_batch_v): the entropy stage's table of the chunk - filled in pinned memory, uploaded in stream order -
+    // and, for the read-back, where each stream lands in pin_out (pinned: the shader reads it where it lies)
+    EntropyFrameTable *h_frames = nullptr, *d_frames = nullptr;
+    unsigned long long *h_rb_off = nullptr;
     int first = 0, count = 0; // frames [first, first+count) are in flight in this slot
     int pending = 0;          // pieces of the chunk's work not yet finished (SlotGate); 0 = the slot is free
     size_t rb_row = 0;        // row pitch of the streams read back into pin_out (0: they went straight to the caller)
@@ -215,7 +219,16 @@ struct tic_ctx {
     size_t last_dbatch_work_used = 0, last_dbatch_work_held = 0; // its range, the bytes of work buffer it carves, the bytes the context held
     // batch pipeline buffers, kept across calls (pinned allocations are expensive)
     std::vector<Slot> bslots;
-    int bslot_h = -1, bslot_w = -1, bslot_chunk = 0;
+    // what every slot holds at least: bytes of staged pixels, of coefficients, of the pinned landing buffer, of stream areas, of entropy
+    // workspace, and frames per chunk
+    struct SlotNeed {
+        size_t img = 0, coef = 0, pin_out = 0, streams = 0, work = 0;
+        int frames = 0;
+        bool covers(const SlotNeed &o) const {
+            return img >= o.img && coef >= o.coef && pin_out >= o.pin_out && streams >= o.streams && work >= o.work && frames >= o.frames;
+        }
+    } bslot_cap;
+    int last_vbatch_frames = 0, last_vbatch_single = 0, last_vbatch_chunks = 0, last_vbatch_launches = 0; // tic_last_compress_batch_v
     // host side of the batch pipeline: the device's NUMA node and the CPUs of that node this process may run on
     int numa_node = -1;
     bool numa_bind = true;      // the pipeline's own threads (staging, read-back, hand-out) bind themselves to those CPUs
@@ -399,9 +412,9 @@ void DecWorkspace::release() {
 }
 
 void Slot::release() {
-    for (void *p : {(void *)pin_in, (void *)pin_out, (void *)h_lens, (void *)h_err})
+    for (void *p : {(void *)pin_in, (void *)pin_out, (void *)h_lens, (void *)h_err, (void *)h_frames, (void *)h_rb_off})
         if (p) (void)hipHostFree(p);
-    for (void *p : {d_img, d_coef, d_work, (void *)d_lens, (void *)d_err, d_streams})
+    for (void *p : {d_img, d_coef, d_work, (void *)d_lens, (void *)d_err, d_streams, (void *)d_frames})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : {done, rb_done})
         if (e) (void)hipEventDestroy(e);
@@ -2062,9 +2075,7 @@ int tic_compress_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdif
 // is handed out to the caller (the host coder's pipeline: coded by the workers).  Chunk c takes slot c % kBatchSlots once that is free.
 constexpr int kBatchSlots = 4;
 
-// Row pitch of staged frames: rows that are already a multiple of 8 bytes are staged back to back (one memcpy per
-// frame when the caller's rows are contiguous too); other widths are padded so that 8-byte row loads stay aligned.
-static inline size_t batch_pitch(int w) { return (w % 8 == 0) ? (size_t)w : align_up((size_t)w, 256); }
+// (row pitch of staged frames: batch_pitch, tic_host_pipeline.h)
 
 // What a batch call works out once: blocks per frame, the staged row pitch, bytes of a frame's pixels and coefficients, the distance of two
 // streams in a slot, frames per chunk (0: the call had nothing to put through the pipeline).
@@ -2189,35 +2200,50 @@ static hipError_t upload_chunk(tic_ctx *ctx, Slot &s, size_t img_bytes, size_t p
     return hipMemcpyAsync(s.d_img, s.pin_in, img_bytes * cnt, hipMemcpyHostToDevice, st);
 }
 
-static int ensure_batch_slots(tic_ctx *ctx, int h, int w, int chunk) {
-    if ((int)ctx->bslots.size() == kBatchSlots && ctx->bslot_h == h && ctx->bslot_w == w && ctx->bslot_chunk >= chunk) return TIC_OK;
-    const size_t nblk = num_blocks(h, w);
-    const size_t need_img = batch_pitch(w) * (size_t)h * chunk, need_coef = nblk * 128 * chunk;
+// The context's slots hold at least `need` (sizes in bytes and a frame count: frames of one size and mixed frames share them).  They grow
+// to the larger of what they held and what is asked for, so that calls of different shapes in turn do not allocate in turn.
+static int ensure_batch_slots(tic_ctx *ctx, tic_ctx::SlotNeed need) {
+    if ((int)ctx->bslots.size() == kBatchSlots && ctx->bslot_cap.covers(need)) return TIC_OK;
+    const tic_ctx::SlotNeed &old = ctx->bslot_cap;
+    need.img = std::max(need.img, old.img), need.coef = std::max(need.coef, old.coef), need.pin_out = std::max(need.pin_out, old.pin_out);
+    need.streams = std::max(need.streams, old.streams), need.work = std::max(need.work, old.work), need.frames = std::max(need.frames, old.frames);
     for (auto &sl : ctx->bslots) sl.release();
     ctx->bslots.assign(kBatchSlots, Slot());
-    ctx->bslot_h = ctx->bslot_w = -1;
-    ctx->bslot_chunk = 0;
+    ctx->bslot_cap = tic_ctx::SlotNeed();
+    const size_t nf = (size_t)need.frames;
     for (auto &sl : ctx->bslots) {
         hipError_t e;
-        if ((e = hipHostMalloc((void **)&sl.pin_in, need_img, hipHostMallocDefault)) != hipSuccess ||
-            (e = hipHostMalloc((void **)&sl.pin_out, need_coef, hipHostMallocDefault)) != hipSuccess ||
-            (e = hipMalloc(&sl.d_img, need_img)) != hipSuccess || (e = hipMalloc(&sl.d_coef, need_coef)) != hipSuccess ||
+        if ((e = hipHostMalloc((void **)&sl.pin_in, need.img, hipHostMallocDefault)) != hipSuccess ||
+            (e = hipHostMalloc((void **)&sl.pin_out, need.pin_out, hipHostMallocDefault)) != hipSuccess ||
+            (e = hipMalloc(&sl.d_img, need.img)) != hipSuccess || (e = hipMalloc(&sl.d_coef, need.coef)) != hipSuccess ||
             (e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)) != hipSuccess ||
             (e = hipEventCreateWithFlags(&sl.rb_done, hipEventDisableTiming)) != hipSuccess)
             return set_err(ctx, TIC_E_HIP, "batch buffer allocation failed: %s", hipGetErrorString(e));
-        sl.work_bytes = entropy_fused_work_bytes((nblk + 8) * (size_t)chunk); // (every frame's partitions are rounded up)
+        sl.work_bytes = need.work;
         if ((e = hipMalloc(&sl.d_work, sl.work_bytes)) != hipSuccess ||
-            (e = hipMalloc((void **)&sl.d_lens, chunk * sizeof(unsigned long long))) != hipSuccess ||
-            (e = hipHostMalloc((void **)&sl.h_lens, chunk * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess ||
+            (e = hipMalloc((void **)&sl.d_lens, nf * sizeof(unsigned long long))) != hipSuccess ||
+            (e = hipHostMalloc((void **)&sl.h_lens, nf * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess ||
             (e = hipMalloc((void **)&sl.d_err, 2 * sizeof(int))) != hipSuccess || (e = hipMemset(sl.d_err, 0, 2 * sizeof(int))) != hipSuccess ||
             (e = hipHostMalloc((void **)&sl.h_err, sizeof(int), hipHostMallocDefault)) != hipSuccess ||
-            (e = hipMalloc(&sl.d_streams, align_up(compress_bound(h, w), 16) * (size_t)chunk)) != hipSuccess)
+            (e = hipMalloc(&sl.d_streams, need.streams)) != hipSuccess ||
+            (e = hipHostMalloc((void **)&sl.h_frames, sizeof(EntropyFrameTable), hipHostMallocDefault)) != hipSuccess ||
+            (e = hipMalloc((void **)&sl.d_frames, sizeof(EntropyFrameTable))) != hipSuccess ||
+            (e = hipHostMalloc((void **)&sl.h_rb_off, kEntropyMaxFrames * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess)
             return set_err(ctx, TIC_E_HIP, "batch entropy workspace allocation failed: %s", hipGetErrorString(e));
     }
-    ctx->bslot_h = h;
-    ctx->bslot_w = w;
-    ctx->bslot_chunk = chunk;
+    ctx->bslot_cap = need;
     return TIC_OK;
+}
+// ... for `chunk` frames of h x w
+static tic_ctx::SlotNeed uniform_slot_need(int h, int w, int chunk) {
+    const size_t nblk = num_blocks(h, w);
+    tic_ctx::SlotNeed need;
+    need.img = batch_pitch(w) * (size_t)h * chunk;
+    need.coef = need.pin_out = nblk * 128 * chunk;
+    need.streams = align_up(compress_bound(h, w), 16) * (size_t)chunk;
+    need.work = entropy_fused_work_bytes((nblk + 8) * (size_t)chunk); // (every frame's partitions are rounded up)
+    need.frames = chunk;
+    return need;
 }
 
 // The front end of both pipelines: argument checks (`device_entropy`: the stricter ones of the calls whose streams the device writes),
@@ -2242,7 +2268,7 @@ static int batch_begin(tic_ctx *ctx, const uint8_t *const *images, int n, int h,
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t pitch = batch_pitch(w), img_bytes = pitch * (size_t)h;
     const int chunk = chunk_frames(n, img_bytes);
-    rc = ensure_batch_slots(ctx, h, w, chunk);
+    rc = ensure_batch_slots(ctx, uniform_slot_need(h, w, chunk));
     if (rc) return rc;
     for (auto &sl : ctx->bslots) sl.pending = 0;
     ctx->last_batch_direct_frames = ctx->last_batch_staged_frames = ctx->last_batch_autoreg_frames = ctx->last_batch_zero_copy = 0;
@@ -2292,27 +2318,35 @@ struct SlotGate {
 // frame where merge_frames sees one), then `rest(s, st)` - what the pipeline wants on the stream behind the transform - and the slot's
 // `done` event.
 extern "C++" { // (templates inside the C-ABI block)
-template <class Rest>
-static int enqueue_chunk(tic_ctx *ctx, const BatchPlan &p, Slot &s, hipStream_t st, const uint8_t *const *images, int first, int cnt,
-                         ptrdiff_t row_stride, int h, int w, int quality, Rest rest) {
+// The order of a chunk on its stream, for frames of one size and for mixed frames alike: upload(&direct) - *direct = frames that came from
+// where the caller holds them - then transform(), rest(s, st), the slot's `done` event.  `first`, `cnt`: what the slot's consumers find in it.
+template <class Upload, class Transform, class Rest>
+static int enqueue_on_slot(tic_ctx *ctx, Slot &s, hipStream_t st, int first, int cnt, Upload upload, Transform transform, Rest rest) {
     s.first = first;
     s.count = cnt;
-    DctqArgs a = make_args(ctx, s.d_img, h, w, (ptrdiff_t)p.pitch, quality, s.d_coef);
-    a.fallback_count = nullptr;
-    const int rc = set_frames(ctx, a, cnt, h, w, (ptrdiff_t)p.pitch, (ptrdiff_t)p.img_bytes, (ptrdiff_t)p.coef_bytes);
-    if (rc) return rc;
-    merge_frames(a);
     int direct = 0;
-    hipError_t e = upload_chunk(ctx, s, p.img_bytes, p.pitch, images, first, cnt, row_stride, h, w, st, &direct);
+    hipError_t e = upload(&direct);
     ctx->last_batch_direct_frames += direct;
     ctx->last_batch_staged_frames += cnt - direct;
     BT_START();
-    if (e == hipSuccess) e = launch_dctq(a, 2, st);
+    if (e == hipSuccess) e = transform();
     if (e == hipSuccess) e = rest(s, st);
     if (e == hipSuccess) e = hipEventRecord(s.done, st);
     BT_STOP(1);
     if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "batch enqueue failed at frame %d: %s", first, hipGetErrorString(e));
     return TIC_OK;
+}
+template <class Rest>
+static int enqueue_chunk(tic_ctx *ctx, const BatchPlan &p, Slot &s, hipStream_t st, const uint8_t *const *images, int first, int cnt,
+                         ptrdiff_t row_stride, int h, int w, int quality, Rest rest) {
+    DctqArgs a = make_args(ctx, s.d_img, h, w, (ptrdiff_t)p.pitch, quality, s.d_coef);
+    a.fallback_count = nullptr;
+    const int rc = set_frames(ctx, a, cnt, h, w, (ptrdiff_t)p.pitch, (ptrdiff_t)p.img_bytes, (ptrdiff_t)p.coef_bytes);
+    if (rc) return rc;
+    merge_frames(a);
+    return enqueue_on_slot(
+        ctx, s, st, first, cnt, [&](int *direct) { return upload_chunk(ctx, s, p.img_bytes, p.pitch, images, first, cnt, row_stride, h, w, st, direct); },
+        [&]() { return launch_dctq(a, 2, st); }, rest);
 }
 
 // Read-back of a chunk's streams by the SHADER, not by a DMA engine: `row` pieces of V (16 or 8 bytes) of every row from device memory into
@@ -2337,6 +2371,16 @@ static hipError_t launch_readback(const void *src, size_t src_pitch, void *dst, 
 }
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
+// ... in descriptor form (mixed batches): frame blockIdx.y's stream - lens[y] bytes at the offset its record names, whole 16-byte pieces -
+// to dst + dst_off[y].  Only the bytes a stream has cross the link, whatever the frames' sizes.
+__global__ __launch_bounds__(256) void readback_frames_kernel(const unsigned char *__restrict__ src, const EntropyFrameTable *__restrict__ frames,
+                                                              const unsigned long long *__restrict__ lens, const unsigned long long *__restrict__ dst_off,
+                                                              unsigned char *__restrict__ dst) {
+    const u32x4v *sp = reinterpret_cast<const u32x4v *>(src + frames->rec[blockIdx.y].out_off);
+    u32x4v *dp = reinterpret_cast<u32x4v *>(dst + dst_off[blockIdx.y]);
+    const size_t pieces = (size_t)((lens[blockIdx.y] + 15ull) / 16ull);
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < pieces; i += (size_t)gridDim.x * 256u) __builtin_nontemporal_store(sp[i], dp + i);
+}
 
 // The end of a batch call: the pipeline's threads (their queues are closed: each drains its own first), the streams, the frames pinned for
 // the call - behind its last copy - and the slots.
@@ -2509,13 +2553,13 @@ static int hand_out_chunk(tic_ctx *ctx, Slot &s, uint8_t *const *outs) {
 // A batch of ONE chunk (the reference's benchmark set: 49 frames of 512 x 512) runs on the calling thread: enqueue, wait, read back, hand out.
 // Starting the two pipeline threads costs more than the chunk's work when the host is busy - their first wake-up came 3-10 ms late in
 // one call in three on a shared box (tools/batch_small_probe.py: chunk_wait 0.008 ms, the reader found the chunk long finished).
-static int batch_device_entropy(tic_ctx *ctx, const uint8_t *const *images, int n, int h, int w, ptrdiff_t row_stride, int quality,
-                                uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
-    BatchPlan p;
-    const int rc = batch_begin(ctx, images, n, h, w, row_stride, quality, true, true, outs, caps, out_lens, &p);
-    if (rc || p.chunk == 0) return rc;
+// (The driver is written once for frames of one size and for mixed frames: enqueue(c, slot, stream, par) queues chunk c - par: which of the
+// slot's two error flags it uses -, read(slot, zero_copy) is read_back, hand(slot) is hand_out_chunk.)
+extern "C++" {
+template <class Enqueue, class Read, class Hand>
+static int device_entropy_pipeline(tic_ctx *ctx, int nchunks, Enqueue enqueue, Read read, Hand hand) {
     std::vector<Slot> &slots = ctx->bslots;
-    const bool inline_path = n <= p.chunk;
+    const bool inline_path = nchunks <= 1;
     SlotGate gate;
     ClosableQueue<int> q_read, q_hand; // slots to read back / to hand out, in submission order
     std::vector<std::thread> threads;
@@ -2525,7 +2569,7 @@ static int batch_device_entropy(tic_ctx *ctx, const uint8_t *const *images, int 
             (void)hipSetDevice(ctx->device);
             int k;
             while (q_read.pop(k)) {
-                const int r = read_back(ctx, p, slots[k], ctx->rstream, outs, caps, out_lens, false);
+                const int r = read(slots[k], false);
                 if (r == TIC_OK) {
                     q_hand.push(k);
                 } else { // nothing to hand out
@@ -2539,33 +2583,25 @@ static int batch_device_entropy(tic_ctx *ctx, const uint8_t *const *images, int 
             bind_pipeline_thread(ctx);
             int k;
             while (q_hand.pop(k)) {
-                const int r = hand_out_chunk(ctx, slots[k], outs);
+                const int r = hand(slots[k]);
                 if (r != TIC_OK) gate.fail(r);
                 gate.finish(slots[k]);
             }
         });
     }
-    int result = TIC_OK, c = 0;
-    for (int first = 0; first < n; first += p.chunk, c++) {
-        const int cnt = n - first < p.chunk ? n - first : p.chunk, si = c % kBatchSlots;
+    int result = TIC_OK;
+    for (int c = 0; c < nchunks; c++) {
+        const int si = c % kBatchSlots;
         Slot &s = slots[si];
         gate.claim(ctx, s, 1);
         if (gate.error() != TIC_OK) break;
         const int par = s.parity;
         s.parity ^= 1;
-        result = enqueue_chunk(ctx, p, s, ctx->bstream[c & 1], images, first, cnt, row_stride, h, w, quality, [&](Slot &sl, hipStream_t st) {
-            // entropy stage of the whole chunk: pack + place (headers, lengths); no zero fill
-            hipError_t e = entropy_gpu_fused((const int16_t *)sl.d_coef, p.nblk, cnt, ctx->d_huff, sl.d_work, sl.work_bytes, sl.d_streams, p.bound,
-                                             (p.bound - 16) / 4, h, w, quality, sl.d_lens, nullptr, sl.d_err + par, sl.d_err + (par ^ 1),
-                                             quality <= ctx->ent_lane_max_quality ? kEntropyLanePerBlock : kEntropyEightLanes, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(sl.h_lens, sl.d_lens, cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(sl.h_err, sl.d_err + par, sizeof(int), hipMemcpyDeviceToHost, st);
-            return e;
-        });
+        result = enqueue(c, s, ctx->bstream[c & 1], par);
         if (result != TIC_OK) break;
         if (inline_path) {
-            result = read_back(ctx, p, s, ctx->rstream, outs, caps, out_lens, true);
-            if (result == TIC_OK) result = hand_out_chunk(ctx, s, outs);
+            result = read(s, true);
+            if (result == TIC_OK) result = hand(s);
             break;
         }
         q_read.push(si);
@@ -2573,6 +2609,30 @@ static int batch_device_entropy(tic_ctx *ctx, const uint8_t *const *images, int 
     q_read.close();
     batch_end(ctx, threads);
     return result != TIC_OK ? result : gate.error();
+}
+}
+
+static int batch_device_entropy(tic_ctx *ctx, const uint8_t *const *images, int n, int h, int w, ptrdiff_t row_stride, int quality,
+                                uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
+    BatchPlan p;
+    const int rc = batch_begin(ctx, images, n, h, w, row_stride, quality, true, true, outs, caps, out_lens, &p);
+    if (rc || p.chunk == 0) return rc;
+    return device_entropy_pipeline(
+        ctx, (n + p.chunk - 1) / p.chunk,
+        [&](int c, Slot &s, hipStream_t stream, int par) {
+            const int first = c * p.chunk, cnt = n - first < p.chunk ? n - first : p.chunk;
+            return enqueue_chunk(ctx, p, s, stream, images, first, cnt, row_stride, h, w, quality, [&](Slot &sl, hipStream_t st) {
+                // entropy stage of the whole chunk: pack + place (headers, lengths); no zero fill
+                hipError_t e = entropy_gpu_fused((const int16_t *)sl.d_coef, p.nblk, cnt, ctx->d_huff, sl.d_work, sl.work_bytes, sl.d_streams, p.bound,
+                                                 (p.bound - 16) / 4, h, w, quality, sl.d_lens, nullptr, sl.d_err + par, sl.d_err + (par ^ 1),
+                                                 quality <= ctx->ent_lane_max_quality ? kEntropyLanePerBlock : kEntropyEightLanes, st);
+                if (e == hipSuccess) e = hipMemcpyAsync(sl.h_lens, sl.d_lens, cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+                if (e == hipSuccess) e = hipMemcpyAsync(sl.h_err, sl.d_err + par, sizeof(int), hipMemcpyDeviceToHost, st);
+                return e;
+            });
+        },
+        [&](Slot &s, bool zero_copy) { return read_back(ctx, p, s, ctx->rstream, outs, caps, out_lens, zero_copy); },
+        [&](Slot &s) { return hand_out_chunk(ctx, s, outs); });
 }
 
 int tic_compress_batch(tic_ctx *ctx, const uint8_t *const *images, int n, int h, int w, ptrdiff_t row_stride, int quality,
@@ -2587,6 +2647,237 @@ int tic_compress_batch(tic_ctx *ctx, const uint8_t *const *images, int n, int h,
         return rc;
     }
     return batch_host_coder(ctx, images, n, h, w, row_stride, quality, nullptr, outs, caps, out_lens, threads, true);
+}
+
+// ---- mixed batches: frames of any sizes and qualities in one call (tic_compress_batch_v) -----------------------------------------------------
+// The plan (plan_mixed_batch, tic_host_pipeline.h) orders the frames by (quality, width, height), cuts chunks by bytes and by count and names,
+// per chunk, the runs of neighbours the transform takes in one launch each.  A chunk then goes the way a chunk of equal frames goes -
+// enqueue_on_slot, device_entropy_pipeline, SlotGate, batch_end - with the entropy stage in descriptor form (entropy_gpu_fused_v: ONE pack and ONE
+// place launch for the chunk, whatever its frames) and a read-back that brings down each stream's own bytes.  Device entropy only; no zero-copy
+// route (the streams of a mixed call are not rows of one length); no registration of the caller's frames beyond what the caller did itself:
+// pinned, dense frames are copied from where they lie, everything else is staged.
+struct MixedCall {
+    const uint8_t *const *images;
+    const ptrdiff_t *row_strides;
+    uint8_t *const *outs;
+    const size_t *caps;
+    size_t *out_lens;
+};
+
+// Upload of a mixed chunk: every frame pinned where it lies and dense at the staged pitch - a copy per stretch of frames that follow each other in
+// memory as they do in the chunk -, else all of them staged into the slot's pinned buffer by a few threads and ONE copy.
+static hipError_t upload_chunk_v(tic_ctx *ctx, Slot &s, const MixedPlan &p, const MixedChunk &c, const MixedCall &io, hipStream_t st, int *direct) {
+    *direct = 0;
+    const MixedFrame *fr = &p.frames[(size_t)c.first];
+    bool pinned = true;
+    for (int k = 0; k < c.count && pinned; k++) {
+        const uint8_t *img = io.images[fr[k].index];
+        pinned = (size_t)io.row_strides[fr[k].index] == fr[k].pitch && host_pointer_is_pinned(img) && host_pointer_is_pinned(img + fr[k].img_bytes - 1);
+    }
+    if (pinned) {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < c.count && e == hipSuccess;) {
+            int m = 1;
+            size_t bytes = fr[k].img_bytes;
+            while (k + m < c.count && io.images[fr[k + m].index] == io.images[fr[k].index] + bytes) bytes += fr[k + m++].img_bytes;
+            e = hipMemcpyAsync((char *)s.d_img + fr[k].img_off, io.images[fr[k].index], bytes, hipMemcpyHostToDevice, st);
+            k += m;
+        }
+        if (e == hipSuccess) {
+            *direct = c.count;
+            return hipSuccess;
+        }
+        (void)hipGetLastError(); // (a copy the runtime refuses: the staged route writes the device buffer again, in stream order)
+    }
+    BT_START();
+    unsigned hw = std::thread::hardware_concurrency();
+    int T = ctx->stage_threads > 0 ? ctx->stage_threads : (int)(hw ? hw / 2 : 4);
+    T = T < 1 ? 1 : (T > 8 ? 8 : T);
+    if (T > c.count) T = c.count;
+    if (c.img_bytes < (4u << 20)) T = 1;
+    uint8_t *pin = s.pin_in;
+    run_strided(c.count, T, [ctx]() { bind_pipeline_thread(ctx); },
+                [=](int k) { stage_frame(pin + fr[k].img_off, fr[k].pitch, io.images[fr[k].index], io.row_strides[fr[k].index], fr[k].h, fr[k].w); });
+    BT_STOP(0);
+    return hipMemcpyAsync(s.d_img, s.pin_in, c.img_bytes, hipMemcpyHostToDevice, st);
+}
+
+// Finishing a mixed chunk, part 1 (read_back's counterpart): its lengths, then ONE launch that packs every stream's own bytes into the slot's
+// pinned buffer, 64 bytes apart at least.
+static int read_back_v(tic_ctx *ctx, const MixedPlan &p, Slot &s, hipStream_t st, const MixedCall &io) {
+    BT_START();
+    const hipError_t ev = hipEventSynchronize(s.done);
+    BT_STOP(2);
+    if (ev != hipSuccess) return set_err(ctx, TIC_E_HIP, "batch chunk failed");
+    if (*s.h_err == 1) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code (reference raises KeyError)");
+    if (*s.h_err == 4) return kRetryEightLanes; // a block exceeds the lane-per-block kernel's strings: the call is run again (tic_compress_batch_v)
+    if (*s.h_err) return set_err(ctx, TIC_E_SPACE, "device entropy stage: stream buffer too small");
+    size_t off = 0, maxlen = 0;
+    for (int k = 0; k < s.count; k++) {
+        const MixedFrame &f = p.frames[(size_t)(s.first + k)];
+        const size_t len = (size_t)s.h_lens[k];
+        if (len > io.caps[f.index] || len > f.bound) return set_err(ctx, TIC_E_SPACE, "output buffer of frame %d too small (%zu bytes needed)", f.index, len);
+        io.out_lens[f.index] = len;
+        s.h_rb_off[k] = off;
+        off += align_up(len, 64);
+        maxlen = len > maxlen ? len : maxlen;
+    }
+    if (off > ctx->bslot_cap.pin_out) return set_err(ctx, TIC_E_HIP, "stream read-back: landing buffer too small"); // (sized for it: mixed_slot_need)
+    BT_START();
+    // (the shader reads the lengths and the landing offsets where the host holds them: pinned memory, complete before the launch)
+    const unsigned gx = (unsigned)std::min<size_t>(64, (maxlen / 16 + 255) / 256 + 1);
+    hipLaunchKernelGGL(readback_frames_kernel, dim3(gx, (unsigned)s.count), dim3(256), 0, st, (const unsigned char *)s.d_streams, s.d_frames, s.h_lens,
+                       s.h_rb_off, (unsigned char *)s.pin_out);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(s.rb_done, st);
+    BT_STOP(3);
+    if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "stream read-back failed: %s", hipGetErrorString(e));
+    return TIC_OK;
+}
+
+// ... part 2: out of the pinned buffer to where the caller wants each stream
+static int hand_out_chunk_v(tic_ctx *ctx, const MixedPlan &p, Slot &s, const MixedCall &io) {
+    BT_START();
+    if (hipEventSynchronize(s.rb_done) != hipSuccess) return set_err(ctx, TIC_E_HIP, "stream read-back failed");
+    const MixedFrame *fr = &p.frames[(size_t)s.first];
+    const char *src = (const char *)s.pin_out;
+    const unsigned long long *lens = s.h_lens, *offs = s.h_rb_off;
+    size_t total = 0;
+    for (int k = 0; k < s.count; k++) total += (size_t)lens[k];
+    const int T = s.count < 4 || total < (4u << 20) ? 1 : 4;
+    uint8_t *const *outs = io.outs;
+    run_strided(s.count, T, [ctx]() { bind_pipeline_thread(ctx); }, [=](int k) { memcpy(outs[fr[k].index], src + offs[k], (size_t)lens[k]); });
+    BT_STOP(4);
+    return TIC_OK;
+}
+
+static tic_ctx::SlotNeed mixed_slot_need(const MixedPlan &p) {
+    tic_ctx::SlotNeed need;
+    need.img = p.max_img;
+    need.coef = p.max_nblk * 128;
+    need.streams = p.max_stream;
+    need.pin_out = p.max_stream + 64 * (size_t)p.max_count; // every stream rounded up to 64 bytes (read_back_v)
+    need.work = entropy_fused_work_bytes_v(p.max_nblk, (size_t)p.max_count);
+    need.frames = p.max_count;
+    return need;
+}
+
+// One run of the pipeline over the plan's chunks.  kRetryEightLanes: a chunk that ran the lane-per-block kernel raised code 4; *retry_quality is
+// that chunk's lowest quality.
+static int batch_mixed_pipeline(tic_ctx *ctx, const MixedPlan &p, const MixedCall &io, int *retry_quality) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int rc = ensure_batch_slots(ctx, mixed_slot_need(p));
+    if (rc) return rc;
+    for (auto &sl : ctx->bslots) sl.pending = 0;
+    int launches = 0;
+    const int result = device_entropy_pipeline(
+        ctx, (int)p.chunks.size(),
+        [&](int ci, Slot &s, hipStream_t stream, int par) {
+            const MixedChunk &c = p.chunks[(size_t)ci];
+            const MixedFrame *fr = &p.frames[(size_t)c.first];
+            // lane per block only when EVERY frame of the chunk may take it (the plan orders by quality: the first frame's is the lowest, the last
+            // frame's the highest)
+            const int mode = fr[c.count - 1].quality <= ctx->ent_lane_max_quality ? kEntropyLanePerBlock : kEntropyEightLanes;
+            size_t nparts, ngroups, nplaces;
+            if (!mixed_chunk_table(p, c, mode, s.h_frames, &nparts, &ngroups, &nplaces)) return set_err(ctx, TIC_E_ARG, "mixed batch: chunk %d has no table", ci);
+            return enqueue_on_slot(
+                ctx, s, stream, c.first, c.count, [&](int *direct) { return upload_chunk_v(ctx, s, p, c, io, stream, direct); },
+                [&]() {
+                    hipError_t e = hipSuccess;
+                    for (size_t r = 0; r < c.runs.size() && e == hipSuccess; r++) { // a run of neighbours is one tall frame
+                        const MixedFrame &f = p.frames[(size_t)c.runs[r].first];
+                        DctqArgs a = make_args(ctx, (const char *)s.d_img + f.img_off, c.runs[r].h_total, f.w, (ptrdiff_t)f.pitch, f.quality,
+                                               (int16_t *)s.d_coef + f.first_block * 64);
+                        a.fallback_count = nullptr;
+                        e = launch_dctq(a, 2, stream);
+                        launches++;
+                    }
+                    return e;
+                },
+                [&](Slot &sl, hipStream_t st) {
+                    hipError_t e = hipMemcpyAsync(sl.d_frames, sl.h_frames, sizeof(EntropyFrameTable), hipMemcpyHostToDevice, st);
+                    if (e == hipSuccess)
+                        e = entropy_gpu_fused_v((const int16_t *)sl.d_coef, sl.h_frames, sl.d_frames, c.count, ctx->d_huff, sl.d_work, sl.work_bytes, sl.d_streams,
+                                                sl.d_lens, sl.d_err + par, sl.d_err + (par ^ 1), mode, st);
+                    if (e == hipSuccess) e = hipMemcpyAsync(sl.h_lens, sl.d_lens, c.count * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+                    if (e == hipSuccess) e = hipMemcpyAsync(sl.h_err, sl.d_err + par, sizeof(int), hipMemcpyDeviceToHost, st);
+                    return e;
+                });
+        },
+        [&](Slot &s, bool) {
+            const int r = read_back_v(ctx, p, s, ctx->rstream, io);
+            const int q = p.frames[(size_t)s.first].quality; // (the reading thread alone writes this; the caller reads it behind batch_end's join)
+            if (r == kRetryEightLanes && (*retry_quality == 0 || q < *retry_quality)) *retry_quality = q;
+            return r;
+        },
+        [&](Slot &s) { return hand_out_chunk_v(ctx, p, s, io); });
+    ctx->last_vbatch_launches = launches;
+    return result;
+}
+
+int tic_compress_batch_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                         const int *qualities, uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    // every check before any work: nothing is written while a frame of the call is unacceptable
+    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
+    ctx->last_vbatch_frames = ctx->last_vbatch_single = ctx->last_vbatch_chunks = ctx->last_vbatch_launches = 0;
+    if (n == 0) return TIC_OK;
+    if (!images || !hs || !ws || !row_strides || !qualities || !outs || !caps || !out_lens) return set_err(ctx, TIC_E_ARG, "null array argument");
+    for (int i = 0; i < n; i++) {
+        const int rc = check_stream_geometry(ctx, hs[i], ws[i], row_strides[i], qualities[i]);
+        if (rc) {
+            const std::string why = ctx->err;
+            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
+        }
+        if (!outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
+        if (!images[i] && num_blocks(hs[i], ws[i]) != 0) return set_err(ctx, TIC_E_ARG, "frame %d: null image", i);
+    }
+    int chunk_frames = kMixedChunkFrames;
+    size_t chunk_bytes = kMixedChunkBytes;
+    if (const char *e = test_hook("TIC_BATCH_CHUNK")) chunk_frames = atoi(e); // (out of range: the default)
+    if (const char *e = test_hook("TIC_BATCH_CHUNK_BYTES")) chunk_bytes = strtoull(e, nullptr, 10) ? (size_t)strtoull(e, nullptr, 10) : chunk_bytes;
+    const MixedPlan p = plan_mixed_batch(hs, ws, qualities, n, chunk_frames, chunk_bytes);
+    const MixedCall io = {images, row_strides, outs, caps, out_lens};
+    ctx->last_batch_direct_frames = ctx->last_batch_staged_frames = ctx->last_batch_autoreg_frames = ctx->last_batch_zero_copy = 0;
+    ctx->bt = BatchTrace();
+    for (int i : p.empty) { // frames without blocks: the host's header-only stream
+        const int rc = entropy_encode(nullptr, hs[i], ws[i], qualities[i], outs[i], caps[i], &out_lens[i]);
+        if (rc) return set_err(ctx, rc, "frame %d: output buffer too small for a header", i);
+    }
+    if (!p.frames.empty()) {
+        int retry_quality = 0;
+        int rc = batch_mixed_pipeline(ctx, p, io, &retry_quality);
+        if (rc == kRetryEightLanes) {
+            // The flag does not say which frame of the chunk has the long block, so the bound drops below the chunk's LOWEST quality: this chunk and
+            // every later one (qualities ascend) then run the 8-lane kernel, the chunks in front passed as they were - one more run settles it.
+            ctx->ent_lane_max_quality = retry_quality - 1;
+            retry_quality = 0;
+            rc = batch_mixed_pipeline(ctx, p, io, &retry_quality);
+        }
+        if (rc) return rc == kRetryEightLanes ? set_err(ctx, TIC_E_HIP, "mixed batch: the 8-lane packing kernel refused a block") : rc;
+    }
+    ctx->last_vbatch_frames = (int)p.frames.size();
+    ctx->last_vbatch_chunks = (int)p.chunks.size();
+    for (int i : p.single) { // what the batch kernels do not take, behind the batch, frame by frame
+        const int rc = tic_compress(ctx, images[i], hs[i], ws[i], row_strides[i], qualities[i], outs[i], caps[i], &out_lens[i]);
+        if (rc) {
+            const std::string why = ctx->err;
+            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
+        }
+        ctx->last_vbatch_single++;
+    }
+    return TIC_OK;
+}
+
+int tic_last_compress_batch_v(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks, int *transform_launches) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (batch_frames) *batch_frames = ctx->last_vbatch_frames;
+    if (single_frames) *single_frames = ctx->last_vbatch_single;
+    if (chunks) *chunks = ctx->last_vbatch_chunks;
+    if (transform_launches) *transform_launches = ctx->last_vbatch_launches;
+    return TIC_OK;
 }
 
 // One batch over several contexts - normally one per GPU of the node - from ONE process: a host thread per context, contiguous shards

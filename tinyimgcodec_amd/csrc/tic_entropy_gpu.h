@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "tic_entropy_frames.h"
+
 namespace tic {
 
 // Huffman tables as the kernels use them: the codeword already shifted left by the size category (the value bits are
@@ -26,7 +28,7 @@ void build_huff_dev(HuffDev *t);
 // mode: kEntropyLanePerBlock - the packing kernel with a lane per block (a wave = 64 blocks, up to 512 bits per block);
 //       *d_err = 4 when a block needs more: the caller runs the stage again with kEntropyEightLanes, the packing kernel with
 //       8 lanes per block, which has no such limit (any block the format allows).  Both feed the same placing kernel.
-enum { kEntropyLanePerBlock = 0, kEntropyEightLanes = 1 };
+// (kEntropyLanePerBlock, kEntropyEightLanes: tic_entropy_frames.h)
 size_t entropy_fused_work_bytes(size_t nblocks_total);
 hipError_t entropy_gpu_fused(const int16_t *d_zz, size_t blocks_per_frame, int nframes, const HuffDev *d_tab, void *d_work,
                              size_t work_bytes, void *d_out, size_t out_frame_stride, size_t cap_words, int h, int w, int quality,
@@ -37,5 +39,16 @@ hipError_t entropy_gpu_fused(const int16_t *d_zz, size_t blocks_per_frame, int n
 // flag: the header's fourth word.  0 = a default-table stream (payload zero-padded to a byte, codec.py:102-114).  1 << 30 = a stream of the
 // reference's integer encoder (img.c:183-192): `quality` is its setting 0..3 and the payload ends as BB_flushBits ends it (img.h:36-40) -
 // floor(bits / 8) whole bytes and ONE more byte with the pending bits, a zero byte when there are none; lengths and the fit test count it.
+
+// The stage in descriptor form: frames of any sizes and qualities in ONE pack and ONE place launch.  h_frames / d_frames: the same table
+// (tic_entropy_frames.h) on the host - the launcher takes the grid sizes from it - and on the device, complete before `stream` reaches the
+// launches; nframes 1..kEntropyMaxFrames, every frame with at least one block and at most 8,192 groups (no tile-sum level here: the caller
+// codes larger frames alone), the records laid out for `mode` (fill_entropy_table).  Frame f's stream starts at d_out + rec[f].out_off and may
+// hold rec[f].cap_words payload words; d_lens[f] receives its length.  *d_err / *d_err_next and the workspace as above: d_work of
+// entropy_fused_work_bytes_v(total blocks, nframes) bytes.
+size_t entropy_fused_work_bytes_v(size_t nblocks_total, size_t nframes);
+hipError_t entropy_gpu_fused_v(const int16_t *d_zz, const EntropyFrameTable *h_frames, const EntropyFrameTable *d_frames, int nframes,
+                               const HuffDev *d_tab, void *d_work, size_t work_bytes, void *d_out, unsigned long long *d_lens, int *d_err,
+                               int *d_err_next, int mode, hipStream_t stream);
 
 } // namespace tic

@@ -285,12 +285,52 @@ __device__ __forceinline__ uint32_t wave_prefix_sum_u32(uint32_t x) {
     return (uint32_t)v;
 }
 
-template <int ABL> // ABL != 0: timing-only builds (tools/), wrong output
-__global__ __launch_bounds__(kGroup * 64) void entropy_pack_kernel(const int16_t *__restrict__ zz, const HuffDev *__restrict__ tab,
-                                                            unsigned long long blocks_per_frame, unsigned long long parts_per_frame,
-                                                            unsigned long long groups_per_frame, uint32_t *__restrict__ stage,
-                                                            uint32_t *__restrict__ nbits, uint32_t *__restrict__ gsum,
-                                                            int *__restrict__ err_flag) {
+// ---- which frame a workgroup works on ---------------------------------------------------------------------------------------------
+// The kernels' bodies see their frame through a view: where its blocks, partitions and group sums begin and how many it has.  The uniform
+// launches (frames of one size: entropy_gpu_fused) derive it from the workgroup's index by a division, the descriptor form
+// (entropy_gpu_fused_v) reads it from the launch's table of records.  Everything behind the view is one body per kernel.
+struct PackFrame {
+    unsigned long long first_block; // the frame's first block in zz
+    unsigned long long blocks;      // blocks of the frame
+    unsigned long long first_part;  // the frame's first partition in nbits / stage
+    unsigned long long parts;       // partitions of the frame
+    unsigned long long g;           // this workgroup's group inside the frame
+};
+struct PlaceFrame {
+    unsigned long long frame;       // index of the frame in the launch (lens[frame]; frame 0 writes *err_next and the status)
+    unsigned long long gp;          // this workgroup's place inside the frame
+    unsigned long long first_part, parts;
+    unsigned long long first_group, groups;
+    unsigned long long first_tile, tiles; // tile sums (0 tiles: none)
+    unsigned char *out;             // the frame's stream: header, then payload
+    unsigned long long cap_words;
+    int h, w, quality;
+};
+__device__ __forceinline__ PackFrame uniform_pack_frame(unsigned long long blocks_per_frame, unsigned long long parts_per_frame,
+                                                        unsigned long long groups_per_frame) {
+    const unsigned long long frame = blockIdx.x / groups_per_frame;
+    return PackFrame{frame * blocks_per_frame, blocks_per_frame, frame * parts_per_frame, parts_per_frame, blockIdx.x - frame * groups_per_frame};
+}
+// Descriptor form: the frame of workgroup `idx` is the last one whose first workgroup is not behind idx.  Every lane of a wave loads one entry
+// of the prefix table (64 entries, 0xffffffff behind the last frame) and the wave counts the entries <= idx: one load round trip, and the
+// result - a population count of a ballot - is a scalar, so that the record's fields come by scalar loads and everything derived from them
+// stays wave-uniform (a binary search would be six dependent round trips; a group -> frame map would have to be uploaded per chunk and grows
+// with the frames' sizes).  All 64 lanes are active here: the kernels call it first, their workgroups are whole waves.
+__device__ __forceinline__ int find_frame(const uint32_t *__restrict__ first, uint32_t idx) {
+    const uint32_t v = first[threadIdx.x & 63];
+    return __builtin_amdgcn_readfirstlane(__popcll(__ballot(v <= idx)) - 1);
+}
+__device__ __forceinline__ PackFrame table_pack_frame(const EntropyFrameTable *__restrict__ ft, unsigned part_blocks) {
+    const EntropyFrameRec &r = ft->rec[find_frame(ft->first_group, blockIdx.x)];
+    return PackFrame{r.first_block, r.nblocks, (unsigned long long)r.first_part, (r.nblocks + part_blocks - 1ull) / part_blocks,
+                     (unsigned long long)(blockIdx.x - r.first_group)};
+}
+
+// (locate() gives the workgroup's view; a body calls it where the frame is first needed, behind the loads that do not depend on it)
+template <int ABL, class Locate> // ABL != 0: timing-only builds (tools/), wrong output
+__device__ __forceinline__ void entropy_pack_body(const int16_t *__restrict__ zz, const HuffDev *__restrict__ tab, Locate locate,
+                                                  uint32_t *__restrict__ stage, uint32_t *__restrict__ nbits, uint32_t *__restrict__ gsum,
+                                                  int *__restrict__ err_flag) {
     __shared__ uint2 ac_tab[256];
     __shared__ uint2 dc_tab[16];
     __shared__ uint32_t wbits[kGroup];
@@ -306,16 +346,17 @@ __global__ __launch_bounds__(kGroup * 64) void entropy_pack_kernel(const int16_t
     reinterpret_cast<uint4 *>(image)[64 + lane] = make_uint4(0u, 0u, 0u, 0u);
     // one workgroup per (frame, group of kGroup partitions); a wave per partition = 8 blocks.  The coefficient load and the
     // zero-run scan need no table: they run in front of the barrier that publishes the tables, not behind it.
-    const unsigned long long frame = blockIdx.x / groups_per_frame, g = blockIdx.x - frame * groups_per_frame;
-    const unsigned long long pif = g * (unsigned long long)kGroup + (unsigned long long)wave;
-    const unsigned long long part = frame * parts_per_frame + pif;
+    const PackFrame fv = locate();
+    const unsigned long long blocks_per_frame = fv.blocks, parts_per_frame = fv.parts;
+    const unsigned long long pif = fv.g * (unsigned long long)kGroup + (unsigned long long)wave;
+    const unsigned long long part = fv.first_part + pif;
     const bool active = pif < parts_per_frame;
     uint32_t wave_bits = 0;
     const unsigned long long first_in_frame = pif * 8ull;
     const unsigned long long bif = first_in_frame + (unsigned long long)(lane >> 3); // block index inside the frame
     const int k = lane & 7;
     const bool valid = active && bif < blocks_per_frame;
-    const unsigned long long frame_first = frame * blocks_per_frame;
+    const unsigned long long frame_first = fv.first_block;
     const unsigned long long blk = frame_first + (valid ? bif : blocks_per_frame - 1);
     int16_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int dc_diff = 0;
@@ -472,6 +513,21 @@ __global__ __launch_bounds__(kGroup * 64) void entropy_pack_kernel(const int16_t
     }
 }
 
+template <int ABL>
+__global__ __launch_bounds__(kGroup * 64) void entropy_pack_kernel(const int16_t *__restrict__ zz, const HuffDev *__restrict__ tab,
+                                                            unsigned long long blocks_per_frame, unsigned long long parts_per_frame,
+                                                            unsigned long long groups_per_frame, uint32_t *__restrict__ stage,
+                                                            uint32_t *__restrict__ nbits, uint32_t *__restrict__ gsum,
+                                                            int *__restrict__ err_flag) {
+    entropy_pack_body<ABL>(zz, tab, [=]() { return uniform_pack_frame(blocks_per_frame, parts_per_frame, groups_per_frame); }, stage, nbits, gsum, err_flag);
+}
+// ... in descriptor form: frames of any sizes, a workgroup finds its own in the table
+__global__ __launch_bounds__(kGroup * 64) void entropy_pack_kernel_v(const int16_t *__restrict__ zz, const HuffDev *__restrict__ tab,
+                                                              const EntropyFrameTable *__restrict__ frames, uint32_t *__restrict__ stage,
+                                                              uint32_t *__restrict__ nbits, uint32_t *__restrict__ gsum,
+                                                              int *__restrict__ err_flag) {
+    entropy_pack_body<0>(zz, tab, [=]() { return table_pack_frame(frames, 8u); }, stage, nbits, gsum, err_flag);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // The packing kernel, round-3 form: a LANE per block, a wave per partition of 64 blocks.
@@ -502,12 +558,10 @@ struct PackL {
     static constexpr int kStageWords = kImageWords;                        // staging slot of a partition
 };
 
-template <int W, int ABL = 0> // ABL != 0: timing-only instantiations (1: no walk, 2: no coefficient loads, 4: no slot store, 8: no merge); the library instantiates <W, 0> only
-__global__ __launch_bounds__(kGroupL * 64) void entropy_pack_lane_kernel(const int16_t *__restrict__ zz, const HuffDev *__restrict__ tab,
-                                                                     unsigned long long blocks_per_frame, unsigned long long parts_per_frame,
-                                                                     unsigned long long groups_per_frame, uint32_t *__restrict__ stage,
-                                                                     uint32_t *__restrict__ nbits, uint32_t *__restrict__ gsum,
-                                                                     int *__restrict__ err_flag) {
+template <int W, int ABL, class Locate> // ABL != 0: timing-only instantiations (1: no walk, 2: no coefficient loads, 4: no slot store, 8: no merge); the library instantiates <W, 0> only
+__device__ __forceinline__ void entropy_pack_lane_body(const int16_t *__restrict__ zz, const HuffDev *__restrict__ tab, Locate locate,
+                                                       uint32_t *__restrict__ stage, uint32_t *__restrict__ nbits, uint32_t *__restrict__ gsum,
+                                                       int *__restrict__ err_flag) {
     typedef PackL<W> P;
     __shared__ uint32_t ac_tab[256];
     __shared__ uint32_t dc_tab[16];
@@ -517,9 +571,10 @@ __global__ __launch_bounds__(kGroupL * 64) void entropy_pack_lane_kernel(const i
     ac_tab[threadIdx.x] = tab->ac_pack[threadIdx.x]; // 256 threads, 256 entries
     if (threadIdx.x < 16) dc_tab[threadIdx.x] = tab->dc_pack[threadIdx.x];
     uint32_t *buf = buf_all[wave];
-    const unsigned long long frame = blockIdx.x / groups_per_frame, g = blockIdx.x - frame * groups_per_frame;
-    const unsigned long long pif = g * (unsigned long long)kGroupL + (unsigned long long)wave; // partition inside the frame
-    const unsigned long long part = frame * parts_per_frame + pif;
+    const PackFrame fv = locate();
+    const unsigned long long blocks_per_frame = fv.blocks, parts_per_frame = fv.parts;
+    const unsigned long long pif = fv.g * (unsigned long long)kGroupL + (unsigned long long)wave; // partition inside the frame
+    const unsigned long long part = fv.first_part + pif;
     const bool active = pif < parts_per_frame;
     const unsigned long long first_in_frame = pif * (unsigned long long)kPB;
     const unsigned long long nblk_part = !active ? 0ull : (blocks_per_frame - first_in_frame < (unsigned long long)kPB ? blocks_per_frame - first_in_frame : (unsigned long long)kPB);
@@ -527,7 +582,7 @@ __global__ __launch_bounds__(kGroupL * 64) void entropy_pack_lane_kernel(const i
     uint32_t wave_bits = 0;
     if (active) {
         // ---- coefficients: 8 KiB per wave in eight coalesced 1 KiB loads, transposed through LDS: lane l ends with block l --------
-        const int16_t *src = zz + (frame * blocks_per_frame + first_in_frame) * 64ull;
+        const int16_t *src = zz + (fv.first_block + first_in_frame) * 64ull;
         uint4 ld[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) {
@@ -671,6 +726,22 @@ __global__ __launch_bounds__(kGroupL * 64) void entropy_pack_lane_kernel(const i
     if (threadIdx.x == 0) gsum[blockIdx.x] = wbits[0] + wbits[1] + wbits[2] + wbits[3]; // bits of the group: the coarse level of the stream offsets
 }
 
+template <int W, int ABL = 0>
+__global__ __launch_bounds__(kGroupL * 64) void entropy_pack_lane_kernel(const int16_t *__restrict__ zz, const HuffDev *__restrict__ tab,
+                                                                     unsigned long long blocks_per_frame, unsigned long long parts_per_frame,
+                                                                     unsigned long long groups_per_frame, uint32_t *__restrict__ stage,
+                                                                     uint32_t *__restrict__ nbits, uint32_t *__restrict__ gsum,
+                                                                     int *__restrict__ err_flag) {
+    entropy_pack_lane_body<W, ABL>(zz, tab, [=]() { return uniform_pack_frame(blocks_per_frame, parts_per_frame, groups_per_frame); }, stage, nbits, gsum, err_flag);
+}
+template <int W> // ... in descriptor form
+__global__ __launch_bounds__(kGroupL * 64) void entropy_pack_lane_kernel_v(const int16_t *__restrict__ zz, const HuffDev *__restrict__ tab,
+                                                                       const EntropyFrameTable *__restrict__ frames, uint32_t *__restrict__ stage,
+                                                                       uint32_t *__restrict__ nbits, uint32_t *__restrict__ gsum,
+                                                                       int *__restrict__ err_flag) {
+    entropy_pack_lane_body<W, 0>(zz, tab, [=]() { return table_pack_frame(frames, (unsigned)kPB); }, stage, nbits, gsum, err_flag);
+}
+
 constexpr int kTileGroups = 256; // groups per tile sum: the second level of the offsets, only for frames of many groups
 
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
@@ -703,14 +774,13 @@ constexpr int kSlotLds = 64; // words of every partition's slot a workgroup fetc
 // per staging slot; kHeads: the head of every slot is fetched into LDS up front (partitions of 8 blocks: a slot seldom has more than
 // 64 words); partitions of 64 blocks are read from memory, every word by the lane that assembles it (coalesced).
 template <int ABL, int kPlace, int kGrp, int kSlotWords, bool kHeads> // ABL != 0: timing-only builds (tools/), wrong output
-__global__ __launch_bounds__(256) void entropy_place_kernel(const uint32_t *__restrict__ stage, const uint32_t *__restrict__ nbits,
-                                                            const uint32_t *__restrict__ gsum, const unsigned long long *__restrict__ tile_sum,
-                                                            unsigned long long parts_per_frame, unsigned long long groups_per_frame,
-                                                            unsigned long long places_per_frame, unsigned long long tiles_per_frame,
-                                                            unsigned char *__restrict__ out, unsigned long long out_frame_stride,
-                                                            unsigned long long cap_words, int h, int w, int quality,
-                                                            unsigned long long *__restrict__ lens, int *__restrict__ err_flag,
-                                                            int *__restrict__ err_next, unsigned long long *__restrict__ status, uint32_t flag) {
+__device__ __forceinline__ void entropy_place_body(const uint32_t *__restrict__ stage, const uint32_t *__restrict__ nbits,
+                                                   const uint32_t *__restrict__ gsum, const unsigned long long *__restrict__ tile_sum,
+                                                   const PlaceFrame &fv, unsigned long long *__restrict__ lens, int *__restrict__ err_flag,
+                                                   int *__restrict__ err_next, unsigned long long *__restrict__ status, uint32_t flag) {
+    const unsigned long long parts_per_frame = fv.parts, groups_per_frame = fv.groups, tiles_per_frame = fv.tiles, cap_words = fv.cap_words;
+    const unsigned long long frame = fv.frame, gp = fv.gp;
+    unsigned char *const fout = fv.out;
     constexpr int kN = kPlace + 3;             // its own partitions and the three behind them (the last word may run into those)
     constexpr int kPer = (kN + 3) / 4;         // slots a wave fetches
     __shared__ uint32_t roff[kN + 1]; // first bit of partition p0 + i, counted from bit 0 of word base_word (empty past the frame's end)
@@ -718,11 +788,10 @@ __global__ __launch_bounds__(256) void entropy_place_kernel(const uint32_t *__re
     __shared__ unsigned long long ws[2][4];
     __shared__ int long_slot;
     __shared__ uint32_t lds[kHeads ? kN * kSlotLds : 1];
-    const unsigned long long frame = blockIdx.x / places_per_frame, gp = blockIdx.x - frame * places_per_frame;
     const unsigned long long p0 = gp * (unsigned long long)kPlace;
     const unsigned long long g = gp * (unsigned long long)(kPlace / kGrp); // first packing group of this workgroup
-    const uint32_t *fn = nbits + frame * parts_per_frame;
-    const uint32_t *fstage = stage + (frame * parts_per_frame + p0) * (unsigned long long)kSlotWords;
+    const uint32_t *fn = nbits + fv.first_part;
+    const uint32_t *fstage = stage + (fv.first_part + p0) * (unsigned long long)kSlotWords;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // ---- every load of the prologue, back to back --------------------------------------------------------------------------
     const unsigned long long pl = p0 + (unsigned long long)lane;
@@ -730,10 +799,10 @@ __global__ __launch_bounds__(256) void entropy_place_kernel(const uint32_t *__re
     unsigned long long before = 0, total = 0;
     {   // first bit of partition p0 = the group sums before group g (through the tile sums when the frame has them); the
         // frame's first workgroup also needs the frame's total
-        const uint32_t *fg = gsum + frame * groups_per_frame;
+        const uint32_t *fg = gsum + fv.first_group;
         unsigned long long first = 0; // first group summed directly
         if (tiles_per_frame) {
-            const unsigned long long *fts = tile_sum + frame * tiles_per_frame;
+            const unsigned long long *fts = tile_sum + fv.first_tile;
             const unsigned long long tile = g / (unsigned long long)kTileGroups;
             first = tile * (unsigned long long)kTileGroups;
             const unsigned long long upto = gp == 0 ? tiles_per_frame : tile;
@@ -799,7 +868,7 @@ __global__ __launch_bounds__(256) void entropy_place_kernel(const uint32_t *__re
     }
     __syncthreads();
     const bool in_lds = long_slot == 0;
-    uint32_t *dst = reinterpret_cast<uint32_t *>(out + frame * out_frame_stride + 16) + base_word;
+    uint32_t *dst = reinterpret_cast<uint32_t *>(fout + 16) + base_word;
     const unsigned long long room_words = cap_words > base_word ? cap_words - base_word : 0ull; // words of the caller's buffer from base_word on
     auto assemble = [&](auto fetch) {
         // words that lie inside one partition: a funnel shift of two staged words, the shift the same for the whole partition
@@ -850,10 +919,10 @@ __global__ __launch_bounds__(256) void entropy_place_kernel(const uint32_t *__re
     else
         assemble([&](int i, uint32_t w0) { return fstage[(unsigned long long)i * (unsigned long long)kSlotWords + w0]; });
     if (gp == 0 && threadIdx.x == 0) { // make_header (codec.py:102-114), the frame's length, the caller's status
-        uint32_t *hdr = reinterpret_cast<uint32_t *>(out + frame * out_frame_stride);
-        hdr[0] = (uint32_t)h; // struct.pack("III") little-endian == native order here
-        hdr[1] = (uint32_t)w;
-        hdr[2] = (uint32_t)quality;
+        uint32_t *hdr = reinterpret_cast<uint32_t *>(fout);
+        hdr[0] = (uint32_t)fv.h; // struct.pack("III") little-endian == native order here
+        hdr[1] = (uint32_t)fv.w;
+        hdr[2] = (uint32_t)fv.quality;
         hdr[3] = flag; // 0: default tables (codec.py:111); 1 << 30: a scaled-DCT stream (img.c:185)
         // a scaled-DCT stream ends as BB_flushBits ends it (img.h:36-40): ONE more byte behind the last whole byte, the pending bits
         // zero-padded - a zero byte when the payload ends on a byte boundary.  The words the partitions wrote are zero-padded already;
@@ -862,7 +931,7 @@ __global__ __launch_bounds__(256) void entropy_place_kernel(const uint32_t *__re
         const unsigned long long bytes = flush ? (frame_bits >> 3) + 1ull : (frame_bits + 7ull) >> 3;
         if (lens) lens[frame] = 16ull + bytes;
         const bool over = ((bytes + 3ull) >> 2) > cap_words;
-        if (flush && !over && (frame_bits & 31ull) == 0ull) store_u32_wt(reinterpret_cast<uint32_t *>(out + frame * out_frame_stride + 16) + (frame_bits >> 5), 0u);
+        if (flush && !over && (frame_bits & 31ull) == 0ull) store_u32_wt(reinterpret_cast<uint32_t *>(fout + 16) + (frame_bits >> 5), 0u);
         if (over) atomicMax(err_flag, 2);
         if (frame == 0ull) {
             *err_next = 0; // the flag the NEXT call uses (two flags in turn: no memset between calls)
@@ -875,6 +944,35 @@ __global__ __launch_bounds__(256) void entropy_place_kernel(const uint32_t *__re
     }
 }
 
+template <int ABL, int kPlace, int kGrp, int kSlotWords, bool kHeads>
+__global__ __launch_bounds__(256) void entropy_place_kernel(const uint32_t *__restrict__ stage, const uint32_t *__restrict__ nbits,
+                                                            const uint32_t *__restrict__ gsum, const unsigned long long *__restrict__ tile_sum,
+                                                            unsigned long long parts_per_frame, unsigned long long groups_per_frame,
+                                                            unsigned long long places_per_frame, unsigned long long tiles_per_frame,
+                                                            unsigned char *__restrict__ out, unsigned long long out_frame_stride,
+                                                            unsigned long long cap_words, int h, int w, int quality,
+                                                            unsigned long long *__restrict__ lens, int *__restrict__ err_flag,
+                                                            int *__restrict__ err_next, unsigned long long *__restrict__ status, uint32_t flag) {
+    const unsigned long long frame = blockIdx.x / places_per_frame;
+    const PlaceFrame fv = {frame, blockIdx.x - frame * places_per_frame, frame * parts_per_frame, parts_per_frame, frame * groups_per_frame, groups_per_frame,
+                           frame * tiles_per_frame, tiles_per_frame, out + frame * out_frame_stride, cap_words, h, w, quality};
+    entropy_place_body<ABL, kPlace, kGrp, kSlotWords, kHeads>(stage, nbits, gsum, tile_sum, fv, lens, err_flag, err_next, status, flag);
+}
+// ... in descriptor form: no tile sums (a frame has at most kEntropyMaxGroups groups), a default-table stream, no status block
+template <int kPlace, int kGrp, int kSlotWords, bool kHeads, int kPartBlocks>
+__global__ __launch_bounds__(256) void entropy_place_kernel_v(const uint32_t *__restrict__ stage, const uint32_t *__restrict__ nbits,
+                                                              const uint32_t *__restrict__ gsum, const EntropyFrameTable *__restrict__ frames,
+                                                              unsigned char *__restrict__ out, unsigned long long *__restrict__ lens,
+                                                              int *__restrict__ err_flag, int *__restrict__ err_next) {
+    const int f = find_frame(frames->first_place, blockIdx.x);
+    const EntropyFrameRec &r = frames->rec[f];
+    const unsigned long long parts = (r.nblocks + (unsigned long long)kPartBlocks - 1ull) / (unsigned long long)kPartBlocks;
+    const PlaceFrame fv = {(unsigned long long)f, (unsigned long long)(blockIdx.x - r.first_place), (unsigned long long)r.first_part, parts,
+                           (unsigned long long)r.first_group, (parts + (unsigned long long)kGrp - 1ull) / (unsigned long long)kGrp, 0ull, 0ull,
+                           out + r.out_off, r.cap_words, r.h, r.w, r.quality};
+    entropy_place_body<0, kPlace, kGrp, kSlotWords, kHeads>(stage, nbits, gsum, nullptr, fv, lens, err_flag, err_next, nullptr, 0u);
+}
+
 } // namespace
 
 // Workspace layout: [tile sums u64 x cap | group sums u32 x cap | bits per partition u32 x cap | staging slots]; cap = partitions
@@ -884,6 +982,9 @@ __global__ __launch_bounds__(256) void entropy_place_kernel(const uint32_t *__re
 constexpr int kLaneW = 16;                                   // words per block of the lane-per-block packing kernel: 512 bits
 static constexpr size_t kPerPart = 8 + 4 + 4 + (size_t)kStageWords * 4;
 static_assert((size_t)PackL<kLaneW>::kStageWords <= 8 * (size_t)kStageWords, "a 64-block slot fits the room of eight 8-block slots");
+
+// (descriptor form: every frame's partitions are rounded up - to 8 blocks, or to a 64-block slot that takes the room of 2.4 8-block ones)
+size_t entropy_fused_work_bytes_v(size_t nblocks_total, size_t nframes) { return entropy_fused_work_bytes(nblocks_total + 64 * nframes); }
 
 size_t entropy_fused_work_bytes(size_t nblocks_total) {
     const size_t npart = (nblocks_total + 7) / 8 + 8 * 9; // (+ a partition of 64 blocks rounded up per frame end, generously)
@@ -998,6 +1099,51 @@ hipError_t entropy_gpu_fused(const int16_t *d_zz, size_t blocks_per_frame, int n
 #endif
     }
 #undef TIC_PLACE_ARGS
+    return hipGetLastError();
+}
+
+static_assert(kPB == 64 && kGroupL == 4 && kGroup == 16, "entropy_geom (tic_entropy_frames.h) states the kernels' constants");
+
+hipError_t entropy_gpu_fused_v(const int16_t *d_zz, const EntropyFrameTable *h_frames, const EntropyFrameTable *d_frames, int nframes,
+                               const HuffDev *d_tab, void *d_work, size_t work_bytes, void *d_out, unsigned long long *d_lens, int *d_err,
+                               int *d_err_next, int mode, hipStream_t stream) {
+    if (nframes <= 0) return hipSuccess;
+    if (nframes > kEntropyMaxFrames || !h_frames || !d_frames) return hipErrorInvalidValue;
+    const bool lane_form = mode == kEntropyLanePerBlock;
+    const EntropyGeom gm = entropy_geom(mode);
+    // the launch's totals, and the table checked against what the kernels assume of it: prefix sums without gaps, no frame beyond the direct sums
+    size_t npart = 0, ngroup = 0, nplace = 0;
+    for (int f = 0; f < nframes; f++) {
+        const EntropyFrameRec &r = h_frames->rec[f];
+        const size_t parts = ((size_t)r.nblocks + gm.part_blocks - 1) / gm.part_blocks;
+        const size_t groups = (parts + gm.group_parts - 1) / gm.group_parts, places = (parts + gm.place_parts - 1) / gm.place_parts;
+        if (r.nblocks == 0 || groups > kEntropyMaxGroups || r.first_part != npart || r.first_group != ngroup || r.first_place != nplace ||
+            h_frames->first_group[f] != ngroup || h_frames->first_place[f] != nplace || (r.out_off & 15ull) != 0)
+            return hipErrorInvalidValue;
+        npart += parts, ngroup += groups, nplace += places;
+    }
+    for (int f = nframes; f < kEntropyMaxFrames; f++)
+        if (h_frames->first_group[f] != 0xffffffffu || h_frames->first_place[f] != 0xffffffffu) return hipErrorInvalidValue;
+    if (work_bytes < 256 + kPerPart) return hipErrorInvalidValue;
+    const size_t cap_parts = (work_bytes - 256) / kPerPart; // in 8-block partitions, as in entropy_gpu_fused: the same workspace layout
+    const size_t slot_words = lane_form ? (size_t)PackL<kLaneW>::kStageWords : (size_t)kStageWords;
+    if (npart > cap_parts || ngroup > cap_parts || ngroup > 0x7fffffffull || npart * slot_words > cap_parts * (size_t)kStageWords) return hipErrorInvalidValue;
+    unsigned long long *tile_sum = (unsigned long long *)d_work;
+    uint32_t *gsum = (uint32_t *)(tile_sum + cap_parts);
+    uint32_t *nbits = gsum + cap_parts;
+    uint32_t *stage = nbits + cap_parts;
+    if (lane_form)
+        hipLaunchKernelGGL((entropy_pack_lane_kernel_v<kLaneW>), dim3((unsigned)ngroup), dim3(kGroupL * 64), 0, stream, d_zz, d_tab, d_frames, stage, nbits, gsum, d_err);
+    else
+        hipLaunchKernelGGL(entropy_pack_kernel_v, dim3((unsigned)ngroup), dim3(kGroup * 64), 0, stream, d_zz, d_tab, d_frames, stage, nbits, gsum, d_err);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (lane_form)
+        hipLaunchKernelGGL((entropy_place_kernel_v<8, kGroupL, PackL<kLaneW>::kStageWords, false, kPB>), dim3((unsigned)nplace), dim3(256), 0, stream, stage, nbits,
+                           gsum, d_frames, (unsigned char *)d_out, d_lens, d_err, d_err_next);
+    else
+        hipLaunchKernelGGL((entropy_place_kernel_v<32, kGroup, kStageWords, true, 8>), dim3((unsigned)nplace), dim3(256), 0, stream, stage, nbits, gsum, d_frames,
+                           (unsigned char *)d_out, d_lens, d_err, d_err_next);
     return hipGetLastError();
 }
 

@@ -3,6 +3,7 @@
 
     python -m tinyimgcodec_amd.encode_cli input.(gif|png|jpg|npy|raw) output.img [--quality 50] [--shape H W] [--scaled {best,high,med,low}]
                                          [--max-bytes N | --min-psnr DB [--min-quality 1] [--max-quality 99]]
+                                         [--also INPUT OUTPUT]...
 
 Prints "<n> bytes" and "Compression Ratio: <w*h/n>:1" exactly as the reference does.  Inputs: anything Pillow
 opens (converted to "L" as the reference does), a .npy array, or headerless 8-bit gray (.raw with --shape) so that
@@ -15,7 +16,10 @@ reading raw pixels; header flag 1 << 30); --quality is then ignored, and height 
 "Quality: <q>" as a third line; it cannot be combined with --scaled or an explicit --quality.
 
 --min-psnr DB writes the smallest stream of that range whose round trip reaches DB decibels (compress_to_psnr) and prints "Quality: <q>"
-and "PSNR: <dB>" as third and fourth lines; the same restrictions, and not together with --max-bytes."""
+and "PSNR: <dB>" as third and fourth lines; the same restrictions, and not together with --max-bytes.
+
+--also INPUT OUTPUT (repeatable) codes further files in the same call: all images, of whatever sizes, go through ONE compress_batch() at --quality,
+and the two lines are printed per file.  Plain --quality only."""
 import argparse
 import sys
 
@@ -46,15 +50,28 @@ def main(argv=None):
     target.add_argument("--min-psnr", type=float, metavar="DB", help="write the smallest stream whose round trip reaches DB decibels")
     ap.add_argument("--min-quality", type=int, default=None, help="with --max-bytes / --min-psnr: lowest quality tried (default 1)")
     ap.add_argument("--max-quality", type=int, default=None, help="with --max-bytes / --min-psnr: highest quality tried (default 99)")
+    ap.add_argument("--also", nargs=2, action="append", metavar=("INPUT", "OUTPUT"), help="a further file, coded in the same compress_batch() call (repeatable)")
     args = ap.parse_args(argv)
     searching = args.max_bytes is not None or args.min_psnr is not None
     if searching and (args.scaled or args.quality is not None):
         ap.error("--max-bytes / --min-psnr cannot be combined with --scaled or --quality")
     if not searching and (args.min_quality is not None or args.max_quality is not None):
         ap.error("--min-quality / --max-quality need --max-bytes or --min-psnr")
-    from . import compress, compress_scaled, compress_to_psnr, compress_to_size
+    if args.also and (searching or args.scaled):
+        ap.error("--also takes a plain --quality only")
+    from . import compress, compress_batch, compress_scaled, compress_to_psnr, compress_to_size
 
     im = load_gray(args.input, args.shape)
+    if args.also:
+        paths = [(args.input, args.output)] + [tuple(p) for p in args.also]
+        images = [im] + [load_gray(p[0], args.shape) for p in paths[1:]]
+        outs = compress_batch(images, [50 if args.quality is None else args.quality] * len(images))
+        for (_, dst), a, out in zip(paths, images, outs):
+            print(f"{len(out)} bytes")
+            print(f"Compression Ratio: {a.shape[1] * a.shape[0] / len(out)}:1")
+            with open(dst, "wb") as f:
+                f.write(out)
+        return 0
     chosen = reached = None
     qrange = (1 if args.min_quality is None else args.min_quality, 99 if args.max_quality is None else args.max_quality)
     if args.max_bytes is not None:
