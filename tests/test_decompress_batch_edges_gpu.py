@@ -280,3 +280,80 @@ def test_a_refused_chunk_falls_back(ctx, oracle, golden, monkeypatch):
     assert rc == N.TIC_OK and counts(L, ctx.handle)[0] >= 8
     for k, (o, w_) in enumerate(zip(outs, want)):
         assert np.array_equal(o[: w_.size].reshape(w_.shape), w_), k
+
+
+def device_decoder_takes(nblocks, nbytes):
+    """csrc/tic_api.hip device_decoder_takes at its defaults: at least 1,024 blocks and 8,192 stream bits behind the 16-byte header."""
+    return nblocks >= 1024 and nbytes * 8 >= 128 + 8192
+
+
+@pytest.fixture(scope="module")
+def ten_streams(ctx, oracle):
+    """Ten streams for chunks of three: four 256 x 256 frames of noise (1,024 blocks: the smallest frame the device decoder takes) at q = 50, 90,
+    50, 10, a 264 x 260 one (row pitch 264 in the device buffer), 203 x 517 at q = 90, 64 x 64 (too short: single-frame), an empty image, the first
+    stream cut at two thirds (taken, then flagged: single-frame), one more 256 x 256 -> (streams, the oracle's images, E = how many the batch takes)."""
+    L = N.load()
+    imgs = [(rand_frame(71, 256, 256), 50), (rand_frame(72, 256, 256), 90), (rand_frame(73, 256, 256), 50), (rand_frame(74, 256, 256), 10),
+            (rand_frame(75, 264, 260), 50), (rand_frame(76, 203, 517), 90), (rand_frame(77, 64, 64), 50), (np.zeros((0, 8), np.uint8), 50)]
+    streams = [T.compress(im, q, ctx=ctx) for im, q in imgs]
+    streams.append(streams[0][: len(streams[0]) * 2 // 3])
+    streams.append(T.compress(rand_frame(78, 256, 256), 50, ctx=ctx))
+    want = [oracle.decompress(s) for s in streams]
+    takes = [device_decoder_takes(L.tic_num_blocks(hd["height"], hd["width"]), len(s)) for hd, s in zip(map(T.parse_header, streams), streams)]
+    assert takes == [True] * 6 + [False, False, True, True] and sum(1 for w_ in want if w_.size) == 9
+    return streams, want, sum(takes)
+
+
+def decode_scattered(L, handle, streams, want):
+    """One tic_decompress_batch into scattered destinations, each 64 bytes longer than its frame and pre-filled with 0xCD: every frame the oracle's,
+    hs / ws right, the guard bytes untouched -> the call's counts."""
+    outs = [np.full(w_.size + 64, 0xCD, np.uint8) for w_ in want]
+    rc, geo = run_batch(L, handle, streams, [o.ctypes.data for o in outs], [w_.size for w_ in want])
+    assert rc == N.TIC_OK, L.tic_last_error(handle).decode()
+    for k, (o, w_) in enumerate(zip(outs, want)):
+        assert geo[k] == w_.shape, (k, geo[k])
+        assert np.array_equal(o[: w_.size].reshape(w_.shape), w_), k
+        assert o[w_.size:].size == 64 and (o[w_.size:] == 0xCD).all(), k
+    return counts(L, handle)
+
+
+def test_several_chunks(ctx, ten_streams, monkeypatch):
+    """TIC_DBATCH_CHUNK (test-hooks build only) sets the frames per chunk: with 3 the ten streams are ceil(E / 3) chunks - the second and third packed
+    into the upload buffer the first left, descriptors, ranges, tiles and workgroups starting over, the single-frame list collecting over chunks
+    (the cut stream is flagged in the third) - and with 1 a chunk per frame; without the hook one chunk.  Every time every frame is the oracle's."""
+    L = N.load()
+    if not L.tic_build_has_test_hooks():
+        pytest.skip("needs chunks of 3 frames (TIC_DBATCH_CHUNK, a test hook)")
+    streams, want, E = ten_streams
+    assert E == 8
+    monkeypatch.setenv("TIC_DBATCH_CHUNK", "3")
+    nb, ns, nc, nd = decode_scattered(L, ctx.handle, streams, want)
+    print("chunks of 3: batch_frames %d, single_frames %d, chunks %d, direct_frames %d" % (nb, ns, nc, nd))
+    assert nc == (E + 2) // 3 and nb + ns == 9 and ns >= 2 and nb >= E - 1
+    monkeypatch.setenv("TIC_DBATCH_CHUNK", "1")
+    nb, ns, nc, nd = decode_scattered(L, ctx.handle, streams, want)
+    print("chunks of 1: batch_frames %d, single_frames %d, chunks %d, direct_frames %d" % (nb, ns, nc, nd))
+    assert nc == E and nb + ns == 9 and ns >= 2 and nb >= E - 1
+    monkeypatch.delenv("TIC_DBATCH_CHUNK")
+    nb, ns, nc, nd = decode_scattered(L, ctx.handle, streams, want)
+    print("no hook: batch_frames %d, single_frames %d, chunks %d, direct_frames %d" % (nb, ns, nc, nd))
+    assert nc == 1 and nb + ns == 9 and ns >= 2 and nb >= E - 1
+
+
+def test_every_chunk_refused(ctx, ten_streams, monkeypatch):
+    """The same streams in chunks of 3 with TIC_DBATCH_WORK_CAP=4096: the launcher refuses all three chunks, each refusal drains the stream before the
+    next chunk is packed into the same pinned upload buffer, and every frame takes the single-frame call.  The call behind it, without the two
+    hooks, decodes in chunks again."""
+    L = N.load()
+    if not L.tic_build_has_test_hooks():
+        pytest.skip("needs TIC_DBATCH_CHUNK and TIC_DBATCH_WORK_CAP (test hooks)")
+    streams, want, E = ten_streams
+    monkeypatch.setenv("TIC_DBATCH_CHUNK", "3")
+    monkeypatch.setenv("TIC_DBATCH_WORK_CAP", "4096")
+    nb, ns, nc, nd = decode_scattered(L, ctx.handle, streams, want)
+    print("every chunk refused: batch_frames %d, single_frames %d, chunks %d, direct_frames %d" % (nb, ns, nc, nd))
+    assert (nb, ns, nc) == (0, 9, 0)
+    monkeypatch.delenv("TIC_DBATCH_CHUNK")
+    monkeypatch.delenv("TIC_DBATCH_WORK_CAP")
+    nb, ns, nc, nd = decode_scattered(L, ctx.handle, streams, want)
+    assert nc == 1 and nb >= E - 1 and nb + ns == 9

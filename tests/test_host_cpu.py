@@ -367,3 +367,29 @@ def test_host_pipeline_header_under_the_sanitizers(tmp_path):
         r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0 and r.stdout.strip().endswith("pipeline_selftest ok") and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, \
             name + ": " + r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_decode_batch_plan_under_the_sanitizers(tmp_path):
+    """Everything tic_decompress_batch works out from geometries and stream lengths alone lives in csrc/tic_decode_plan.h - which frames go into
+    which chunk, a frame's words, ranges, blocks and pixels inside its chunk, the chunk's totals, range and window, the upload buffer's layout - and
+    tests/native/decplan_selftest.cpp runs it on the CPU under the address and undefined-behaviour sanitizers: seeded batches of 0..1,100 frames
+    (widths that are no multiple of 8, frames the decoder does not take, empty frames, lengths from the decoder's floor to 4 MB) under the
+    production limits and under small ones (1, 3 and 7 frames, a few KB of streams, fewer pixels than one frame).  Every taken frame is in exactly
+    one chunk, in the caller's order; only a single frame passes a limit, and the next frame would pass one; stream regions are 16-byte and pixel
+    regions 256-byte aligned, touch nothing and end at the totals; range, window, ranges and first blocks equal their definitions written out
+    naively; the work buffer's provision covers the carve-up at the chunk's range; the upload buffer's pieces are aligned and in order; and one
+    case is derived by hand.  With --break-cut the sweep runs on a cut that tests the limits after the frame joined, and must find its
+    counterexamples: the sweep can fail."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no host compiler")
+    exe = tmp_path / "decplan_selftest"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-o", str(exe),
+                    os.path.join(ROOT, "tests", "native", "decplan_selftest.cpp"), os.path.join(ROOT, "tinyimgcodec_amd", "csrc", "tic_entropy.cpp")], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("decplan_selftest ok") and ", 0 counterexamples" in r.stdout and \
+        "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stdout[-2000:] + r.stderr[-2000:]
+    b = subprocess.run([str(exe), "--break-cut"], capture_output=True, text=True, timeout=300)
+    assert b.returncode == 1 and "decplan_selftest FAILED (broken cut)" in b.stdout and "counterexample: only a single frame passes a byte limit" in b.stdout and \
+        "Sanitizer" not in b.stderr and "runtime error" not in b.stderr, b.stdout[-2000:] + b.stderr[-2000:]

@@ -19,6 +19,7 @@
 
 #include "../../include/tinyimgcodec_hip.h"
 #include "tic_adaptive.h"
+#include "tic_decode_plan.h"
 #include "tic_entropy.h"
 #include "tic_entropy_dec_gpu.h"
 #include "tic_entropy_gpu.h"
@@ -2084,7 +2085,8 @@ struct BatchPlan {
     int chunk = 0;
 };
 
-static void stage_frame(uint8_t *dst, size_t pitch, const uint8_t *src, ptrdiff_t row_stride, int h, int w) {
+// h rows of w bytes from one pitch to another: one memcpy when both sides are dense.
+static void copy_rows(uint8_t *dst, size_t pitch, const uint8_t *src, ptrdiff_t row_stride, int h, int w) {
     if ((size_t)row_stride == pitch && pitch == (size_t)w) {
         memcpy(dst, src, (size_t)h * (size_t)w);
         return;
@@ -2102,7 +2104,7 @@ static void stage_chunk(const tic_ctx *ctx, uint8_t *pin, size_t img_bytes, size
     if (T > cnt) T = cnt;
     if (img_bytes * (size_t)cnt < (4u << 20)) T = 1;
     run_strided(cnt, T, [ctx]() { bind_pipeline_thread(ctx); },
-                [=](int k) { stage_frame(pin + (size_t)k * img_bytes, pitch, images[first + k], row_stride, h, w); });
+                [=](int k) { copy_rows(pin + (size_t)k * img_bytes, pitch, images[first + k], row_stride, h, w); });
 }
 
 static bool host_pointer_is_pinned(const void *p) {
@@ -2697,7 +2699,7 @@ static hipError_t upload_chunk_v(tic_ctx *ctx, Slot &s, const MixedPlan &p, cons
     if (c.img_bytes < (4u << 20)) T = 1;
     uint8_t *pin = s.pin_in;
     run_strided(c.count, T, [ctx]() { bind_pipeline_thread(ctx); },
-                [=](int k) { stage_frame(pin + fr[k].img_off, fr[k].pitch, io.images[fr[k].index], io.row_strides[fr[k].index], fr[k].h, fr[k].w); });
+                [=](int k) { copy_rows(pin + fr[k].img_off, fr[k].pitch, io.images[fr[k].index], io.row_strides[fr[k].index], fr[k].h, fr[k].w); });
     BT_STOP(0);
     return hipMemcpyAsync(s.d_img, s.pin_in, c.img_bytes, hipMemcpyHostToDevice, st);
 }
@@ -3117,7 +3119,7 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
     // a small image on its way to host memory: the kernels store its rows (8-byte aligned, back to back) into the context's host-mapped
     // buffer, and one memcpy behind the wait that reads the status takes them to the caller - no copy command, no second wait
     // (a 512 x 512 image: 30 us between the last kernel and the end of the read-back, profiles/r05_decoder.txt)
-    const size_t pitch8 = align_up((size_t)w, 8);
+    const size_t pitch8 = dec_pix_pitch(w);
     const bool host_pix = !out_on_device && pitch8 * (size_t)h <= kDecHostPixBytes && !test_hook("TIC_DECODE_NO_HOSTPIX");
     if (host_pix) {
         rc = ensure_small(ctx, kSmallHostBytes);
@@ -3216,8 +3218,7 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
         if (direct || host_pix || !big.empty()) HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (the caller's pixels are complete when this returns)
     }
     if (host_pix) { // (the stream has drained: the kernels' stores have arrived)
-        if (pitch8 == (size_t)w) memcpy(out, ctx->h_small, (size_t)h * (size_t)w);
-        else for (int y = 0; y < h; y++) memcpy(out + (size_t)y * (size_t)w, ctx->h_small + (size_t)y * pitch8, (size_t)w);
+        copy_rows(out, (size_t)w, ctx->h_small, (ptrdiff_t)pitch8, h, w);
     } else if (!direct) {
         HIPCHK(ctx, hipMemcpy2DAsync(out, out_on_device ? out_stride : (size_t)w, ctx->d_img, pitch, (size_t)w, (size_t)h,
                                      out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
@@ -3325,6 +3326,149 @@ int tic_decompress(tic_ctx *ctx, const uint8_t *data, size_t len, uint8_t *out, 
     return TIC_OK;
 }
 
+// ---- tic_decompress_batch: a chunk's three stages.  The plan (tic_decode_plan.h) says which frames a chunk holds and where their words, ranges,
+// blocks and pixels lie in its buffers; the buffers themselves are the context's (ctx->dbat).  `pf`: the chunk's frames, c.count of them.
+struct DecBatchIO { // the caller's arrays
+    const uint8_t *const *streams;
+    const size_t *lens;
+    uint8_t *const *outs;
+    const size_t *caps;
+};
+
+// Descriptors, buffers, ONE upload - descriptors, the frame of every measure wave, the frame of every fused workgroup, the streams - and the two
+// launches.  *refused: the launcher's host-side checks said no (every one of them comes before its first launch): nothing runs, and the stream
+// has drained - the upload still read the pinned buffer the next chunk is packed into.
+static int dbatch_enqueue(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame *pf, const DecPlanChunk &c, bool *refused) {
+    tic_ctx::DecBatch &B = ctx->dbat;
+    const uint32_t F = (uint32_t)c.count;
+    std::vector<DecFrame> frames(F);
+    uint32_t tiles = 0, wgs = 0;
+    for (uint32_t k = 0; k < F; k++) {
+        const DecPlanFrame &f = pf[k];
+        DecFrame &d = frames[k];
+        d.word0 = f.word0, d.nwords = f.nwords, d.last_mask = f.last_mask;
+        d.stream_bits = d.fast_end = f.stream_bits;
+        d.nranges = f.nranges, d.range0 = f.range0;
+        d.tile0 = tiles, d.ntiles = entropy_decode_batch_tiles(f.nranges, c.range_bits);
+        d.blk0 = f.blk0, d.nblocks = (uint32_t)f.nblk;
+        d.wg0 = wgs, d.nwgs = entropy_decode_batch_wgs(f.nblk);
+        d.pad_ = 0;
+        d.idct = dec_idct_args(ctx, f.h, f.w, f.quality, -1, nullptr /* set below, when the pixel buffer exists */, (long)f.pitch, io.streams[f.index]);
+        tiles += d.ntiles, wgs += d.nwgs;
+    }
+    const DecUploadLayout up(F, tiles, wgs, c.words);
+    int rc;
+    if (up.up_bytes > B.in_cap) { // the pinned upload buffer and its device mirror grow together
+        size_t hcap = B.in_cap, dcap = B.in_cap;
+        B.in_cap = 0;
+        rc = grow_pinned(ctx, B.h_in, hcap, up.up_bytes, up.up_bytes + up.up_bytes / 4);
+        if (rc) return rc;
+        rc = grow_dev(ctx, B.d_in, dcap, up.up_bytes, up.up_bytes + up.up_bytes / 4);
+        if (rc) return rc;
+        B.in_cap = dcap;
+    }
+    rc = grow_dev(ctx, B.d_pix, B.pix_cap, c.pix_bytes, c.pix_bytes + c.pix_bytes / 4);
+    if (rc) return rc;
+    const size_t wb = dec_work_provision_bytes(F, c.ranges288, c.blocks);
+    rc = B.ws.grow(ctx, wb, wb + wb / 4, 4 * (size_t)((tiles > wgs ? tiles : wgs) + 2), F, F < 256 ? 256 : 2 * (size_t)F);
+    if (rc) return rc;
+    BT_START();
+    for (uint32_t k = 0; k < F; k++) frames[k].idct.out = B.d_pix + pf[k].pix_off;
+    memcpy(B.h_in + up.o_frames, frames.data(), F * sizeof(DecFrame));
+    uint32_t *tf = (uint32_t *)(B.h_in + up.o_tiles), *wf = (uint32_t *)(B.h_in + up.o_wgs);
+    for (uint32_t k = 0; k < F; k++) {
+        for (uint32_t t = 0; t < frames[k].ntiles; t++) tf[frames[k].tile0 + t] = k;
+        for (uint32_t g = 0; g < frames[k].nwgs; g++) wf[frames[k].wg0 + g] = k;
+    }
+    for (uint32_t k = 0; k < F; k++) // (the bytes behind a stream's last word are never read: no need to clear them)
+        memcpy(B.h_in + up.o_streams + (size_t)pf[k].word0 * 4, io.streams[pf[k].index], pf[k].len);
+    rc = B.ws.begin(ctx, ctx->stream, F);
+    if (rc) return rc;
+    BT_STOP(0);
+    BT_START();
+    size_t work_held = B.ws.work_bytes;
+    if (const char *e = test_hook("TIC_DBATCH_WORK_CAP")) work_held = (size_t)atoll(e) < work_held ? (size_t)atoll(e) : work_held; // (tests: a launcher that refuses)
+    ctx->last_dbatch_range = c.range_bits;
+    ctx->last_dbatch_work_used = dec_work_carve_bytes(F, c.ranges, c.blocks, c.range_bits);
+    ctx->last_dbatch_work_held = work_held;
+    HIPCHK(ctx, hipMemcpyAsync(B.d_in, B.h_in, up.up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const hipError_t le = entropy_decode_idct_gpu_batch(B.d_in + up.o_streams, (const DecFrame *)(B.d_in + up.o_frames), (const uint32_t *)(B.d_in + up.o_tiles),
+                                                        (const uint32_t *)(B.d_in + up.o_wgs), F, tiles, wgs, c.ranges, c.blocks, c.small_win, ctx->d_dec_luts, B.ws.work, work_held,
+                                                        B.ws.desc, B.ws.desc_words, B.ws.epoch, B.ws.d_status, c.range_bits, ctx->stream);
+    if (le == hipErrorInvalidValue) {
+        (void)hipGetLastError();
+        *refused = true;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return TIC_OK;
+    }
+    HIPCHK(ctx, le);
+    BT_STOP(1);
+    return TIC_OK;
+}
+
+// The pixels come down: one copy into the caller's memory where the frames are dense and follow each other there (*direct), else one copy
+// into pinned memory (dbatch_settle hands it out).
+// (the direct copy is `total` bytes long, the device buffer's padding between two frames included: it may only cover bytes the caller gave away -
+//  a frame of a whole number of 256 B has none behind it, elsewhere caps[] must reach to the next frame; an arena of frames at
+//  256-byte aligned distances with caps[i] = h * w takes the pinned route, and the bytes between its frames stay the caller's)
+static int dbatch_download(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame *pf, const DecPlanChunk &c, bool *direct) {
+    tic_ctx::DecBatch &B = ctx->dbat;
+    const size_t F = (size_t)c.count;
+    BT_START();
+    bool dense = true;
+    for (size_t k = 0; k < F && dense; k++) dense = pf[k].pitch == (size_t)pf[k].w;
+    dense = dense && frames_are_one_arena(F, [&](size_t k) {
+                return ArenaFrame{io.outs[pf[k].index], pf[k].pix_off, (size_t)pf[k].h * (size_t)pf[k].w, io.caps[pf[k].index]};
+            });
+    *direct = false;
+    if (dense && ctx->auto_register) {
+        uint8_t *const out0 = io.outs[pf[0].index];
+        const size_t total = pf[F - 1].pix_off + (size_t)pf[F - 1].h * (size_t)pf[F - 1].w;
+        bool pinned = host_pointer_is_pinned(out0) && host_pointer_is_pinned(out0 + total - 1);
+        void *reg = nullptr;
+        if (!pinned && total >= (256u << 10)) pinned = (reg = pin_range(out0, total)) != nullptr;
+        if (pinned) {
+            hipError_t e = hipMemcpyAsync(out0, B.d_pix, total, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            *direct = e == hipSuccess;
+            if (!*direct) (void)hipGetLastError();
+        }
+        if (reg && hipHostUnregister(reg) != hipSuccess) (void)hipGetLastError();
+    }
+    if (!*direct) {
+        const int rc = grow_pinned(ctx, B.h_pix, B.hpix_cap, c.pix_bytes, c.pix_bytes + c.pix_bytes / 4);
+        if (rc) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(B.h_pix, B.d_pix, c.pix_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    BT_STOP(2);
+    ctx->last_dbatch_chunks++;
+    ctx->last_dbatch_direct += *direct ? (int)F : 0;
+    return TIC_OK;
+}
+
+// What the kernels report, frame by frame (dec_status_complete): a frame that is complete counts, any other goes to `later`; then the complete
+// ones leave the pinned buffer on a few threads, unless the download was direct.
+static void dbatch_settle(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame *pf, const DecPlanChunk &c, bool direct, std::vector<int> *later) {
+    tic_ctx::DecBatch &B = ctx->dbat;
+    const int F = c.count;
+    std::vector<char> good((size_t)F);
+    for (int k = 0; k < F; k++) {
+        good[(size_t)k] = dec_status_complete(B.ws.h_status[k], io.streams[pf[k].index], pf[k].nblk);
+        if (good[(size_t)k]) ctx->last_dbatch_frames++;
+        else later->push_back(pf[k].index);
+    }
+    BT_START();
+    if (!direct) {
+        const int T = c.pix_bytes < (2u << 20) || F < 2 ? 1 : (F < 8 ? F : 8);
+        run_strided(F, T, [ctx]() { bind_pipeline_thread(ctx); }, [&](int k) {
+            const DecPlanFrame &f = pf[k];
+            if (good[(size_t)k]) copy_rows(io.outs[f.index], (size_t)f.w, B.h_pix + f.pix_off, (ptrdiff_t)f.pitch, f.h, f.w);
+        });
+    }
+    BT_STOP(4);
+}
+
 // decompress() of MANY streams at once (the mirror of tic_compress_batch; the reference's benchmark loop, tests/benchmark.py:12-23, decodes
 // 49 streams of 512 x 512 per quality one call after the other: 94-105 us each, launch and copy latency).  The streams of a chunk are packed
 // into one pinned buffer behind their descriptors and go up in ONE copy; ONE measure launch and ONE fused launch decode all of them (the
@@ -3346,9 +3490,10 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
     ctx->last_dbatch_work_used = ctx->last_dbatch_work_held = 0;
     ctx->bt = BatchTrace(); // (tic_last_batch_phases: [0] packing the upload buffer, [1] enqueue, [2] wait + download, [4] hand-out, [5] single-frame calls)
     if (n == 0) return TIC_OK;
-    struct Fr { int h, w, q; size_t nblk; bool batch; };
-    std::vector<Fr> fr((size_t)n);
-    for (int i = 0; i < n; i++) { // the checks of tic_decompress, for every frame, before any work
+    // ---- the checks of tic_decompress, for every frame, before any work
+    std::vector<DecPlanIn> in((size_t)n);
+    std::vector<int> later; // frames for the single-frame call
+    for (int i = 0; i < n; i++) {
         StreamHead sh;
         const int rc = check_header(ctx, streams[i], lens[i], &sh, i);
         if (rc) return rc;
@@ -3356,197 +3501,43 @@ int tic_decompress_batch(tic_ctx *ctx, const uint8_t *const *streams, const size
         if (nb && (!outs[i] || (size_t)sh.h * (size_t)sh.w > caps[i])) return set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small", i);
         if (hs) hs[i] = sh.h;
         if (ws) ws[i] = sh.w;
-        fr[(size_t)i] = {sh.h, sh.w, sh.quality, nb,
+        in[(size_t)i] = {sh.h, sh.w, sh.quality, lens[i],
                          nb != 0 && sh.scaled_exp < 0 && device_decoder_takes(nb, lens[i]) && !test_hook("TIC_DECODE_HOST") && !test_hook("TIC_DECODE_SERIAL")};
+        if (nb && !in[(size_t)i].takes) later.push_back(i);
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_dec_tables(ctx);
+    const int rc = ensure_dec_tables(ctx);
     if (rc) return rc;
-    tic_ctx::DecBatch &B = ctx->dbat;
-    // chunks: frames in order, while the chunk's streams, pixels and frame count stay inside the limits (one 512 x 512 benchmark set - 49
-    // frames, 12.8 MB of pixels - is one chunk; sixteen 4096^2 frames are one)
-    constexpr size_t kMaxIn = 96u << 20, kMaxPix = 288u << 20;
-    constexpr int kMaxFrames = 1024;
+    // ---- the plan: chunks of frames in order, inside the limits (one 512 x 512 benchmark set - 49 frames, 12.8 MB of pixels - is one chunk;
+    // sixteen 4096^2 frames are one)
+    DecPlanLimits lim = {(size_t)96 << 20, (size_t)288 << 20, 1024};
+    if (const char *e = test_hook("TIC_DBATCH_CHUNK")) lim.frames = atoi(e) >= 1 && atoi(e) <= 1024 ? atoi(e) : lim.frames; // (tests: several chunks)
+    const DecPlan plan = plan_decode_batch(in.data(), n, lim);
+    // ---- the chunks, one after the other
+    const DecBatchIO io = {streams, lens, outs, caps};
     int result = TIC_OK;
     std::string first_err; // (the text of an error inside a chunk: the single-frame calls behind it write their own)
     auto fail = [&](int rc) { if (result == TIC_OK) result = rc; };
-    std::vector<int> later; // frames for the single-frame call
-    for (int i = 0; i < n; i++)
-        if (!fr[(size_t)i].batch && fr[(size_t)i].nblk) later.push_back(i);
-    int i0 = 0;
-    while (i0 < n) {
-        // ---- the chunk's frames and the layout of its buffers
-        std::vector<int> ids;
-        size_t in_bytes = 0, pix_bytes = 0, ranges288 = 0, blocks = 0;
-        int range_bits = 0;
-        bool small_win = true;
-        int i1 = i0;
-        for (; i1 < n; i1++) {
-            const Fr &f = fr[(size_t)i1];
-            if (!f.batch) continue;
-            const size_t pitch = (size_t)(f.w % 8 == 0 ? f.w : (f.w + 7) / 8 * 8);
-            const size_t sb = align_up(lens[i1], 16) + 16, pb = align_up(pitch * (size_t)f.h, 256);
-            if (!ids.empty() && (in_bytes + sb > kMaxIn || pix_bytes + pb > kMaxPix || (int)ids.size() >= kMaxFrames)) break;
-            ids.push_back(i1);
-            in_bytes += sb, pix_bytes += pb, blocks += f.nblk, ranges288 += lens[i1] * 8 / 288 + 2;
-            const int rb = decode_range_bits(lens[i1], f.nblk);
-            range_bits = rb > range_bits ? rb : range_bits;
-            small_win = small_win && lens[i1] * 8 / f.nblk <= 240;
+    for (const DecPlanChunk &c : plan.chunks) {
+        const DecPlanFrame *pf = &plan.frames[(size_t)c.first];
+        bool refused = false, direct = false;
+        int crc = dbatch_enqueue(ctx, io, pf, c, &refused);
+        if (crc == TIC_OK && !refused) crc = dbatch_download(ctx, io, pf, c, &direct);
+        if (crc == TIC_OK && !refused) {
+            dbatch_settle(ctx, io, pf, c, direct, &later);
+            continue;
         }
-        i0 = i1;
-        if (ids.empty()) break;
-        const uint32_t F = (uint32_t)ids.size();
-        bool refused = false; // the launcher's host-side checks said no: nothing was launched
-        // (a function of its own: whatever ends it early - a failed allocation, copy or launch - comes back here, and the frames still go somewhere)
-        const int chunk_rc = [&]() -> int {
-        std::vector<DecFrame> frames(F);
-        std::vector<size_t> pix_off(F), pitches(F);
-        uint32_t tiles = 0, wgs = 0, ranges = 0;
-        size_t blk = 0, words = 0, poff = 0;
-        for (uint32_t k = 0; k < F; k++) {
-            const int i = ids[k];
-            const Fr &f = fr[(size_t)i];
-            DecFrame &d = frames[k];
-            const size_t len = lens[i];
-            d.word0 = (uint32_t)words;
-            d.nwords = (uint32_t)((len + 3) / 4);
-            d.last_mask = (len & 3) ? 0xffffffffu << (8u * (4u - (uint32_t)(len & 3))) : 0xffffffffu;
-            d.stream_bits = d.fast_end = (uint32_t)(len * 8);
-            d.nranges = entropy_decode_batch_ranges(len, range_bits);
-            d.range0 = ranges;
-            d.tile0 = tiles;
-            d.ntiles = entropy_decode_batch_tiles(d.nranges, range_bits);
-            d.blk0 = (uint32_t)blk;
-            d.nblocks = (uint32_t)f.nblk;
-            d.wg0 = wgs;
-            d.nwgs = entropy_decode_batch_wgs(f.nblk);
-            d.pad_ = 0;
-            pitches[k] = (size_t)(f.w % 8 == 0 ? f.w : (f.w + 7) / 8 * 8);
-            pix_off[k] = poff;
-            d.idct = dec_idct_args(ctx, f.h, f.w, f.q, -1, nullptr /* set below, when the pixel buffer exists */, (long)pitches[k], streams[i]);
-            words += (align_up(len, 16) + 16) / 4;
-            ranges += d.nranges, tiles += d.ntiles, wgs += d.nwgs, blk += f.nblk;
-            poff += align_up(pitches[k] * (size_t)f.h, 256);
-        }
-        // one upload: descriptors, the frame of every measure wave, the frame of every fused workgroup, the streams
-        const size_t o_frames = 0, o_tiles = align_up(o_frames + F * sizeof(DecFrame), 256), o_wgs = align_up(o_tiles + (size_t)tiles * 4, 256),
-                     o_streams = align_up(o_wgs + (size_t)wgs * 4, 256), up_bytes = o_streams + words * 4;
-        if (up_bytes > B.in_cap) { // the pinned upload buffer and its device mirror grow together
-            size_t hcap = B.in_cap, dcap = B.in_cap;
-            B.in_cap = 0;
-            rc = grow_pinned(ctx, B.h_in, hcap, up_bytes, up_bytes + up_bytes / 4);
-            if (rc) return rc;
-            rc = grow_dev(ctx, B.d_in, dcap, up_bytes, up_bytes + up_bytes / 4);
-            if (rc) return rc;
-            B.in_cap = dcap;
-        }
-        rc = grow_dev(ctx, B.d_pix, B.pix_cap, poff, poff + poff / 4);
-        if (rc) return rc;
-        const size_t wb = entropy_decode_batch_work_bytes(ranges288, blocks, F);
-        rc = B.ws.grow(ctx, wb, wb + wb / 4, 4 * (size_t)((tiles > wgs ? tiles : wgs) + 2), F, F < 256 ? 256 : 2 * (size_t)F);
-        if (rc) return rc;
-        BT_START();
-        for (uint32_t k = 0; k < F; k++) frames[k].idct.out = B.d_pix + pix_off[k];
-        memcpy(B.h_in + o_frames, frames.data(), F * sizeof(DecFrame));
-        {
-            uint32_t *tf = (uint32_t *)(B.h_in + o_tiles), *wf = (uint32_t *)(B.h_in + o_wgs);
-            for (uint32_t k = 0; k < F; k++) {
-                for (uint32_t t = 0; t < frames[k].ntiles; t++) tf[frames[k].tile0 + t] = k;
-                for (uint32_t g = 0; g < frames[k].nwgs; g++) wf[frames[k].wg0 + g] = k;
-            }
-            for (uint32_t k = 0; k < F; k++) { // (the bytes behind a stream's last word are never read: no need to clear them)
-                memcpy(B.h_in + o_streams + (size_t)frames[k].word0 * 4, streams[ids[k]], lens[ids[k]]);
-            }
-        }
-        rc = B.ws.begin(ctx, ctx->stream, F);
-        if (rc) return rc;
-        BT_STOP(0);
-        BT_START();
-        size_t work_held = B.ws.work_bytes;
-        if (const char *e = test_hook("TIC_DBATCH_WORK_CAP")) work_held = (size_t)atoll(e) < work_held ? (size_t)atoll(e) : work_held; // (tests: a launcher that refuses)
-        ctx->last_dbatch_range = range_bits;
-        ctx->last_dbatch_work_used = dec_work_carve_bytes(F, ranges, blk, range_bits);
-        ctx->last_dbatch_work_held = work_held;
-        HIPCHK(ctx, hipMemcpyAsync(B.d_in, B.h_in, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-        const hipError_t le = entropy_decode_idct_gpu_batch(B.d_in + o_streams, (const DecFrame *)(B.d_in + o_frames), (const uint32_t *)(B.d_in + o_tiles), (const uint32_t *)(B.d_in + o_wgs), F,
-                                                            tiles, wgs, ranges, blk, small_win, ctx->d_dec_luts, B.ws.work, work_held, B.ws.desc, B.ws.desc_words, B.ws.epoch, B.ws.d_status,
-                                                            range_bits, ctx->stream);
-        if (le == hipErrorInvalidValue) { // refused: every check of the launcher that says so comes before its first launch
-            (void)hipGetLastError();
-            refused = true;
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (the upload still reads the pinned buffer the next chunk is packed into)
-            return TIC_OK;
-        }
-        HIPCHK(ctx, le);
-        BT_STOP(1);
-        BT_START();
-        // ---- the pixels come down: one copy into the caller's memory where the frames are dense and follow each other there, else one copy
-        // into pinned memory and a few threads
-        // (the copy is `total` bytes long, the device buffer's padding between two frames included: it may only cover bytes the caller gave away -
-        //  a frame of a whole number of 256 B has none behind it, elsewhere caps[] must reach to the next frame; an arena of frames at
-        //  256-byte aligned distances with caps[i] = h * w takes the pinned route, and the bytes between its frames stay the caller's)
-        bool dense = true;
-        for (uint32_t k = 0; k < F && dense; k++) dense = pitches[k] == (size_t)fr[(size_t)ids[k]].w;
-        dense = dense && frames_are_one_arena(F, [&](size_t k) {
-                    const Fr &f = fr[(size_t)ids[k]];
-                    return ArenaFrame{outs[ids[k]], pix_off[k], (size_t)f.h * (size_t)f.w, caps[ids[k]]};
-                });
-        bool direct = false;
-        if (dense && ctx->auto_register) {
-            const size_t total = pix_off[F - 1] + (size_t)fr[(size_t)ids[F - 1]].h * (size_t)fr[(size_t)ids[F - 1]].w;
-            bool pinned = host_pointer_is_pinned(outs[ids[0]]) && host_pointer_is_pinned(outs[ids[0]] + total - 1);
-            void *reg = nullptr;
-            if (!pinned && total >= (256u << 10)) pinned = (reg = pin_range(outs[ids[0]], total)) != nullptr;
-            if (pinned) {
-                hipError_t e = hipMemcpyAsync(outs[ids[0]], B.d_pix, total, hipMemcpyDeviceToHost, ctx->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                direct = e == hipSuccess;
-                if (!direct) (void)hipGetLastError();
-            }
-            if (reg && hipHostUnregister(reg) != hipSuccess) (void)hipGetLastError();
-        }
-        if (!direct) {
-            rc = grow_pinned(ctx, B.h_pix, B.hpix_cap, poff, poff + poff / 4);
-            if (rc) return rc;
-            HIPCHK(ctx, hipMemcpyAsync(B.h_pix, B.d_pix, poff, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        BT_STOP(2);
-        ctx->last_dbatch_chunks++;
-        ctx->last_dbatch_direct += direct ? (int)F : 0;
-        // ---- what the kernels report, frame by frame: the header they saw, nothing flagged, every block produced
-        std::vector<char> good(F);
-        for (uint32_t k = 0; k < F; k++) {
-            const DecStatus &st = B.ws.h_status[k];
-            good[k] = memcmp(st.head, streams[ids[k]], 16) == 0 && st.giveup == 0 && st.m == (unsigned long long)frames[k].nblocks;
-            if (good[k]) ctx->last_dbatch_frames++;
-            else later.push_back(ids[k]);
-        }
-        BT_START();
-        if (!direct) {
-            const int T = poff < (2u << 20) || F < 2 ? 1 : (F < 8 ? (int)F : 8);
-            run_strided((int)F, T, [ctx]() { bind_pipeline_thread(ctx); }, [&](int k) {
-                if (!good[(size_t)k]) return;
-                const Fr &f = fr[(size_t)ids[(size_t)k]];
-                const uint8_t *src = B.h_pix + pix_off[(size_t)k];
-                if (pitches[(size_t)k] == (size_t)f.w) memcpy(outs[ids[(size_t)k]], src, (size_t)f.h * (size_t)f.w);
-                else for (int y = 0; y < f.h; y++) memcpy(outs[ids[(size_t)k]] + (size_t)y * (size_t)f.w, src + (size_t)y * pitches[(size_t)k], (size_t)f.w);
-            });
-        }
-        BT_STOP(4);
-        return TIC_OK;
-        }();
-        if (chunk_rc != TIC_OK || refused) { // (every early way out lies in front of the status words: none of the chunk's frames is counted or queued yet)
-            later.insert(later.end(), ids.begin(), ids.end());
-            if (chunk_rc != TIC_OK) { // the first error stands (its text too: kept below); no further chunk is tried, what they would have held goes one by one
-                fail(chunk_rc);
-                first_err = ctx->err;
-                for (; i0 < n; i0++)
-                    if (fr[(size_t)i0].batch) later.push_back(i0);
-            }
-        }
+        // refused, or ended early by a failed allocation, copy or launch (every such way out lies in front of the status words: none of the
+        // chunk's frames is counted or queued yet): its frames go one by one.  An error is the first and stands (its text too: kept below); no
+        // further chunk is tried, what they would have held goes one by one as well
+        const size_t last = crc != TIC_OK ? plan.frames.size() : (size_t)(c.first + c.count);
+        for (size_t k = (size_t)c.first; k < last; k++) later.push_back(plan.frames[k].index);
+        if (crc == TIC_OK) continue;
+        fail(crc);
+        first_err = ctx->err;
+        break;
     }
-    // frames the batch did not take, or did not finish: the single-frame call, with everything it knows (second run, host decoders)
+    // ---- frames the batch did not take, or did not finish: the single-frame call, with everything it knows (second run, host decoders)
     std::sort(later.begin(), later.end());
     for (int i : later) {
         const int rc = tic_decompress(ctx, streams[i], lens[i], outs[i], caps[i]);
@@ -3738,7 +3729,7 @@ int tic_decompress_async_result(tic_ctx *ctx, long long ticket, int wait, int *h
         }
         DecStatus st;
         memcpy(&st, sl.ws.h_status, sizeof st); // (host-mapped: the slot's stream has drained)
-        if (memcmp(st.head, sl.head, 16) == 0 && st.giveup == 0 && st.m == sl.n) {
+        if (dec_status_complete(st, sl.head, sl.n)) {
             ctx->last_decode_path = 1;
             ctx->last_decode_giveup = 0;
             ctx->last_decode_guess = 1;

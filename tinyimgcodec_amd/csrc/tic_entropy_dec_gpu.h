@@ -2,7 +2,9 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-// TIC_DEC_WORKSPACE_ONLY: only the workspace arithmetic below, for a host compiler without the HIP headers (tests/native/decws_selftest.cpp)
+#include <string.h>
+// TIC_DEC_WORKSPACE_ONLY: the workspace arithmetic and the plain structs below, without the launchers - for a host compiler without the HIP
+// headers (tests/native/decws_selftest.cpp, decplan_selftest.cpp)
 #ifndef TIC_DEC_WORKSPACE_ONLY
 #include <hip/hip_runtime.h>
 #define TIC_DEC_HD __host__ __device__
@@ -59,8 +61,6 @@ inline size_t dec_work_provision_bytes(size_t nframes, size_t total_ranges_288, 
 }
 inline size_t dec_ranges_288(size_t stream_bytes) { return stream_bytes * 8 / kDecRangeMin + 2; } // a frame's share of total_ranges_288
 
-#ifndef TIC_DEC_WORKSPACE_ONLY
-
 // The host decoder's look-up tables (tic_entropy.cpp EncTables::Dec): the next 11 / 16 stream bits -> (code length << 8) | symbol,
 // 0 when no codeword (of at most 11 bits, for the short tables) is a prefix of them.
 struct DecLutsDev {
@@ -91,6 +91,10 @@ struct DecStatus {
     unsigned long long pos_out; // first stream bit behind block m - 1
     uint32_t head[4];           // the stream's first 16 bytes as the kernels saw them (a caller that launched on a GUESS of the header compares)
 };
+// A run behind which nothing is left to do: the kernels saw the header the caller decoded for, flagged nothing and produced every block.
+inline bool dec_status_complete(const DecStatus &st, const void *head16, size_t nblocks) {
+    return memcmp(st.head, head16, 16) == 0 && st.giveup == 0 && st.m == (unsigned long long)nblocks;
+}
 
 // Where the pixels go and how the coefficients become pixels (the inverse stage of decode(), codec.py:46-70): the arguments of
 // idct_kernel, minus the coefficient array - the fused kernel never writes one.
@@ -122,6 +126,8 @@ struct DecFrame {
     DecIdctArgs idct;                   // where its pixels go, its geometry, constants and header
 };
 
+#ifndef TIC_DEC_WORKSPACE_ONLY
+
 size_t entropy_decode_gpu_work_bytes(size_t stream_bytes, size_t nblocks);
 // d_stream_words: the whole stream (header included) in device memory, 4-byte aligned; the 4-byte word that holds its last byte is
 // read whole (the bytes behind the stream's end are masked off), nothing behind that word is touched.  range_bits: stream bits per lane, a value entropy_decode_gpu_range_ok() accepts - an odd
@@ -144,10 +150,8 @@ hipError_t entropy_decode_idct_gpu(const void *d_stream_words, size_t stream_byt
 // every wave of the measure grid and of every workgroup of the fused grid; d_status: nframes entries, zeroed by the caller; the sums'
 // look-back words and the epoch as above; small_win: every stream has at most 240 bits per block on average.  A frame whose status comes back
 // with giveup != 0 or m != its block count is the caller's to decode again on its own.
-size_t entropy_decode_batch_work_bytes(size_t total_ranges_288, size_t total_blocks, size_t nframes);
 uint32_t entropy_decode_batch_tiles(uint32_t nranges, int range_bits);
 uint32_t entropy_decode_batch_wgs(size_t nblocks);
-uint32_t entropy_decode_batch_ranges(size_t stream_bytes, int range_bits);
 hipError_t entropy_decode_idct_gpu_batch(const void *d_words_all, const DecFrame *d_frames, const uint32_t *d_tile_frame, const uint32_t *d_wg_frame, uint32_t nframes,
                                          uint32_t total_tiles, uint32_t total_wgs, uint32_t total_ranges, size_t total_blocks, bool small_win, const DecLutsDev *d_luts, void *d_work,
                                          size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, DecStatus *d_status, int range_bits, hipStream_t stream,

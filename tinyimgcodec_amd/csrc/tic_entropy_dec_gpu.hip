@@ -950,12 +950,8 @@ hipError_t entropy_decode_idct_gpu(const void *d_stream_words, size_t stream_byt
 }
 
 
-size_t entropy_decode_batch_work_bytes(size_t total_ranges_288, size_t total_blocks, size_t nframes) {
-    return dec_work_provision_bytes(nframes, total_ranges_288, total_blocks);
-}
 uint32_t entropy_decode_batch_tiles(uint32_t nranges, int range_bits) { const uint32_t owned = 64u - dec_shadows(range_bits); return (nranges + owned - 1u) / owned; }
 uint32_t entropy_decode_batch_wgs(size_t nblocks) { return (uint32_t)((nblocks + kDecodeWG - 1) / kDecodeWG); }
-uint32_t entropy_decode_batch_ranges(size_t stream_bytes, int range_bits) { return (uint32_t)dec_ranges_of(stream_bytes * 8, range_bits); }
 
 hipError_t entropy_decode_idct_gpu_batch(const void *d_words_all, const DecFrame *d_frames, const uint32_t *d_tile_frame, const uint32_t *d_wg_frame, uint32_t nframes,
                                          uint32_t total_tiles, uint32_t total_wgs, uint32_t total_ranges, size_t total_blocks, bool small_win, const DecLutsDev *d_luts, void *d_work,
