@@ -292,13 +292,26 @@ def lane_limit_blocks(L, over_at):
 
 
 def dc_edges_blocks(sign, ac63):
+    """Differences of +-2047 at block 0 and at DC_EDGES, in turn; every other difference is seeded inside +-5 and keeps the running DC
+    next to a level: between two edges 0 or +-2047 as the edges leave it, and from block 512 on a ramp from 0 to -+2047, so that the
+    last edge brings the DC home.  (A decoder's pixels show a DC only near 0 - a block at +-2047 is clipped under every header - and a
+    wrong DC difference moves every block behind it: with blocks near 0 behind every block, the last one included, any such error
+    shows; tests/test_decoder_streams_cpu.py test_dc_visibility.)"""
     rng = np.random.default_rng(505)
-    d = rng.integers(-5, 6, BASE_N)
-    s = sign
-    d[0] = s * 2047
-    for b in DC_EDGES:
-        s = -s
-        d[b] = s * 2047
+    edges = (0,) + DC_EDGES
+    last, ramp_from = DC_EDGES[-1], DC_EDGES[-2]
+    d = np.zeros(BASE_N, np.int64)
+    s, dc, level = -sign, 0, 0
+    for b in range(BASE_N):
+        if b in edges:
+            s = -s
+            d[b] = s * 2047
+            level += s * 2047
+        else:
+            if b > ramp_from:  # (the level in front of the last edge: the far side of it)
+                level = s * 2047 * (b - ramp_from) // (last - 1 - ramp_from)
+            d[b] = int(np.clip(level - dc + int(rng.integers(-3, 4)), -5, 5))
+        dc += int(d[b])
     zz = np.zeros((BASE_N, 64), np.int64)
     zz[:, 0] = np.cumsum(d)
     if ac63:

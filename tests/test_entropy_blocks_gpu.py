@@ -10,7 +10,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import decoder_streams as DS
 import entropy_blocks as EB
+import inverse_edges as IE
 
 import tinyimgcodec_amd as T
 from tinyimgcodec_amd import _native as N
@@ -38,6 +40,17 @@ def frames(fx, lengths):
     for name, fr in out.items():
         assert EB.coeff_sha(fr["zz"]) == fx[name]["coeffs_sha256"], name
     return out
+
+
+@pytest.fixture(scope="module")
+def decoded():
+    """tests/golden/decoder_streams.json: what the reference decodes the frames to."""
+    return DS.load_fixture()
+
+
+@pytest.fixture(scope="module")
+def decoder_frames(lengths):
+    return DS.build_frames(lengths)
 
 
 def names(fx, family):
@@ -180,10 +193,12 @@ def test_size_kernel(dev, fx, frames, family):
 
 
 @pytest.mark.parametrize("family", EB.FAMILIES)
-def test_adaptive_kernels(dev, fx, frames, family):
+def test_adaptive_kernels(dev, fx, frames, decoded, family):
     """T.entropy_encode_adaptive: the stream the reference wrote with the frame's own tables (the three adaptive kernels; the table itself
     is built on the host), or its exception - OverflowError for a category 16, which the table's 4-bit field cannot hold.  The library's
-    decoder reads every stream back without complaint."""
+    decoder reads every stream back to the pixels of the reference's decode() of the frame's dictionary (its own decompress() misreads
+    the adaptive flag): as recorded with the default-table stream of the same frame and quality where tests/golden/decoder_streams.json
+    has one, else the digest recorded there for this purpose."""
     for name in names(fx, family):
         e, fr = fx[name], frames[name]
         if "raises" in e["adaptive"]:
@@ -195,3 +210,22 @@ def test_adaptive_kernels(dev, fx, frames, family):
         assert (len(got), EB.sha(got)) == (e["adaptive"]["bytes"], e["adaptive"]["sha256"]), (name, len(got), e["adaptive"]["bytes"])
         px = T.decompress_adaptive(got, ctx=dev.ctx)
         assert px.shape == (fr["h"], fr["w"]) and px.dtype == np.uint8, name
+        if name in decoded["frames"]:
+            want = decoded["frames"][name]["streams"]["q%d" % fr["quality"]]["pixels_sha256"]
+        else:
+            want = decoded["adaptive_pixels"][name]
+        assert IE.px_sha(px) == want, (name, "the adaptive decode kernels' pixels are not the reference's")
+
+
+@pytest.mark.parametrize("name", [n for n, e in DS.load_fixture()["frames"].items() if e["family"] in DS.NEW_FAMILIES and not DS.is_twin(n)])
+def test_adaptive_kernels_on_the_decoder_frames(dev, decoded, decoder_frames, oracle, name):
+    """The frames built for the device decoder (tests/decoder_streams.py: every fused pair, every long codeword, spikes, full ranges, the
+    int16 boundary of the DC) with their own tables: entropy_encode_adaptive -> decompress_adaptive gives the pixels the reference
+    decoded the default-table stream of the same coefficients and quality to."""
+    fr = decoder_frames[name]
+    q = max(v[1] for v in fr["variants"] if not v[0])
+    got = T.entropy_encode_adaptive(fr["zz"], fr["h"], fr["w"], q, ctx=dev.ctx)
+    px = T.decompress_adaptive(got, ctx=dev.ctx)
+    if px.shape != (fr["h"], fr["w"]) or IE.px_sha(px) != decoded["frames"][name]["streams"]["q%d" % q]["pixels_sha256"]:
+        want = oracle.decompress(DS.with_header(DS.payload_stream(oracle, fr), fr, (0, q)))  # (diagnosis only: the same coefficients)
+        pytest.fail("%s q%d: %s" % (name, q, DS.first_difference(px, want)))
