@@ -446,6 +446,25 @@ int tic_compress_adaptive(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrd
  * of tic_entropy_encode, on the GPU. */
 int tic_entropy_encode_adaptive(tic_ctx *ctx, const int16_t *coeffs_zz, int h, int w, int quality, uint8_t *out, size_t cap,
                                 size_t *out_len);
+/* Adaptive streams for a batch of frames of any sizes, a quality each, in one call: outs[i] receives what
+ * tic_compress_adaptive(images[i], hs[i], ws[i], row_strides[i], qualities[i]) writes, byte for byte.  The frames go through the mixed
+ * batch's plan and pipeline (tic_compress_batch_v) in chunks of up to 64: per chunk one statistics launch, one read-back of the chunk's
+ * statistics, the tables on the host, one upload, one launch each of the three packing kernels.  A frame larger than a chunk is coded
+ * by tic_compress_adaptive behind the batch.
+ * Every argument is checked before any work ("frame %d: ..." in tic_last_error): TIC_E_ARG for null arrays or pointers, bad geometry,
+ * or a frame without blocks (the reference raises IndexError there), TIC_E_QUALITY for a quality outside 1..99.
+ * A frame whose stream is longer than caps[i] is not packed and nothing is written to outs[i]; out_lens[i] receives the size needed,
+ * every other frame is coded as usual, and the call returns TIC_E_SPACE at its end: out_lens[i] > caps[i] marks exactly the unwritten
+ * frames.  TIC_E_RANGE (naming the frame) as tic_compress_adaptive. */
+int tic_compress_batch_adaptive_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws,
+                                  const ptrdiff_t *row_strides, const int *qualities, uint8_t *const *outs, const size_t *caps,
+                                  size_t *out_lens);
+/* The coefficient-domain twin: coeffs[i] = int16 [N_i][64] zig-zag coefficients with absolute DC (tic_entropy_encode_adaptive's layout);
+ * the same chunks and kernels without upload of pixels or transform. */
+int tic_entropy_encode_adaptive_batch(tic_ctx *ctx, const int16_t *const *coeffs, int n, const int *hs, const int *ws,
+                                      const int *qualities, uint8_t *const *outs, const size_t *caps, size_t *out_lens);
+/* What the last of these two calls did: frames coded in chunks, frames coded one by one behind them, chunks (null pointers are skipped). */
+int tic_last_compress_batch_adaptive(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks);
 /* The table alone, on the host (calc_huffman_table huffman.py:101-108 + write_huffman_table codec.py:73-84): per symbol its count and
  * first-occurrence key (DC: index = size category, key = block; AC: index = (run << 4) | size, key = block * 64 + ordinal of the symbol
  * in the block's run-length list) -> per symbol codeword (right-aligned) and length (0 for symbols that do not occur, and for the

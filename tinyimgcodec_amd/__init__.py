@@ -8,9 +8,9 @@ control: rd_points (size and exact round-trip error per quality), roundtrip_psnr
 than a PSNR), roundtrip_sse_scaled and psnr_from_sse.
 """
 from ._native import Context, NativeError, NativeUnavailable
-from .codec import (compress, compress_adaptive, compress_batch, compress_scaled, compress_to_psnr, compress_to_size, compressed_size,
+from .codec import (compress, compress_adaptive, compress_batch, compress_batch_adaptive, compress_scaled, compress_to_psnr, compress_to_size, compressed_size,
                     compressed_sizes, dctq, dctq_scaled, decode, decompress, decompress_adaptive, decompress_batch, encode, entropy_encode,
-                    entropy_encode_adaptive, entropy_encode_scaled, entropy_size, max_sse_for_psnr, parse_header, psnr_from_sse, rd_points,
+                    entropy_encode_adaptive, entropy_encode_adaptive_batch, entropy_encode_scaled, entropy_size, max_sse_for_psnr, parse_header, psnr_from_sse, rd_points,
                     roundtrip_psnr, roundtrip_sse_scaled)
 
 __version__ = "0.1.0"

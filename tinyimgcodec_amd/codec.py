@@ -12,6 +12,8 @@ huffman.py:101-194), under names of their own because compress() keeps raising f
 
     compress_adaptive(image, quality=50) -> bytes   the reference's adaptive stream, byte for byte
     entropy_encode_adaptive(coeffs_zz, height, width, quality) -> bytes   the same from int16 [N, 64] zig-zag coefficients
+    compress_batch_adaptive(images, quality=50) -> [bytes]   compress_adaptive() per frame, any shapes, a quality each, in one call
+    entropy_encode_adaptive_batch(coeffs_list, shapes, qualities) -> [bytes]   the same from coefficients
     decompress_adaptive(data) -> np.ndarray[uint8]  reads such a stream as written
 
 and, for the reference's standalone integer encoder (c/img.c, c/encode.c: 8-bit-constant AAN DCT, reciprocal quantiser with four
@@ -656,6 +658,112 @@ def entropy_encode_adaptive(coeffs_zz, height, width, quality, ctx=None):
     with ctx.lock:
         return _adaptive_encode(ctx, L.tic_entropy_encode_adaptive, (zz.ctypes.data, height, width, q),
                                 L.tic_compress_bound(height, width) + 4096)
+
+
+def _adaptive_batch(ctx, call, frames, caps_l):
+    """call(n, index list, outp, caps, lens) -> rc of one adaptive batch entry point over the listed frames; the landing pool lives on the
+    context.  After TIC_E_SPACE one second call, for exactly the frames the library left unwritten, with the sizes it reported."""
+    n = len(frames)
+    streams = [None] * n
+    todo, caps_l = list(range(n)), list(caps_l)
+    with ctx.lock:
+        for attempt in range(2):
+            m = len(todo)
+            offs = np.concatenate(([0], np.cumsum([(caps_l[i] + 63) // 64 * 64 for i in todo]))).astype(np.int64)
+            pool = getattr(ctx, "_adapt_batch_pool", None)  # (first-touch page faults, as compress_batch's pool)
+            if pool is None or pool.size < offs[-1]:
+                pool = ctx._adapt_batch_pool = np.empty(int(offs[-1]), dtype=np.uint8)
+            base = pool.ctypes.data
+            outp = (C.c_void_p * m)(*[base + int(o) for o in offs[:-1]])
+            caps = (C.c_size_t * m)(*[caps_l[i] for i in todo])
+            lens = (C.c_size_t * m)()
+            rc = call(m, todo, outp, caps, lens)
+            if rc == N.TIC_E_RANGE:  # a category above 15 (int2ba in write_huffman_table, codec.py:73-84), or a code past 64 bits
+                raise OverflowError(N.load().tic_last_error(ctx.handle).decode())
+            if rc != N.TIC_E_SPACE or attempt == 1:
+                ctx.check(rc)
+            short = []
+            for k, i in enumerate(todo):
+                if lens[k] > caps_l[i]:
+                    caps_l[i] = int(lens[k])
+                    short.append(i)
+                else:
+                    streams[i] = pool[int(offs[k]): int(offs[k]) + lens[k]].tobytes()
+            todo = short
+            if not todo:
+                break
+    return streams
+
+
+def _per_frame_qualities(quality, n):
+    per_frame = not isinstance(quality, (int, float, np.integer, np.floating, bool, np.bool_, str, bytes)) and hasattr(quality, "__len__")
+    if not per_frame:
+        return [quality] * n
+    if len(quality) != n:
+        raise ValueError("quality has %d entries for %d frames" % (len(quality), n))
+    return list(quality)
+
+
+def compress_batch_adaptive(images, quality=50, ctx=None):
+    """compress_adaptive() for a list of frames of any shapes in ONE call -> list of bytes (frame order): every stream is what
+    compress_adaptive(image, q) gives, i.e. the reference's compress(image, q, auto_generate_huffman_table=True), byte for byte.
+    `quality`: an int, or a sequence with one entry per frame.  The exceptions are compress_adaptive's, raised for the first offending
+    frame before any GPU work (pixel range, quality, a frame without blocks) or from the call (OverflowError names the frame)."""
+    images = list(images)
+    quals = _per_frame_qualities(quality, len(images))
+    L = N.load()
+    frames, qs = [], []
+    for im, qi in zip(images, quals):
+        img, h, w = _as_u8_image(im)
+        qs.append(_check_quality(qi, packs_header=True))
+        if L.tic_num_blocks(h, w) == 0:
+            raise IndexError("index -1 is out of bounds for axis 0 with size 0")  # calc_huffman_table on an empty symbol list
+        frames.append((img, h, w))
+    if not frames:
+        return []
+    ctx = _ctx(ctx)
+
+    def call(m, idx, outp, caps, lens):
+        inp = (C.c_void_p * m)(*[frames[i][0].ctypes.data for i in idx])
+        hs = (C.c_int * m)(*[frames[i][1] for i in idx])
+        ws = (C.c_int * m)(*[frames[i][2] for i in idx])
+        strides = (C.c_ssize_t * m)(*[frames[i][0].strides[0] for i in idx])
+        qa = (C.c_int * m)(*[qs[i] for i in idx])
+        return L.tic_compress_batch_adaptive_v(ctx.handle, inp, m, hs, ws, strides, qa, outp, caps, lens)
+
+    return _adaptive_batch(ctx, call, frames, [L.tic_compress_bound(f[1], f[2]) + 4096 for f in frames])
+
+
+def entropy_encode_adaptive_batch(coeffs_list, shapes, qualities, ctx=None):
+    """The coefficient-domain twin of compress_batch_adaptive(): coeffs_list[i] = int16 [N_i, 64] zig-zag coefficients (absolute DC) of a
+    frame of shapes[i] = (height, width) -> entropy_encode_adaptive(coeffs_list[i], height, width, qualities[i]) per frame, in one call."""
+    coeffs_list, shapes = list(coeffs_list), [(int(h), int(w)) for h, w in shapes]
+    if len(shapes) != len(coeffs_list):
+        raise ValueError("%d shapes for %d frames" % (len(shapes), len(coeffs_list)))
+    quals = _per_frame_qualities(qualities, len(coeffs_list))
+    L = N.load()
+    frames, qs = [], []
+    for zz, (h, w), qi in zip(coeffs_list, shapes, quals):
+        qs.append(_check_quality(qi, packs_header=True))
+        nb = L.tic_num_blocks(h, w)
+        zz = np.ascontiguousarray(zz, dtype=np.int16)
+        if zz.shape != (nb, 64):
+            raise ValueError("coefficients of shape %r do not match %d blocks of 64" % (zz.shape, nb))
+        if nb == 0:
+            raise IndexError("index -1 is out of bounds for axis 0 with size 0")
+        frames.append((zz, h, w))
+    if not frames:
+        return []
+    ctx = _ctx(ctx)
+
+    def call(m, idx, outp, caps, lens):
+        inp = (C.c_void_p * m)(*[frames[i][0].ctypes.data for i in idx])
+        hs = (C.c_int * m)(*[frames[i][1] for i in idx])
+        ws = (C.c_int * m)(*[frames[i][2] for i in idx])
+        qa = (C.c_int * m)(*[qs[i] for i in idx])
+        return L.tic_entropy_encode_adaptive_batch(ctx.handle, inp, m, hs, ws, qa, outp, caps, lens)
+
+    return _adaptive_batch(ctx, call, frames, [L.tic_compress_bound(f[1], f[2]) + 4096 for f in frames])
 
 
 def decompress_adaptive(data, ctx=None):

@@ -6,29 +6,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "tic_adaptive_frames.h"
+
 namespace tic {
 
-// Symbol bins of the adaptive tables: AC (run << 4) | size at 0..255, DC size category c at kAdaptDcBin + c.
-constexpr int kAdaptDcBin = 256, kAdaptBins = 272;
-// Longest symbol (code + value bits) the packing kernel and the decoder take.
-constexpr int kAdaptMaxSymbolBits = 64;
-// Serialized table bits at most: 2 x 16 count bits, 16 DC entries of 8 + 15 bits, 256 AC entries of 16 + 64 bits.
-constexpr size_t kAdaptMaxTableBytes = (32 + 16 * 23 + 256 * 80 + 7) / 8;
-
-// What the statistics kernel leaves per frame: symbol counts and first-occurrence keys (DC: block index; AC: block * 64 + ordinal of
-// the symbol in the block's run-length list, huffman.py:12-33), and an error word (1: a DC category or AC size above 15, which the
-// reference's write_huffman_table cannot store, codec.py:73-84).
-struct AdaptStats {
-    unsigned long long count[kAdaptBins];
-    unsigned long long first[kAdaptBins]; // ~0: the symbol does not occur
-    unsigned int err;
-};
-
-// The table as the packing kernels use it: codeword (right-aligned, up to 64 bits) and its length per bin.
-struct HuffWide {
-    unsigned long long code[kAdaptBins];
-    unsigned int len[kAdaptBins];
-};
+// (symbol bins, AdaptStats, HuffWide and the records of the descriptor form: tic_adaptive_frames.h, free of HIP)
 
 // HuffmanTree.__init__ / value_to_bitstring_table (huffman.py:137-194) of DC and AC from counts and first-occurrence keys, and
 // write_huffman_table (codec.py:73-84) into `table` (MSB first, zero-padded): TIC_OK, TIC_E_RANGE (a symbol longer than
@@ -101,5 +83,16 @@ size_t adaptive_work_bytes(size_t nblocks);
 hipError_t adaptive_stats(const int16_t *d_zz, size_t nblocks, AdaptStats *d_stats, hipStream_t stream);
 hipError_t adaptive_pack(const int16_t *d_zz, size_t nblocks, const HuffWide *d_tab, void *d_work, uint32_t *d_out,
                          unsigned long long base_bits, unsigned long long out_words, unsigned int *d_err, hipStream_t stream);
+
+// Descriptor form: ONE launch per kernel for the `count` frames of a chunk (at most kEntropyMaxFrames), coefficients back to back in d_zz,
+// `ngroups` workgroups in all (fill_adaptive_table).  d_stats: an AdaptStats per frame; the statistics launch resets them itself.  The
+// packing: frame k uses d_tabs[k], its record's base_bits, out_words and area at d_streams + out_off - zeroed by the caller; its header and
+// table, d_heads + k * kAdaptHeadStride, are copied in here (whole words up to base_bits).  Frames marked `skip` are left alone.
+// d_bbits: a word per block of the chunk, d_gsum: 8 bytes per workgroup.  *d_err = 1 where a frame would write at or past its out_words.
+hipError_t adaptive_stats_v(const int16_t *d_zz, const AdaptFrameTable *d_frames, int count, size_t ngroups, AdaptStats *d_stats,
+                            hipStream_t stream);
+hipError_t adaptive_pack_v(const int16_t *d_zz, const AdaptFrameTable *d_frames, int count, size_t ngroups, const HuffWide *d_tabs,
+                           const uint8_t *d_heads, uint32_t *d_bbits, unsigned long long *d_gsum, void *d_streams, unsigned int *d_err,
+                           hipStream_t stream);
 
 } // namespace tic

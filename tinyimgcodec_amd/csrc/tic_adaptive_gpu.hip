@@ -12,6 +12,11 @@
 //                           big-endian 32-bit words: words the block shares with a neighbour (its first and last) by atomicOr into
 //                           the zeroed stream, the words between by plain stores.
 // The table itself is built on the host between the statistics and the packing (tic_adaptive.cpp): one read-back of 4.4 KB.
+//
+// Every kernel is written once, as the work of ONE workgroup on ONE frame (stats_group, bits_group, scan_groups, write_group), and
+// launched in two forms: for a single frame (the workgroup's index is its group), and in descriptor form for the frames of a chunk
+// (adaptive_*_v_kernel: the workgroup finds its frame in an AdaptFrameTable, tic_adaptive_frames.h, and works on that frame's blocks,
+// statistics, table, sums and stream area with frame-local indices - block 0 of every frame is raw, no read reaches a neighbour).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -21,6 +26,7 @@ namespace tic {
 namespace {
 
 constexpr int kThreads = 256; // blocks per workgroup
+static_assert(kThreads == (int)kAdaptGroupBlocks, "the host plan counts workgroups of this many blocks");
 constexpr int kRow = 33;      // LDS words per block (32 + 1 against bank conflicts)
 
 __device__ __forceinline__ int bit_len(uint32_t a) { return a ? 32 - __clz((int)a) : 0; } // utils.py:9-10
@@ -92,8 +98,8 @@ __device__ __forceinline__ bool block_symbols(const uint32_t *row, int diff, F &
     return ok;
 }
 
-__global__ __launch_bounds__(kThreads) void adaptive_stats_kernel(const int16_t *__restrict__ zz, unsigned long long n,
-                                                                  AdaptStats *__restrict__ st) {
+// Workgroup g of a frame of n blocks at zz: its statistics into st.
+__device__ __forceinline__ void stats_group(const int16_t *__restrict__ zz, unsigned long long n, unsigned long long g, AdaptStats *__restrict__ st) {
     __shared__ uint32_t blk[kThreads * kRow];
     __shared__ uint32_t s_count[kAdaptBins];
     __shared__ unsigned long long s_first[kAdaptBins];
@@ -104,7 +110,7 @@ __global__ __launch_bounds__(kThreads) void adaptive_stats_kernel(const int16_t 
         s_first[i] = ~0ull;
     }
     if (t == 0) s_err = 0u;
-    const unsigned long long b0 = (unsigned long long)blockIdx.x * kThreads, b = b0 + (unsigned long long)t;
+    const unsigned long long b0 = g * kThreads, b = b0 + (unsigned long long)t;
     load_blocks(zz, n, b0, blk);
     __syncthreads();
     if (b < n) {
@@ -123,16 +129,20 @@ __global__ __launch_bounds__(kThreads) void adaptive_stats_kernel(const int16_t 
         }
     if (t == 0 && s_err) atomicOr(&st->err, 1u);
 }
+__global__ __launch_bounds__(kThreads) void adaptive_stats_kernel(const int16_t *__restrict__ zz, unsigned long long n,
+                                                                  AdaptStats *__restrict__ st) {
+    stats_group(zz, n, blockIdx.x, st);
+}
 
-__global__ __launch_bounds__(kThreads) void adaptive_bits_kernel(const int16_t *__restrict__ zz, unsigned long long n,
-                                                                 const HuffWide *__restrict__ tab, uint32_t *__restrict__ bbits,
-                                                                 unsigned long long *__restrict__ gsum) {
+// Workgroup g of a frame: bits per block into bbits (the frame's), their sum into *gsum (the workgroup's).
+__device__ __forceinline__ void bits_group(const int16_t *__restrict__ zz, unsigned long long n, unsigned long long g,
+                                           const HuffWide *__restrict__ tab, uint32_t *__restrict__ bbits, unsigned long long *__restrict__ gsum) {
     __shared__ uint32_t blk[kThreads * kRow];
     __shared__ uint32_t s_len[kAdaptBins];
     __shared__ unsigned long long s_sum[kThreads / 64];
     const int t = (int)threadIdx.x;
     for (int i = t; i < kAdaptBins; i += kThreads) s_len[i] = tab->len[i];
-    const unsigned long long b0 = (unsigned long long)blockIdx.x * kThreads, b = b0 + (unsigned long long)t;
+    const unsigned long long b0 = g * kThreads, b = b0 + (unsigned long long)t;
     load_blocks(zz, n, b0, blk);
     __syncthreads();
     uint32_t bits = 0;
@@ -145,14 +155,19 @@ __global__ __launch_bounds__(kThreads) void adaptive_bits_kernel(const int16_t *
     if ((t & 63) == 0) s_sum[t >> 6] = s;
     __syncthreads();
     if (t == 0) {
-        unsigned long long g = 0;
-        for (int i = 0; i < kThreads / 64; i++) g += s_sum[i];
-        gsum[blockIdx.x] = g;
+        unsigned long long sum = 0;
+        for (int i = 0; i < kThreads / 64; i++) sum += s_sum[i];
+        *gsum = sum;
     }
+}
+__global__ __launch_bounds__(kThreads) void adaptive_bits_kernel(const int16_t *__restrict__ zz, unsigned long long n,
+                                                                 const HuffWide *__restrict__ tab, uint32_t *__restrict__ bbits,
+                                                                 unsigned long long *__restrict__ gsum) {
+    bits_group(zz, n, blockIdx.x, tab, bbits, gsum + blockIdx.x);
 }
 
 // Exclusive prefix of gsum[0, groups) in place, one workgroup.
-__global__ __launch_bounds__(1024) void adaptive_scan_kernel(unsigned long long *__restrict__ gsum, unsigned long long groups) {
+__device__ __forceinline__ void scan_groups(unsigned long long *__restrict__ gsum, unsigned long long groups) {
     __shared__ unsigned long long s[1024];
     __shared__ unsigned long long carry;
     const int t = (int)threadIdx.x;
@@ -175,6 +190,9 @@ __global__ __launch_bounds__(1024) void adaptive_scan_kernel(unsigned long long 
         if (t == 1023) carry = c + s[1023];
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(1024) void adaptive_scan_kernel(unsigned long long *__restrict__ gsum, unsigned long long groups) {
+    scan_groups(gsum, groups);
 }
 
 // MSB-first bits into big-endian 32-bit words from bit `pos` of the stream on.  The first word (shared with what lies before) and the
@@ -220,11 +238,11 @@ struct WordWriter {
     }
 };
 
-__global__ __launch_bounds__(kThreads) void adaptive_write_kernel(const int16_t *__restrict__ zz, unsigned long long n,
-                                                                  const HuffWide *__restrict__ tab, const uint32_t *__restrict__ bbits,
-                                                                  const unsigned long long *__restrict__ goff, uint32_t *__restrict__ out,
-                                                                  unsigned long long base_bits, unsigned long long out_words,
-                                                                  uint32_t *__restrict__ err) {
+// Workgroup g of a frame: its blocks' symbols into the frame's stream `out` behind base_bits + goff (the workgroup's offset) bits.
+__device__ __forceinline__ void write_group(const int16_t *__restrict__ zz, unsigned long long n, unsigned long long g,
+                                            const HuffWide *__restrict__ tab, const uint32_t *__restrict__ bbits, unsigned long long goff,
+                                            uint32_t *__restrict__ out, unsigned long long base_bits, unsigned long long out_words,
+                                            uint32_t *__restrict__ err) {
     __shared__ uint32_t blk[kThreads * kRow];
     __shared__ unsigned long long s_code[kAdaptBins];
     __shared__ uint32_t s_len[kAdaptBins];
@@ -234,7 +252,7 @@ __global__ __launch_bounds__(kThreads) void adaptive_write_kernel(const int16_t 
         s_code[i] = tab->code[i];
         s_len[i] = tab->len[i];
     }
-    const unsigned long long b0 = (unsigned long long)blockIdx.x * kThreads, b = b0 + (unsigned long long)t;
+    const unsigned long long b0 = g * kThreads, b = b0 + (unsigned long long)t;
     load_blocks(zz, n, b0, blk);
     const uint32_t mine = b < n ? bbits[b] : 0u;
     s_scan[t] = mine;
@@ -246,13 +264,79 @@ __global__ __launch_bounds__(kThreads) void adaptive_write_kernel(const int16_t 
         __syncthreads();
     }
     if (b >= n || mine == 0u) return;
-    const unsigned long long pos = base_bits + goff[blockIdx.x] + s_scan[t] - mine;
+    const unsigned long long pos = base_bits + goff + s_scan[t] - mine;
     WordWriter wr{out, pos >> 5, out_words, 0ull, (uint32_t)(pos & 31ull), true, err};
     (void)block_symbols(blk + t * kRow, dc_diff(zz, blk, b), [&](int bin, uint32_t value, int size, int) {
         wr.put(s_code[bin], s_len[bin]);
         wr.put32(value, (uint32_t)size);
     });
     wr.finish();
+}
+__global__ __launch_bounds__(kThreads) void adaptive_write_kernel(const int16_t *__restrict__ zz, unsigned long long n,
+                                                                  const HuffWide *__restrict__ tab, const uint32_t *__restrict__ bbits,
+                                                                  const unsigned long long *__restrict__ goff, uint32_t *__restrict__ out,
+                                                                  unsigned long long base_bits, unsigned long long out_words,
+                                                                  uint32_t *__restrict__ err) {
+    write_group(zz, n, blockIdx.x, tab, bbits, goff[blockIdx.x], out, base_bits, out_words, err);
+}
+
+// ---- descriptor form: the frames of a chunk in one launch per kernel ---------------------------------------------------------------------
+// The frame of workgroup `idx`: the last one whose first workgroup is not behind idx (find_frame of tic_entropy_gpu.hip: one load per lane
+// of the 64-entry prefix table, 0xffffffff behind the last frame, and a ballot; the result is wave-uniform).  The kernels call it first,
+// with whole waves.
+__device__ __forceinline__ int find_frame(const uint32_t *__restrict__ first, uint32_t idx) {
+    const uint32_t v = first[threadIdx.x & 63];
+    return __builtin_amdgcn_readfirstlane(__popcll(__ballot(v <= idx)) - 1);
+}
+
+// The chunk's statistics start empty: counts left by the slot's previous chunk would be added to.
+__global__ __launch_bounds__(kThreads) void adaptive_stats_reset_kernel(AdaptStats *__restrict__ st) {
+    AdaptStats *s = st + blockIdx.x;
+    for (int i = (int)threadIdx.x; i < kAdaptBins; i += kThreads) {
+        s->count[i] = 0ull;
+        s->first[i] = ~0ull;
+    }
+    if (threadIdx.x == 0) s->err = 0u;
+}
+
+__global__ __launch_bounds__(kThreads) void adaptive_stats_v_kernel(const int16_t *__restrict__ zz, const AdaptFrameTable *__restrict__ ft,
+                                                                    AdaptStats *__restrict__ st) {
+    const int f = find_frame(ft->first_group, blockIdx.x);
+    const AdaptFrameRec &r = ft->rec[f];
+    stats_group(zz + r.first_block * 64ull, r.nblocks, blockIdx.x - r.first_group, st + f);
+}
+
+__global__ __launch_bounds__(kThreads) void adaptive_bits_v_kernel(const int16_t *__restrict__ zz, const AdaptFrameTable *__restrict__ ft,
+                                                                   const HuffWide *__restrict__ tabs, uint32_t *__restrict__ bbits,
+                                                                   unsigned long long *__restrict__ gsum) {
+    const int f = find_frame(ft->first_group, blockIdx.x);
+    const AdaptFrameRec &r = ft->rec[f];
+    if (r.skip) return;
+    bits_group(zz + r.first_block * 64ull, r.nblocks, blockIdx.x - r.first_group, tabs + f, bbits + r.first_block, gsum + blockIdx.x);
+}
+
+// One workgroup per frame: the frame's header and table into its (zeroed) area - whole words up to base_bits; the blocks around that bit
+// OR theirs in behind this launch - and the exclusive prefix of the frame's own workgroup sums.
+__global__ __launch_bounds__(1024) void adaptive_scan_v_kernel(const AdaptFrameTable *__restrict__ ft, const uint8_t *__restrict__ heads,
+                                                               unsigned long long *__restrict__ gsum, unsigned char *__restrict__ streams) {
+    const AdaptFrameRec &r = ft->rec[blockIdx.x];
+    if (r.skip) return;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(heads + (size_t)blockIdx.x * kAdaptHeadStride);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(streams + r.out_off);
+    const unsigned long long head_words = ((unsigned long long)r.base_bits + 31ull) / 32ull;
+    for (unsigned long long i = threadIdx.x; i < head_words && i < r.out_words; i += 1024) dst[i] = src[i];
+    scan_groups(gsum + r.first_group, r.ngroups);
+}
+
+__global__ __launch_bounds__(kThreads) void adaptive_write_v_kernel(const int16_t *__restrict__ zz, const AdaptFrameTable *__restrict__ ft,
+                                                                    const HuffWide *__restrict__ tabs, const uint32_t *__restrict__ bbits,
+                                                                    const unsigned long long *__restrict__ goff, unsigned char *__restrict__ streams,
+                                                                    uint32_t *__restrict__ err) {
+    const int f = find_frame(ft->first_group, blockIdx.x);
+    const AdaptFrameRec &r = ft->rec[f];
+    if (r.skip) return;
+    write_group(zz + r.first_block * 64ull, r.nblocks, blockIdx.x - r.first_group, tabs + f, bbits + r.first_block, goff[blockIdx.x],
+                reinterpret_cast<uint32_t *>(streams + r.out_off), r.base_bits, r.out_words, err);
 }
 
 inline unsigned long long groups_of(size_t n) { return (n + kThreads - 1) / kThreads; }
@@ -282,6 +366,31 @@ hipError_t adaptive_pack(const int16_t *d_zz, size_t nblocks, const HuffWide *d_
     if (e != hipSuccess) return e;
     adaptive_write_kernel<<<dim3((unsigned)groups), dim3(kThreads), 0, stream>>>(d_zz, nblocks, d_tab, bbits, gsum, d_out, base_bits,
                                                                                    out_words, d_err);
+    return hipGetLastError();
+}
+
+hipError_t adaptive_stats_v(const int16_t *d_zz, const AdaptFrameTable *d_frames, int count, size_t ngroups, AdaptStats *d_stats,
+                            hipStream_t stream) {
+    if (count < 1 || count > kEntropyMaxFrames || ngroups == 0 || ngroups > 0x7fffffffu) return hipErrorInvalidValue;
+    adaptive_stats_reset_kernel<<<dim3((unsigned)count), dim3(kThreads), 0, stream>>>(d_stats);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    adaptive_stats_v_kernel<<<dim3((unsigned)ngroups), dim3(kThreads), 0, stream>>>(d_zz, d_frames, d_stats);
+    return hipGetLastError();
+}
+
+hipError_t adaptive_pack_v(const int16_t *d_zz, const AdaptFrameTable *d_frames, int count, size_t ngroups, const HuffWide *d_tabs,
+                           const uint8_t *d_heads, uint32_t *d_bbits, unsigned long long *d_gsum, void *d_streams, unsigned int *d_err,
+                           hipStream_t stream) {
+    if (count < 1 || count > kEntropyMaxFrames || ngroups == 0 || ngroups > 0x7fffffffu) return hipErrorInvalidValue;
+    adaptive_bits_v_kernel<<<dim3((unsigned)ngroups), dim3(kThreads), 0, stream>>>(d_zz, d_frames, d_tabs, d_bbits, d_gsum);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    adaptive_scan_v_kernel<<<dim3((unsigned)count), dim3(1024), 0, stream>>>(d_frames, d_heads, d_gsum, (unsigned char *)d_streams);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    adaptive_write_v_kernel<<<dim3((unsigned)ngroups), dim3(kThreads), 0, stream>>>(d_zz, d_frames, d_tabs, d_bbits, d_gsum,
+                                                                                     (unsigned char *)d_streams, d_err);
     return hipGetLastError();
 }
 

@@ -79,6 +79,12 @@ struct Slot {
     // and, for the read-back, where each stream lands in pin_out (pinned: the shader reads it where it lies)
     EntropyFrameTable *h_frames = nullptr, *d_frames = nullptr;
     unsigned long long *h_rb_off = nullptr;
+    // adaptive batches (tic_compress_batch_adaptive_v): the chunk's statistics, tables, headers and bit counts, carved by adaptive_slot_layout
+    // (tic_adaptive_frames.h), and the pinned mirror of their host-visible part.  Stream lengths are known only behind the statistics, so a
+    // chunk may find d_streams or pin_out short and grow THIS slot's: streams_cap / pin_out_cap then say what it holds (0: what every slot holds)
+    char *d_adapt = nullptr, *h_adapt = nullptr;
+    size_t adapt_bytes = 0, h_adapt_bytes = 0;
+    size_t streams_cap = 0, pin_out_cap = 0;
     int first = 0, count = 0; // frames [first, first+count) are in flight in this slot
     int pending = 0;          // pieces of the chunk's work not yet finished (SlotGate); 0 = the slot is free
     size_t rb_row = 0;        // row pitch of the streams read back into pin_out (0: they went straight to the caller)
@@ -230,6 +236,7 @@ struct tic_ctx {
         }
     } bslot_cap;
     int last_vbatch_frames = 0, last_vbatch_single = 0, last_vbatch_chunks = 0, last_vbatch_launches = 0; // tic_last_compress_batch_v
+    int last_abatch_frames = 0, last_abatch_single = 0, last_abatch_chunks = 0;                           // tic_last_compress_batch_adaptive
     // host side of the batch pipeline: the device's NUMA node and the CPUs of that node this process may run on
     int numa_node = -1;
     bool numa_bind = true;      // the pipeline's own threads (staging, read-back, hand-out) bind themselves to those CPUs
@@ -413,9 +420,9 @@ void DecWorkspace::release() {
 }
 
 void Slot::release() {
-    for (void *p : {(void *)pin_in, (void *)pin_out, (void *)h_lens, (void *)h_err, (void *)h_frames, (void *)h_rb_off})
+    for (void *p : {(void *)pin_in, (void *)pin_out, (void *)h_lens, (void *)h_err, (void *)h_frames, (void *)h_rb_off, (void *)h_adapt})
         if (p) (void)hipHostFree(p);
-    for (void *p : {d_img, d_coef, d_work, (void *)d_lens, (void *)d_err, d_streams, (void *)d_frames})
+    for (void *p : {d_img, d_coef, d_work, (void *)d_lens, (void *)d_err, d_streams, (void *)d_frames, (void *)d_adapt})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : {done, rb_done})
         if (e) (void)hipEventDestroy(e);
@@ -2753,6 +2760,20 @@ static int hand_out_chunk_v(tic_ctx *ctx, const MixedPlan &p, Slot &s, const Mix
     return TIC_OK;
 }
 
+// The transform of a mixed chunk: one launch per run of neighbours (a run is one tall frame).  *launches counts them.
+static hipError_t transform_chunk_v(tic_ctx *ctx, Slot &s, const MixedPlan &p, const MixedChunk &c, hipStream_t stream, int *launches) {
+    hipError_t e = hipSuccess;
+    for (size_t r = 0; r < c.runs.size() && e == hipSuccess; r++) {
+        const MixedFrame &f = p.frames[(size_t)c.runs[r].first];
+        DctqArgs a = make_args(ctx, (const char *)s.d_img + f.img_off, c.runs[r].h_total, f.w, (ptrdiff_t)f.pitch, f.quality,
+                               (int16_t *)s.d_coef + f.first_block * 64);
+        a.fallback_count = nullptr;
+        e = launch_dctq(a, 2, stream);
+        (*launches)++;
+    }
+    return e;
+}
+
 static tic_ctx::SlotNeed mixed_slot_need(const MixedPlan &p) {
     tic_ctx::SlotNeed need;
     need.img = p.max_img;
@@ -2784,18 +2805,7 @@ static int batch_mixed_pipeline(tic_ctx *ctx, const MixedPlan &p, const MixedCal
             if (!mixed_chunk_table(p, c, mode, s.h_frames, &nparts, &ngroups, &nplaces)) return set_err(ctx, TIC_E_ARG, "mixed batch: chunk %d has no table", ci);
             return enqueue_on_slot(
                 ctx, s, stream, c.first, c.count, [&](int *direct) { return upload_chunk_v(ctx, s, p, c, io, stream, direct); },
-                [&]() {
-                    hipError_t e = hipSuccess;
-                    for (size_t r = 0; r < c.runs.size() && e == hipSuccess; r++) { // a run of neighbours is one tall frame
-                        const MixedFrame &f = p.frames[(size_t)c.runs[r].first];
-                        DctqArgs a = make_args(ctx, (const char *)s.d_img + f.img_off, c.runs[r].h_total, f.w, (ptrdiff_t)f.pitch, f.quality,
-                                               (int16_t *)s.d_coef + f.first_block * 64);
-                        a.fallback_count = nullptr;
-                        e = launch_dctq(a, 2, stream);
-                        launches++;
-                    }
-                    return e;
-                },
+                [&]() { return transform_chunk_v(ctx, s, p, c, stream, &launches); },
                 [&](Slot &sl, hipStream_t st) {
                     hipError_t e = hipMemcpyAsync(sl.d_frames, sl.h_frames, sizeof(EntropyFrameTable), hipMemcpyHostToDevice, st);
                     if (e == hipSuccess)
@@ -3881,6 +3891,260 @@ int tic_entropy_encode_adaptive(tic_ctx *ctx, const int16_t *coeffs_zz, int h, i
     if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, coeffs_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
     return adaptive_encode_dev(ctx, n, h, w, quality, out, cap, out_len);
+}
+
+// ---- adaptive batches: per-image tables for frames of any sizes and qualities in one call (tic_compress_batch_adaptive_v) ----------------------
+// The mixed batch's plan, slots and pipeline (plan_mixed_batch, enqueue_on_slot, device_entropy_pipeline) with the adaptive encoder's two device
+// halves in descriptor form (adaptive_stats_v, adaptive_pack_v) around the host's table build:
+//   enqueue (calling thread)  upload, transform runs, the chunk's frame table, statistics (the launch resets them), ONE copy of the chunk's
+//                             statistics into the slot's pinned mirror, the slot's `done` event;
+//   read (second thread)      per frame the table (huffman_table_build) and the exact stream length from counts x lengths; stream areas from
+//                             those lengths; ONE upload of frame table, code tables and headers + serialized tables; bits / scan / write; the
+//                             read-back of every stream's own bytes into the pinned landing buffer; `rb_done`;
+//   hand-out (third thread)   hand_out_chunk_v.
+// A frame whose stream does not fit the caller's buffer is not packed: its out_lens entry holds the need and the call ends in TIC_E_SPACE.
+struct AdaptCall {
+    const int16_t *const *coeffs; // the coefficient entry's frames (null: `io.images` are pixels)
+    MixedCall io;
+    int short_frames;             // frames left unwritten for want of space (the reading thread counts; read behind batch_end's join)
+};
+
+struct AdaptSlotView { // a slot's adaptive buffers as chunk of `count` frames carves them
+    AdaptSlotLayout l;
+    AdaptStats *h_stats, *d_stats;
+    AdaptFrameTable *h_frames, *d_frames;
+    EntropyFrameTable *h_rb, *d_rb;
+    HuffWide *h_tabs, *d_tabs;
+    uint8_t *h_heads, *d_heads;
+    uint32_t *h_err, *d_err;
+};
+static AdaptSlotView adapt_view(const Slot &s, size_t count, size_t nblk, size_t ngroups) {
+    AdaptSlotView v;
+    v.l = adaptive_slot_layout(count, nblk, ngroups);
+    v.h_stats = (AdaptStats *)(s.h_adapt + v.l.stats), v.d_stats = (AdaptStats *)(s.d_adapt + v.l.stats);
+    v.h_frames = (AdaptFrameTable *)(s.h_adapt + v.l.frames), v.d_frames = (AdaptFrameTable *)(s.d_adapt + v.l.frames);
+    v.h_rb = (EntropyFrameTable *)(s.h_adapt + v.l.rb_frames), v.d_rb = (EntropyFrameTable *)(s.d_adapt + v.l.rb_frames);
+    v.h_tabs = (HuffWide *)(s.h_adapt + v.l.tabs), v.d_tabs = (HuffWide *)(s.d_adapt + v.l.tabs);
+    v.h_heads = (uint8_t *)(s.h_adapt + v.l.heads), v.d_heads = (uint8_t *)(s.d_adapt + v.l.heads);
+    v.h_err = (uint32_t *)(s.h_adapt + v.l.err), v.d_err = (uint32_t *)(s.d_adapt + v.l.err);
+    return v;
+}
+
+// Every slot holds the largest chunk's adaptive buffers (a frame's workgroups are rounded up: at most one more per frame).
+static int ensure_adapt_slots(tic_ctx *ctx, const MixedPlan &p) {
+    const AdaptSlotLayout l = adaptive_slot_layout((size_t)p.max_count, p.max_nblk, p.max_nblk / kAdaptGroupBlocks + (size_t)p.max_count);
+    for (auto &sl : ctx->bslots) {
+        int rc = grow_dev(ctx, sl.d_adapt, sl.adapt_bytes, l.end);
+        if (rc == TIC_OK) rc = grow_pinned(ctx, sl.h_adapt, sl.h_adapt_bytes, l.upload_end);
+        if (rc) return rc;
+    }
+    return TIC_OK;
+}
+
+// The read stage of an adaptive chunk (see above).  Only this slot's buffers are written.
+static int adaptive_pack_chunk(tic_ctx *ctx, const MixedPlan &p, Slot &s, hipStream_t st, AdaptCall &call) {
+    BT_START();
+    const hipError_t ev = hipEventSynchronize(s.done);
+    BT_STOP(2);
+    if (ev != hipSuccess) return set_err(ctx, TIC_E_HIP, "batch chunk failed");
+    BT_START();
+    const MixedFrame *fr = &p.frames[(size_t)s.first];
+    const int count = s.count;
+    size_t nblk = 0, ngroups = 0;
+    for (int k = 0; k < count; k++) nblk += fr[k].nblk, ngroups += (fr[k].nblk + kAdaptGroupBlocks - 1) / kAdaptGroupBlocks;
+    const AdaptSlotView v = adapt_view(s, (size_t)count, nblk, ngroups);
+    unsigned long long total_bits[kEntropyMaxFrames];
+    uint32_t base_bits[kEntropyMaxFrames];
+    for (int k = 0; k < count; k++) {
+        const MixedFrame &f = fr[k];
+        const AdaptStats &hs = v.h_stats[k];
+        if (hs.err)
+            return set_err(ctx, TIC_E_RANGE, "frame %d: a DC category or AC size above 15 (write_huffman_table has 4 bits for it, codec.py:73-84)", f.index);
+        uint8_t *head = v.h_heads + (size_t)k * kAdaptHeadStride;
+        memset(head, 0, kAdaptHeadStride);
+        write_header(head, f.h, f.w, f.quality);
+        head[12] = 0x80; // write_uint(1 << 31, 32): most significant bit first (codec.py:111)
+        unsigned long long dc_code[16], ac_code[256];
+        uint8_t dc_len[16], ac_len[256];
+        size_t tbits = 0;
+        const int rc = huffman_table_build(hs.count + kAdaptDcBin, hs.first + kAdaptDcBin, hs.count, hs.first, dc_code, dc_len, ac_code, ac_len, head + 16,
+                                           kAdaptMaxTableBytes, &tbits);
+        if (rc == TIC_E_RANGE) return set_err(ctx, rc, "frame %d: a Huffman code of this frame and its value bits exceed %d bits", f.index, kAdaptMaxSymbolBits);
+        if (rc) return set_err(ctx, rc, "frame %d: Huffman table build failed", f.index);
+        HuffWide &tab = v.h_tabs[k];
+        unsigned long long payload = 0;
+        for (int i = 0; i < kAdaptBins; i++) {
+            const bool dc = i >= kAdaptDcBin;
+            tab.code[i] = dc ? dc_code[i - kAdaptDcBin] : ac_code[i];
+            tab.len[i] = dc ? dc_len[i - kAdaptDcBin] : ac_len[i];
+            payload += hs.count[i] * (tab.len[i] + (unsigned)(dc ? i - kAdaptDcBin : i & 15));
+        }
+        base_bits[k] = (uint32_t)(128 + tbits);
+        const unsigned long long total = 128ull + tbits + payload;
+        const size_t bytes = (size_t)((total + 7) / 8);
+        call.io.out_lens[f.index] = bytes;
+        const bool fits = bytes <= call.io.caps[f.index];
+        if (!fits) call.short_frames++;
+        total_bits[k] = fits ? total : 0ull;
+        s.h_lens[k] = fits ? bytes : 0ull; // (nothing of an unpacked frame is read back or handed out)
+    }
+    size_t stream_bytes = 0, landing = 0, maxlen = 0;
+    assign_adaptive_streams(v.h_frames, count, total_bits, base_bits, &stream_bytes);
+    for (int k = 0; k < count; k++) {
+        v.h_rb->rec[k].out_off = v.h_frames->rec[k].out_off; // (all the read-back kernel reads of its table)
+        s.h_rb_off[k] = landing;
+        landing += align_up((size_t)s.h_lens[k], 64);
+        maxlen = std::max(maxlen, (size_t)s.h_lens[k]);
+    }
+    // (nothing is in flight on this slot's buffers: its previous chunk was handed out before this one claimed it)
+    if (!s.streams_cap) s.streams_cap = ctx->bslot_cap.streams;
+    if (!s.pin_out_cap) s.pin_out_cap = ctx->bslot_cap.pin_out;
+    int rc = grow_dev(ctx, s.d_streams, s.streams_cap, stream_bytes, stream_bytes + stream_bytes / 4);
+    if (rc == TIC_OK) rc = grow_pinned(ctx, s.pin_out, s.pin_out_cap, landing, landing + landing / 4);
+    if (rc) return rc;
+    *v.h_err = 0u;
+    hipError_t e = stream_bytes ? hipMemsetAsync(s.d_streams, 0, stream_bytes, st) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpyAsync(s.d_adapt + v.l.err, s.h_adapt + v.l.err, v.l.upload_end - v.l.err, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = adaptive_pack_v((const int16_t *)s.d_coef, v.d_frames, count, ngroups, v.d_tabs, v.d_heads, (uint32_t *)(s.d_adapt + v.l.bbits),
+                            (unsigned long long *)(s.d_adapt + v.l.gsum), s.d_streams, v.d_err, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s.h_err, v.d_err, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) {
+        const unsigned gx = (unsigned)std::min<size_t>(64, (maxlen / 16 + 255) / 256 + 1);
+        hipLaunchKernelGGL(readback_frames_kernel, dim3(gx, (unsigned)count), dim3(256), 0, st, (const unsigned char *)s.d_streams, v.d_rb, s.h_lens, s.h_rb_off,
+                           (unsigned char *)s.pin_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(s.rb_done, st);
+    BT_STOP(3);
+    if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "adaptive batch: packing or read-back of the chunk at frame %d failed: %s", s.first, hipGetErrorString(e));
+    return TIC_OK;
+}
+
+static int batch_adaptive_pipeline(tic_ctx *ctx, const MixedPlan &p, AdaptCall &call) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_batch_slots(ctx, mixed_slot_need(p));
+    if (rc == TIC_OK) rc = ensure_adapt_slots(ctx, p);
+    if (rc) return rc;
+    for (auto &sl : ctx->bslots) sl.pending = 0;
+    int launches = 0;
+    return device_entropy_pipeline(
+        ctx, (int)p.chunks.size(),
+        [&](int ci, Slot &s, hipStream_t stream, int) {
+            const MixedChunk &c = p.chunks[(size_t)ci];
+            const MixedFrame *fr = &p.frames[(size_t)c.first];
+            AdaptFrameTable t;
+            size_t nblk, ngroups;
+            if (!adaptive_chunk_table(p, c, &t, &nblk, &ngroups)) return set_err(ctx, TIC_E_ARG, "adaptive batch: chunk %d has no table", ci);
+            const AdaptSlotView v = adapt_view(s, (size_t)c.count, nblk, ngroups);
+            if (v.l.end > s.adapt_bytes || v.l.upload_end > s.h_adapt_bytes) return set_err(ctx, TIC_E_HIP, "adaptive batch: slot buffers too small for chunk %d", ci);
+            *v.h_frames = t;
+            return enqueue_on_slot(
+                ctx, s, stream, c.first, c.count,
+                [&](int *direct) {
+                    if (!call.coeffs) return upload_chunk_v(ctx, s, p, c, call.io, stream, direct);
+                    hipError_t e = hipSuccess;
+                    for (int k = 0; k < c.count && e == hipSuccess; k++)
+                        e = hipMemcpyAsync((int16_t *)s.d_coef + fr[k].first_block * 64, call.coeffs[fr[k].index], fr[k].nblk * 128, hipMemcpyHostToDevice, stream);
+                    *direct = c.count;
+                    return e;
+                },
+                [&]() { return call.coeffs ? hipSuccess : transform_chunk_v(ctx, s, p, c, stream, &launches); },
+                [&](Slot &sl, hipStream_t st) {
+                    hipError_t e = hipMemcpyAsync(v.d_frames, v.h_frames, sizeof(AdaptFrameTable), hipMemcpyHostToDevice, st);
+                    if (e == hipSuccess) e = adaptive_stats_v((const int16_t *)sl.d_coef, v.d_frames, c.count, ngroups, v.d_stats, st);
+                    if (e == hipSuccess) e = hipMemcpyAsync(v.h_stats, v.d_stats, (size_t)c.count * sizeof(AdaptStats), hipMemcpyDeviceToHost, st);
+                    return e;
+                });
+        },
+        [&](Slot &s, bool) { return adaptive_pack_chunk(ctx, p, s, ctx->rstream, call); },
+        [&](Slot &s) {
+            if (hipEventSynchronize(s.rb_done) != hipSuccess) return set_err(ctx, TIC_E_HIP, "stream read-back failed");
+            if (*s.h_err) return set_err(ctx, TIC_E_HIP, "packing reached past a stream's computed length (statistics and packing disagree)");
+            return hand_out_chunk_v(ctx, p, s, call.io);
+        });
+}
+
+// Both entries: `images` (pixels, row_strides) or `coeffs` (int16 [N_i][64], absolute DC).  Every check before any work.
+static int compress_batch_adaptive_impl(tic_ctx *ctx, const uint8_t *const *images, const int16_t *const *coeffs, int n, const int *hs, const int *ws,
+                                        const ptrdiff_t *row_strides, const int *qualities, uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
+    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
+    ctx->last_abatch_frames = ctx->last_abatch_single = ctx->last_abatch_chunks = 0;
+    if (n == 0) return TIC_OK;
+    if ((!images && !coeffs) || !hs || !ws || (images && !row_strides) || !qualities || !outs || !caps || !out_lens)
+        return set_err(ctx, TIC_E_ARG, "null array argument");
+    for (int i = 0; i < n; i++) {
+        int rc = TIC_OK;
+        if (images)
+            rc = check_stream_geometry(ctx, hs[i], ws[i], row_strides[i], qualities[i]);
+        else if (hs[i] < 0 || ws[i] < 0)
+            rc = set_err(ctx, TIC_E_ARG, "negative image size");
+        else if (qualities[i] < 1 || qualities[i] > 99)
+            rc = set_err(ctx, TIC_E_QUALITY, "quality %d outside 1..99", qualities[i]);
+        if (rc) {
+            const std::string why = ctx->err;
+            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
+        }
+        if (num_blocks(hs[i], ws[i]) == 0)
+            return set_err(ctx, TIC_E_ARG, "frame %d: an image without blocks has no symbols to build a table from (the reference raises IndexError)", i);
+        if (!outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
+        if (images ? !images[i] : !coeffs[i]) return set_err(ctx, TIC_E_ARG, images ? "frame %d: null image" : "frame %d: null coefficient pointer", i);
+    }
+    int chunk_frames = kMixedChunkFrames;
+    size_t chunk_bytes = kMixedChunkBytes;
+    if (const char *e = test_hook("TIC_BATCH_CHUNK")) chunk_frames = atoi(e); // (out of range: the default)
+    if (const char *e = test_hook("TIC_BATCH_CHUNK_BYTES")) chunk_bytes = strtoull(e, nullptr, 10) ? (size_t)strtoull(e, nullptr, 10) : chunk_bytes;
+    const MixedPlan p = plan_mixed_batch(hs, ws, qualities, n, chunk_frames, chunk_bytes);
+    AdaptCall call = {coeffs, {images, row_strides, outs, caps, out_lens}, 0};
+    ctx->last_batch_direct_frames = ctx->last_batch_staged_frames = ctx->last_batch_autoreg_frames = ctx->last_batch_zero_copy = 0;
+    ctx->bt = BatchTrace();
+    if (!p.frames.empty()) {
+        const int rc = batch_adaptive_pipeline(ctx, p, call);
+        if (rc) return rc;
+    }
+    ctx->last_abatch_frames = (int)p.frames.size();
+    ctx->last_abatch_chunks = (int)p.chunks.size();
+    for (int i : p.single) { // what a chunk does not hold, behind the batch, frame by frame
+        const int rc = images ? tic_compress_adaptive(ctx, images[i], hs[i], ws[i], row_strides[i], qualities[i], outs[i], caps[i], &out_lens[i])
+                              : tic_entropy_encode_adaptive(ctx, coeffs[i], hs[i], ws[i], qualities[i], outs[i], caps[i], &out_lens[i]);
+        ctx->last_abatch_single++;
+        if (rc == TIC_E_SPACE && out_lens[i] > caps[i]) {
+            call.short_frames++;
+            continue;
+        }
+        if (rc) {
+            const std::string why = ctx->err;
+            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
+        }
+    }
+    if (call.short_frames)
+        return set_err(ctx, TIC_E_SPACE, "%d frame(s) not written: output buffer too small (out_lens holds the sizes needed)", call.short_frames);
+    return TIC_OK;
+}
+
+int tic_compress_batch_adaptive_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                                  const int *qualities, uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (n > 0 && !images) return set_err(ctx, TIC_E_ARG, "null array argument");
+    return compress_batch_adaptive_impl(ctx, images, nullptr, n, hs, ws, row_strides, qualities, outs, caps, out_lens);
+}
+
+int tic_entropy_encode_adaptive_batch(tic_ctx *ctx, const int16_t *const *coeffs, int n, const int *hs, const int *ws, const int *qualities,
+                                      uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (n > 0 && !coeffs) return set_err(ctx, TIC_E_ARG, "null array argument");
+    return compress_batch_adaptive_impl(ctx, nullptr, coeffs, n, hs, ws, nullptr, qualities, outs, caps, out_lens);
+}
+
+int tic_last_compress_batch_adaptive(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (batch_frames) *batch_frames = ctx->last_abatch_frames;
+    if (single_frames) *single_frames = ctx->last_abatch_single;
+    if (chunks) *chunks = ctx->last_abatch_chunks;
+    return TIC_OK;
 }
 
 // Streams with an embedded table the DEVICE decoder takes (tic_adaptive_dec_gpu.hip): every stream of at least 16,384 blocks, and
