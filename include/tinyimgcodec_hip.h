@@ -492,6 +492,27 @@ int tic_decompress_adaptive(tic_ctx *ctx, const uint8_t *data, size_t len, uint8
  * words: up to 3 bytes behind `len`, to the next 4-byte boundary, are read (and masked); any other address is copied first. */
 int tic_decompress_adaptive_dev(tic_ctx *ctx, const void *d_stream, size_t len, void *d_out, ptrdiff_t out_stride, size_t out_cap, int *h,
                                 int *w);
+/* tic_decompress_adaptive of MANY streams in one call; arguments as tic_decompress_batch.  Frame i: what tic_decompress_adaptive(ctx,
+ * streams[i], lens[i], outs[i], caps[i]) gives, geometry in hs[i] / ws[i] (either may be null).  The frames the batch kernels take - at
+ * least one block, a table that parses and has no code of length zero, bit positions that fit 32 bits; no size threshold - are cut into
+ * chunks in the caller's order; a chunk goes up in ONE copy (descriptors, a look-up table per frame, the streams), is decoded by one
+ * launch per kernel (three rounds of the stitch with the passes and the inverse transform behind them; sixteen more rounds, once, when a
+ * frame of the chunk has not settled) and comes down in ONE copy - straight into the caller's memory where the frames are dense and
+ * follow each other there, else through a pinned buffer.  Every frame not taken, and every frame the kernels give up on, goes through
+ * tic_decompress_adaptive afterwards, in index order; fewer than two taken frames make the whole call a loop of single calls (n == 1 is
+ * exactly the single call).  Errors: the header checks of tic_decompress_adaptive run for every frame before any work (the first
+ * offending frame's error, prefixed "frame %d:", nothing decoded); an error while decoding is the first one met, and every frame that
+ * did not itself fail is complete.  n == 0: TIC_OK. */
+int tic_decompress_batch_adaptive(tic_ctx *ctx, const uint8_t *const *streams, const size_t *lens, int n, uint8_t *const *outs,
+                                  const size_t *caps, int *hs, int *ws);
+/* How the last such call went: frames decoded by the batch kernels, frames that took the single call, chunks (null pointers are skipped). */
+int tic_last_decompress_batch_adaptive(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks);
+/* ... and the frames of its chunks whose pixels came down straight into the caller's memory (0: every chunk went through the pinned buffer). */
+int tic_last_decompress_batch_adaptive_direct(tic_ctx *ctx);
+/* The device decoder's geometry for an adaptive stream of `len` bytes whose payload starts at bit `payload_bit` (128 + table bits) and
+ * holds `nblocks` blocks: stream bits per lane and the number of such ranges (a workgroup walks 256 of them).  Pure arithmetic, no
+ * context; TIC_E_ARG for a stream the device decoder cannot address.  Either pointer may be null. */
+int tic_adaptive_decode_geometry(size_t len, size_t payload_bit, size_t nblocks, int *range_bits, size_t *nranges);
 
 /* ---- the reference's integer encoder: c/img.c + c/encode.c, the standalone C program ("scaled DCT" streams) ------------------------
  *      The stream is what the library calls IMG_init -> IMG_encodeHeader -> IMG_encodeBlock per block in raster order ->

@@ -214,6 +214,13 @@ SIGNATURES = {
     ),
     "tic_decompress_adaptive": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "tic_decompress_adaptive_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_ssize_t, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tic_decompress_batch_adaptive": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    ),
+    "tic_last_decompress_batch_adaptive": (C.c_int, [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tic_last_decompress_batch_adaptive_direct": (C.c_int, [_ctxp]),
+    "tic_adaptive_decode_geometry": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "tic_compress_scaled_bound": (C.c_size_t, [C.c_int, C.c_int]),
     "tic_dctq_scaled": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p]),
     "tic_dctq_scaled_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p]),

@@ -15,6 +15,7 @@ huffman.py:101-194), under names of their own because compress() keeps raising f
     compress_batch_adaptive(images, quality=50) -> [bytes]   compress_adaptive() per frame, any shapes, a quality each, in one call
     entropy_encode_adaptive_batch(coeffs_list, shapes, qualities) -> [bytes]   the same from coefficients
     decompress_adaptive(data) -> np.ndarray[uint8]  reads such a stream as written
+    decompress_batch_adaptive(streams) -> [np.ndarray[uint8]]   decompress_adaptive() per stream, any shapes, in one call
 
 and, for the reference's standalone integer encoder (c/img.c, c/encode.c: 8-bit-constant AAN DCT, reciprocal quantiser with four
 settings, header flag 1 << 30 - the streams decompress() reads through its scaled_dct branch):
@@ -786,6 +787,47 @@ def decompress_adaptive(data, ctx=None):
             raise ValueError(N.load().tic_last_error(ctx.handle).decode())
         ctx.check(rc)
     return out
+
+
+def decompress_batch_adaptive(streams, ctx=None):
+    """decompress_adaptive() of many streams in one call -> list of uint8 arrays (stream order): the mirror of compress_batch_adaptive.
+    Every element is what decompress_adaptive() returns for that stream; the exceptions are decompress_adaptive()'s - ValueError naming
+    the frame: the first offending header's before anything is decoded, else the first stream's that fails to decode (every other frame
+    has been decoded by then).  The streams and a look-up table each go up in one copy, one launch per kernel decodes a chunk of them
+    whatever their sizes, the pixels come down in one copy (tic_decompress_batch_adaptive); flat and one-block frames, and anything the
+    kernels give up on, take the single call behind the batch."""
+    bufs = [_as_bytes_view(d) for d in streams]
+    n = len(bufs)
+    if n == 0:
+        return []
+    shapes = []
+    for i, b in enumerate(bufs):
+        if b.size < 16:
+            raise ValueError("frame %d: stream shorter than its 16-byte header" % i)
+        hd = parse_header(b)
+        if hd["height"] < 0 or hd["width"] < 0:
+            raise ValueError("frame %d: negative image size in the header" % i)
+        shapes.append((hd["height"], hd["width"]))
+    ctx = _ctx(ctx)  # (behind the checks that need no device)
+    # one block for all frames, as decompress_batch: the library copies the pixels of a chunk straight into it where they are dense
+    sizes = [h * w for h, w in shapes]
+    block = np.zeros(sum(sizes), dtype=np.uint8)
+    outs, at = [], 0
+    for (h, w), sz in zip(shapes, sizes):
+        outs.append(block[at:at + sz].reshape(h, w) if sz else np.zeros((h, w), np.uint8))
+        at += sz
+    L = N.load()
+    sp = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    sl = (C.c_size_t * n)(*[b.size for b in bufs])
+    op = (C.c_void_p * n)(*[o.ctypes.data if o.size else None for o in outs])
+    oc = (C.c_size_t * n)(*[o.size for o in outs])
+    with ctx.lock:
+        rc = L.tic_decompress_batch_adaptive(ctx.handle, sp, sl, n, op, oc, None, None)
+        if rc in (N.TIC_E_STREAM, N.TIC_E_SPACE):
+            msg = L.tic_last_error(ctx.handle).decode()
+            raise ValueError(msg if msg.startswith("frame ") else "frame 0: " + msg)  # (a batch of one is the single call: its message names no frame)
+        ctx.check(rc)
+    return outs
 
 
 def _as_bytes_view(data):

@@ -284,6 +284,14 @@ int adaptive_parse_table(const uint8_t *data, size_t len, AdaptTable *t, const c
     return parse_table(data, len, r, dc, ac, t, why);
 }
 
+bool adaptive_dec_tab_buildable(const AdaptTable &t) {
+    for (int i = 0; i < t.ndc; i++)
+        if (t.dc_len[i] == 0) return false;
+    for (int i = 0; i < t.nac; i++)
+        if (t.ac_len[i] == 0) return false;
+    return true;
+}
+
 bool adaptive_dec_tab_build(const AdaptTable &t, AdaptDecTab *out) {
     memset(out, 0, sizeof *out);
     for (int k = 0; k < 2; k++) {

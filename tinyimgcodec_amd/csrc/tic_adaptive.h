@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "tic_adaptive_decode_plan.h"
 #include "tic_adaptive_frames.h"
 
 namespace tic {
@@ -53,6 +54,7 @@ struct AdaptDecTab {
 // False when a code has length zero (the one-symbol tree of a flat frame: its symbols take no bits, so there is nothing to
 // synchronise on): such a stream is the host decoder's.
 bool adaptive_dec_tab_build(const AdaptTable &t, AdaptDecTab *out);
+bool adaptive_dec_tab_buildable(const AdaptTable &t); // whether it would succeed, without building (the batch's take rule)
 
 // Device decoder (tic_adaptive_dec_gpu.hip): the payload of `len` stream bytes at d_stream (4-byte aligned; the bytes of its last word
 // behind `len` are masked) from bit `payload_bit` -> d_zz = int16 [nblocks][64] zig-zag with the DC integrated.  d_work:
@@ -74,6 +76,24 @@ int adaptive_dec_range_bits(size_t len, size_t payload_bit, size_t nblocks);
 size_t adaptive_dec_work_bytes(size_t len, size_t payload_bit, size_t nblocks, int range_bits);
 hipError_t adaptive_decode_gpu(const void *d_stream, size_t len, size_t payload_bit, size_t nblocks, int range_bits, const AdaptDecTab *d_tab,
                                void *d_work, AdaptDecStatus *d_status, int16_t *d_zz, int round0, int nrounds, bool finish, hipStream_t stream);
+
+// Descriptor form: the frames of a chunk (tic_adaptive_decode_plan.h) in one launch per kernel.  All pointers are device memory: `frames`
+// the chunk's descriptors, rwg_frame / bwg_frame the frame of every workgroup of the range and block grids, `tabs` an AdaptDecTab per
+// frame kAdaptDecTabSlot bytes apart, `words` the chunk's stream buffer, `work` adaptive_dec_batch_work_bytes(ranges, blocks) bytes, `cs`
+// the chunk's status with the frames' (`fs`) right behind it, `zz` int16 [blocks][64].  Rounds and `finish` as adaptive_decode_gpu, at
+// most kAdaptBatchRounds rounds; what the passes leave for a frame counts only when the last round launched moved none of ITS exits.
+struct AdaptDecBatch {
+    const AdaptDecFrame *frames;
+    const uint32_t *rwg_frame, *bwg_frame;
+    const char *tabs;
+    const uint32_t *words;
+    void *work;
+    AdaptDecChunkStatus *cs;
+    AdaptDecFrameStatus *fs;
+    int16_t *zz;
+    uint32_t nframes, ranges, blocks, range_wgs, block_wgs;
+};
+hipError_t adaptive_decode_gpu_batch(const AdaptDecBatch &a, int round0, int nrounds, bool finish, hipStream_t stream);
 
 // Device part of the encoder (tic_adaptive_gpu.hip).  d_stats: statistics of the n blocks of d_zz (zero the counts and the error, set the
 // first keys to ~0 before).  The packing: d_out (32-bit words, zeroed, the header and table bits already in place) receives the

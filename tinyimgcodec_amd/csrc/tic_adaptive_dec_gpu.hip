@@ -23,6 +23,25 @@
 // Anything unusual ON THE CHAIN before block N - such an incident, the stream's end, a running DC outside int16 - sets a give-up bit:
 // the caller then runs the host decoder, which alone words errors.  Bits behind block N are ignored, as on the host.
 // Stream words are read from memory (L2-resident: 64 lanes a range apart), the tables from LDS.
+//
+// DESCRIPTOR FORM (adaptive_decode_gpu_batch, the kernels named *_v): the same five kernels for the frames of a chunk
+// (tic_adaptive_decode_plan.h), one launch each.  Every workgroup looks its frame up in an uploaded table (a workgroup of the range and
+// block grids) or is its frame's own (the two sums: grid = frames), reads the frame's descriptor and stages THAT frame's tables in LDS.
+// Nothing crosses a frame: a workgroup's 256 lanes are consecutive ranges (or blocks) of one frame, the first lane of a frame's first
+// workgroup starts at the frame's payload_bit, the DC sum starts over with every frame, and a frame's Stream is its own words, word
+// count and last-word mask inside the chunk's stream buffer - window() never reads another frame's bytes, nor the padding between them.
+// Exits, walked-from bits, counts and incidents lie in chunk-wide arrays at the frame's range0, block positions, DC differences and
+// coefficients at its blk0.  Status is per frame (give-up bits, blocks on the chain, exits moved per round) plus ONE count per round
+// for the chunk, so that the host reads one word to know whether every frame has settled.
+// ROUNDS PROTOCOL of a chunk (decided here and in tic_api.hip adbatch_decode, nowhere else):
+//   1. rounds 0..2, the passes and the inverse transform are launched at once; one status read-back, one synchronisation - the single
+//      call's optimistic path;
+//   2. if round 2 moved an exit anywhere in the chunk, rounds 3..18 are launched and nothing else (a workgroup of a frame whose last
+//      round moved none of its exits leaves at once: a fixed point stays one);
+//   3. a frame round 18 still moved is marked kAdaptGiveupNoSync by the caller - its single call has all kAdaptDecMaxRounds rounds;
+//   4. the passes and the inverse transform run once more for the whole chunk: settled frames get the same result again, the frames that
+//      settled in rounds 3..18 their first true one.
+// So one pathological frame (the long-code fixture: its chain advances a workgroup per launch) holds a chunk for 16 launches, not 512.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -30,6 +49,7 @@
 #include "tic_adaptive.h"
 
 namespace tic {
+static_assert(sizeof(AdaptDecTab) == kAdaptDecTabBytes && kAdaptDecTabSlot >= kAdaptDecTabBytes && kAdaptDecTabSlot % 256 == 0, "the plan's table slot");
 namespace {
 
 constexpr int kThreads = 256, kScanThreads = 1024;
@@ -313,6 +333,165 @@ __global__ void __launch_bounds__(kScanThreads) adapt_dec_dc(Geo g, void *work, 
     if (out_of_range) atomicOr(&st->giveup, kAdaptGiveupDc);
 }
 
+
+// ---- descriptor form: the frames of a chunk in one launch per kernel (see the header comment) ---------------------------------------
+__device__ __forceinline__ Geo geo_of(const AdaptDecFrame &F, const uint32_t *__restrict__ words_all) {
+    Geo g;
+    g.s.words = words_all + F.word0, g.s.nwords = F.nwords, g.s.last_mask = F.last_mask, g.s.total_bits = F.total_bits;
+    g.base = F.payload_bit, g.range = F.range_bits, g.nranges = F.nranges, g.nblocks = F.nblocks;
+    return g;
+}
+__device__ __forceinline__ const AdaptDecTab *tab_of(const AdaptDecBatch &a, uint32_t f) {
+    return (const AdaptDecTab *)(a.tabs + (size_t)f * kAdaptDecTabSlot);
+}
+// the chunk's work arrays from the frame's first range and block on
+__device__ __forceinline__ Work carve_frame(const AdaptDecBatch &a, const AdaptDecFrame &F) {
+    Work w = carve(a.work, a.ranges, a.blocks);
+    w.exit_bit[0] += F.range0, w.exit_bit[1] += F.range0, w.from += F.range0, w.count += F.range0, w.bad_at += F.range0, w.first += F.range0;
+    w.pos += F.blk0, w.dcdiff += F.blk0;
+    return w;
+}
+
+// adapt_dec_round for the workgroup's frame.  The exits it moved are counted once per workgroup, for the frame and for the chunk.
+__global__ void __launch_bounds__(kThreads) adapt_dec_round_v(AdaptDecBatch a, int round) {
+    __shared__ AdaptDecTab tab;
+    __shared__ uint32_t ex[kThreads];
+    __shared__ uint32_t moved;
+    const uint32_t f = a.rwg_frame[blockIdx.x];
+    AdaptDecFrameStatus *st = a.fs + f;
+    if (round >= kAdaptBatchRounds0 && st->changed[round - 1] == 0) return; // (the whole workgroup: this frame has settled, and a fixed point stays one)
+    const AdaptDecFrame F = a.frames[f];
+    stage_tab(&tab, tab_of(a, f));
+    const Geo g = geo_of(F, a.words);
+    const Work w = carve_frame(a, F);
+    const uint32_t t = (blockIdx.x - F.rwg0) * kThreads + threadIdx.x; // the range inside the frame
+    const bool valid = t < g.nranges;
+    const uint32_t *in = w.exit_bit[(round & 1) ^ 1];
+    uint32_t *out = w.exit_bit[round & 1];
+    uint32_t from = kNone, x = 0, cnt = 0, bad = kNone, entry = 0;
+    bool walked = false;
+    if (valid) {
+        entry = (round == 0 || t == 0) ? g.base + t * g.range : in[t - 1u];
+        if (round != 0) from = w.from[t], x = in[t];
+    }
+    const uint32_t x0 = x;
+    for (int it = 0; it <= kThreads; it++) {
+        bool m = false;
+        if (valid && entry != from) {
+            uint32_t nx;
+            cnt = walk_range(tab, g.s, entry, range_limit(g, t), &nx, &bad, nullptr, 0);
+            m = !walked && round == 0 ? true : nx != x;
+            from = entry, x = nx, walked = true;
+        }
+        ex[threadIdx.x] = x;
+        if (threadIdx.x == 0) moved = 0u;
+        __syncthreads();
+        if (m) moved = 1u;
+        __syncthreads();
+        const bool again = moved != 0u;
+        if (valid && threadIdx.x > 0) entry = ex[threadIdx.x - 1u];
+        __syncthreads();
+        if (!again) break;
+    }
+    if (valid) {
+        if (walked) w.from[t] = from, w.count[t] = cnt, w.bad_at[t] = bad;
+        out[t] = x;
+    }
+    const int n = __syncthreads_count(valid && round != 0 && x != x0);
+    if (threadIdx.x != 0) return;
+    if (round == 0) {
+        st->changed[0] = 1u, a.cs->changed[0] = 1u; // (every workgroup stores the same word)
+    } else if (n) {
+        atomicAdd(&st->changed[round], (uint32_t)n); // (few: the walks of round 0 fall in step within their range nearly everywhere)
+        atomicAdd(&a.cs->changed[round], (uint32_t)n);
+    }
+}
+
+// adapt_dec_scan, a workgroup per frame.  The frame's give-up bits and block count are written afresh: the passes may run twice.
+__global__ void __launch_bounds__(kScanThreads) adapt_dec_scan_v(AdaptDecBatch a) {
+    __shared__ uint32_t lds[kScanThreads];
+    const AdaptDecFrame F = a.frames[blockIdx.x];
+    const Work w = carve_frame(a, F);
+    const uint32_t per = (F.nranges + kScanThreads - 1u) / kScanThreads;
+    const uint32_t t0 = min(threadIdx.x * per, F.nranges), t1 = min(t0 + per, F.nranges);
+    uint32_t sum = 0;
+    for (uint32_t t = t0; t < t1; t++) sum += w.count[t];
+    const uint32_t incl = block_scan(sum, lds);
+    uint32_t run = incl - sum;
+    bool incident = false;
+    for (uint32_t t = t0; t < t1; t++) {
+        w.first[t] = run;
+        const uint32_t bad = w.bad_at[t];
+        if (bad != kNone && (unsigned long long)run + bad < F.nblocks) incident = true;
+        run += w.count[t];
+    }
+    const bool any = __syncthreads_or(incident) != 0;
+    if (threadIdx.x == kScanThreads - 1u) {
+        AdaptDecFrameStatus *st = a.fs + blockIdx.x;
+        st->blocks = incl;
+        st->giveup = (any ? kAdaptGiveupIncident : 0u) | (incl < F.nblocks ? kAdaptGiveupShort : 0u);
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) adapt_dec_positions_v(AdaptDecBatch a) {
+    __shared__ AdaptDecTab tab;
+    const uint32_t f = a.rwg_frame[blockIdx.x];
+    const AdaptDecFrame F = a.frames[f];
+    stage_tab(&tab, tab_of(a, f));
+    const uint32_t t = (blockIdx.x - F.rwg0) * kThreads + threadIdx.x;
+    if (t >= F.nranges) return;
+    const Geo g = geo_of(F, a.words);
+    const Work w = carve_frame(a, F);
+    const uint32_t first = w.first[t];
+    if (first >= F.nblocks || w.count[t] == 0) return;
+    uint32_t x, bad;
+    (void)walk_range(tab, g.s, w.from[t], range_limit(g, t), &x, &bad, w.pos + first, F.nblocks - first); // (inside the frame's own blocks)
+}
+
+__global__ void __launch_bounds__(kThreads) adapt_dec_blocks_v(AdaptDecBatch a) {
+    __shared__ AdaptDecTab tab;
+    const uint32_t f = a.bwg_frame[blockIdx.x];
+    const AdaptDecFrame F = a.frames[f];
+    stage_tab(&tab, tab_of(a, f));
+    const uint32_t b = (blockIdx.x - F.bwg0) * kThreads + threadIdx.x; // the block inside the frame
+    if (b >= F.nblocks) return;
+    const Geo g = geo_of(F, a.words);
+    const Work w = carve_frame(a, F);
+    int16_t *row = a.zz + ((size_t)F.blk0 + b) * 64;
+    uint4 *row4 = (uint4 *)row;
+#pragma unroll
+    for (int i = 0; i < 8; i++) row4[i] = make_uint4(0, 0, 0, 0);
+    int dc = 0;
+    // (as in adapt_dec_blocks: whatever an unsettled or short chain leaves in pos[] is walked within the frame's stream and written within the row)
+    const uint32_t p = b < a.fs[f].blocks ? w.pos[b] : g.s.total_bits;
+    if (p < g.s.total_bits) {
+        uint32_t next;
+        (void)walk_block(tab, g.s, p, &next, row, &dc);
+    }
+    w.dcdiff[b] = dc;
+}
+
+// adapt_dec_dc, a workgroup per frame: the sum starts over with every frame (codec.py:53)
+__global__ void __launch_bounds__(kScanThreads) adapt_dec_dc_v(AdaptDecBatch a) {
+    __shared__ long long lds[kScanThreads];
+    const AdaptDecFrame F = a.frames[blockIdx.x];
+    const Work w = carve_frame(a, F);
+    int16_t *zz = a.zz + (size_t)F.blk0 * 64;
+    const uint32_t per = (F.nblocks + kScanThreads - 1u) / kScanThreads;
+    const uint32_t b0 = min(threadIdx.x * per, F.nblocks), b1 = min(b0 + per, F.nblocks);
+    long long sum = 0;
+    for (uint32_t b = b0; b < b1; b++) sum += w.dcdiff[b];
+    long long run = block_scan(sum, lds) - sum;
+    bool out_of_range = false;
+    for (uint32_t b = b0; b < b1; b++) {
+        run += w.dcdiff[b];
+        if (run < -32768 || run > 32767) out_of_range = true;
+        zz[(size_t)b * 64] = (int16_t)run;
+    }
+    const bool any = __syncthreads_or(out_of_range) != 0;
+    if (any && threadIdx.x == 0) a.fs[blockIdx.x].giveup |= kAdaptGiveupDc; // (this workgroup alone writes the frame's status in this launch)
+}
+
 // (a stream of fewer than 2^32 - 8,192 bits, checked by the caller: bit positions are 32-bit, and a walk may step past the end by a symbol)
 inline uint32_t ranges_of(size_t len, size_t payload_bit, int range_bits) {
     const size_t payload = len * 8 - payload_bit;
@@ -323,11 +502,7 @@ inline uint32_t ranges_of(size_t len, size_t payload_bit, int range_bits) {
 
 // Stream bits per lane: two average blocks, 256 at least (a lane's walk is one dependent chain of look-ups: its length is the kernel's
 // time), 4,096 at most.
-int adaptive_dec_range_bits(size_t len, size_t payload_bit, size_t nblocks) {
-    const size_t payload = len * 8 - payload_bit;
-    const size_t r = 2 * payload / (nblocks ? nblocks : 1);
-    return (int)(r < 256 ? 256 : (r > 4096 ? 4096 : r));
-}
+int adaptive_dec_range_bits(size_t len, size_t payload_bit, size_t nblocks) { return adaptive_dec_range_rule(len, payload_bit, nblocks); }
 
 size_t adaptive_dec_work_bytes(size_t len, size_t payload_bit, size_t nblocks, int range_bits) {
     return ((size_t)ranges_of(len, payload_bit, range_bits) * 6 + nblocks * 2) * 4;
@@ -361,6 +536,24 @@ hipError_t adaptive_decode_gpu(const void *d_stream, size_t len, size_t payload_
     adapt_dec_positions<<<range_grid, kThreads, 0, stream>>>(g, d_tab, d_work);
     adapt_dec_blocks<<<block_grid, kThreads, 0, stream>>>(g, d_tab, d_work, d_status, d_zz);
     adapt_dec_dc<<<1, kScanThreads, 0, stream>>>(g, d_work, d_status, d_zz);
+    return hipGetLastError();
+}
+
+// The descriptor form's launcher: rounds [round0, round0 + nrounds) for every frame of the chunk and, with `finish`, the passes behind them.
+// round0 = 0 starts a decode and zeroes the status words.  The host-side checks come before the first launch.
+hipError_t adaptive_decode_gpu_batch(const AdaptDecBatch &a, int round0, int nrounds, bool finish, hipStream_t stream) {
+    if (!a.frames || !a.rwg_frame || !a.bwg_frame || !a.tabs || !a.words || !a.work || !a.cs || !a.fs || !a.zz || ((uintptr_t)a.words & 3u) ||
+        ((uintptr_t)a.tabs & 7u) || ((uintptr_t)a.zz & 15u) || a.nframes == 0 || a.ranges == 0 || a.blocks == 0 || a.range_wgs == 0 || a.block_wgs == 0 ||
+        round0 < 0 || nrounds < 0 || round0 + nrounds > kAdaptBatchRounds || (nrounds == 0 && !finish))
+        return hipErrorInvalidValue;
+    hipError_t e;
+    if (round0 == 0 && (e = hipMemsetAsync(a.cs, 0, sizeof(AdaptDecChunkStatus) + (size_t)a.nframes * sizeof(AdaptDecFrameStatus), stream)) != hipSuccess) return e;
+    for (int r = round0; r < round0 + nrounds; r++) adapt_dec_round_v<<<a.range_wgs, kThreads, 0, stream>>>(a, r);
+    if (!finish) return hipGetLastError();
+    adapt_dec_scan_v<<<a.nframes, kScanThreads, 0, stream>>>(a);
+    adapt_dec_positions_v<<<a.range_wgs, kThreads, 0, stream>>>(a);
+    adapt_dec_blocks_v<<<a.block_wgs, kThreads, 0, stream>>>(a);
+    adapt_dec_dc_v<<<a.nframes, kScanThreads, 0, stream>>>(a);
     return hipGetLastError();
 }
 

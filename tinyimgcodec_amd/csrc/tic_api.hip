@@ -271,6 +271,13 @@ struct tic_ctx {
     AdaptDecStatus *d_adec_status = nullptr;
     void *d_adec_work = nullptr;
     size_t adec_work_bytes = 0;
+    // ... and its batch form (tic_decompress_batch_adaptive): a chunk's status words, work arrays and coefficients in one device buffer
+    // (AdaptDecWorkLayout), the pinned landing buffer of the status words; upload and pixel buffers are the batched decode's (dbat)
+    struct AdaptDecBatchBuf {
+        char *d_work = nullptr, *h_status = nullptr;
+        size_t work_cap = 0, status_cap = 0;
+    } adbat;
+    int last_adbatch_frames = 0, last_adbatch_single = 0, last_adbatch_chunks = 0, last_adbatch_direct = 0; // tic_last_decompress_batch_adaptive (_direct)
     // rate control (tic_stream_sizes_dev, tic_compress_to_size_dev): the size kernel's table, a result per probe on the device and its
     // pinned landing buffer, and what the last search did
     SizeTabDev *d_size_tab = nullptr;
@@ -508,6 +515,8 @@ void tic_destroy(tic_ctx *ctx) {
     if (ctx->d_adapt_out) (void)hipFree(ctx->d_adapt_out);
     if (ctx->d_adec_tab) (void)hipFree(ctx->d_adec_tab); // the status words live in the same block
     if (ctx->d_adec_work) (void)hipFree(ctx->d_adec_work);
+    if (ctx->adbat.d_work) (void)hipFree(ctx->adbat.d_work);
+    if (ctx->adbat.h_status) (void)hipHostFree(ctx->adbat.h_status);
     if (ctx->d_size_tab) (void)hipFree(ctx->d_size_tab);
     if (ctx->d_rate) (void)hipFree(ctx->d_rate);
     if (ctx->h_rate) (void)hipHostFree(ctx->h_rate);
@@ -3345,6 +3354,21 @@ struct DecBatchIO { // the caller's arrays
     const size_t *caps;
 };
 
+// The buffers both batch decoders share (ctx->dbat): the pinned upload buffer and its device mirror grow together; the chunk's pixel buffer.
+static int dbatch_grow(tic_ctx *ctx, size_t up_bytes, size_t pix_bytes) {
+    tic_ctx::DecBatch &B = ctx->dbat;
+    if (up_bytes > B.in_cap) {
+        size_t hcap = B.in_cap, dcap = B.in_cap;
+        B.in_cap = 0;
+        int rc = grow_pinned(ctx, B.h_in, hcap, up_bytes, up_bytes + up_bytes / 4);
+        if (rc) return rc;
+        rc = grow_dev(ctx, B.d_in, dcap, up_bytes, up_bytes + up_bytes / 4);
+        if (rc) return rc;
+        B.in_cap = dcap;
+    }
+    return grow_dev(ctx, B.d_pix, B.pix_cap, pix_bytes, pix_bytes + pix_bytes / 4);
+}
+
 // Descriptors, buffers, ONE upload - descriptors, the frame of every measure wave, the frame of every fused workgroup, the streams - and the two
 // launches.  *refused: the launcher's host-side checks said no (every one of them comes before its first launch): nothing runs, and the stream
 // has drained - the upload still read the pinned buffer the next chunk is packed into.
@@ -3368,16 +3392,7 @@ static int dbatch_enqueue(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame
     }
     const DecUploadLayout up(F, tiles, wgs, c.words);
     int rc;
-    if (up.up_bytes > B.in_cap) { // the pinned upload buffer and its device mirror grow together
-        size_t hcap = B.in_cap, dcap = B.in_cap;
-        B.in_cap = 0;
-        rc = grow_pinned(ctx, B.h_in, hcap, up.up_bytes, up.up_bytes + up.up_bytes / 4);
-        if (rc) return rc;
-        rc = grow_dev(ctx, B.d_in, dcap, up.up_bytes, up.up_bytes + up.up_bytes / 4);
-        if (rc) return rc;
-        B.in_cap = dcap;
-    }
-    rc = grow_dev(ctx, B.d_pix, B.pix_cap, c.pix_bytes, c.pix_bytes + c.pix_bytes / 4);
+    rc = dbatch_grow(ctx, up.up_bytes, c.pix_bytes);
     if (rc) return rc;
     const size_t wb = dec_work_provision_bytes(F, c.ranges288, c.blocks);
     rc = B.ws.grow(ctx, wb, wb + wb / 4, 4 * (size_t)((tiles > wgs ? tiles : wgs) + 2), F, F < 256 ? 256 : 2 * (size_t)F);
@@ -3421,9 +3436,9 @@ static int dbatch_enqueue(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame
 // (the direct copy is `total` bytes long, the device buffer's padding between two frames included: it may only cover bytes the caller gave away -
 //  a frame of a whole number of 256 B has none behind it, elsewhere caps[] must reach to the next frame; an arena of frames at
 //  256-byte aligned distances with caps[i] = h * w takes the pinned route, and the bytes between its frames stay the caller's)
-static int dbatch_download(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame *pf, const DecPlanChunk &c, bool *direct) {
+// (shared by tic_decompress_batch and tic_decompress_batch_adaptive: Frame is a frame of either plan - index, h, w, pitch, pix_off)
+extern "C++" template <class Frame> static int dbatch_pixels_down(tic_ctx *ctx, const DecBatchIO &io, const Frame *pf, size_t F, size_t pix_bytes, bool *direct) {
     tic_ctx::DecBatch &B = ctx->dbat;
-    const size_t F = (size_t)c.count;
     BT_START();
     bool dense = true;
     for (size_t k = 0; k < F && dense; k++) dense = pf[k].pitch == (size_t)pf[k].w;
@@ -3446,19 +3461,38 @@ static int dbatch_download(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFram
         if (reg && hipHostUnregister(reg) != hipSuccess) (void)hipGetLastError();
     }
     if (!*direct) {
-        const int rc = grow_pinned(ctx, B.h_pix, B.hpix_cap, c.pix_bytes, c.pix_bytes + c.pix_bytes / 4);
+        const int rc = grow_pinned(ctx, B.h_pix, B.hpix_cap, pix_bytes, pix_bytes + pix_bytes / 4);
         if (rc) return rc;
-        HIPCHK(ctx, hipMemcpyAsync(B.h_pix, B.d_pix, c.pix_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(B.h_pix, B.d_pix, pix_bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     BT_STOP(2);
+    return TIC_OK;
+}
+static int dbatch_download(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame *pf, const DecPlanChunk &c, bool *direct) {
+    const int rc = dbatch_pixels_down(ctx, io, pf, (size_t)c.count, c.pix_bytes, direct);
+    if (rc) return rc;
     ctx->last_dbatch_chunks++;
-    ctx->last_dbatch_direct += *direct ? (int)F : 0;
+    ctx->last_dbatch_direct += *direct ? c.count : 0;
     return TIC_OK;
 }
 
+// The complete frames (good[k]) leave the pinned buffer on a few threads, unless the download was direct.
+extern "C++" template <class Frame> static void dbatch_hand_out(tic_ctx *ctx, const DecBatchIO &io, const Frame *pf, int F, size_t pix_bytes, bool direct, const std::vector<char> &good) {
+    tic_ctx::DecBatch &B = ctx->dbat;
+    BT_START();
+    if (!direct) {
+        const int T = pix_bytes < (2u << 20) || F < 2 ? 1 : (F < 8 ? F : 8);
+        run_strided(F, T, [ctx]() { bind_pipeline_thread(ctx); }, [&](int k) {
+            const Frame &f = pf[k];
+            if (good[(size_t)k]) copy_rows(io.outs[f.index], (size_t)f.w, B.h_pix + f.pix_off, (ptrdiff_t)f.pitch, f.h, f.w);
+        });
+    }
+    BT_STOP(4);
+}
+
 // What the kernels report, frame by frame (dec_status_complete): a frame that is complete counts, any other goes to `later`; then the complete
-// ones leave the pinned buffer on a few threads, unless the download was direct.
+// ones are handed out.
 static void dbatch_settle(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame *pf, const DecPlanChunk &c, bool direct, std::vector<int> *later) {
     tic_ctx::DecBatch &B = ctx->dbat;
     const int F = c.count;
@@ -3468,15 +3502,7 @@ static void dbatch_settle(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame
         if (good[(size_t)k]) ctx->last_dbatch_frames++;
         else later->push_back(pf[k].index);
     }
-    BT_START();
-    if (!direct) {
-        const int T = c.pix_bytes < (2u << 20) || F < 2 ? 1 : (F < 8 ? F : 8);
-        run_strided(F, T, [ctx]() { bind_pipeline_thread(ctx); }, [&](int k) {
-            const DecPlanFrame &f = pf[k];
-            if (good[(size_t)k]) copy_rows(io.outs[f.index], (size_t)f.w, B.h_pix + f.pix_off, (ptrdiff_t)f.pitch, f.h, f.w);
-        });
-    }
-    BT_STOP(4);
+    dbatch_hand_out(ctx, io, pf, F, c.pix_bytes, direct, good);
 }
 
 // decompress() of MANY streams at once (the mirror of tic_compress_batch; the reference's benchmark loop, tests/benchmark.py:12-23, decodes
@@ -4159,9 +4185,8 @@ static bool adaptive_device_takes(size_t n, size_t len, size_t payload_bit) {
     if (const char *e = test_hook("TIC_DECODE_MIN_BLOCKS")) min_blocks = (size_t)atol(e);
     if (const char *e = test_hook("TIC_DECODE_MIN_BITS")) min_bits = (size_t)atol(e);
     if (test_hook("TIC_DECODE_HOST")) return false;
-    const size_t bits = len * 8;
-    if (n == 0 || n >= (1ull << 31) || bits <= payload_bit || bits + 8192 >= (1ull << 32)) return false;
-    return n >= 16384 || (n >= min_blocks && bits - payload_bit >= min_bits);
+    if (!adaptive_dec_fits(n, len, payload_bit)) return false;
+    return n >= 16384 || (n >= min_blocks && len * 8 - payload_bit >= min_bits);
 }
 
 // The device decoder on a stream it takes, with the tables in ctx->adec_tab: coefficients into ctx->d_coef.  *done = false (and TIC_OK) after a give-up
@@ -4274,17 +4299,245 @@ static int decompress_adaptive_impl(tic_ctx *ctx, const uint8_t *data, size_t le
     return idct_from_device(ctx, h, w, q, -1, out, out_on_device, out_stride);
 }
 
+// The header checks of tic_decompress_adaptive and tic_decompress_batch_adaptive.  frame >= 0: the messages name the frame of a batch.
+static int check_adaptive_header(tic_ctx *ctx, const uint8_t *data, size_t len, const uint8_t *out, size_t cap, int *h_out, int *w_out, int *q_out, int frame = -1) {
+    char pre[32] = "";
+    if (frame >= 0) snprintf(pre, sizeof pre, "frame %d: ", frame);
+    int h = 0, w = 0, q = 0;
+    uint32_t flag = 0;
+    if (parse_header(data, len, &h, &w, &q, &flag) != TIC_OK) return set_err(ctx, TIC_E_STREAM, "%sstream shorter than its 16-byte header", pre);
+    if (h < 0 || w < 0) return set_err(ctx, TIC_E_STREAM, "%snegative image size in the header", pre);
+    if (q < 1 || q > 99) return set_err(ctx, TIC_E_STREAM, "%squality %d in the header outside 1..99", pre, q);
+    if ((size_t)h * (size_t)w > cap || (!out && h && w)) return set_err(ctx, TIC_E_SPACE, "%soutput buffer too small", pre);
+    *h_out = h, *w_out = w, *q_out = q;
+    return TIC_OK;
+}
+
 int tic_decompress_adaptive(tic_ctx *ctx, const uint8_t *data, size_t len, uint8_t *out, size_t cap) {
     TIC_LOCK(ctx);
     if (!ctx) return TIC_E_ARG;
     ctx->last_decode_giveup = 0;
     int h = 0, w = 0, q = 0;
-    uint32_t flag = 0;
-    if (parse_header(data, len, &h, &w, &q, &flag) != TIC_OK) return set_err(ctx, TIC_E_STREAM, "stream shorter than its 16-byte header");
-    if (h < 0 || w < 0) return set_err(ctx, TIC_E_STREAM, "negative image size in the header");
-    if (q < 1 || q > 99) return set_err(ctx, TIC_E_STREAM, "quality %d in the header outside 1..99", q);
-    if ((size_t)h * (size_t)w > cap || (!out && h && w)) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
+    const int rc = check_adaptive_header(ctx, data, len, out, cap, &h, &w, &q);
+    if (rc) return rc;
     return decompress_adaptive_impl(ctx, data, len, false, data, len, h, w, q, out, false, 0);
+}
+
+// ---- tic_decompress_batch_adaptive: decompress_adaptive() of MANY streams at once ---------------------------------------------------------------
+// The fixed cost of a device decode of an adaptive stream - seven launches, a table upload, a status read-back, a synchronisation
+// (profiles/adaptive_decode.txt section 1) - is per submission, not per frame: the frames of a chunk (tic_adaptive_decode_plan.h) share ONE
+// upload (descriptors, workgroup tables, a look-up table per frame built on the host, the streams), one launch per kernel of the descriptor
+// form (tic_adaptive_dec_gpu.hip), one launch of the inverse transform (idct_batch_kernel) and one download (dbatch_pixels_down).
+
+// Which frames the batch kernels take: blocks, a table that parses and builds (no code of length zero: the flat and one-block frames are
+// the host decoder's), bit positions that fit 32 bits, and no TIC_DECODE_HOST in the hooks build.  The size thresholds of
+// adaptive_device_takes (kAdaptDevMinBlocks / kAdaptDevMinBits) do NOT apply: they were measured against the fixed cost of a submission, and
+// the frames of a batch share that cost.  No floor on frames or payload per call is applied beyond "two taken frames at least" (a call
+// with fewer is the single call, thresholds included): tools/adaptive_decode_batch_timing.py measures the batch against the loop on small
+// and large frames (profiles/adaptive_decode_batch.txt), and a floor is to be settled from there, not guessed here.
+static bool adaptive_batch_takes(size_t nblocks, const uint8_t *data, size_t len, AdaptTable *t) {
+    if (nblocks == 0 || test_hook("TIC_DECODE_HOST")) return false;
+    if (adaptive_parse_table(data, len < 16 + kAdaptMaxTableBytes ? len : 16 + kAdaptMaxTableBytes, t, nullptr) != TIC_OK) return false;
+    return adaptive_dec_tab_buildable(*t) && adaptive_dec_fits(nblocks, len, t->payload_bit);
+}
+
+// A chunk through the kernels: buffers, ONE upload, the rounds protocol (tic_adaptive_dec_gpu.hip header comment), the pixels in ctx->dbat.d_pix.
+// good[k]: frame k is complete there.  Every way out with an error lies in front of `good`.
+static int adbatch_decode(tic_ctx *ctx, const DecBatchIO &io, const AdaptDecPlanFrame *pf, const AdaptDecPlanChunk &c, const AdaptTable *tabs, std::vector<char> *good) {
+    tic_ctx::DecBatch &B = ctx->dbat;
+    tic_ctx::AdaptDecBatchBuf &A = ctx->adbat;
+    const uint32_t F = (uint32_t)c.count;
+    size_t iwgs = 0;
+    std::vector<IdctArgs> ia(F);
+    for (uint32_t k = 0; k < F; k++) {
+        ia[k] = idct_args(dec_idct_args(ctx, pf[k].h, pf[k].w, pf[k].quality, -1, nullptr, (long)pf[k].pitch, nullptr), nullptr);
+        iwgs += (size_t)idct_batch_wgs(ia[k].ntiles);
+    }
+    const AdaptDecUploadLayout up(c, sizeof(IdctArgs), iwgs);
+    const AdaptDecWorkLayout wl(c);
+    int rc = dbatch_grow(ctx, up.up_bytes, c.pix_bytes);
+    if (rc) return rc;
+    rc = grow_dev(ctx, A.d_work, A.work_cap, wl.bytes, wl.bytes + wl.bytes / 4);
+    if (rc) return rc;
+    rc = grow_pinned(ctx, A.h_status, A.status_cap, wl.status_bytes, 2 * wl.status_bytes);
+    if (rc) return rc;
+    BT_START();
+    AdaptDecFrame *hf = (AdaptDecFrame *)(B.h_in + up.o_frames);
+    IdctArgs *hia = (IdctArgs *)(B.h_in + up.o_idct_args);
+    uint2 *hiw = (uint2 *)(B.h_in + up.o_idct_wgs);
+    adec_plan_fill_wg_tables(pf, c.count, (uint32_t *)(B.h_in + up.o_rwg), (uint32_t *)(B.h_in + up.o_bwg));
+    size_t g = 0;
+    for (uint32_t k = 0; k < F; k++) {
+        const AdaptDecPlanFrame &f = pf[k];
+        hf[k] = f.d;
+        ia[k].coeffs = (const int16_t *)(A.d_work + wl.o_coef) + (size_t)f.d.blk0 * 64;
+        ia[k].out = B.d_pix + f.pix_off;
+        memcpy(&hia[k], &ia[k], sizeof(IdctArgs));
+        for (int t = 0; t < ia[k].ntiles; t += idct_batch_tiles_per_wg()) hiw[g++] = make_uint2(k, (uint32_t)t);
+        if (!adaptive_dec_tab_build(tabs[k], (AdaptDecTab *)(B.h_in + up.o_tabs + f.tab_off))) return set_err(ctx, TIC_E_ARG, "frame %d: no look-up table for a table that parsed", f.index);
+        memcpy(B.h_in + up.o_streams + (size_t)f.d.word0 * 4, io.streams[f.index], f.len); // (the bytes behind a stream's last word are never read)
+    }
+    BT_STOP(0);
+    BT_START();
+    HIPCHK(ctx, hipMemcpyAsync(B.d_in, B.h_in, up.up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    AdaptDecBatch a;
+    a.frames = (const AdaptDecFrame *)(B.d_in + up.o_frames);
+    a.rwg_frame = (const uint32_t *)(B.d_in + up.o_rwg), a.bwg_frame = (const uint32_t *)(B.d_in + up.o_bwg);
+    a.tabs = (const char *)(B.d_in + up.o_tabs);
+    a.words = (const uint32_t *)(B.d_in + up.o_streams);
+    a.work = A.d_work + wl.o_work;
+    a.cs = (AdaptDecChunkStatus *)(A.d_work + wl.o_status);
+    a.fs = (AdaptDecFrameStatus *)(a.cs + 1);
+    a.zz = (int16_t *)(A.d_work + wl.o_coef);
+    a.nframes = F, a.ranges = c.ranges, a.blocks = (uint32_t)c.blocks, a.range_wgs = c.range_wgs, a.block_wgs = c.block_wgs;
+    const AdaptDecChunkStatus *cs = (const AdaptDecChunkStatus *)A.h_status;
+    const AdaptDecFrameStatus *fs = (const AdaptDecFrameStatus *)(cs + 1);
+    const auto run = [&](int round0, int nrounds, bool finish) -> int {
+        HIPCHK(ctx, adaptive_decode_gpu_batch(a, round0, nrounds, finish, ctx->stream));
+        if (finish) HIPCHK(ctx, launch_idct_batch((const IdctArgs *)(B.d_in + up.o_idct_args), (const uint2 *)(B.d_in + up.o_idct_wgs), iwgs, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(A.h_status, a.cs, wl.status_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (test_hook("TIC_DECODE_TRACE")) {
+            const int lastr = round0 + nrounds - 1; // (the last round launched so far: round0 >= 1 where nrounds is 0)
+            uint32_t moving = 0;
+            for (uint32_t k = 0; k < F; k++) moving += fs[k].changed[lastr] != 0;
+            fprintf(stderr, "adaptive batch decode: %u frames, rounds %d..%d%s, exits moved in round %d: %u, frames still moving: %u\n", F, round0, lastr,
+                    finish ? " and the passes" : "", lastr, cs->changed[lastr], moving);
+        }
+        return TIC_OK;
+    };
+    int last = kAdaptBatchRounds0 - 1;
+    rc = run(0, kAdaptBatchRounds0, true);
+    if (rc) return rc;
+    if (cs->changed[last]) {
+        rc = run(kAdaptBatchRounds0, kAdaptBatchRoundsMore, false);
+        if (rc) return rc;
+        last = kAdaptBatchRounds - 1;
+        rc = run(kAdaptBatchRounds, 0, true); // (a frame round 18 still moved is marked below: whatever the passes leave of it is never handed out)
+        if (rc) return rc;
+    }
+    BT_STOP(1);
+    good->assign(F, 0);
+    // (a frame that settled early keeps zeros in the rounds it left at once)
+    for (uint32_t k = 0; k < F; k++) (*good)[k] = (fs[k].giveup | (fs[k].changed[last] ? kAdaptGiveupNoSync : 0u)) == 0;
+    return TIC_OK;
+}
+
+int tic_decompress_batch_adaptive(tic_ctx *ctx, const uint8_t *const *streams, const size_t *lens, int n, uint8_t *const *outs, const size_t *caps, int *hs, int *ws) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (n < 0 || (n > 0 && (!streams || !lens || !outs || !caps))) return set_err(ctx, TIC_E_ARG, "bad batch arguments");
+    ctx->last_adbatch_frames = ctx->last_adbatch_single = ctx->last_adbatch_chunks = ctx->last_adbatch_direct = 0;
+    ctx->bt = BatchTrace(); // (tic_last_batch_phases: [0] packing the upload buffer, [1] upload, kernels and status, [2] download, [4] hand-out, [5] single-frame calls)
+    if (n == 0) return TIC_OK;
+    if (n == 1) { // exactly the single call
+        const int rc = tic_decompress_adaptive(ctx, streams[0], lens[0], outs[0], caps[0]);
+        if (rc == TIC_OK || lens[0] >= 16) {
+            int h = 0, w = 0, q = 0;
+            uint32_t flag = 0;
+            (void)parse_header(streams[0], lens[0], &h, &w, &q, &flag);
+            if (hs) hs[0] = h;
+            if (ws) ws[0] = w;
+        }
+        ctx->last_adbatch_single = 1;
+        return rc;
+    }
+    // ---- the checks of tic_decompress_adaptive, for every frame, before any work
+    std::vector<AdaptDecPlanIn> in((size_t)n);
+    std::vector<AdaptTable> tabs; // of the frames taken, in order
+    std::vector<int> later;       // frames for the single-frame call
+    {
+        AdaptTable t;
+        for (int i = 0; i < n; i++) {
+            int h = 0, w = 0, q = 0;
+            const int rc = check_adaptive_header(ctx, streams[i], lens[i], outs[i], caps[i], &h, &w, &q, i);
+            if (rc) return rc;
+            if (hs) hs[i] = h;
+            if (ws) ws[i] = w;
+            in[(size_t)i] = {h, w, q, lens[i], 0, adaptive_batch_takes(num_blocks(h, w), streams[i], lens[i], &t)};
+            if (in[(size_t)i].takes) in[(size_t)i].payload_bit = t.payload_bit, tabs.push_back(t);
+        }
+    }
+    if (tabs.size() < 2) { // (adaptive_batch_takes: no batch of one)
+        for (AdaptDecPlanIn &f : in) f.takes = false;
+        tabs.clear();
+    }
+    for (int i = 0; i < n; i++)
+        if (!in[(size_t)i].takes) later.push_back(i);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // ---- the plan: chunks of frames in order, inside the limits (the 294 frames of the benchmark set - 77 MB of pixels, 154 MB of coefficients,
+    // 4 MB of tables - are one chunk; so are sixteen 1080p frames)
+    AdaptDecPlanLimits lim = {(size_t)96 << 20, (size_t)288 << 20, (size_t)256 << 20, (size_t)16 << 20, 1024};
+    if (const char *e = test_hook("TIC_ADBATCH_CHUNK")) lim.frames = atoi(e) >= 1 && atoi(e) <= 1024 ? atoi(e) : lim.frames; // (tests: several chunks)
+    const AdaptDecPlan plan = plan_adaptive_decode_batch(in.data(), n, lim);
+    const DecBatchIO io = {streams, lens, outs, caps};
+    int result = TIC_OK;
+    std::string first_err; // (the text of an error inside a chunk: the single-frame calls behind it write their own)
+    for (const AdaptDecPlanChunk &c : plan.chunks) {
+        const AdaptDecPlanFrame *pf = &plan.frames[(size_t)c.first];
+        std::vector<char> good;
+        bool direct = false;
+        int crc = adbatch_decode(ctx, io, pf, c, &tabs[(size_t)c.first], &good);
+        if (crc == TIC_OK) crc = dbatch_pixels_down(ctx, io, pf, (size_t)c.count, c.pix_bytes, &direct);
+        if (crc == TIC_OK) {
+            ctx->last_adbatch_chunks++;
+            ctx->last_adbatch_direct += direct ? c.count : 0;
+            for (int k = 0; k < c.count; k++) {
+                if (good[(size_t)k]) ctx->last_adbatch_frames++;
+                else later.push_back(pf[k].index);
+            }
+            dbatch_hand_out(ctx, io, pf, c.count, c.pix_bytes, direct, good);
+            continue;
+        }
+        // ended early by a failed allocation, copy or launch: its frames and those of the chunks behind it go one by one; the error is the first and stands
+        for (size_t k = (size_t)c.first; k < plan.frames.size(); k++) later.push_back(plan.frames[k].index);
+        result = crc;
+        first_err = ctx->err;
+        break;
+    }
+    // ---- frames the batch did not take, or gave up on: the single call, which alone decides between pixels and TIC_E_STREAM and words the message.
+    // (after a direct download a given-up frame's bytes in the caller's buffer hold what the kernels left: the single call overwrites them, or fails)
+    std::sort(later.begin(), later.end());
+    BT_START();
+    for (int i : later) {
+        const int rc = tic_decompress_adaptive(ctx, streams[i], lens[i], outs[i], caps[i]);
+        ctx->last_adbatch_single++;
+        if (rc != TIC_OK && result == TIC_OK) {
+            const std::string m = ctx->err;
+            result = set_err(ctx, rc, "frame %d: %s", i, m.c_str());
+            first_err = ctx->err;
+        }
+    }
+    BT_STOP(5);
+    if (!first_err.empty()) ctx->err = first_err;
+    return result;
+}
+
+// How the last tic_decompress_batch_adaptive went: frames decoded by the batch kernels, frames that took the single call (not taken, or given
+// up on), chunks.  Any pointer may be null.
+int tic_last_decompress_batch_adaptive(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (batch_frames) *batch_frames = ctx->last_adbatch_frames;
+    if (single_frames) *single_frames = ctx->last_adbatch_single;
+    if (chunks) *chunks = ctx->last_adbatch_chunks;
+    return TIC_OK;
+}
+
+// ... and the frames of its chunks whose pixels were copied straight into the caller's memory (the direct download)
+int tic_last_decompress_batch_adaptive_direct(tic_ctx *ctx) {
+    TIC_LOCK(ctx);
+    return ctx ? ctx->last_adbatch_direct : TIC_E_ARG;
+}
+
+// The device decoder's geometry for a stream of `len` bytes whose payload starts at bit `payload_bit` and holds `nblocks` blocks: stream
+// bits per lane (adaptive_dec_range_bits) and the number of ranges - a workgroup of the range grid holds 256 of them.  Pure arithmetic.
+int tic_adaptive_decode_geometry(size_t len, size_t payload_bit, size_t nblocks, int *range_bits, size_t *nranges) {
+    if (!adaptive_dec_fits(nblocks, len, payload_bit)) return TIC_E_ARG;
+    const int r = adaptive_dec_range_rule(len, payload_bit, nblocks);
+    if (range_bits) *range_bits = r;
+    if (nranges) *nranges = adaptive_dec_ranges_of(len, payload_bit, r);
+    return TIC_OK;
 }
 
 int tic_decompress_adaptive_dev(tic_ctx *ctx, const void *d_stream, size_t len, void *d_out, ptrdiff_t out_stride, size_t out_cap, int *h_out, int *w_out) {

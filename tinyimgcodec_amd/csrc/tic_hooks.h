@@ -14,6 +14,7 @@
 //   TIC_BATCH_CHUNK         tic_compress_batch, tic_compress_batch_v, tic_compress_batch_adaptive_v: frames per chunk instead of the choice by frame size
 //   TIC_BATCH_CHUNK_BYTES   tic_compress_batch_v, tic_compress_batch_adaptive_v: staged pixels per chunk instead of 32 MB (a larger frame is coded alone, behind the batch)
 //   TIC_DBATCH_CHUNK        tic_decompress_batch: frames per chunk instead of 1,024 (1 ... 1024; anything else is ignored)
+//   TIC_ADBATCH_CHUNK       tic_decompress_batch_adaptive: frames per chunk instead of 1,024 (1 ... 1024; anything else is ignored)
 //   TIC_DBATCH_WORK_CAP     tic_decompress_batch: at most this many bytes of work buffer are handed to the batch launcher (it refuses a chunk that needs more)
 //   TIC_DECODE_NO_GUESS     tic_decompress_dev always reads the header first (no launch on a guess of it)
 //   TIC_NO_SMALL_PATH       tic_compress of small frames through the device stream buffer and a DMA copy, as large ones (not through host-mapped memory)

@@ -103,6 +103,11 @@ int dctq_kernel_id(int abi_variant);
 hipError_t launch_dctq(DctqArgs a, int variant, hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 hipError_t launch_dctq_wide(const WideArgs &a, hipStream_t stream);
 hipError_t launch_idct(const IdctArgs &a, hipStream_t stream);
+// One launch for the frames of a chunk: d_args[f] (device memory; whole-frame form, no dc32) and a table of nwgs workgroups, {frame, first
+// tile} each - idct_batch_wgs(ntiles) workgroups per frame, idct_batch_tiles_per_wg() tiles apart.
+int idct_batch_wgs(int ntiles);
+int idct_batch_tiles_per_wg();
+hipError_t launch_idct_batch(const IdctArgs *d_args, const uint2 *d_wgs, size_t nwgs, hipStream_t stream);
 hipError_t launch_idct_sse(const IdctArgs &a, const SseArgs &m, hipStream_t stream);
 hipError_t launch_selftest_transpose(const void *in, void *out_dpp, void *out_ref, int nthreads, hipStream_t stream);
 

@@ -889,12 +889,12 @@ __constant__ int kAnnScalesInt[64] = {
 // kWideDc: the DC comes from a.dc32 (IdctArgs: a stream whose running DC left int16), everything else as ever
 // kMeasure: the measuring epilogue (idct_sse_kernel): the decoded pixels are compared with the frame `m` describes instead of being stored
 template <bool kWideDc, bool kMeasure = false>
-__device__ __forceinline__ void idct_body(const IdctArgs &a, const SseArgs *m = nullptr) {
+__device__ __forceinline__ void idct_body(const IdctArgs &a, int wg_tile0, const SseArgs *m = nullptr) {
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[kWavesPerWG][kLdsWaveBytes / 4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = lane >> 3, i = lane & 7;
     uint32_t *lds = lds_all[wave];
-    const int tile = blockIdx.x * kWavesPerWG + wave;
+    const int tile = wg_tile0 + wave; // (wg_tile0: the workgroup's first tile)
     const DctqConsts *__restrict__ C = a.consts;
     Strip s = make_strip(tile, a.ntiles, a.tiles_x, a.bw, b);
     if (a.first_block >= 0) { // block-range form: 8 consecutive blocks of the raster order per wave
@@ -1024,10 +1024,17 @@ __device__ __forceinline__ void idct_body(const IdctArgs &a, const SseArgs *m = 
             if (x0 + k < a.w) p[k] = (uint8_t)px[k];
     }
 }
-__global__ __launch_bounds__(kWavesPerWG * 64) void idct_kernel(IdctArgs a) { idct_body<false>(a); }
-__global__ __launch_bounds__(kWavesPerWG * 64) void idct_wide_dc_kernel(IdctArgs a) { idct_body<true>(a); }
+__global__ __launch_bounds__(kWavesPerWG * 64) void idct_kernel(IdctArgs a) { idct_body<false>(a, blockIdx.x * kWavesPerWG); }
+__global__ __launch_bounds__(kWavesPerWG * 64) void idct_wide_dc_kernel(IdctArgs a) { idct_body<true>(a, blockIdx.x * kWavesPerWG); }
 // The measuring instantiation: decode and compare, no pixel written (tic_distortion_dev, tic_rd_points_dev, tic_compress_to_psnr_dev).
-__global__ __launch_bounds__(kWavesPerWG * 64) void idct_sse_kernel(IdctArgs a, SseArgs m) { idct_body<false, true>(a, &m); }
+__global__ __launch_bounds__(kWavesPerWG * 64) void idct_sse_kernel(IdctArgs a, SseArgs m) { idct_body<false, true>(a, blockIdx.x * kWavesPerWG, &m); }
+// The descriptor form: the frames of a chunk in one launch (tic_decompress_batch_adaptive).  Workgroup g transforms the kWavesPerWG tiles from
+// wgs[g].y on of frame wgs[g].x, whose arguments are args[wgs[g].x]; a frame has ceil(ntiles / kWavesPerWG) workgroups.
+__global__ __launch_bounds__(kWavesPerWG * 64) void idct_batch_kernel(const IdctArgs *__restrict__ args, const uint2 *__restrict__ wgs) {
+    const uint2 e = wgs[blockIdx.x];
+    const IdctArgs a = args[e.x];
+    idct_body<false>(a, (int)e.y);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // Self-test kernel: checks the DPP byte transpose against the shuffle formulation on arbitrary data.
@@ -1254,6 +1261,14 @@ hipError_t launch_idct(const IdctArgs &a, hipStream_t stream) {
     dim3 grid(grid_for(a.ntiles)), block(kWavesPerWG * 64);
     if (a.dc32) hipLaunchKernelGGL(idct_wide_dc_kernel, grid, block, 0, stream, a);
     else hipLaunchKernelGGL(idct_kernel, grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+int idct_batch_wgs(int ntiles) { return grid_for(ntiles); }
+int idct_batch_tiles_per_wg() { return kWavesPerWG; }
+hipError_t launch_idct_batch(const IdctArgs *d_args, const uint2 *d_wgs, size_t nwgs, hipStream_t stream) {
+    if (!d_args || !d_wgs || nwgs == 0 || nwgs > 0x7fffffffu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(idct_batch_kernel, dim3((uint32_t)nwgs), dim3(kWavesPerWG * 64), 0, stream, d_args, d_wgs);
     return hipGetLastError();
 }
 
