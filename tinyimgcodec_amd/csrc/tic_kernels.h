@@ -46,10 +46,12 @@ struct DctqArgs {
     int nframes;
     long frame_stride_in, frame_stride_out;
     unsigned long long *dbg; // diagnostic builds only: per-wave s_memtime stamps (8 per wave), else null
-    // strip kernel (round 2): division-free prologue.  q = mulhi(n, magic) with magic = floor(2^32 / d) + 1 is n / d for
-    // n * d < 2^32 (checked by the launcher).  The team schedule runs on a 2-D grid (x = team, y = round) and takes the
-    // rows of round r from byte r of split_lo (byte 8: split_hi).
-    uint32_t magic_fast_tx, magic_tstep;
+    // The strip kernel's start does not read this struct: its schedule words travel in front of it as scalar kernel arguments
+    // (StripHead, StripWarm: tic_strip_plan.h, whose strip_plan() computes everything from nwaves to here).  The launcher still
+    // fills the fields - the kernel's rare paths and the exact kernel's remainder mode read them.
+    // q = mulhi(n, magic) with magic = floor(2^32 / d) + 1 is n / d for n * d < 2^32 (checked by the plan).  The team schedule runs
+    // on a 2-D grid (x = team, y = round) and takes the rows of round r from byte r of split_lo (byte 8: split_hi).
+    uint32_t magic_fast_tx, magic_tstep; // (magic_tstep: of round_wgs, round-interleaved schedule only)
     unsigned long long split_lo, split_hi;
 };
 

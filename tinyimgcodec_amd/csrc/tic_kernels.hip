@@ -18,6 +18,7 @@
 //           behind the loop in float64 (wave_redo_block / second_level_8), and only what that cannot decide takes the exact order.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,6 +26,7 @@
 
 #include "tic_hooks.h"
 #include "tic_kernels.h"
+#include "tic_strip_plan.h"
 #include "tic_math.h"
 
 namespace tic {
@@ -99,6 +101,7 @@ __device__ __forceinline__ int reflect_index(int i, int n) {
 }
 
 constexpr int kWavesPerWG = 4;      // (8-wave workgroups, three per CU, measured level: profiles/r02_ab_wg8.txt)
+static_assert(kWavesPerWG == kStripWavesPerWG, "tic_strip_plan.h plans for this workgroup");
 constexpr int kLdsStrideDw = 68;    // dwords per block in the transpose buffer (64 + 4 pad; bank analysis in DESIGN.md)
 constexpr int kZzStrideB = 144;     // bytes per block in the zig-zag staging buffer (128 + 16 pad)
 constexpr int kLdsWaveBytes = 8 * kLdsStrideDw * 4; // 2176 B per wave (>= 8*144)
@@ -272,7 +275,6 @@ constexpr int kTHalfDw = 272;                     // dword offset of the half th
                                                   // 32-lane write group fall into different banks)
 constexpr int kZzWaveBytes = 8 * kZzStrideB;      // 1152 B zig-zag staging per wave; its first 640 B double as the byte-transpose buffer
 constexpr int kPxBlkBytes = 80;                   // byte-transpose buffer: 64 pixel bytes per block + 16 (bank spread of the b64 writes)
-constexpr int kMaxStripsPerWave = 16;             // a grid is "larger than the chip" when its waves would walk more strips than this
 constexpr int kChunkStrips = 8;                   // chunked schedule: strips per wave (a workgroup streams 32 adjacent strips).  With the
                                                   // sc1 nt stores 8 beats round 2's 16: 256 x 1080p 270 against 288 us, 8192^2 37.3 against
                                                   // 38.4, 16384^2 120 against 121 (profiles/r03_ab_chunk.txt)
@@ -305,7 +307,6 @@ __device__ __forceinline__ void store16_wt_nt(const void *sbase, uint32_t voff, 
     asm volatile("global_store_dwordx4 %0, %1, %2 sc1 nt" : : "v"(voff), "v"(d), "s"(sbase) : "memory");
 }
 
-constexpr int kMaxStripsPerWave2 = 64;                 // one bit per strip of a wave's walk in the exact-redo mask
 constexpr int kBatch = 8;                              // entries of the wave's batch
 constexpr int kBatchWaveBytes = kBatch * (128 + 64) + 64; // images, pixel rows, ids
 
@@ -446,6 +447,26 @@ __device__ __forceinline__ uint32_t second_level_8(uint32_t colLo, uint32_t colH
     return und;
 }
 
+// The strip kernel's arguments as they lie in the kernel-argument segment (every argument at its natural alignment, in order).
+struct StripKernargs {
+    const uint8_t *img;
+    const DctqConsts *consts;
+    StripHead hd;
+    StripWarm w;
+    DctqArgs a;
+};
+static_assert(offsetof(StripKernargs, hd) == 16 && sizeof(StripHead) == 40 && offsetof(StripKernargs, w) == 64, "leading scalars, then one line");
+
+// An LDS pointer as the 32-bit address the ds instructions take, and back.
+template <class T>
+__device__ __forceinline__ uint32_t lds_addr(T *p) {
+    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)(p);
+}
+template <class T>
+__device__ __forceinline__ T *lds_ptr(uint32_t v) {
+    return (T *)(__attribute__((address_space(3))) T *)(uintptr_t)v;
+}
+
 // kCols: the pass order of the fast path.  true  - columns first, byte transpose through LDS, ties from the exact column sums (rational_quad):
 //                 grids that fit the chip at once, where every wave owns its strips in advance and the launch ends with the unluckiest one;
 //        false - rows first, the pixels converted straight out of the landing registers (no byte transpose: 22 LDS cycles and a dependent
@@ -453,8 +474,17 @@ __device__ __forceinline__ uint32_t second_level_8(uint32_t colLo, uint32_t colH
 //                 rounds (16384^2, batches), where workgroups are dispatched as others finish and what counts is the average cost per
 //                 strip - 16384^2 at q = 10 / 50 / 90: 107 / 119 / 127 us rows first against 123 / 130 / 137 us columns first
 //                 (profiles/r05_config5.json, r04_config5.json).  Same results, bit for bit (tests run both orders on every rare-path frame).
+//
+// Arguments: the image, the constants and the schedule words of StripHead (tic_strip_plan.h) come first, as scalars - 14 dwords, which
+// the file is compiled to preload (-mllvm -amdgpu-kernarg-preload-count=11, csrc/Makefile: they arrive in user SGPRs s[2:15] at wave
+// launch where the firmware preloads, and through the compiler's compatibility prologue at the kernel's entry where it does not).  The
+// constant-block load, both pixel loads and the walk's start state need nothing else, so no scalar-memory wait stands in front of
+// them.  `w` is the one 64-byte line of what the start needs next (block indices, the output pointer); `a` is read by the rare paths only.
 template <bool kCols>
-__global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr(72))) void dctq_strip_kernel(DctqArgs a) {
+__global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr(72))) void dctq_strip_kernel(
+    const uint8_t *img, const DctqConsts *consts, unsigned long long hd_split, uint32_t hd_stride, uint32_t hd_misc, uint32_t hd_tstep,
+    uint32_t hd_nfast, uint32_t hd_fast_tx, uint32_t hd_magic_fast_tx, uint32_t hd_in_step32, uint32_t hd_step_tx, StripWarm w, DctqArgs a) {
+    const StripHead hd = {hd_split, hd_stride, hd_misc, hd_tstep, hd_nfast, hd_fast_tx, hd_magic_fast_tx, hd_in_step32, hd_step_tx};
     __shared__ __attribute__((aligned(16))) uint32_t ldsT_all[kWavesPerWG][kTWaveBytes / 4];
     __shared__ __attribute__((aligned(16))) uint32_t ldsZ_all[kWavesPerWG][kZzWaveBytes / 4];
     __shared__ __attribute__((aligned(16))) unsigned char cst_blk[kStripBlkBytes]; // constants, shared by the workgroup
@@ -468,9 +498,12 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
     uint4 *bat_img = reinterpret_cast<uint4 *>(bat_all[wave]);                      // [kBatch][8] 16-byte pieces: zig-zag images
     uint2 *bat_pix = reinterpret_cast<uint2 *>(bat_all[wave] + kBatch * 32);        // [kBatch][8] pixel rows
     uint32_t *bat_id = bat_all[wave] + kBatch * 48;                                 // [kBatch] block index
-    const DctqConsts *__restrict__ C = a.consts;
-    a.img += (long)blockIdx.z * a.frame_stride_in; // batch of frames: one grid plane per frame
-    a.out = reinterpret_cast<int16_t *>(reinterpret_cast<char *>(a.out) + (long)blockIdx.z * a.frame_stride_out);
+    const DctqConsts *__restrict__ C = consts;
+    const uint8_t *img_s = img;
+    if (__builtin_expect(blockIdx.z != 0, 0)) { // batch of frames: one grid plane per frame (a branch: plane 0 does not wait for the stride)
+        asm volatile("" : : : "memory");
+        img_s += (long)blockIdx.z * w.frame_stride_in;
+    }
 
     const int lr = lane >> 3, lb = lane & 7; // load phase: pixel row lr of block lb
     const int b = lane >> 3, i = lane & 7;   // compute phase: pixel column c = i of block b (pass 1), frequency row u = i (pass 2)
@@ -478,7 +511,8 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
     uint32_t n_second = 0, n_quad = 0;       // blocks recomputed in float64, strips through rational_quad (statistics)
     int nE = 0;                              // entries in the batch (wave-uniform)
     int t_first, n_my;
-    const uint32_t st_off = (uint32_t)lane * 16u; // lane offset inside a strip's 1 KiB output
+    int16_t *out_f; // the plane's output
+    uint32_t st_off = (uint32_t)lane * 16u; // lane offset inside a strip's 1 KiB output
     {
         typedef float f32x4 __attribute__((ext_vector_type(4)));
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -497,59 +531,21 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
             const uint32_t fo = piece * 16u;
             asm volatile("global_load_dwordx4 v[76:79], %0, %1" : : "v"(fo), "s"(C->strip_blk) : "memory", "v76", "v77", "v78", "v79"); // (lands in reserved registers: see TIC_LOAD)
         }
-        // LDS layouts of the loop (conflict-free: tools/lds_bank_model.py, DESIGN.md 5.1)
-        //   byte transpose : block lb's pixel row lr at lb*80 + lr*8; lane (b, c) reads byte r*8 + c of block b, r = 0..7
-        //   dword transpose: value (u, c) of block b at dword (c>>2)*272 + u*32 + 4*(b ^ s(u)) + (c&3), s(u) = 4 for u in {2,3,6,7}
-        //   zig-zag staging: scan position p of block b at byte (p>>3)*128 + 16*(b ^ f(p>>3)) + 2*(p&7), f(c) = bit 1 of c | 4 * bit 2 of c
-        const uint32_t px_wr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)(ldsZ + lb * kPxBlkBytes + lr * 8);
-        const uint8_t *px_rd = reinterpret_cast<const uint8_t *>(ldsZ + b * kPxBlkBytes + i);
-        // (pass 1 runs in the compute layout - lane 8*b + c - columns first, in the load layout - lane 8*r + b - rows first; the half
-        //  offset of 272 dwords keeps the compute layout's 32-lane write groups conflict-free, the load layout needs none: 256)
-        constexpr int kHalf = kCols ? kTHalfDw : 256;
-        const int p1a = kCols ? i : lr, p1b = kCols ? b : lb;
-        uint32_t *twA = ldsT + (p1a >> 2) * kHalf + (p1a & 3) + 4 * p1b;       // outputs {0,1,4,5}: + k*32 dwords
-        uint32_t *twB = ldsT + (p1a >> 2) * kHalf + (p1a & 3) + 4 * (p1b ^ 4); // outputs {2,3,6,7}
-        const uint4 *tr = reinterpret_cast<const uint4 *>(
-            __builtin_assume_aligned(ldsT + i * 32 + 4 * (b ^ (4 * ((i >> 1) & 1))), 16)); // first half; the second kHalf dwords on
-        const uint32_t ld_off = (uint32_t)(lr * (int)a.stride + lb * 8); // lane offset from the strip's first pixel
+        const uint32_t ld_off = (uint32_t)lr * hd.stride + (uint32_t)lb * 8u; // lane offset from the strip's first pixel
 
-        // Strip walk: one scalar cursor (that of the prefetch).  Its start state takes ~25 scalar instructions: no division
-        // (magic multipliers from the launcher), no per-workgroup memory.  (Measured: the round-1 prologue's ~250 scalar
-        // instructions per wave - four integer divisions - made the last of a CU's five workgroups issue its first load 3,000
-        // cycles after the first, the 20 waves of a CU share one scalar unit; a table of per-wave start states read with s_load
-        // was as slow: the scalar cache serves misses to distinct lines one by one.)
-        uint32_t tf, t_lim;
-        if (a.team_count > 0) { // 2-D grid: x = team, y = round
-            const uint32_t r = blockIdx.y;
-            const uint32_t row0 = (uint32_t)((r < 8u ? a.split_lo >> (8u * r) : a.split_hi) & 0xffull);
-            const uint32_t row1 = (uint32_t)((r < 7u ? a.split_lo >> (8u * r + 8u) : a.split_hi) & 0xffull);
-            tf = (row0 * (uint32_t)a.team_count + blockIdx.x) * kWavesPerWG + (uint32_t)wave;
-            t_lim = tf + (row1 - row0) * (uint32_t)a.tstep;
-        } else if (a.round_wgs > 0) {
-            const uint32_t rho = a.magic_tstep ? __umulhi(blockIdx.x, a.magic_tstep /* = magic of round_wgs in this schedule */) : blockIdx.x;
-            const uint32_t wl = blockIdx.x - rho * (uint32_t)a.round_wgs;
-            const uint32_t base = rho * (uint32_t)a.round_wgs * (uint32_t)a.wg_span;
-            tf = base + wl * kWavesPerWG + (uint32_t)wave;
-            t_lim = base + (uint32_t)a.round_wgs * (uint32_t)a.wg_span;
-        } else {
-            tf = blockIdx.x * (uint32_t)a.wg_stride + (uint32_t)wave;
-            t_lim = blockIdx.x * (uint32_t)a.wg_stride + (uint32_t)a.wg_span;
-        }
-        tf = __builtin_amdgcn_readfirstlane(tf);
-        const uint32_t nfast = (uint32_t)a.fast_ty * (uint32_t)a.fast_tx; // strips handled here: complete, 8-byte aligned, no padding
-        const uint32_t t_end = t_lim < nfast ? t_lim : nfast;                 // first strip past this wave's walk
-        n_my = 0;
-        if (tf < t_end) n_my = (a.round_wgs > 0 || a.magic_tstep == 0u) ? (int)((t_end - tf + (uint32_t)a.tstep - 1u) / (uint32_t)a.tstep)
-                                                                        : (int)__umulhi(t_end - tf + (uint32_t)a.tstep - 1u, a.magic_tstep);
-        if (n_my == 0) tf = 0; // a wave without strips loads (and discards) strip 0
-        t_first = (int)tf;
-        const uint32_t ty_first = a.magic_fast_tx ? __umulhi(tf, a.magic_fast_tx) : tf; // (magic 0: one strip per row)
-        int txp = (int)(tf - ty_first * (uint32_t)a.fast_tx);
-        uint32_t in_off = ty_first * (uint32_t)(8 * a.stride) + (uint32_t)txp * 64u; // frames are < 4 GiB (launcher)
-        uint32_t oblk = ty_first * (uint32_t)a.bw + (uint32_t)txp * 8u;
+        // Strip walk: one scalar cursor (that of the prefetch).  Its start state is strip_cursor (tic_strip_plan.h, walked on the host by
+        // tests/native/strip_plan_selftest.cpp) over preloaded words: no scalar-memory wait, no division in the rows and chunk schedules,
+        // no per-workgroup memory.  Counts of the shipped binary: DESIGN.md 5.1.  (Measured in round 1: a prologue of ~250 scalar
+        // instructions per wave - four integer divisions - made the last of a CU's five workgroups issue its first load 3,000 cycles
+        // after the first, the 20 waves of a CU share one scalar unit; a table of per-wave start states read with s_load was as slow:
+        // the scalar cache serves misses to distinct lines one by one.)
+        const StripCursor cur = strip_cursor(hd, w, blockIdx.x, blockIdx.y, (uint32_t)wave);
+        n_my = cur.n_my;
+        t_first = (int)cur.t_first;
+        uint32_t txp = cur.txp, in_off = cur.in_off, oblk;
+        const uint32_t in_wrap32 = strip_in_wrap(hd);
         uint32_t src_off = 0; // a load past the end of the walk re-reads the wave's last strip (strip 0 if it has none)
         int n_issued = 0;
-        const uint8_t *img_s = a.img;
         // Pixel loads land in RESERVED registers v72..v79: the kernel is compiled with amdgpu_num_vgpr(72), so the compiler
         // allocates v0..v71 only, and the asm statements below name v72.. explicitly (declared as clobbers, which makes the
         // kernel descriptor cover them: 80 registers, six waves per SIMD).  The compiler never sees a loaded value: it goes from the
@@ -567,8 +563,16 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
         src_off = n_issued < n_my ? in_off : src_off;                                                        \
         OB = oblk;                                                                                           \
         asm volatile("global_load_dwordx2 v[" R "], %0, %1" : : "v"(ld_off), "s"(img_s + src_off) : TIC_RSV_CLOBBER); \
-        n_issued++; txp += a.step_tx; in_off += a.in_step32; oblk += a.oblk_step;                            \
-        if (__builtin_expect(txp >= a.fast_tx, 0)) { txp -= a.fast_tx; in_off += a.in_wrap32; oblk += a.oblk_wrap; } \
+        n_issued++;                                                                                          \
+        strip_step(txp, in_off, oblk, hd.step_tx, hd.fast_tx, hd.in_step32, in_wrap32, w);                   \
+    } while (0)
+    // the first two loads: the pixel offsets alone (the block indices need `w`, which must not be waited for in front of a load)
+#define TIC_LOAD_HEAD(R, WRAP)                                                                               \
+    do {                                                                                                     \
+        src_off = n_issued < n_my ? in_off : src_off;                                                        \
+        asm volatile("global_load_dwordx2 v[" R "], %0, %1" : : "v"(ld_off), "s"(img_s + src_off) : TIC_RSV_CLOBBER); \
+        n_issued++;                                                                                          \
+        WRAP = strip_step_in(txp, in_off, hd.step_tx, hd.fast_tx, hd.in_step32, in_wrap32);                  \
     } while (0)
     // waits until all but the N youngest vector-memory operations are done, then sends the strip's pixel rows from the landing pair
     // v[R] (which keeps the strip's bytes until the pair is loaded again, two strips later: the batch fetches the raw words from
@@ -582,8 +586,45 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
                  : "=v"(D[0]), "=v"(D[1]), "=v"(D[2]), "=v"(D[3]), "=v"(D[4]), "=v"(D[5]), "=v"(D[6]), "=v"(D[7]) : : TIC_RSV_CLOBBER)
         uint32_t ob0, ob1, ob2;
         uint32_t kstrip = 0; // ordinal of the strip in this wave's walk
-        TIC_LOAD("72:73", ob0);
-        TIC_LOAD("74:75", ob1);
+        bool wrap0, wrap1;
+        uint32_t ty0 = cur.ty, tx0 = cur.txp;
+        TIC_LOAD_HEAD("72:73", wrap0);
+        TIC_LOAD_HEAD("74:75", wrap1);
+        // (the words of the round schedule are named here so that they stay live up to this point on every path: the compiler requests
+        //  the whole line of `w` at the kernel's entry, and a path that let a requested register die would have to wait for the line
+        //  before it could reuse the register - in front of the loads)
+        asm volatile("; block indices: behind the loads" : "+s"(ty0), "+s"(tx0) : "s"(w.round_wgs), "s"(w.round_span), "s"(w.magic_round_wgs) : TIC_RSV_CLOBBER);
+        oblk = strip_oblk(ty0, tx0, w);
+        ob0 = oblk;
+        strip_step_blk(oblk, wrap0, w);
+        ob1 = oblk;
+        strip_step_blk(oblk, wrap1, w);
+        // While the three loads fly: every address of the loop that does not depend on the constants.  (The empty statement pins the
+        // values in front of the wait - statements of this kind keep their order; left alone, the compiler computes them behind the barrier.)
+        // LDS layouts of the loop (conflict-free: tools/lds_bank_model.py, DESIGN.md 5.1)
+        //   byte transpose : block lb's pixel row lr at lb*80 + lr*8; lane (b, c) reads byte r*8 + c of block b, r = 0..7
+        //   dword transpose: value (u, c) of block b at dword (c>>2)*272 + u*32 + 4*(b ^ s(u)) + (c&3), s(u) = 4 for u in {2,3,6,7}
+        //   zig-zag staging: scan position p of block b at byte (p>>3)*128 + 16*(b ^ f(p>>3)) + 2*(p&7), f(c) = bit 1 of c | 4 * bit 2 of c
+        // (pass 1 runs in the compute layout - lane 8*b + c - columns first, in the load layout - lane 8*r + b - rows first; the half
+        //  offset of 272 dwords keeps the compute layout's 32-lane write groups conflict-free, the load layout needs none: 256)
+        constexpr int kHalf = kCols ? kTHalfDw : 256;
+        const int p1a = kCols ? i : lr, p1b = kCols ? b : lb;
+        uint32_t px_wr = lds_addr(ldsZ + lb * kPxBlkBytes + lr * 8);
+        uint32_t o_px_rd = lds_addr(ldsZ + b * kPxBlkBytes + i);
+        uint32_t o_twA = lds_addr(ldsT + (p1a >> 2) * kHalf + (p1a & 3) + 4 * p1b);       // outputs {0,1,4,5}: + k*32 dwords
+        uint32_t o_twB = lds_addr(ldsT + (p1a >> 2) * kHalf + (p1a & 3) + 4 * (p1b ^ 4)); // outputs {2,3,6,7}
+        // (the two 16-byte reads are pinned as indices of 16-byte pieces: the pointers keep the alignment ds_read_b128 needs)
+        uint32_t q_tr = (uint32_t)(i * 8 + (b ^ (4 * ((i >> 1) & 1))));                    // first half; the second kHalf dwords on
+        uint32_t q_zr = (uint32_t)(i * 8 + (b ^ (kCols ? (((i >> 1) & 1) | (i & 4)) : (4 * ((i >> 1) & 1)))));
+        uint32_t o_zb = lds_addr(ldsZ); // (zz_ptr's base)
+        asm volatile("; addresses of the loop" : "+v"(px_wr), "+v"(o_px_rd), "+v"(o_twA), "+v"(o_twB), "+v"(q_tr), "+v"(q_zr), "+v"(o_zb), "+v"(st_off) : : TIC_RSV_CLOBBER);
+        const uint8_t *px_rd = lds_ptr<const uint8_t>(o_px_rd);
+        uint32_t *twA = lds_ptr<uint32_t>(o_twA), *twB = lds_ptr<uint32_t>(o_twB);
+        const uint4 *tr = reinterpret_cast<const uint4 *>(__builtin_assume_aligned(ldsT, 16)) + q_tr;
+        const uint4 *zr = reinterpret_cast<const uint4 *>(__builtin_assume_aligned(ldsZ, 16)) + q_zr;
+        char *zb = lds_ptr<char>(o_zb);
+        // batch of frames: the plane's output
+        out_f = reinterpret_cast<int16_t *>(reinterpret_cast<char *>(w.out) + (long)blockIdx.z * w.frame_stride_out);
         // the constant piece is older than the pixel loads: it has landed when only those are in flight.  (Issuing the second
         // pixel load behind the barrier instead: +0.13 us, profiles/r02_ab_opt_switches.txt.)
         asm volatile("s_waitcnt vmcnt(2)\n\tv_mov_b32 %0, v76\n\tv_mov_b32 %1, v77\n\tv_mov_b32 %2, v78\n\tv_mov_b32 %3, v79"
@@ -599,12 +640,10 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
         zzv = *reinterpret_cast<const u32x4 *>(cst_blk + (kCols ? kBlkZz : kBlkZzT) + i * 16);
         auto zz_ptr = [&](uint32_t ofs) { // ofs = 2 * scan position of the coefficient
             const uint32_t c = ofs >> 4; // (the chunk's swizzle: found by search for either lane mapping, tools/lds_bank_model.py)
-            return reinterpret_cast<int16_t *>(ldsZ + c * 128 + (ofs & 15) + 16 * (b ^ (kCols ? (((c >> 1) & 1) | (c & 4)) : (4 * ((c >> 1) & 1)))));
+            return reinterpret_cast<int16_t *>(zb + c * 128 + (ofs & 15) + 16 * (b ^ (kCols ? (((c >> 1) & 1) | (c & 4)) : (4 * ((c >> 1) & 1)))));
         };
         int16_t *zp0 = zz_ptr(zzv.x & 0xffff), *zp1 = zz_ptr(zzv.x >> 16), *zp2 = zz_ptr(zzv.y & 0xffff), *zp3 = zz_ptr(zzv.y >> 16);
         int16_t *zp4 = zz_ptr(zzv.z & 0xffff), *zp5 = zz_ptr(zzv.z >> 16), *zp6 = zz_ptr(zzv.w & 0xffff), *zp7 = zz_ptr(zzv.w >> 16);
-        const uint4 *zr = reinterpret_cast<const uint4 *>(
-            __builtin_assume_aligned(ldsZ + 16 * (i * 8 + (b ^ (kCols ? (((i >> 1) & 1) | (i & 4)) : (4 * ((i >> 1) & 1))))), 16));
         wave_lds_fence();
 
         int left = n_my;
@@ -674,7 +713,7 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
             wave_lds_fence();
             const uint4 val = *zr;
             wave_lds_fence();
-            const char *dst = reinterpret_cast<const char *>(a.out) + ((unsigned long long)ob << 7); // (scalar: the strip's 1 KiB)
+            const char *dst = reinterpret_cast<const char *>(out_f) + ((unsigned long long)ob << 7); // (scalar: the strip's 1 KiB)
             // ---- an irrational coefficient inside its guard band (one strip in seventy at q = 50, one in fourteen at q = 90) ------
             const unsigned long long mG = cA | (cB & ~kRat);
             if (__builtin_expect(mG != 0ull, 0)) {
@@ -735,10 +774,19 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
         // batch pass; profiles/r04_tail_experiments.txt).  The statement stays as a scheduling fence with the same clobbers.
         asm volatile("; end of the strip walk" : : : TIC_RSV_CLOBBER);
 #undef TIC_LOAD
+#undef TIC_LOAD_HEAD
 #undef TIC_TAKE_COLS
 #undef TIC_TAKE_ROWS
 #undef TIC_RSV_CLOBBER
     }
+    // The rare paths behind the loop read DctqArgs.  They ask for it HERE, through the kernel-argument pointer (passed through an empty
+    // statement: the compiler cannot move the requests in front of it) - read as `a.field`, every field is requested at the kernel's
+    // entry, and the start's one scalar wait then stands for four more lines of kernel arguments, served one after the other.
+    typedef const __attribute__((address_space(4))) char *kernarg_ptr;
+    kernarg_ptr kargs = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("; rare paths: DctqArgs from here on" : "+s"(kargs));
+    const __attribute__((address_space(4))) DctqArgs *ca = reinterpret_cast<const __attribute__((address_space(4))) DctqArgs *>(kargs + offsetof(StripKernargs, a));
+    (void)a;
     // ---- the batch pass: blocks with an irrational coefficient inside its guard band ----------------------------------------
     if (nE != 0) {
         const double *cst_cos = reinterpret_cast<const double *>(cst_blk + kBlkCos);   // orthonormal DCT-II matrix, index k*8+n
@@ -794,13 +842,13 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
         }
         wave_lds_fence();
         const uint4 val = bat_img[e * 8 + i];
-        if (have) store16_wt_nt(reinterpret_cast<char *>(a.out) + ((unsigned long long)blk << 7) + (uint32_t)i * 16u, val);
+        if (have) store16_wt_nt(reinterpret_cast<char *>(out_f) + ((unsigned long long)blk << 7) + (uint32_t)i * 16u, val);
     }
-    if (a.fallback_count != nullptr && lane == 0) { // diagnostics (tic_set_stats): never in a timed launch
-        if (n_second != 0) atomicAdd(a.fallback_count, (unsigned long long)n_second);
-        if (n_quad != 0) atomicAdd(a.fallback_count + 1, (unsigned long long)n_quad);
-        if (mask_exact != 0ull) atomicAdd(a.fallback_count + 2, (unsigned long long)__builtin_popcountll(mask_exact));
-        if (nE != 0) atomicMax(a.fallback_count + 3, (unsigned long long)nE);
+    if (ca->fallback_count != nullptr && lane == 0) { // diagnostics (tic_set_stats): never in a timed launch
+        if (n_second != 0) atomicAdd(ca->fallback_count, (unsigned long long)n_second);
+        if (n_quad != 0) atomicAdd(ca->fallback_count + 1, (unsigned long long)n_quad);
+        if (mask_exact != 0ull) atomicAdd(ca->fallback_count + 2, (unsigned long long)__builtin_popcountll(mask_exact));
+        if (nE != 0) atomicMax(ca->fallback_count + 3, (unsigned long long)nE);
     }
     // ---- strips the batch had no room for: the exact operation order, whole strip ---------------------------------------
     if (mask_exact == 0ull) return;
@@ -810,22 +858,22 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
                             (uint16_t)zzn.z, (uint16_t)(zzn.z >> 16), (uint16_t)zzn.w, (uint16_t)(zzn.w >> 16)};
     for (unsigned long long todo = mask_exact; todo != 0ull; todo &= todo - 1ull) {
         const int k = __builtin_ctzll(todo);
-        const long t = (long)t_first + (long)k * a.tstep; // strip index inside the fast rectangle
-        const int ty = (int)(t / a.fast_tx), tx = (int)(t - (long)ty * a.fast_tx);
+        const long t = (long)t_first + (long)k * ca->tstep; // strip index inside the fast rectangle
+        const int ty = (int)(t / ca->fast_tx), tx = (int)(t - (long)ty * ca->fast_tx);
         Strip s;
         s.by = ty;
         s.bx = tx * 8 + b;
         s.valid = true;
-        s.oblk = (size_t)ty * a.bw + s.bx;
+        s.oblk = (size_t)ty * ca->bw + s.bx;
         uint32_t lo, hi;
-        load_block_row(a.img, a.h, a.w, a.stride, true, s, i, lo, hi);
+        load_block_row(img_s, ca->h, ca->w, ca->stride, true, s, i, lo, hi);
         transpose8x8_bytes(lo, hi, i);
         int q[8];
         // the second level for the whole strip; the exact order only if it leaves something undecided (a tie of a rational
         // coefficient included: this path has no column sums at hand)
         const uint32_t und = second_level_8(lo, hi, ldsT, b, i, reinterpret_cast<const double *>(cst_blk + kBlkMul64), q);
         if (__ballot(und != 0u) != 0ull) exact_block(lo, hi, ldsT, b, i, C, q);
-        store_zigzag(reinterpret_cast<uint32_t *>(ldsZ), b, i, zz, q, a.out, s);
+        store_zigzag(reinterpret_cast<uint32_t *>(ldsZ), b, i, zz, q, out_f, s);
     }
 }
 
@@ -1129,118 +1177,52 @@ hipError_t launch_dctq(DctqArgs a, int variant, hipStream_t stream, hipEvent_t e
         }
     }
     const int bh = a.ntiles / a.tiles_x;
-    a.fast_tx = (a.aligned8 && (long)a.h * a.stride < (1L << 32)) ? a.w / 64 : 0; // 32-bit pixel offsets in the walk
-    a.fast_ty = a.h / 8;
-    const int nfast = a.fast_tx * a.fast_ty;
-    if (nfast > 0) {
-        // persistent waves, each looping over its strips; one mask bit per strip of a wave's walk: at most 64 strips per wave
-        const int max_strips = kMaxStripsPerWave2;
-        int wgs = grid_for(nfast);
-        // persistent grid = exactly the workgroups the chip holds at once (CUs x resident workgroups per CU): a larger
-        // grid runs in two uneven rounds, a smaller one leaves wave slots empty (measured: 15.0 us at 1280 workgroups
-        // vs 16.3 us at 2048 on a 4096^2 frame)
-        static int cus = 256;
-        static const int resident = [] {
-            int dev = 0, per_cu = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dctq_strip_kernel<true>, kWavesPerWG * 64, 0) != hipSuccess || per_cu < 1)
-                per_cu = 4;
-            // 80 VGPRs and 22 KiB of LDS allow 6 workgroups per CU (7 measured no better when the kernel still fitted them:
-            // a seventh lengthens the start ramp by as much as it hides, profiles/r02_ab_occupancy.txt)
-            if (per_cu > 6) per_cu = 6;
-            return cus * per_cu;
-        }();
-        const Tunables tune = tunables();
-        const int cap_env = tune.max_wgs > 0 ? tune.max_wgs : resident;
-        int cap = cap_env / nf; // a batch shares the chip's wave slots between its frames
-        if (cap < 64) cap = 64;
-        if (wgs > cap) wgs = cap;
-        const int min_wgs = (nfast + kWavesPerWG * max_strips - 1) / (kWavesPerWG * max_strips);
-        if (wgs < min_wgs) wgs = min_wgs; // strips per wave are bounded (exact-redo mask)
-        a.nwaves = wgs * kWavesPerWG;
-        a.wg_stride = kWavesPerWG;
-        a.tstep = a.nwaves;
-        a.wg_span = nfast;
-        a.round_wgs = 0;
-        a.team_count = 0;
-        const int S = tune.chunk < 1 ? 1 : (tune.chunk > max_strips ? max_strips : tune.chunk);
-        const int min_wgs16 = (nfast + kWavesPerWG * kMaxStripsPerWave - 1) / (kWavesPerWG * kMaxStripsPerWave);
-        const bool multi_round = (long)min_wgs16 * nf > (long)cap_env; // more workgroups than the chip holds at once
-        if (tune.sched == 1 && multi_round) { // each workgroup streams a contiguous chunk of 4*S strips
-            a.wg_stride = a.wg_span = kWavesPerWG * S;
-            a.tstep = kWavesPerWG;
-            wgs = (nfast + a.wg_stride - 1) / a.wg_stride;
-            a.nwaves = wgs * kWavesPerWG;
-        } else if (tune.sched == 2 && multi_round && nf == 1) { // rounds of `resident` workgroups walking a dense range together
-            a.round_wgs = cap_env;
-            a.wg_span = kWavesPerWG * S;
-            a.tstep = a.round_wgs * kWavesPerWG;
-            wgs = (nfast + a.wg_span - 1) / a.wg_span; // the last round may hold workgroups with nothing to do
-            wgs = (wgs + a.round_wgs - 1) / a.round_wgs * a.round_wgs;
-            a.nwaves = wgs * kWavesPerWG;
-        }
-        if (!multi_round && nf == 1 && tune.split[0] > 0 && wgs == cap_env && wgs % cus == 0 && wgs / cus <= 8) {
-            // the whole grid is resident: teams of wgs/cus workgroups, rows split by the per-round weights
-            const int R = wgs / cus;
-            a.team_count = cus;
-            a.tstep = cus * kWavesPerWG;
-            const int rows_total = (nfast + a.tstep - 1) / a.tstep;
-            double wsum = 0;
-            for (int r = 0; r < R; r++) wsum += tune.split[r] > 0 ? tune.split[r] : 1;
-            double acc = 0;
-            a.split[0] = 0;
-            for (int r = 0; r < R; r++) {
-                acc += tune.split[r] > 0 ? tune.split[r] : 1;
-                a.split[r + 1] = (int)(rows_total * acc / wsum + 0.5);
-                if (a.split[r + 1] - a.split[r] > max_strips) a.team_count = 0; // strips per wave are bounded: fall back
-            }
-            a.split[R] = rows_total;
-            if (rows_total > 255) a.team_count = 0; // the kernel takes the row boundaries as bytes
-            if (a.team_count == 0) a.tstep = a.nwaves;
-        }
-        a.step_ty = a.tstep / a.fast_tx;
-        a.step_tx = a.tstep % a.fast_tx;
-        a.in_step32 = (uint32_t)((long)a.step_ty * 8 * a.stride + (long)a.step_tx * 64);
-        a.in_wrap32 = (uint32_t)(8 * a.stride - (long)a.fast_tx * 64);
-        a.oblk_step = (uint32_t)((long)a.step_ty * a.bw + (long)a.step_tx * 8);
-        a.oblk_wrap = (uint32_t)((long)a.bw - (long)a.fast_tx * 8);
-        // division-free prologue (magic multipliers), team schedule on a 2-D grid.  Exactness of the magic divisions:
-        // n * d < 2^32 for every dividend n the prologue can form; frames beyond that (more than ~10^5 pixels wide and
-        // millions of strips) go through the exact kernel as a whole
-        dim3 grid(wgs, 1, nf);
-        const unsigned long long dmax = (unsigned long long)(a.round_wgs > 0 ? a.round_wgs : a.tstep);
-        if ((unsigned long long)nfast * (unsigned long long)a.fast_tx >= (1ull << 32) ||
-            ((unsigned long long)nfast + dmax) * dmax >= (1ull << 32)) {
-            a.fast_tx = a.fast_ty = 0;
-        } else {
-            auto magic = [](long d) { return d <= 1 ? 0u : (uint32_t)((1ull << 32) / (unsigned long long)d + 1ull); }; // 0: divisor 1
-            a.magic_fast_tx = magic(a.fast_tx);
-            a.magic_tstep = magic(a.round_wgs > 0 ? a.round_wgs : a.tstep);
-            a.split_lo = a.split_hi = 0;
-            if (a.team_count > 0) {
-                const int R = wgs / a.team_count;
-                for (int k = 0; k <= R; k++) {
-                    if (k < 8) a.split_lo |= (unsigned long long)(a.split[k] & 0xff) << (8 * k);
-                    else a.split_hi = (unsigned long long)(a.split[k] & 0xff);
-                }
-                grid = dim3(a.team_count, R, nf);
-            }
-            // pass order: columns first where the whole grid is resident at once (static shares: the tail decides), rows first for grids
-            // of several rounds (dynamic dispatch: the average cost per strip decides); TIC_ORDER (test hook) forces one
-            const bool cols = tune.order < 0 ? !multi_round : tune.order == 1;
-            if (ev_start && ev_stop) { // the dispatch packet's own time stamps (tic_dctq_dev_timed_warm's per-launch times)
-                if (cols)
-                    hipExtLaunchKernelGGL(dctq_strip_kernel<true>, grid, block, 0, stream, ev_start, ev_stop, 0, a);
-                else
-                    hipExtLaunchKernelGGL(dctq_strip_kernel<false>, grid, block, 0, stream, ev_start, ev_stop, 0, a);
-            } else if (cols)
-                hipLaunchKernelGGL(dctq_strip_kernel<true>, grid, block, 0, stream, a);
-            else
-                hipLaunchKernelGGL(dctq_strip_kernel<false>, grid, block, 0, stream, a);
-        }
-    } else {
-        a.fast_tx = a.fast_ty = 0;
+    // persistent grid = exactly the workgroups the chip holds at once (CUs x resident workgroups per CU): a larger
+    // grid runs in two uneven rounds, a smaller one leaves wave slots empty (measured: 15.0 us at 1280 workgroups
+    // vs 16.3 us at 2048 on a 4096^2 frame)
+    static int cus = 256;
+    static const int resident = [] {
+        int dev = 0, per_cu = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dctq_strip_kernel<true>, kWavesPerWG * 64, 0) != hipSuccess || per_cu < 1)
+            per_cu = 4;
+        // 80 VGPRs and 22 KiB of LDS allow 6 workgroups per CU (7 measured no better when the kernel still fitted them:
+        // a seventh lengthens the start ramp by as much as it hides, profiles/r02_ab_occupancy.txt)
+        if (per_cu > 6) per_cu = 6;
+        return cus * per_cu;
+    }();
+    const Tunables tune = tunables();
+    // the schedule: tic_strip_plan.h (strided, chunked, round-interleaved or team; the words of the kernel's start state)
+    StripTune st;
+    st.cus = cus, st.resident = resident, st.max_wgs = tune.max_wgs, st.sched = tune.sched, st.chunk = tune.chunk;
+    for (int k = 0; k < 8; k++) st.split[k] = tune.split[k];
+    const StripFrame fr = {a.h, a.w, a.stride, a.bw, a.aligned8, nf};
+    const StripPlan pl = strip_plan(fr, st);
+    a.fast_tx = pl.fast_tx;
+    a.fast_ty = pl.fast_ty;
+    if (pl.launch) {
+        // the same schedule in DctqArgs, for the kernel's rare paths (the exact redo of a strip finds it by t_first + k * tstep)
+        a.nwaves = pl.nwaves, a.wg_stride = pl.wg_stride, a.tstep = pl.tstep, a.wg_span = pl.wg_span, a.round_wgs = pl.round_wgs;
+        a.team_count = pl.team_count, a.step_ty = pl.step_ty, a.step_tx = pl.step_tx;
+        for (int k = 0; k < 9; k++) a.split[k] = pl.split[k];
+        a.in_step32 = pl.hd.in_step32, a.in_wrap32 = pl.in_wrap32, a.oblk_step = pl.wm.oblk_step, a.oblk_wrap = pl.wm.oblk_wrap;
+        a.magic_fast_tx = pl.hd.magic_fast_tx, a.magic_tstep = pl.wm.magic_round_wgs;
+        a.split_lo = pl.hd.split, a.split_hi = (pl.hd.misc >> 8) & 0xffu;
+        const StripHead &hd = pl.hd;
+        StripWarm wm = pl.wm;
+        wm.out = a.out, wm.frame_stride_in = a.frame_stride_in, wm.frame_stride_out = a.frame_stride_out;
+        const dim3 grid(pl.grid_x, pl.grid_y, nf);
+        // pass order: columns first where the whole grid is resident at once (static shares: the tail decides), rows first for grids
+        // of several rounds (dynamic dispatch: the average cost per strip decides); TIC_ORDER (test hook) forces one
+        const bool cols = tune.order < 0 ? !pl.multi_round : tune.order == 1;
+        auto *kern = cols ? dctq_strip_kernel<true> : dctq_strip_kernel<false>;
+        if (ev_start && ev_stop) // the dispatch packet's own time stamps (tic_dctq_dev_timed_warm's per-launch times)
+            hipExtLaunchKernelGGL(kern, grid, block, 0, stream, ev_start, ev_stop, 0, a.img, a.consts, hd.split, hd.stride, hd.misc, hd.tstep, hd.nfast,
+                                  hd.fast_tx, hd.magic_fast_tx, hd.in_step32, hd.step_tx, wm, a);
+        else
+            hipLaunchKernelGGL(kern, grid, block, 0, stream, a.img, a.consts, hd.split, hd.stride, hd.misc, hd.tstep, hd.nfast, hd.fast_tx,
+                               hd.magic_fast_tx, hd.in_step32, hd.step_tx, wm, a);
     }
     const int nrem = bh * (a.tiles_x - a.fast_tx) + (bh - a.fast_ty) * a.fast_tx;
     if (nrem > 0) {
