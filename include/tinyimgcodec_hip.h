@@ -320,6 +320,36 @@ int tic_compress_batch_v(tic_ctx *ctx, const uint8_t *const *images, int n, cons
  * run of neighbouring frames of one width and quality whose heights are multiples of 8).  Any pointer may be NULL. */
 int tic_last_compress_batch_v(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks, int *transform_launches);
 
+/* ---- rate control for a batch ------------------------------------------------------------------------------------------------------
+ * tic_stream_sizes of n frames of ANY sizes in one call: sizes[i * nq + j] is what tic_stream_sizes gives for frame i at qualities[j]
+ * (-1 where a coefficient has no Huffman code, 16 for a frame without blocks) - the reference's whole benchmark table
+ * (tests/benchmark.py: 49 images x 6 qualities) is one call.  All arguments are checked before any work ("frame i: ..." for the first
+ * offending frame, as tic_compress_batch_v).  The frames are cut into tic_compress_batch_v's chunks (64 frames, 32 MB of pixels), ordered
+ * by (width, height); per chunk one upload, every probe queued - a transform launch per probe, neighbours of equal width at one quality
+ * whose heights are multiples of 8 in one launch, and one launch of the size kernel's descriptor form per 64 probes - and one read-back.
+ * Frames the batch does not take (tic_compress_batch_v's) go through tic_stream_sizes behind it. */
+int tic_stream_sizes_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                       const int *qualities, int nq, long long *sizes);
+/* tic_compress_to_size of n frames of ANY sizes, each within its own budget max_bytes[i], over one quality range: frame i gets exactly
+ * what tic_compress_to_size(image i, max_bytes[i], qmin, qmax) gives - outs[i] (caps[i] bytes), out_lens[i], qualities[i] - and status[i]:
+ *     TIC_OK        the stream, its length and its quality are set; no byte of outs[i] behind out_lens[i] is written
+ *     TIC_E_SPACE   qmin exceeds the budget: out_lens[i] = its length at qmin; or the chosen stream exceeds caps[i]: out_lens[i] = its length
+ *     TIC_E_RANGE   qmin has a coefficient without a Huffman code
+ * outs[i] is untouched on every failure.  The call returns the first non-OK status in frame order (tic_last_error: that frame's message,
+ * "frame i: ..."); the other frames are delivered all the same.  Argument errors (a bad range TIC_E_QUALITY; a bad size or stride, a null
+ * image, buffer or array TIC_E_ARG) are found before any work and write nothing.
+ * Phase 1, per chunk of the plan above: one upload, then the bisections of all its frames in lockstep - every round one submission of
+ * each unsettled frame's next middles (1 to 3 steps ahead, by the chunk's size), one read-back, one wait: at most 7 rounds for 1..99.
+ * Phase 2: the streams of all fitting frames from tic_compress_batch_v at the qualities found (their pixels are uploaded a second time);
+ * a length that contradicts its probe is TIC_E_HIP.  Frames the batch does not take go through tic_compress_to_size behind it. */
+int tic_compress_batch_to_size(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                               const size_t *max_bytes, int qmin, int qmax, uint8_t *const *outs, const size_t *caps, size_t *out_lens,
+                               int *qualities, int *status);
+/* How the last tic_stream_sizes_v / tic_compress_batch_to_size went: frames through the batch / frames handled one by one behind it /
+ * chunks / probes queued / host waits of phase 1 (one per chunk for the sizes, one per round of a chunk for the search) / launches of the
+ * size kernel's descriptor form.  Any pointer may be NULL. */
+int tic_last_rate_batch(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks, int *probes, int *search_waits, int *size_launches);
+
 /* The same batch spread over nctx contexts - one per GPU of the node - by ONE process: a host thread per context, contiguous
  * shards of ceil(n / nctx) frames in frame order, no exchange between the shards; out_lens in frame order.  What a caller that
  * loops over images (/root/reference/tests/benchmark.py:12-23) gets from a multi-GPU node without a launcher.  Returns the first

@@ -161,6 +161,19 @@ SIGNATURES = {
          C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
     ),
     "tic_last_compress_batch_v": (C.c_int, [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tic_stream_sizes_v": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ssize_t), C.c_void_p, C.c_int, C.c_void_p],
+    ),
+    "tic_compress_batch_to_size": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ssize_t), C.POINTER(C.c_size_t), C.c_int, C.c_int,
+         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    ),
+    "tic_last_rate_batch": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    ),
     "tic_compress_batch_multi": (
         C.c_int,
         [C.POINTER(_ctxp), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.POINTER(C.c_void_p),

@@ -416,6 +416,85 @@ def compress_to_size(image, max_bytes, min_quality=1, max_quality=99, ctx=None):
         return out[: n.value].tobytes(), int(q.value)
 
 
+def _frame_arrays(frames):
+    """The per-frame arguments the calls for mixed frames share: image pointers, heights, widths, row strides."""
+    n = len(frames)
+    inp = (C.c_void_p * n)(*[f[0].ctypes.data if f[0].size else None for f in frames])
+    hs = (C.c_int * n)(*[f[1] for f in frames])
+    ws = (C.c_int * n)(*[f[2] for f in frames])
+    strides = (C.c_ssize_t * n)(*[max(f[2], 1) for f in frames])
+    return inp, hs, ws, strides
+
+
+def compressed_sizes_batch(images, qualities, ctx=None):
+    """compressed_sizes(image, qualities) of every image of a list, of any shapes, in one call -> int64 array (n, nq); -1 where compress()
+    would raise KeyError.  The reference's whole benchmark table (49 images x 6 qualities) is one call: per chunk of up to 64 frames one
+    upload, every probe queued, one read-back (tic_stream_sizes_v).  8-bit images only; an invalid quality raises what compress() raises for
+    it, before any GPU work."""
+    frames = [_as_u8_image(im) for im in images]
+    qs = [_check_quality(q, packs_header=True) for q in qualities]
+    sizes = np.zeros((len(frames), len(qs)), dtype=np.int64)
+    if not frames or not qs:
+        return sizes
+    ctx = _ctx(ctx)
+    qarr = np.asarray(qs, dtype=np.intc)
+    inp, hs, ws, strides = _frame_arrays(frames)
+    with ctx.lock:
+        ctx.check(N.load().tic_stream_sizes_v(ctx.handle, inp, len(frames), hs, ws, strides, qarr.ctypes.data, len(qs), sizes.ctypes.data))
+    return sizes
+
+
+def compress_batch_to_size(images, max_bytes, min_quality=1, max_quality=99, ctx=None):
+    """compress_to_size(image, max_bytes, min_quality, max_quality) of every image of a list, of any shapes, in one call ->
+    [(bytes, quality), ...].  max_bytes: one budget for all, or a sequence with one per frame.  The bisections of up to 64 frames run in
+    lockstep - one submission and one wait per round for all of them - and the streams of all frames come from one mixed batch
+    (tic_compress_batch_to_size).  Argument errors are compress_to_size's, raised before any GPU work; a frame that fails raises, for the
+    first such frame, what compress_to_size raises for it, the message prefixed "frame i: ".  8-bit images only."""
+    frames = [_as_u8_image(im) for im in images]
+    qmin = _check_quality(min_quality, packs_header=True)
+    qmax = _check_quality(max_quality, packs_header=True)
+    if qmin > qmax:
+        raise ValueError("min_quality %d above max_quality %d" % (qmin, qmax))
+    n = len(frames)
+    if hasattr(max_bytes, "__len__"):
+        if len(max_bytes) != n:
+            raise ValueError("max_bytes has %d entries for %d frames" % (len(max_bytes), n))
+        budgets = [int(b) for b in max_bytes]
+    else:
+        budgets = [int(max_bytes)] * n
+    if any(b < 0 for b in budgets):
+        raise ValueError("max_bytes must not be negative")
+    if not frames:
+        return []
+    ctx = _ctx(ctx)
+    L = N.load()
+    caps_l = [L.tic_compress_bound(f[1], f[2]) for f in frames]
+    offs = np.concatenate(([0], np.cumsum([(c + 63) // 64 * 64 for c in caps_l]))).astype(np.int64)
+    inp, hs, ws, strides = _frame_arrays(frames)
+    with ctx.lock:
+        pool = getattr(ctx, "_mixed_pool", None)  # compress_batch()'s landing buffer for mixed frames
+        if pool is None or pool.size < offs[-1]:
+            pool = ctx._mixed_pool = np.empty(int(offs[-1]), dtype=np.uint8)
+        base = pool.ctypes.data
+        outp = (C.c_void_p * n)(*[base + int(o) for o in offs[:-1]])
+        caps = (C.c_size_t * n)(*caps_l)
+        budg = (C.c_size_t * n)(*budgets)
+        lens = (C.c_size_t * n)()
+        qout = (C.c_int * n)()
+        status = (C.c_int * n)()
+        rc = L.tic_compress_batch_to_size(ctx.handle, inp, n, hs, ws, strides, budg, qmin, qmax, outp, caps, lens, qout, status)
+        bad = next((i for i in range(n) if status[i] != N.TIC_OK), None)
+        if bad is None:
+            ctx.check(rc)  # (a failure of the call itself: no frame to name)
+        elif status[bad] == N.TIC_E_RANGE:
+            raise KeyError("frame %d: coefficient magnitude has no Huffman code" % bad)
+        elif status[bad] == N.TIC_E_SPACE:
+            raise ValueError("frame %d: %d bytes at quality %d exceed max_bytes = %d" % (bad, lens[bad], qmin, budgets[bad]))
+        else:
+            ctx.check(status[bad])
+        return [(pool[int(offs[i]): int(offs[i]) + lens[i]].tobytes(), int(qout[i])) for i in range(n)]
+
+
 def psnr_from_sse(sse, npixels, max_pixel=255):
     """PSNR in dB from a sum of squared differences over `npixels` pixels, with the operations of the reference's tests/psnr.py (its
     np.mean of the squares is the exact integer sum divided by the count): inf for a sum of 0.  The one place PSNR is defined for

@@ -284,6 +284,13 @@ struct tic_ctx {
     SizeResult *d_rate = nullptr, *h_rate = nullptr;
     size_t rate_dev_bytes = 0, rate_host_bytes = 0;
     int last_rate_probes = 0, last_rate_waits = 0;
+    // ... their batch forms (tic_stream_sizes_v, tic_compress_batch_to_size): the pinned buffer a chunk's pixels are staged in (the chunk
+    // itself and its probes' coefficients live in d_img / d_coef), the probe tables of one submission, and what the last call did
+    uint8_t *h_rate_pix = nullptr;
+    size_t rate_pix_cap = 0;
+    SizeProbeTable *h_rate_tabs = nullptr, *d_rate_tabs = nullptr;
+    size_t rate_tabs_host_bytes = 0, rate_tabs_dev_bytes = 0;
+    int last_rbatch_frames = 0, last_rbatch_single = 0, last_rbatch_chunks = 0, last_rbatch_probes = 0, last_rbatch_waits = 0, last_rbatch_launches = 0;
 };
 
 // NUMA node of a device (its PCI function's numa_node in sysfs) and the CPUs of that node within this process's affinity mask.
@@ -520,6 +527,9 @@ void tic_destroy(tic_ctx *ctx) {
     if (ctx->d_size_tab) (void)hipFree(ctx->d_size_tab);
     if (ctx->d_rate) (void)hipFree(ctx->d_rate);
     if (ctx->h_rate) (void)hipHostFree(ctx->h_rate);
+    if (ctx->h_rate_pix) (void)hipHostFree(ctx->h_rate_pix);
+    if (ctx->h_rate_tabs) (void)hipHostFree(ctx->h_rate_tabs);
+    if (ctx->d_rate_tabs) (void)hipFree(ctx->d_rate_tabs);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1534,19 +1544,10 @@ int tic_stream_sizes(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t
     return tic_stream_sizes_dev(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, qualities, nq, sizes);
 }
 
-// The search.  Its contract is the bisection of the header (tic_compress_to_size_dev); what is free is WHEN a quality is probed.  One
-// submission probes every middle the bisection can reach within `depth` further steps from where it stands (2^depth - 1 probes, the
-// first one qmin as well), then the bisection is replayed over the known sizes as far as they carry.  A wait costs about what a probe
-// of a 4096^2 frame does (some 15 us), a probe of a small frame a fraction of that: deep look-ahead for small frames, none for
-// frames beyond 4096^2.  Sizes: -1 = no code, kRateUnknown = not probed.
-constexpr long long kRateUnknown = -2;
-static void rate_candidates(int lo, int hi, int depth, const long long *known, int *out, int *nout) {
-    if (lo >= hi || depth == 0) return;
-    const int mid = (lo + hi + 1) / 2;
-    if (known[mid] == kRateUnknown) out[(*nout)++] = mid;
-    rate_candidates(mid, hi, depth - 1, known, out, nout);
-    rate_candidates(lo, mid - 1, depth - 1, known, out, nout);
-}
+// The search.  Its contract is the bisection of the header (tic_compress_to_size_dev); what is free is WHEN a quality is probed:
+// rate_candidates (tic_rate_plan.h, shared with the batch form) names the middles reachable within `depth` further steps.  A wait costs
+// about what a probe of a 4096^2 frame does (some 15 us), a probe of a small frame a fraction of that: deep look-ahead for small frames,
+// none for frames beyond 4096^2.
 
 // The last step of a search (by size or by distortion) that ended at quality q, whose probe said `len` bytes: transform, pack and place
 // into the context's own buffer, then exactly its bytes into the caller's - the length is known from the probe, so the copy is queued
@@ -2836,6 +2837,14 @@ static int batch_mixed_pipeline(tic_ctx *ctx, const MixedPlan &p, const MixedCal
     return result;
 }
 
+// The chunk limits of the calls that go by plan_mixed_batch: 64 frames and 32 MB of staged pixels, or what the test hooks say.
+static void mixed_chunk_limits(int *chunk_frames, size_t *chunk_bytes) {
+    *chunk_frames = kMixedChunkFrames;
+    *chunk_bytes = kMixedChunkBytes;
+    if (const char *e = test_hook("TIC_BATCH_CHUNK")) *chunk_frames = atoi(e); // (out of range: the default)
+    if (const char *e = test_hook("TIC_BATCH_CHUNK_BYTES")) *chunk_bytes = strtoull(e, nullptr, 10) ? (size_t)strtoull(e, nullptr, 10) : *chunk_bytes;
+}
+
 int tic_compress_batch_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
                          const int *qualities, uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
     TIC_LOCK(ctx);
@@ -2854,10 +2863,9 @@ int tic_compress_batch_v(tic_ctx *ctx, const uint8_t *const *images, int n, cons
         if (!outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
         if (!images[i] && num_blocks(hs[i], ws[i]) != 0) return set_err(ctx, TIC_E_ARG, "frame %d: null image", i);
     }
-    int chunk_frames = kMixedChunkFrames;
-    size_t chunk_bytes = kMixedChunkBytes;
-    if (const char *e = test_hook("TIC_BATCH_CHUNK")) chunk_frames = atoi(e); // (out of range: the default)
-    if (const char *e = test_hook("TIC_BATCH_CHUNK_BYTES")) chunk_bytes = strtoull(e, nullptr, 10) ? (size_t)strtoull(e, nullptr, 10) : chunk_bytes;
+    int chunk_frames;
+    size_t chunk_bytes;
+    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
     const MixedPlan p = plan_mixed_batch(hs, ws, qualities, n, chunk_frames, chunk_bytes);
     const MixedCall io = {images, row_strides, outs, caps, out_lens};
     ctx->last_batch_direct_frames = ctx->last_batch_staged_frames = ctx->last_batch_autoreg_frames = ctx->last_batch_zero_copy = 0;
@@ -2898,6 +2906,295 @@ int tic_last_compress_batch_v(tic_ctx *ctx, int *batch_frames, int *single_frame
     if (single_frames) *single_frames = ctx->last_vbatch_single;
     if (chunks) *chunks = ctx->last_vbatch_chunks;
     if (transform_launches) *transform_launches = ctx->last_vbatch_launches;
+    return TIC_OK;
+}
+
+// ---- rate control for a batch: the sizes of n frames at a list of qualities, and the best stream of each within its own byte budget -----------
+// (tic_stream_sizes_v, tic_compress_batch_to_size.)  The plan (tic_rate_plan.h) cuts the call into the mixed batch's chunks, ordered by
+// (width, height).  A chunk is staged and uploaded ONCE into the context's scratch image; a SUBMISSION then queues any number of probes of its
+// frames on the context's stream - a transform launch per probe (neighbours of one transform run at one quality: one launch) into the
+// probe's own area of the coefficient workspace, then ONE launch of the size kernel's descriptor form per 64 probes - behind one memset of
+// the results and one copy of the probe tables, and ends in one read-back.  Where a submission's coefficients exceed kRateWorkspaceBytes
+// it goes in passes over the same workspace; the stream orders them.
+struct RateCall {
+    const uint8_t *const *images;
+    const int *hs, *ws;
+    const ptrdiff_t *row_strides;
+};
+
+// Argument checks the two calls share: every frame's geometry at `quality`, its image pointer.  "frame i: ..." for the first offender.
+static int check_rate_frames(tic_ctx *ctx, const RateCall &io, int n, int quality) {
+    for (int i = 0; i < n; i++) {
+        const int rc = check_stream_geometry(ctx, io.hs[i], io.ws[i], io.row_strides[i], quality);
+        if (rc) {
+            const std::string why = ctx->err;
+            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
+        }
+        if (!io.images[i] && num_blocks(io.hs[i], io.ws[i]) != 0) return set_err(ctx, TIC_E_ARG, "frame %d: null image", i);
+    }
+    return TIC_OK;
+}
+
+// Stages chunk `c` at the plan's pitches and queues its ONE upload into the context's scratch image.
+static int upload_rate_chunk(tic_ctx *ctx, const MixedPlan &p, const MixedChunk &c, const RateCall &io) {
+    int rc = ensure_scratch(ctx, c.img_bytes, 0);
+    if (rc) return rc;
+    rc = grow_pinned(ctx, ctx->h_rate_pix, ctx->rate_pix_cap, c.img_bytes);
+    if (rc) return rc;
+    const MixedFrame *fr = &p.frames[(size_t)c.first];
+    uint8_t *pin = ctx->h_rate_pix;
+    const int T = c.count < 4 || c.img_bytes < (4u << 20) ? 1 : 4;
+    run_strided(c.count, T, [ctx]() { bind_pipeline_thread(ctx); },
+                [=](int k) { copy_rows(pin + fr[k].img_off, fr[k].pitch, io.images[fr[k].index], io.row_strides[fr[k].index], fr[k].h, fr[k].w); });
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_img, pin, c.img_bytes, hipMemcpyHostToDevice, ctx->stream));
+    return TIC_OK;
+}
+
+// Queues the probes of `s` (frames of the chunk resident in the scratch image) and the copy of their results into ctx->h_rate, entry i for
+// probe i; the caller waits for the stream.  Nothing of an earlier submission may be in flight: the buffers may grow.
+static int submit_rate_probes(tic_ctx *ctx, const RatePlan &p, RateSubmission &s) {
+    const int np = (int)s.probes.size();
+    layout_rate_submission(p.mixed, s, kRateWorkspaceBytes / 128);
+    int rc = ensure_scratch(ctx, 0, s.max_pass_blocks * 128 + 16);
+    if (rc) return rc;
+    rc = ensure_rate(ctx, (size_t)np);
+    if (rc) return rc;
+    size_t ntabs = 0;
+    for (size_t i = 0; i + 1 < s.pass_first.size(); i++) ntabs += (size_t)(s.pass_first[i + 1] - s.pass_first[i] + kSizeMaxProbes - 1) / kSizeMaxProbes;
+    const size_t tab_bytes = ntabs * sizeof(SizeProbeTable), tab_alloc = align_up(tab_bytes, 16384);
+    rc = grow_pinned(ctx, ctx->h_rate_tabs, ctx->rate_tabs_host_bytes, tab_bytes, tab_alloc);
+    if (rc) return rc;
+    rc = grow_dev(ctx, ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, tab_bytes, tab_alloc);
+    if (rc) return rc;
+    // the tables of every size launch, in launch order
+    std::vector<size_t> tab_groups(ntabs);
+    size_t t = 0;
+    for (size_t i = 0; i + 1 < s.pass_first.size(); i++)
+        for (int first = s.pass_first[i]; first < s.pass_first[i + 1]; first += kSizeMaxProbes, t++) {
+            const int cnt = std::min(kSizeMaxProbes, s.pass_first[i + 1] - first);
+            size_t nblk[kSizeMaxProbes], total = 0;
+            uint32_t result[kSizeMaxProbes];
+            for (int k = 0; k < cnt; k++) nblk[k] = p.mixed.frames[(size_t)s.probes[(size_t)(first + k)].frame].nblk, result[k] = (uint32_t)(first + k);
+            if (!fill_size_probe_table(&ctx->h_rate_tabs[t], cnt, nblk, result, &tab_groups[t], &total))
+                return set_err(ctx, TIC_E_ARG, "rate batch: probes %d.. have no table", first);
+        }
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_rate, 0, (size_t)np * sizeof(SizeResult), ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_rate_tabs, ctx->h_rate_tabs, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    t = 0;
+    for (size_t i = 0; i + 1 < s.pass_first.size(); i++) {
+        const int end = s.pass_first[i + 1];
+        for (int k = s.pass_first[i]; k < end;) {
+            int h_total = 0;
+            const int m = rate_transform_run(p, s, k, end, &h_total);
+            const MixedFrame &f = p.mixed.frames[(size_t)s.probes[(size_t)k].frame];
+            DctqArgs a = make_args(ctx, (const char *)ctx->d_img + f.img_off, h_total, f.w, (ptrdiff_t)f.pitch, s.probes[(size_t)k].quality,
+                                   (int16_t *)ctx->d_coef + s.first_block[(size_t)k] * 64);
+            a.fallback_count = nullptr;
+            HIPCHK(ctx, launch_dctq(a, 2, ctx->stream));
+            k += m;
+        }
+        for (int first = s.pass_first[i]; first < end; first += kSizeMaxProbes, t++) {
+            HIPCHK(ctx, stream_size_gpu_v((const int16_t *)ctx->d_coef + s.first_block[(size_t)first] * 64, ctx->d_rate_tabs + t, tab_groups[t], ctx->d_size_tab,
+                                          ctx->d_rate, ctx->stream));
+            ctx->last_rbatch_launches++;
+        }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_rate, ctx->d_rate, (size_t)np * sizeof(SizeResult), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->last_rbatch_probes += np;
+    return TIC_OK;
+}
+
+static void reset_rate_batch(tic_ctx *ctx) {
+    ctx->last_rbatch_frames = ctx->last_rbatch_single = ctx->last_rbatch_chunks = 0;
+    ctx->last_rbatch_probes = ctx->last_rbatch_waits = ctx->last_rbatch_launches = 0;
+}
+
+int tic_stream_sizes_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides, const int *qualities,
+                       int nq, long long *sizes) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    // every check before any work
+    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
+    if (nq < 0 || (nq > 0 && !qualities)) return set_err(ctx, TIC_E_ARG, "bad quality list");
+    reset_rate_batch(ctx);
+    if (n == 0 || nq == 0) return TIC_OK;
+    if (!images || !hs || !ws || !row_strides || !sizes) return set_err(ctx, TIC_E_ARG, "null array argument");
+    const RateCall io = {images, hs, ws, row_strides};
+    for (int j = 0; j < nq; j++) {
+        const int rc = check_rate_frames(ctx, io, n, qualities[j]);
+        if (rc) return rc;
+    }
+    int chunk_frames;
+    size_t chunk_bytes;
+    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
+    const RatePlan p = plan_rate_batch(hs, ws, n, chunk_frames, chunk_bytes);
+    for (int i : p.mixed.empty) // header only (codec.py:151)
+        for (int j = 0; j < nq; j++) sizes[(size_t)i * nq + j] = 16;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RateSubmission s;
+    for (const MixedChunk &c : p.mixed.chunks) {
+        int rc = upload_rate_chunk(ctx, p.mixed, c, io);
+        if (rc) return rc;
+        s.probes.clear();
+        for (int j = 0; j < nq; j++) // quality by quality: the frames of a transform run are neighbours in the queue
+            for (int k = 0; k < c.count; k++) s.probes.push_back(RateProbe{c.first + k, qualities[j]});
+        rc = submit_rate_probes(ctx, p, s);
+        if (rc) return rc;
+        HIPCHK(ctx, wait_stream(ctx));
+        ctx->last_rbatch_waits++;
+        for (int j = 0; j < nq; j++)
+            for (int k = 0; k < c.count; k++)
+                sizes[(size_t)p.mixed.frames[(size_t)(c.first + k)].index * nq + j] = probe_size(ctx->h_rate[(size_t)j * c.count + k]);
+    }
+    ctx->last_rbatch_frames = (int)p.mixed.frames.size();
+    ctx->last_rbatch_chunks = (int)p.mixed.chunks.size();
+    for (int i : p.mixed.single) { // what the batch does not take, behind it, frame by frame
+        const int rc = tic_stream_sizes(ctx, images[i], hs[i], ws[i], row_strides[i], qualities, nq, sizes + (size_t)i * nq);
+        if (rc) {
+            const std::string why = ctx->err;
+            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
+        }
+        ctx->last_rbatch_single++;
+    }
+    return TIC_OK;
+}
+
+// Phase 1 of tic_compress_batch_to_size for one chunk: its upload, then the bisections of all its frames in lockstep - a round is one
+// submission of every unsettled frame's candidates, one read-back and one wait.  search[f]: plan frame f.
+static int search_rate_chunk(tic_ctx *ctx, const RatePlan &p, int ci, const RateCall &io, RateSearch *search) {
+    const MixedChunk &c = p.mixed.chunks[(size_t)ci];
+    int rc = upload_rate_chunk(ctx, p.mixed, c, io);
+    if (rc) return rc;
+    RateSubmission s;
+    for (;;) {
+        rate_round_probes(c, search, p.depth[(size_t)ci], s.probes);
+        if (s.probes.empty()) return TIC_OK;
+        rc = submit_rate_probes(ctx, p, s);
+        if (rc) return rc;
+        HIPCHK(ctx, wait_stream(ctx));
+        ctx->last_rbatch_waits++;
+        for (size_t i = 0; i < s.probes.size(); i++) search[s.probes[i].frame].known[s.probes[i].quality] = probe_size(ctx->h_rate[i]);
+        for (int k = 0; k < c.count; k++) rate_search_replay(search[c.first + k]);
+    }
+}
+
+int tic_compress_batch_to_size(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                               const size_t *max_bytes, int qmin, int qmax, uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *qualities,
+                               int *status) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    // every check before any work: nothing is written while an argument of the call is unacceptable
+    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
+    if (qmin < 1 || qmax > 99 || qmin > qmax) return set_err(ctx, TIC_E_QUALITY, "quality range %d..%d is not inside 1..99", qmin, qmax);
+    reset_rate_batch(ctx);
+    if (n == 0) return TIC_OK;
+    if (!images || !hs || !ws || !row_strides || !max_bytes || !outs || !caps || !out_lens || !qualities || !status)
+        return set_err(ctx, TIC_E_ARG, "null array argument");
+    const RateCall io = {images, hs, ws, row_strides};
+    int rc = check_rate_frames(ctx, io, n, qmin);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++)
+        if (!outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
+    int chunk_frames;
+    size_t chunk_bytes;
+    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
+    const RatePlan p = plan_rate_batch(hs, ws, n, chunk_frames, chunk_bytes);
+    for (int i = 0; i < n; i++) status[i] = TIC_OK;
+    std::string first_err; // the message of the first failing frame, in frame order
+    int first_bad = n;
+    auto fail = [&](int i, int code) {
+        status[i] = code;
+        if (i < first_bad) first_bad = i, first_err = ctx->err;
+    };
+    for (int i : p.mixed.empty) { // a header at every quality: the bisection ends at qmax
+        if (max_bytes[i] < 16) {
+            out_lens[i] = 16;
+            fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: 16 bytes at quality %d exceed the budget of %zu", i, qmin, max_bytes[i]));
+        } else if (caps[i] < 16) {
+            out_lens[i] = 16;
+            fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small (16 bytes needed, %zu given)", i, caps[i]));
+        } else {
+            write_header(outs[i], hs[i], ws[i], qmax);
+            out_lens[i] = 16, qualities[i] = qmax;
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // phase 1: the searches, chunk by chunk
+    std::vector<RateSearch> search(p.mixed.frames.size());
+    for (size_t f = 0; f < search.size(); f++) rate_search_begin(search[f], qmin, qmax, (unsigned long long)max_bytes[p.mixed.frames[f].index]);
+    for (int ci = 0; ci < (int)p.mixed.chunks.size(); ci++) {
+        rc = search_rate_chunk(ctx, p, ci, io, search.data());
+        if (rc) return rc;
+    }
+    ctx->last_rbatch_frames = (int)p.mixed.frames.size();
+    ctx->last_rbatch_chunks = (int)p.mixed.chunks.size();
+    // phase 2: the streams of the fitting frames, at the qualities found, by the mixed batch (which uploads their pixels again)
+    std::vector<int> sub; // plan frames that get a stream
+    for (size_t f = 0; f < search.size(); f++) {
+        const RateSearch &r = search[f];
+        const int i = p.mixed.frames[f].index;
+        if (r.state == kRateNoCode) {
+            fail(i, set_err(ctx, TIC_E_RANGE, "frame %d: coefficient without a Huffman code at quality %d (reference raises KeyError)", i, qmin));
+        } else if (r.state == kRateTooLarge) {
+            out_lens[i] = (size_t)r.known[qmin];
+            fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: %lld bytes at quality %d exceed the budget of %zu", i, r.known[qmin], qmin, max_bytes[i]));
+        } else if ((size_t)r.known[r.lo] > caps[i]) {
+            out_lens[i] = (size_t)r.known[r.lo];
+            fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small (%lld bytes needed, %zu given)", i, r.known[r.lo], caps[i]));
+        } else {
+            sub.push_back((int)f);
+        }
+    }
+    if (!sub.empty()) {
+        const size_t m = sub.size();
+        std::vector<const uint8_t *> im(m);
+        std::vector<int> sh(m), sw(m), sq(m);
+        std::vector<ptrdiff_t> ss(m);
+        std::vector<uint8_t *> so(m);
+        std::vector<size_t> sc(m), sl(m);
+        for (size_t k = 0; k < m; k++) {
+            const RateSearch &r = search[(size_t)sub[k]];
+            const int i = p.mixed.frames[(size_t)sub[k]].index;
+            im[k] = images[i], sh[k] = hs[i], sw[k] = ws[i], ss[k] = row_strides[i], sq[k] = r.lo;
+            so[k] = outs[i], sc[k] = (size_t)r.known[r.lo], sl[k] = 0; // (the capacity is the probe's length: a longer stream fails before it is written)
+        }
+        rc = tic_compress_batch_v(ctx, im.data(), (int)m, sh.data(), sw.data(), ss.data(), sq.data(), so.data(), sc.data(), sl.data());
+        if (rc == TIC_E_SPACE || rc == TIC_E_RANGE) { // (a stream longer than its probe, or no code where the probe found one)
+            const std::string why = ctx->err;
+            return set_err(ctx, TIC_E_HIP, "the packed streams contradict their probes: %s", why.c_str());
+        }
+        if (rc) return rc;
+        for (size_t k = 0; k < m; k++) {
+            const int i = p.mixed.frames[(size_t)sub[k]].index;
+            if (sl[k] != sc[k]) // (two independent walks over the same coefficients: cannot differ)
+                return set_err(ctx, TIC_E_HIP, "frame %d: the packed stream (%zu bytes) contradicts its probe (%zu bytes)", i, sl[k], sc[k]);
+            out_lens[i] = sl[k], qualities[i] = sq[k];
+        }
+    }
+    for (int i : p.mixed.single) { // what the batch does not take, behind it: the single-frame search
+        rc = tic_compress_to_size(ctx, images[i], hs[i], ws[i], row_strides[i], max_bytes[i], qmin, qmax, outs[i], caps[i], &out_lens[i], &qualities[i]);
+        if (rc) {
+            const std::string why = ctx->err;
+            fail(i, set_err(ctx, rc, "frame %d: %s", i, why.c_str()));
+        }
+        ctx->last_rbatch_single++;
+    }
+    if (first_bad < n) {
+        ctx->err = first_err;
+        return status[first_bad];
+    }
+    return TIC_OK;
+}
+
+int tic_last_rate_batch(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks, int *probes, int *search_waits, int *size_launches) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (batch_frames) *batch_frames = ctx->last_rbatch_frames;
+    if (single_frames) *single_frames = ctx->last_rbatch_single;
+    if (chunks) *chunks = ctx->last_rbatch_chunks;
+    if (probes) *probes = ctx->last_rbatch_probes;
+    if (search_waits) *search_waits = ctx->last_rbatch_waits;
+    if (size_launches) *size_launches = ctx->last_rbatch_launches;
     return TIC_OK;
 }
 
@@ -4116,10 +4413,9 @@ static int compress_batch_adaptive_impl(tic_ctx *ctx, const uint8_t *const *imag
         if (!outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
         if (images ? !images[i] : !coeffs[i]) return set_err(ctx, TIC_E_ARG, images ? "frame %d: null image" : "frame %d: null coefficient pointer", i);
     }
-    int chunk_frames = kMixedChunkFrames;
-    size_t chunk_bytes = kMixedChunkBytes;
-    if (const char *e = test_hook("TIC_BATCH_CHUNK")) chunk_frames = atoi(e); // (out of range: the default)
-    if (const char *e = test_hook("TIC_BATCH_CHUNK_BYTES")) chunk_bytes = strtoull(e, nullptr, 10) ? (size_t)strtoull(e, nullptr, 10) : chunk_bytes;
+    int chunk_frames;
+    size_t chunk_bytes;
+    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
     const MixedPlan p = plan_mixed_batch(hs, ws, qualities, n, chunk_frames, chunk_bytes);
     AdaptCall call = {coeffs, {images, row_strides, outs, caps, out_lens}, 0};
     ctx->last_batch_direct_frames = ctx->last_batch_staged_frames = ctx->last_batch_autoreg_frames = ctx->last_batch_zero_copy = 0;

@@ -11,8 +11,8 @@
 //   TIC_DECODE_SHADOWS      device Huffman decoder: ranges in front of its own that a wave of the measure kernel shadows (1 ... 16; default 4, 8 below 544 bits per range)
 //   TIC_DECODE_ROUNDS       device Huffman decoder: hand-over rounds of the stitch (default 8)
 //   TIC_DECODE_NO_HOSTPIX   tic_decompress of small images through the device image buffer and a DMA copy, as large ones (not through host-mapped memory)
-//   TIC_BATCH_CHUNK         tic_compress_batch, tic_compress_batch_v, tic_compress_batch_adaptive_v: frames per chunk instead of the choice by frame size
-//   TIC_BATCH_CHUNK_BYTES   tic_compress_batch_v, tic_compress_batch_adaptive_v: staged pixels per chunk instead of 32 MB (a larger frame is coded alone, behind the batch)
+//   TIC_BATCH_CHUNK         tic_compress_batch, tic_compress_batch_v, tic_compress_batch_adaptive_v, tic_stream_sizes_v, tic_compress_batch_to_size: frames per chunk instead of the choice by frame size
+//   TIC_BATCH_CHUNK_BYTES   tic_compress_batch_v, tic_compress_batch_adaptive_v, tic_stream_sizes_v, tic_compress_batch_to_size: staged pixels per chunk instead of 32 MB (a larger frame is coded alone, behind the batch)
 //   TIC_DBATCH_CHUNK        tic_decompress_batch: frames per chunk instead of 1,024 (1 ... 1024; anything else is ignored)
 //   TIC_ADBATCH_CHUNK       tic_decompress_batch_adaptive: frames per chunk instead of 1,024 (1 ... 1024; anything else is ignored)
 //   TIC_DBATCH_WORK_CAP     tic_decompress_batch: at most this many bytes of work buffer are handed to the batch launcher (it refuses a chunk that needs more)

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "tic_rate_plan.h"
+
 namespace tic {
 
 // Code lengths as the size kernel looks them up: len[run * kSizeTabSizes + size] = bits a non-zero AC entry of size category `size`
@@ -29,5 +31,11 @@ struct SizeResult {
 // entries).  Reads the coefficients once, writes nothing else.
 hipError_t stream_size_gpu(const int16_t *d_zz, size_t blocks_per_frame, int nframes, const SizeTabDev *d_tab, SizeResult *d_res,
                            hipStream_t stream);
+
+// The descriptor form: ONE launch sums the probes of a SizeProbeTable (tic_rate_plan.h: fill_size_probe_table) - up to kSizeMaxProbes,
+// each a frame's coefficients at one quality with its own block count, back to back from d_zz - into d_res[rec.result].  ngroups: the
+// table's total.  d_probes is read by the kernel: device memory, complete on `stream` before the launch.  The caller zeroes the results.
+hipError_t stream_size_gpu_v(const int16_t *d_zz, const SizeProbeTable *d_probes, size_t ngroups, const SizeTabDev *d_tab, SizeResult *d_res,
+                             hipStream_t stream);
 
 } // namespace tic
