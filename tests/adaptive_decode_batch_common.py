@@ -11,6 +11,7 @@ import tinyimgcodec_amd as T
 from tinyimgcodec_amd import _native as N
 
 from adaptive_batch_common import GOLDEN, load_fixture, make_frame, sha  # noqa: F401  (re-exported)
+from adaptive_tables import longcode_coeffs  # noqa: F401  (re-exported: the synthetic coefficients of make_goldens_adaptive.py)
 
 
 def px_sha(a):
@@ -36,33 +37,6 @@ def case_image(name, h, w):
     if name == "frame_1080p":
         return rand_frame(1234, h, w)
     raise KeyError(name)
-
-
-def longcode_coeffs():
-    """The synthetic coefficients of make_goldens_adaptive.py (Fibonacci AC counts; checked by the fixture's sha256)."""
-    syms = [(2, s) for s in (15, 14, 13)] + [(1, s) for s in range(15, 0, -1)] + [(0, s) for s in range(15, 0, -1)]
-    fib = [1, 1]
-    while len(fib) < len(syms):
-        fib.append(fib[-1] + fib[-2])
-    bidx, spos, vals = [], [], []
-    block, pos = 0, 1
-    for (run, size), cnt in zip(syms, fib):
-        width = run + 1
-        here = (63 - run - pos) // width + 1 if pos + run <= 63 else 0
-        per = (62 - run) // width + 1
-        i = np.arange(cnt)
-        later = np.maximum(i - here, 0)
-        b = np.where(i < here, block, block + 1 + later // per)
-        p = np.where(i < here, pos + i * width, 1 + (later % per) * width)
-        v = (1 << (size - 1)) + (size > 1)
-        bidx.append(b)
-        spos.append(p + run)
-        vals.append(np.where(i % 2 == 0, v, -v))
-        block, pos = int(b[-1]), int(p[-1]) + width
-    zz = np.zeros((block + 1, 64), np.int16)
-    zz[np.concatenate(bidx), np.concatenate(spos)] = np.concatenate(vals)
-    zz[:, 0] = (np.arange(zz.shape[0]) % 5) - 2
-    return zz
 
 
 def table_layout(stream):

@@ -143,8 +143,9 @@ def test_workgroup_boundaries(ctx, fx):
 
 def test_one_frames_give_up_leaves_its_neighbours_alone(ctx, fx):
     """The long-code stream (146,579 blocks; its chain advances a workgroup per launch) between two 64 x 96 noise streams: its pixels are decode()
-    of its coefficients, the neighbours' the fixtures'.  Whether it settles within the batch's nineteen rounds (then it counts as a batch frame) or
-    goes to the single call with its 512 rounds is printed; the sum is asserted."""
+    of its coefficients, the neighbours' the fixtures'.  A model of the stitch (tests/adaptive_tables.py stitch_model, its list for this stream in
+    tests/golden/adaptive_tables.json) settles it in round 280, far behind the batch's nineteen: it is the single call's frame, with its 512
+    rounds, and its neighbours are the batch kernels'."""
     e = fx["longcode"]
     zz = D.longcode_coeffs()
     assert zz.shape[0] == 146579 and D.sha(np.ascontiguousarray(zz.astype("<i2")).tobytes()) == e["coeffs_sha256"]
@@ -161,7 +162,7 @@ def test_one_frames_give_up_leaves_its_neighbours_alone(ctx, fx):
     want = T.decode({"height": e["height"], "width": e["width"], "quality": e["quality"], "scaled_dct": False, "dc": dc,
                      "ac": zz[:, 1:].astype(np.int32)}, ctx=ctx)
     assert np.array_equal(got[1], want)
-    assert figs[0] + figs[1] == 3 and figs[0] >= 2 and figs[2] == 1
+    assert figs == (2, 1, 1)
 
 
 def damaged(s):
