@@ -350,6 +350,45 @@ int tic_compress_batch_to_size(tic_ctx *ctx, const uint8_t *const *images, int n
  * size kernel's descriptor form.  Any pointer may be NULL. */
 int tic_last_rate_batch(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks, int *probes, int *search_waits, int *size_launches);
 
+/* ---- rate-distortion for a batch ---------------------------------------------------------------------------------------------------
+ * tic_rd_points of n frames of ANY sizes in one call: sizes / sse / sse_wrapped[i * nq + j] are what tic_rd_points gives for frame i at
+ * qualities[j] (size -1 where a coefficient has no Huffman code, the sums reported all the same; 16 / 0 / 0 for a frame without blocks) -
+ * the reference's benchmark loop compress -> decompress -> psnr over 49 images x 6 qualities (tests/benchmark.py) is one call.  Argument
+ * checks and their order are tic_stream_sizes_v's; a null sse or sse_wrapped with work to do is TIC_E_ARG.  The route is
+ * tic_stream_sizes_v's: per chunk one upload, one memset of both result arrays, every probe queued quality by quality - per pass over the
+ * workspace the transforms, then per 64 probes one launch of the size kernel's descriptor form and one of the measuring kernel's - one
+ * read-back, one wait.  Frames the batch does not take go through tic_rd_points behind it ("frame i: ..." on error). */
+int tic_rd_points_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                    const int *qualities, int nq, long long *sizes, uint64_t *sse, uint64_t *sse_wrapped);
+/* tic_compress_to_psnr of n frames of ANY sizes, each against its own bound max_sse[i], over one quality range: frame i gets exactly what
+ * tic_compress_to_psnr(image i, max_sse[i], qmin, qmax) gives - outs[i] (caps[i] bytes), out_lens[i], qualities[i], sse[i] - and status[i]:
+ *     TIC_OK        the stream, its length, its quality and its squared error are set; no byte of outs[i] behind out_lens[i] is written
+ *                   (a frame without blocks: the header at qmin, sse[i] = 0)
+ *     TIC_E_RANGE   qmax has a coefficient without a Huffman code: qualities[i] = qmax, sse[i] = its error, out_lens[i] = 0
+ *     TIC_E_SPACE   qmax misses the bound: qualities[i] = qmax, sse[i] = its error, out_lens[i] = 0; or the chosen stream exceeds caps[i]:
+ *                   out_lens[i] = its length (at least 16), sse[i] = its error
+ * outs[i] is untouched on every failure.  The call returns the first non-OK status in frame order (tic_last_error: that frame's message,
+ * "frame i: ..."); the other frames are delivered all the same.  Argument errors are tic_compress_batch_to_size's, found before any work.
+ * Phase 1, per chunk: one upload, then the bisections of all its frames in lockstep - every round one submission of each unsettled frame's
+ * next middles (1 to 3 steps ahead, by the chunk's size; the first round qmax as well), one read-back, one wait: at most 1 + ceil(7 / depth)
+ * rounds.  Phase 2: the streams of the frames that ended well from tic_compress_batch_v at the qualities found; a length that contradicts
+ * its probe is TIC_E_HIP.  Frames the batch does not take go through tic_compress_to_psnr behind it. */
+int tic_compress_batch_to_psnr(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                               const uint64_t *max_sse, int qmin, int qmax, uint8_t *const *outs, const size_t *caps, size_t *out_lens,
+                               int *qualities, uint64_t *sse, int *status);
+/* tic_last_rate_batch reports the two calls above as well (size_launches stays the size launches); *sse_launches: launches of the measuring
+ * kernel's descriptor form by the last of them, or by the last tic_distortion_v_dev.  The pointer may be NULL. */
+int tic_last_rd_batch(tic_ctx *ctx, int *sse_launches);
+/* The measuring kernel's descriptor form alone, synchronous, on n probes: probe i is the hs[i] x ws[i] frame d_images[i] (a host array of
+ * device pointers; rows row_strides[i] bytes apart) against coefficients of the float codec at qualities[i].  The coefficients of all
+ * probes lie back to back at d_coeffs_zz (device layout, tic_num_blocks(hs[i], ws[i]) blocks each).  sums[2 * i], sums[2 * i + 1]: probe
+ * i's two sums (0, 0 without blocks).  One launch per 64 probes with blocks.  Checks as tic_distortion_dev, per probe ("probe i: ..."). */
+int tic_distortion_v_dev(tic_ctx *ctx, const void *d_coeffs_zz, const void *const *d_images, int n, const int *hs, const int *ws,
+                         const ptrdiff_t *row_strides, const int *qualities, uint64_t *sums);
+/* Times those launches alone, as tic_distortion_dev_timed times its one: *ms_total = elapsed milliseconds for `iters` rounds of them. */
+int tic_distortion_v_dev_timed(tic_ctx *ctx, const void *d_coeffs_zz, const void *const *d_images, int n, const int *hs, const int *ws,
+                               const ptrdiff_t *row_strides, const int *qualities, int warm, int iters, float *ms_total);
+
 /* The same batch spread over nctx contexts - one per GPU of the node - by ONE process: a host thread per context, contiguous
  * shards of ceil(n / nctx) frames in frame order, no exchange between the shards; out_lens in frame order.  What a caller that
  * loops over images (/root/reference/tests/benchmark.py:12-23) gets from a multi-GPU node without a launcher.  Returns the first

@@ -174,6 +174,26 @@ SIGNATURES = {
         C.c_int,
         [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     ),
+    "tic_rd_points_v": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ssize_t), C.c_void_p, C.c_int, C.c_void_p,
+         C.c_void_p, C.c_void_p],
+    ),
+    "tic_compress_batch_to_psnr": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ssize_t), C.POINTER(C.c_uint64), C.c_int, C.c_int,
+         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_int)],
+    ),
+    "tic_last_rd_batch": (C.c_int, [_ctxp, C.POINTER(C.c_int)]),
+    "tic_distortion_v_dev": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ssize_t), C.POINTER(C.c_int), C.c_void_p],
+    ),
+    "tic_distortion_v_dev_timed": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ssize_t), C.POINTER(C.c_int), C.c_int,
+         C.c_int, C.POINTER(C.c_float)],
+    ),
     "tic_compress_batch_multi": (
         C.c_int,
         [C.POINTER(_ctxp), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.POINTER(C.c_void_p),

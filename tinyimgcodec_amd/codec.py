@@ -598,6 +598,81 @@ def compress_to_psnr(image, min_psnr, min_quality=1, max_quality=99, ctx=None):
         return out[: n.value].tobytes(), int(q.value), psnr_from_sse(sse.value, h * w)
 
 
+def rd_points_batch(images, qualities, ctx=None):
+    """rd_points(image, qualities) of every image of a list, of any shapes, in one call -> (sizes int64 (n, nq), sse uint64 (n, nq),
+    sse_wrapped uint64 (n, nq)).  The reference's benchmark loop compress -> decompress -> psnr over 49 images x 6 qualities is one call:
+    per chunk of up to 64 frames one upload, every probe queued, one launch of the size kernel and one of the measuring kernel per 64
+    probes, one read-back (tic_rd_points_v).  Validation as compressed_sizes_batch."""
+    frames = [_as_u8_image(im) for im in images]
+    qs = [_check_quality(q, packs_header=True) for q in qualities]
+    sizes = np.zeros((len(frames), len(qs)), dtype=np.int64)
+    sse = np.zeros((len(frames), len(qs)), dtype=np.uint64)
+    wrapped = np.zeros((len(frames), len(qs)), dtype=np.uint64)
+    if not frames or not qs:
+        return sizes, sse, wrapped
+    ctx = _ctx(ctx)
+    qarr = np.asarray(qs, dtype=np.intc)
+    inp, hs, ws, strides = _frame_arrays(frames)
+    with ctx.lock:
+        ctx.check(N.load().tic_rd_points_v(ctx.handle, inp, len(frames), hs, ws, strides, qarr.ctypes.data, len(qs), sizes.ctypes.data,
+                                           sse.ctypes.data, wrapped.ctypes.data))
+    return sizes, sse, wrapped
+
+
+def compress_batch_to_psnr(images, min_psnr, min_quality=1, max_quality=99, ctx=None):
+    """compress_to_psnr(image, min_psnr, min_quality, max_quality) of every image of a list, of any shapes, in one call ->
+    [(bytes, quality, psnr), ...].  min_psnr: one target for all, or a sequence with one per frame; each frame's bound is
+    max_sse_for_psnr of its target over its own h * w pixels, its psnr is psnr_from_sse of its exact squared error.  The bisections of up
+    to 64 frames run in lockstep - one submission and one wait per round for all of them - and the streams of all frames come from one
+    mixed batch (tic_compress_batch_to_psnr).  Argument errors are compress_to_psnr's, raised before any GPU work; a frame that fails
+    raises, for the first such frame, what compress_to_psnr raises for it, the message prefixed "frame i: ".  8-bit images only."""
+    frames = [_as_u8_image(im) for im in images]
+    qmin = _check_quality(min_quality, packs_header=True)
+    qmax = _check_quality(max_quality, packs_header=True)
+    if qmin > qmax:
+        raise ValueError("min_quality %d above max_quality %d" % (qmin, qmax))
+    n = len(frames)
+    if hasattr(min_psnr, "__len__"):
+        if len(min_psnr) != n:
+            raise ValueError("min_psnr has %d entries for %d frames" % (len(min_psnr), n))
+        targets = [float(t) for t in min_psnr]
+    else:
+        targets = [float(min_psnr)] * n
+    bounds = [max_sse_for_psnr(t, f[1] * f[2]) for t, f in zip(targets, frames)]
+    if not frames:
+        return []
+    ctx = _ctx(ctx)
+    L = N.load()
+    caps_l = [L.tic_compress_bound(f[1], f[2]) for f in frames]
+    offs = np.concatenate(([0], np.cumsum([(c + 63) // 64 * 64 for c in caps_l]))).astype(np.int64)
+    inp, hs, ws, strides = _frame_arrays(frames)
+    with ctx.lock:
+        pool = getattr(ctx, "_mixed_pool", None)  # compress_batch()'s landing buffer for mixed frames
+        if pool is None or pool.size < offs[-1]:
+            pool = ctx._mixed_pool = np.empty(int(offs[-1]), dtype=np.uint8)
+        base = pool.ctypes.data
+        outp = (C.c_void_p * n)(*[base + int(o) for o in offs[:-1]])
+        caps = (C.c_size_t * n)(*caps_l)
+        bnd = (C.c_uint64 * n)(*bounds)
+        lens = (C.c_size_t * n)()
+        qout = (C.c_int * n)()
+        sse = (C.c_uint64 * n)()
+        status = (C.c_int * n)()
+        rc = L.tic_compress_batch_to_psnr(ctx.handle, inp, n, hs, ws, strides, bnd, qmin, qmax, outp, caps, lens, qout, sse, status)
+        bad = next((i for i in range(n) if status[i] != N.TIC_OK), None)
+        npix = [f[1] * f[2] for f in frames]
+        if bad is None:
+            ctx.check(rc)  # (a failure of the call itself: no frame to name)
+        elif status[bad] == N.TIC_E_RANGE:
+            raise KeyError("frame %d: coefficient magnitude has no Huffman code" % bad)
+        elif status[bad] == N.TIC_E_SPACE and lens[bad] == 0:
+            raise ValueError("frame %d: %r dB at quality %d fall short of min_psnr = %r"
+                             % (bad, psnr_from_sse(sse[bad], npix[bad]), qmax, targets[bad]))
+        else:
+            ctx.check(status[bad])
+        return [(pool[int(offs[i]): int(offs[i]) + lens[i]].tobytes(), int(qout[i]), psnr_from_sse(sse[i], npix[i])) for i in range(n)]
+
+
 SCALED_SETTINGS = ("best", "high", "med", "low")  # encode.c:20-34; the header's quality field holds the index
 
 

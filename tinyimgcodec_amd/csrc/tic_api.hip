@@ -27,6 +27,7 @@
 #include "tic_host_pipeline.h"
 #include "tic_kernels.h"
 #include "tic_math.h"
+#include "tic_rd_plan.h"
 #include "tic_scaled.h"
 #include "tic_size_gpu.h"
 
@@ -291,6 +292,11 @@ struct tic_ctx {
     SizeProbeTable *h_rate_tabs = nullptr, *d_rate_tabs = nullptr;
     size_t rate_tabs_host_bytes = 0, rate_tabs_dev_bytes = 0;
     int last_rbatch_frames = 0, last_rbatch_single = 0, last_rbatch_chunks = 0, last_rbatch_probes = 0, last_rbatch_waits = 0, last_rbatch_launches = 0;
+    // ... and of rate-distortion control (tic_rd_points_v, tic_compress_batch_to_psnr, tic_distortion_v_dev): the tables of the measuring
+    // kernel's descriptor form, one per launch
+    SseProbeTable *h_rd_tabs = nullptr, *d_rd_tabs = nullptr;
+    size_t rd_tabs_host_bytes = 0, rd_tabs_dev_bytes = 0;
+    int last_rbatch_sse_launches = 0;
 };
 
 // NUMA node of a device (its PCI function's numa_node in sysfs) and the CPUs of that node within this process's affinity mask.
@@ -530,6 +536,8 @@ void tic_destroy(tic_ctx *ctx) {
     if (ctx->h_rate_pix) (void)hipHostFree(ctx->h_rate_pix);
     if (ctx->h_rate_tabs) (void)hipHostFree(ctx->h_rate_tabs);
     if (ctx->d_rate_tabs) (void)hipFree(ctx->d_rate_tabs);
+    if (ctx->h_rd_tabs) (void)hipHostFree(ctx->h_rd_tabs);
+    if (ctx->d_rd_tabs) (void)hipFree(ctx->d_rd_tabs);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1811,14 +1819,7 @@ int tic_rd_points(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t ro
 
 // The search by distortion: the mirror of compress_to_size_impl.  Contract (header, tic_compress_to_psnr_dev): lo, hi = qmin, qmax;
 // while lo < hi: mid = (lo + hi) / 2; meets(mid) ? hi = mid : lo = mid + 1 - the first probe is qmax as well, the look-ahead and its depth
-// per frame size are the size search's.
-static void psnr_candidates(int lo, int hi, int depth, const long long *known, int *out, int *nout) {
-    if (lo >= hi || depth == 0) return;
-    const int mid = (lo + hi) / 2;
-    if (known[mid] == kRateUnknown) out[(*nout)++] = mid;
-    psnr_candidates(lo, mid, depth - 1, known, out, nout);
-    psnr_candidates(mid + 1, hi, depth - 1, known, out, nout);
-}
+// per frame size are the size search's; psnr_candidates (tic_rd_plan.h, shared with the batch form) names the middles.
 
 static int compress_to_psnr_impl(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, uint64_t max_sse, int qmin, int qmax,
                                  void *out, bool out_on_host, size_t cap, size_t *out_len, int *quality, uint64_t *sse) {
@@ -2952,7 +2953,18 @@ static int upload_rate_chunk(tic_ctx *ctx, const MixedPlan &p, const MixedChunk 
 
 // Queues the probes of `s` (frames of the chunk resident in the scratch image) and the copy of their results into ctx->h_rate, entry i for
 // probe i; the caller waits for the stream.  Nothing of an earlier submission may be in flight: the buffers may grow.
-static int submit_rate_probes(tic_ctx *ctx, const RatePlan &p, RateSubmission &s) {
+// distortion: a rate-distortion submission - behind every size launch ONE launch of the measuring kernel's descriptor form on the same probes
+// (idct_sse_kernel_v), its results behind the size results (dist_of(ctx->h_rate, probes)): the same memset clears both, the same copy brings
+// both back.
+static size_t sse_group_cap() { // (TIC_SSE_MAX_GROUPS, a test hook, lowers the cap so that the walk can be tested on frames of a few blocks)
+    if (const char *e = test_hook("TIC_SSE_MAX_GROUPS")) {
+        const long v = atol(e);
+        if (v >= 1 && v <= (long)kSseMaxGroups) return (size_t)v;
+    }
+    return kSseMaxGroups;
+}
+
+static int submit_rate_probes(tic_ctx *ctx, const RatePlan &p, RateSubmission &s, bool distortion = false) {
     const int np = (int)s.probes.size();
     layout_rate_submission(p.mixed, s, kRateWorkspaceBytes / 128);
     int rc = ensure_scratch(ctx, 0, s.max_pass_blocks * 128 + 16);
@@ -2966,8 +2978,14 @@ static int submit_rate_probes(tic_ctx *ctx, const RatePlan &p, RateSubmission &s
     if (rc) return rc;
     rc = grow_dev(ctx, ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, tab_bytes, tab_alloc);
     if (rc) return rc;
-    // the tables of every size launch, in launch order
-    std::vector<size_t> tab_groups(ntabs);
+    const size_t sse_tab_bytes = distortion ? ntabs * sizeof(SseProbeTable) : 0, sse_tab_alloc = align_up(sse_tab_bytes, 16384);
+    rc = grow_pinned(ctx, ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, sse_tab_bytes, sse_tab_alloc);
+    if (rc) return rc;
+    rc = grow_dev(ctx, ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, sse_tab_bytes, sse_tab_alloc);
+    if (rc) return rc;
+    const size_t sse_cap = sse_group_cap();
+    // the tables of every size launch (and of the measuring launch behind it), in launch order
+    std::vector<size_t> tab_groups(ntabs), sse_groups(ntabs);
     size_t t = 0;
     for (size_t i = 0; i + 1 < s.pass_first.size(); i++)
         for (int first = s.pass_first[i]; first < s.pass_first[i + 1]; first += kSizeMaxProbes, t++) {
@@ -2977,9 +2995,22 @@ static int submit_rate_probes(tic_ctx *ctx, const RatePlan &p, RateSubmission &s
             for (int k = 0; k < cnt; k++) nblk[k] = p.mixed.frames[(size_t)s.probes[(size_t)(first + k)].frame].nblk, result[k] = (uint32_t)(first + k);
             if (!fill_size_probe_table(&ctx->h_rate_tabs[t], cnt, nblk, result, &tab_groups[t], &total))
                 return set_err(ctx, TIC_E_ARG, "rate batch: probes %d.. have no table", first);
+            if (distortion) {
+                SseProbeIn in[kSseMaxProbes];
+                for (int k = 0; k < cnt; k++) {
+                    const RateProbe &pr = s.probes[(size_t)(first + k)];
+                    const MixedFrame &f = p.mixed.frames[(size_t)pr.frame];
+                    in[k] = SseProbeIn{(const int16_t *)ctx->d_coef + s.first_block[(size_t)(first + k)] * 64, (const uint8_t *)ctx->d_img + f.img_off,
+                                       ctx->d_consts + pr.quality, (long long)f.pitch, f.h, f.w, (uint32_t)(first + k)};
+                }
+                if (!fill_sse_probe_table(&ctx->h_rd_tabs[t], cnt, in, sse_cap, &sse_groups[t]))
+                    return set_err(ctx, TIC_E_ARG, "rate-distortion batch: probes %d.. have no table", first);
+            }
         }
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_rate, 0, (size_t)np * sizeof(SizeResult), ctx->stream));
+    const size_t res_bytes = (size_t)np * (sizeof(SizeResult) + (distortion ? sizeof(DistortionResult) : 0));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_rate, 0, res_bytes, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_rate_tabs, ctx->h_rate_tabs, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (distortion) HIPCHK(ctx, hipMemcpyAsync(ctx->d_rd_tabs, ctx->h_rd_tabs, sse_tab_bytes, hipMemcpyHostToDevice, ctx->stream));
     t = 0;
     for (size_t i = 0; i + 1 < s.pass_first.size(); i++) {
         const int end = s.pass_first[i + 1];
@@ -2997,16 +3028,20 @@ static int submit_rate_probes(tic_ctx *ctx, const RatePlan &p, RateSubmission &s
             HIPCHK(ctx, stream_size_gpu_v((const int16_t *)ctx->d_coef + s.first_block[(size_t)first] * 64, ctx->d_rate_tabs + t, tab_groups[t], ctx->d_size_tab,
                                           ctx->d_rate, ctx->stream));
             ctx->last_rbatch_launches++;
+            if (distortion) {
+                HIPCHK(ctx, launch_idct_sse_v(ctx->d_rd_tabs + t, sse_groups[t], dist_of(ctx->d_rate, np), ctx->stream));
+                ctx->last_rbatch_sse_launches++;
+            }
         }
     }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_rate, ctx->d_rate, (size_t)np * sizeof(SizeResult), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_rate, ctx->d_rate, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
     ctx->last_rbatch_probes += np;
     return TIC_OK;
 }
 
 static void reset_rate_batch(tic_ctx *ctx) {
     ctx->last_rbatch_frames = ctx->last_rbatch_single = ctx->last_rbatch_chunks = 0;
-    ctx->last_rbatch_probes = ctx->last_rbatch_waits = ctx->last_rbatch_launches = 0;
+    ctx->last_rbatch_probes = ctx->last_rbatch_waits = ctx->last_rbatch_launches = ctx->last_rbatch_sse_launches = 0;
 }
 
 int tic_stream_sizes_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides, const int *qualities,
@@ -3196,6 +3231,312 @@ int tic_last_rate_batch(tic_ctx *ctx, int *batch_frames, int *single_frames, int
     if (search_waits) *search_waits = ctx->last_rbatch_waits;
     if (size_launches) *size_launches = ctx->last_rbatch_launches;
     return TIC_OK;
+}
+
+// ---- rate-distortion for a batch: the (size, error) tables of n frames, and the smallest stream of each at no more than its own error --------
+// (tic_rd_points_v, tic_compress_batch_to_psnr.)  The routes are the two above with a rate-distortion submission (submit_rate_probes,
+// distortion = true): the chunks, the one upload per chunk, the passes over the workspace and the look-ahead depth are the rate plan's; the
+// search by distortion is tic_rd_plan.h's, the mirror of the search by size.
+int tic_rd_points_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides, const int *qualities,
+                    int nq, long long *sizes, uint64_t *sse, uint64_t *sse_wrapped) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    // every check before any work
+    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
+    if (nq < 0 || (nq > 0 && !qualities)) return set_err(ctx, TIC_E_ARG, "bad quality list");
+    reset_rate_batch(ctx);
+    if (n == 0 || nq == 0) return TIC_OK;
+    if (!images || !hs || !ws || !row_strides || !sizes) return set_err(ctx, TIC_E_ARG, "null array argument");
+    if (!sse || !sse_wrapped) return set_err(ctx, TIC_E_ARG, "null result pointer");
+    const RateCall io = {images, hs, ws, row_strides};
+    for (int j = 0; j < nq; j++) {
+        const int rc = check_rate_frames(ctx, io, n, qualities[j]);
+        if (rc) return rc;
+    }
+    int chunk_frames;
+    size_t chunk_bytes;
+    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
+    const RatePlan p = plan_rate_batch(hs, ws, n, chunk_frames, chunk_bytes);
+    for (int i : p.mixed.empty) // header only (codec.py:151): no pixel, no error
+        for (int j = 0; j < nq; j++) {
+            sizes[(size_t)i * nq + j] = 16;
+            sse[(size_t)i * nq + j] = sse_wrapped[(size_t)i * nq + j] = 0;
+        }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RateSubmission s;
+    for (const MixedChunk &c : p.mixed.chunks) {
+        int rc = upload_rate_chunk(ctx, p.mixed, c, io);
+        if (rc) return rc;
+        s.probes.clear();
+        for (int j = 0; j < nq; j++) // quality by quality: the frames of a transform run are neighbours in the queue
+            for (int k = 0; k < c.count; k++) s.probes.push_back(RateProbe{c.first + k, qualities[j]});
+        rc = submit_rate_probes(ctx, p, s, true);
+        if (rc) return rc;
+        HIPCHK(ctx, wait_stream(ctx));
+        ctx->last_rbatch_waits++;
+        const DistortionResult *d = dist_of(ctx->h_rate, (int)s.probes.size());
+        for (int j = 0; j < nq; j++)
+            for (int k = 0; k < c.count; k++) {
+                const size_t at = (size_t)p.mixed.frames[(size_t)(c.first + k)].index * nq + j, pr = (size_t)j * c.count + k;
+                sizes[at] = probe_size(ctx->h_rate[pr]);
+                sse[at] = d[pr].sse;
+                sse_wrapped[at] = d[pr].sse_wrapped;
+            }
+    }
+    ctx->last_rbatch_frames = (int)p.mixed.frames.size();
+    ctx->last_rbatch_chunks = (int)p.mixed.chunks.size();
+    for (int i : p.mixed.single) { // what the batch does not take, behind it, frame by frame
+        const int rc = tic_rd_points(ctx, images[i], hs[i], ws[i], row_strides[i], qualities, nq, sizes + (size_t)i * nq, sse + (size_t)i * nq,
+                                     sse_wrapped + (size_t)i * nq);
+        if (rc) {
+            const std::string why = ctx->err;
+            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
+        }
+        ctx->last_rbatch_single++;
+    }
+    return TIC_OK;
+}
+
+// Phase 1 of tic_compress_batch_to_psnr for one chunk: its upload, then the bisections of all its frames in lockstep - a round is one
+// submission of every unsettled frame's candidates, one read-back and one wait.  search[f]: plan frame f.
+static int search_psnr_chunk(tic_ctx *ctx, const RatePlan &p, int ci, const RateCall &io, PsnrSearch *search) {
+    const MixedChunk &c = p.mixed.chunks[(size_t)ci];
+    int rc = upload_rate_chunk(ctx, p.mixed, c, io);
+    if (rc) return rc;
+    RateSubmission s;
+    for (;;) {
+        psnr_round_probes(c, search, p.depth[(size_t)ci], s.probes);
+        if (s.probes.empty()) return TIC_OK;
+        rc = submit_rate_probes(ctx, p, s, true);
+        if (rc) return rc;
+        HIPCHK(ctx, wait_stream(ctx));
+        ctx->last_rbatch_waits++;
+        const DistortionResult *d = dist_of(ctx->h_rate, (int)s.probes.size());
+        for (size_t i = 0; i < s.probes.size(); i++) {
+            PsnrSearch &r = search[s.probes[i].frame];
+            r.known[s.probes[i].quality] = probe_size(ctx->h_rate[i]);
+            r.known_sse[s.probes[i].quality] = d[i].sse;
+        }
+        for (int k = 0; k < c.count; k++) psnr_search_replay(search[c.first + k]);
+    }
+}
+
+int tic_compress_batch_to_psnr(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                               const uint64_t *max_sse, int qmin, int qmax, uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *qualities,
+                               uint64_t *sse, int *status) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    // every check before any work: nothing is written while an argument of the call is unacceptable
+    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
+    if (qmin < 1 || qmax > 99 || qmin > qmax) return set_err(ctx, TIC_E_QUALITY, "quality range %d..%d is not inside 1..99", qmin, qmax);
+    reset_rate_batch(ctx);
+    if (n == 0) return TIC_OK;
+    if (!images || !hs || !ws || !row_strides || !max_sse || !outs || !caps || !out_lens || !qualities || !sse || !status)
+        return set_err(ctx, TIC_E_ARG, "null array argument");
+    const RateCall io = {images, hs, ws, row_strides};
+    int rc = check_rate_frames(ctx, io, n, qmin);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++)
+        if (!outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
+    int chunk_frames;
+    size_t chunk_bytes;
+    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
+    const RatePlan p = plan_rate_batch(hs, ws, n, chunk_frames, chunk_bytes);
+    for (int i = 0; i < n; i++) status[i] = TIC_OK;
+    std::string first_err; // the message of the first failing frame, in frame order
+    int first_bad = n;
+    auto fail = [&](int i, int code) {
+        status[i] = code;
+        if (i < first_bad) first_bad = i, first_err = ctx->err;
+    };
+    for (int i : p.mixed.empty) { // a header and no error at every quality: the bisection ends at qmin
+        if (caps[i] < 16) {
+            out_lens[i] = 16;
+            fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small (16 bytes needed, %zu given)", i, caps[i]));
+        } else {
+            write_header(outs[i], hs[i], ws[i], qmin);
+            out_lens[i] = 16, qualities[i] = qmin, sse[i] = 0;
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // phase 1: the searches, chunk by chunk
+    std::vector<PsnrSearch> search(p.mixed.frames.size());
+    for (size_t f = 0; f < search.size(); f++) psnr_search_begin(search[f], qmin, qmax, max_sse[p.mixed.frames[f].index]);
+    for (int ci = 0; ci < (int)p.mixed.chunks.size(); ci++) {
+        rc = search_psnr_chunk(ctx, p, ci, io, search.data());
+        if (rc) return rc;
+    }
+    ctx->last_rbatch_frames = (int)p.mixed.frames.size();
+    ctx->last_rbatch_chunks = (int)p.mixed.chunks.size();
+    // phase 2: the streams of the frames that met their bound, at the qualities found, by the mixed batch (which uploads their pixels again)
+    std::vector<int> sub; // plan frames that get a stream
+    for (size_t f = 0; f < search.size(); f++) {
+        const PsnrSearch &r = search[f];
+        const int i = p.mixed.frames[f].index;
+        if (r.state == kPsnrNoCode || r.state == kPsnrOutOfReach) { // the single call's side values: the quality and the error of qmax, no length
+            qualities[i] = qmax, sse[i] = r.known_sse[qmax], out_lens[i] = 0;
+            if (r.state == kPsnrNoCode)
+                fail(i, set_err(ctx, TIC_E_RANGE, "frame %d: coefficient without a Huffman code at quality %d (reference raises KeyError)", i, qmax));
+            else
+                fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: squared error %llu at quality %d exceeds the bound of %llu", i,
+                                (unsigned long long)r.known_sse[qmax], qmax, (unsigned long long)max_sse[i]));
+        } else if ((size_t)r.known[r.lo] > caps[i]) {
+            sse[i] = r.known_sse[r.lo], out_lens[i] = (size_t)r.known[r.lo];
+            fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small (%lld bytes needed, %zu given)", i, r.known[r.lo], caps[i]));
+        } else {
+            sub.push_back((int)f);
+        }
+    }
+    if (!sub.empty()) {
+        const size_t m = sub.size();
+        std::vector<const uint8_t *> im(m);
+        std::vector<int> sh(m), sw(m), sq(m);
+        std::vector<ptrdiff_t> ss(m);
+        std::vector<uint8_t *> so(m);
+        std::vector<size_t> sc(m), sl(m);
+        for (size_t k = 0; k < m; k++) {
+            const PsnrSearch &r = search[(size_t)sub[k]];
+            const int i = p.mixed.frames[(size_t)sub[k]].index;
+            im[k] = images[i], sh[k] = hs[i], sw[k] = ws[i], ss[k] = row_strides[i], sq[k] = r.lo;
+            so[k] = outs[i], sc[k] = (size_t)r.known[r.lo], sl[k] = 0; // (the capacity is the probe's length: a longer stream fails before it is written)
+        }
+        rc = tic_compress_batch_v(ctx, im.data(), (int)m, sh.data(), sw.data(), ss.data(), sq.data(), so.data(), sc.data(), sl.data());
+        if (rc == TIC_E_SPACE || rc == TIC_E_RANGE) { // (a stream longer than its probe, or no code where the probe found one)
+            const std::string why = ctx->err;
+            return set_err(ctx, TIC_E_HIP, "the packed streams contradict their probes: %s", why.c_str());
+        }
+        if (rc) return rc;
+        for (size_t k = 0; k < m; k++) {
+            const PsnrSearch &r = search[(size_t)sub[k]];
+            const int i = p.mixed.frames[(size_t)sub[k]].index;
+            if (sl[k] != sc[k]) // (two independent walks over the same coefficients: cannot differ)
+                return set_err(ctx, TIC_E_HIP, "frame %d: the packed stream (%zu bytes) contradicts its probe (%zu bytes)", i, sl[k], sc[k]);
+            out_lens[i] = sl[k], qualities[i] = sq[k], sse[i] = r.known_sse[r.lo];
+        }
+    }
+    for (int i : p.mixed.single) { // what the batch does not take, behind it: the single-frame search
+        rc = tic_compress_to_psnr(ctx, images[i], hs[i], ws[i], row_strides[i], max_sse[i], qmin, qmax, outs[i], caps[i], &out_lens[i], &qualities[i], &sse[i]);
+        if (rc) {
+            const std::string why = ctx->err;
+            fail(i, set_err(ctx, rc, "frame %d: %s", i, why.c_str()));
+        }
+        ctx->last_rbatch_single++;
+    }
+    if (first_bad < n) {
+        ctx->err = first_err;
+        return status[first_bad];
+    }
+    return TIC_OK;
+}
+
+int tic_last_rd_batch(tic_ctx *ctx, int *sse_launches) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (sse_launches) *sse_launches = ctx->last_rbatch_sse_launches;
+    return TIC_OK;
+}
+
+// The measuring kernel's descriptor form alone, on n probes whose coefficients lie back to back on the device: the tables (one per 64 probes
+// with blocks) into the context's table buffers, the results cleared.  launches[t]: the grid of table t.
+static int queue_distortion_v(tic_ctx *ctx, const void *d_coeffs_zz, const void *const *d_images, int n, const int *hs, const int *ws,
+                              const ptrdiff_t *row_strides, const int *qualities, std::vector<size_t> &launches) {
+    int rc = ensure_rate(ctx, (size_t)n);
+    if (rc) return rc;
+    const size_t ntabs = ((size_t)n + kSseMaxProbes - 1) / kSseMaxProbes; // (an upper bound: probes without blocks take no entry)
+    const size_t tab_bytes = ntabs * sizeof(SseProbeTable), tab_alloc = align_up(tab_bytes, 16384);
+    rc = grow_pinned(ctx, ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, tab_bytes, tab_alloc);
+    if (rc) return rc;
+    rc = grow_dev(ctx, ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, tab_bytes, tab_alloc);
+    if (rc) return rc;
+    const size_t cap = sse_group_cap();
+    launches.clear();
+    SseProbeIn in[kSseMaxProbes];
+    int cnt = 0;
+    size_t blk = 0;
+    auto flush = [&]() {
+        if (cnt == 0) return true;
+        size_t groups = 0;
+        if (!fill_sse_probe_table(&ctx->h_rd_tabs[launches.size()], cnt, in, cap, &groups)) return false;
+        launches.push_back(groups);
+        cnt = 0;
+        return true;
+    };
+    for (int i = 0; i < n; i++) {
+        const size_t nb = num_blocks(hs[i], ws[i]);
+        if (nb == 0) continue;
+        in[cnt++] = SseProbeIn{(const int16_t *)d_coeffs_zz + blk * 64, (const uint8_t *)d_images[i], ctx->d_consts + qualities[i], (long long)row_strides[i],
+                               hs[i], ws[i], (uint32_t)i};
+        blk += nb;
+        if (cnt == kSseMaxProbes && !flush()) return set_err(ctx, TIC_E_ARG, "probe %d: no table", i);
+    }
+    if (!flush()) return set_err(ctx, TIC_E_ARG, "probes have no table");
+    HIPCHK(ctx, hipMemsetAsync(dist_of(ctx->d_rate, n), 0, (size_t)n * sizeof(DistortionResult), ctx->stream));
+    if (!launches.empty())
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_rd_tabs, ctx->h_rd_tabs, launches.size() * sizeof(SseProbeTable), hipMemcpyHostToDevice, ctx->stream));
+    return TIC_OK;
+}
+
+static int check_distortion_v_args(tic_ctx *ctx, const void *d_coeffs_zz, const void *const *d_images, int n, const int *hs, const int *ws,
+                                   const ptrdiff_t *row_strides, const int *qualities, const void *result) {
+    if (!ctx) return TIC_E_ARG;
+    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative probe count %d", n);
+    if (n == 0) return TIC_OK;
+    if (!d_images || !hs || !ws || !row_strides || !qualities || !result) return set_err(ctx, TIC_E_ARG, "null array argument");
+    for (int i = 0; i < n; i++) {
+        const int rc = check_distortion_args(ctx, hs[i], ws[i], row_strides[i], qualities[i], -1, result);
+        if (rc) {
+            const std::string why = ctx->err;
+            return set_err(ctx, rc, "probe %d: %s", i, why.c_str());
+        }
+        if (num_blocks(hs[i], ws[i]) && (!d_coeffs_zz || !d_images[i])) return set_err(ctx, TIC_E_ARG, "probe %d: null device pointer", i);
+    }
+    return TIC_OK;
+}
+
+int tic_distortion_v_dev(tic_ctx *ctx, const void *d_coeffs_zz, const void *const *d_images, int n, const int *hs, const int *ws,
+                         const ptrdiff_t *row_strides, const int *qualities, uint64_t *sums) {
+    TIC_LOCK(ctx);
+    int rc = check_distortion_v_args(ctx, d_coeffs_zz, d_images, n, hs, ws, row_strides, qualities, sums);
+    if (rc || n == 0) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<size_t> launches;
+    rc = queue_distortion_v(ctx, d_coeffs_zz, d_images, n, hs, ws, row_strides, qualities, launches);
+    if (rc) return rc;
+    ctx->last_rbatch_sse_launches = 0;
+    for (size_t t = 0; t < launches.size(); t++) {
+        HIPCHK(ctx, launch_idct_sse_v(ctx->d_rd_tabs + t, launches[t], dist_of(ctx->d_rate, n), ctx->stream));
+        ctx->last_rbatch_sse_launches++;
+    }
+    DistortionResult *h_res = dist_of(ctx->h_rate, n);
+    HIPCHK(ctx, hipMemcpyAsync(h_res, dist_of(ctx->d_rate, n), (size_t)n * sizeof(DistortionResult), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream(ctx));
+    for (int i = 0; i < n; i++) {
+        sums[2 * i] = h_res[i].sse;
+        sums[2 * i + 1] = h_res[i].sse_wrapped;
+    }
+    return TIC_OK;
+}
+
+// Times `iters` back-to-back rounds of its launches on resident coefficients, behind `warm` untimed ones (timed_launches).
+int tic_distortion_v_dev_timed(tic_ctx *ctx, const void *d_coeffs_zz, const void *const *d_images, int n, const int *hs, const int *ws,
+                               const ptrdiff_t *row_strides, const int *qualities, int warm, int iters, float *ms_total) {
+    TIC_LOCK(ctx);
+    int rc = check_distortion_v_args(ctx, d_coeffs_zz, d_images, n, hs, ws, row_strides, qualities, ms_total);
+    if (rc) return rc;
+    if (!ms_total || warm < 0 || iters <= 0) return set_err(ctx, TIC_E_ARG, "bad argument");
+    *ms_total = 0.0f;
+    if (n == 0) return TIC_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<size_t> launches;
+    rc = queue_distortion_v(ctx, d_coeffs_zz, d_images, n, hs, ws, row_strides, qualities, launches);
+    if (rc) return rc;
+    return timed_launches(ctx, warm, iters, ms_total, nullptr, [&](int, hipEvent_t, hipEvent_t) {
+        for (size_t t = 0; t < launches.size(); t++) {
+            const hipError_t e = launch_idct_sse_v(ctx->d_rd_tabs + t, launches[t], dist_of(ctx->d_rate, n), ctx->stream);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    });
 }
 
 // One batch over several contexts - normally one per GPU of the node - from ONE process: a host thread per context, contiguous shards

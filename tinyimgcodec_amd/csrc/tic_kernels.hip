@@ -26,6 +26,7 @@
 
 #include "tic_hooks.h"
 #include "tic_kernels.h"
+#include "tic_rd_plan.h"
 #include "tic_strip_plan.h"
 #include "tic_math.h"
 
@@ -934,16 +935,95 @@ __constant__ int kAnnScalesInt[64] = {
     16384, 22725, 21407, 19266, 16384, 12873, 8867,  4520,  12873, 17855, 16819, 15137, 12873, 10114, 6967,  3552,
     8867,  12299, 11585, 10426, 8867,  6967,  4799,  2446,  4520,  6270,  5906,  5315,  4520,  3552,  2446,  1247};
 
+// The loads of the measuring instantiations go through pointers TYPED as global.  A pointer that is a kernel argument is known to be one; a
+// pointer that a kernel loaded from a record in memory (idct_sse_kernel_v) is a generic one to the compiler, and every access through it a
+// flat load, which counts on the LDS counter too: the eight scatter stores of a tile then wait for memory one by one.  The store kernels keep
+// their plain pointers (and with them their assembly); the choice is one of type, by kMeasure, the expressions are the same.
+#define TIC_GLOBAL __attribute__((address_space(1)))
+typedef uint32_t tic_u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t tic_u32x4 __attribute__((ext_vector_type(4)));
+
+// The measuring epilogue, in two halves that idct_sse_kernel (one tile per wave) and idct_sse_kernel_v (a walk of tiles per wave) share.
+// Sum widths: a tile's eight pixels per lane are at most 8 * 255^2 = 520,200, summed in 32 bits; the lane's running sums over a walk,
+// and everything that leaves the lane - the wave reduction, the LDS words, the atomic's operand - are 64 bits, so no length of walk can
+// wrap them and the plan enforces no bound on it.  (32-bit workgroup sums, the single-tile kernel's first form, wrap from a walk of 32
+// tiles: 2,048 pixels * 255^2 is 2^27.)  Integer sums: the order of arrival does not change the result.
+struct SseAcc {
+    unsigned long long sq = 0, sw = 0; // sum of d * d, sum of (d * d) & 255
+};
+
+// Accumulate this tile: lane i of block b holds decoded row y = 8 by + i, pixels x0 .. x0 + 7 in px[]; it reads the same eight pixels of the
+// original (one 8-byte load where that is aligned and whole, byte loads otherwise: the store path's split) and sums over the pixels INSIDE
+// the frame - what lies beyond h or w (the decoder's cropped padding; in the original whatever the row pitch leaves there) is neither read
+// nor counted.
+__device__ __forceinline__ void sse_accumulate_tile(const Strip &s, int i, int h, int w, const SseArgs &m, const uint32_t px[8], SseAcc &acc) {
+    uint32_t sq = 0, sw = 0;
+    const int y = s.by * 8 + i, x0 = s.bx * 8;
+    if (s.valid && y < h) {
+        const TIC_GLOBAL uint8_t *p = (const TIC_GLOBAL uint8_t *)m.img + (long)y * m.stride + x0;
+        uint32_t lo = 0, hi = 0;
+        if (m.aligned8 && x0 + 8 <= w) {
+            const tic_u32x2 v = *(const TIC_GLOBAL tic_u32x2 *)p;
+            lo = v.x;
+            hi = v.y;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                if (x0 + k < w) {
+                    const uint32_t bt = p[k];
+                    if (k < 4) lo |= bt << (8 * k); else hi |= bt << (8 * (k - 4));
+                }
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int d = (int)px[k] - (int)(((k < 4 ? lo : hi) >> (8 * (k & 3))) & 0xffu);
+            const uint32_t e = x0 + k < w ? (uint32_t)(d * d) : 0u;
+            sq += e;
+            sw += e & 255u;
+        }
+    }
+    acc.sq += sq;
+    acc.sw += sw;
+}
+
+// Reduce and add: the workgroup's sums, ONE 64-bit vector atomic per non-zero sum on `res`.  Every lane of the workgroup must arrive.
+__device__ __forceinline__ void sse_reduce_add(SseAcc acc, DistortionResult *res) {
+    __shared__ unsigned long long wsum[kWavesPerWG][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        acc.sq += __shfl_xor(acc.sq, off, 64);
+        acc.sw += __shfl_xor(acc.sw, off, 64);
+    }
+    if (lane == 0) {
+        wsum[wave][0] = acc.sq;
+        wsum[wave][1] = acc.sw;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tq = 0, tw = 0;
+#pragma unroll
+        for (int k = 0; k < kWavesPerWG; k++) {
+            tq += wsum[k][0];
+            tw += wsum[k][1];
+        }
+        if (tq) atomicAdd(&res->sse, tq); // (tw != 0 implies tq != 0)
+        if (tw) atomicAdd(&res->sse_wrapped, tw);
+    }
+}
+
 // kWideDc: the DC comes from a.dc32 (IdctArgs: a stream whose running DC left int16), everything else as ever
-// kMeasure: the measuring epilogue (idct_sse_kernel): the decoded pixels are compared with the frame `m` describes instead of being stored
+// kMeasure: the measuring epilogue (idct_sse_kernel, idct_sse_kernel_v): the decoded pixels are compared with the frame `m` describes
+// instead of being stored, the tile's sums added to `acc`; the caller ends in sse_reduce_add
 template <bool kWideDc, bool kMeasure = false>
-__device__ __forceinline__ void idct_body(const IdctArgs &a, int wg_tile0, const SseArgs *m = nullptr) {
+__device__ __forceinline__ void idct_body(const IdctArgs &a, int wg_tile0, const SseArgs *m = nullptr, SseAcc *acc = nullptr) {
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[kWavesPerWG][kLdsWaveBytes / 4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = lane >> 3, i = lane & 7;
     uint32_t *lds = lds_all[wave];
     const int tile = wg_tile0 + wave; // (wg_tile0: the workgroup's first tile)
-    const DctqConsts *__restrict__ C = a.consts;
+    using ConstsPtr = std::conditional_t<kMeasure, const TIC_GLOBAL DctqConsts *, const DctqConsts *>;
+    const ConstsPtr __restrict__ C = (ConstsPtr)a.consts;
     Strip s = make_strip(tile, a.ntiles, a.tiles_x, a.bw, b);
     if (a.first_block >= 0) { // block-range form: 8 consecutive blocks of the raster order per wave
         const long blk = a.first_block + (long)tile * 8 + b;
@@ -955,7 +1035,14 @@ __device__ __forceinline__ void idct_body(const IdctArgs &a, int wg_tile0, const
 
     // lane i of block b loads zig-zag entries 8i..8i+7 (16 B), scatters them to natural order in LDS
     uint4 val = make_uint4(0, 0, 0, 0);
-    if (s.valid) val = *reinterpret_cast<const uint4 *>(a.coeffs + s.oblk * 64 + i * 8);
+    if constexpr (kMeasure) {
+        if (s.valid) {
+            const tic_u32x4 v = *(const TIC_GLOBAL tic_u32x4 *)((const TIC_GLOBAL int16_t *)a.coeffs + s.oblk * 64 + i * 8);
+            val = make_uint4(v.x, v.y, v.z, v.w);
+        }
+    } else {
+        if (s.valid) val = *reinterpret_cast<const uint4 *>(a.coeffs + s.oblk * 64 + i * 8);
+    }
     char *blk = reinterpret_cast<char *>(lds) + b * kZzStrideB;
     {
         uint32_t wv[4] = {val.x, val.y, val.z, val.w};
@@ -1001,59 +1088,8 @@ __device__ __forceinline__ void idct_body(const IdctArgs &a, int wg_tile0, const
         v = v > 255.0 ? 255.0 : v;
         px[k] = (uint32_t)(int)v; // truncation toward zero, as astype(np.uint8) on a clipped value
     }
-    if constexpr (kMeasure) {
-        // Round-trip error instead of pixels: lane i of block b holds decoded row y = 8 by + i, pixels x0 .. x0 + 7; it reads the same eight
-        // pixels of the original (one 8-byte load where that is aligned and whole, byte loads otherwise: the store path's split below) and
-        // sums d * d and (d * d) & 255 over the pixels INSIDE the frame - what lies beyond h or w (the decoder's cropped padding; in the
-        // original whatever the row pitch leaves there) is neither read nor counted.  Eight pixels are at most 8 * 255^2 per lane, a
-        // workgroup's 2,048 at most 2^27: 32 bits up to the one 64-bit atomic per sum and workgroup.  Integer sums: the order of arrival
-        // does not change the result.
-        __shared__ uint32_t wsum[kWavesPerWG][2];
-        uint32_t sq = 0, sw = 0;
-        const int y = s.by * 8 + i, x0 = s.bx * 8;
-        if (s.valid && y < a.h) {
-            const uint8_t *p = m->img + (long)y * m->stride + x0;
-            uint32_t lo = 0, hi = 0;
-            if (m->aligned8 && x0 + 8 <= a.w) {
-                const uint2 v = *reinterpret_cast<const uint2 *>(p);
-                lo = v.x;
-                hi = v.y;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 8; k++)
-                    if (x0 + k < a.w) {
-                        const uint32_t bt = p[k];
-                        if (k < 4) lo |= bt << (8 * k); else hi |= bt << (8 * (k - 4));
-                    }
-            }
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int d = (int)px[k] - (int)(((k < 4 ? lo : hi) >> (8 * (k & 3))) & 0xffu);
-                const uint32_t e = x0 + k < a.w ? (uint32_t)(d * d) : 0u;
-                sq += e;
-                sw += e & 255u;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            sq += (uint32_t)__shfl_xor((int)sq, off, 64);
-            sw += (uint32_t)__shfl_xor((int)sw, off, 64);
-        }
-        if (lane == 0) {
-            wsum[wave][0] = sq;
-            wsum[wave][1] = sw;
-        }
-        __syncthreads(); // (every lane of the workgroup arrives: nothing above returns)
-        if (threadIdx.x == 0) {
-            unsigned long long tq = 0, tw = 0;
-#pragma unroll
-            for (int k = 0; k < kWavesPerWG; k++) {
-                tq += wsum[k][0];
-                tw += wsum[k][1];
-            }
-            if (tq) atomicAdd(&m->res->sse, tq); // (tw != 0 implies tq != 0)
-            if (tw) atomicAdd(&m->res->sse_wrapped, tw);
-        }
+    if constexpr (kMeasure) { // round-trip error instead of pixels (nothing above returns: every lane reaches the caller's reduction)
+        sse_accumulate_tile(s, i, a.h, a.w, *m, px, *acc);
         return;
     }
     if (!s.valid) return;
@@ -1075,13 +1111,55 @@ __device__ __forceinline__ void idct_body(const IdctArgs &a, int wg_tile0, const
 __global__ __launch_bounds__(kWavesPerWG * 64) void idct_kernel(IdctArgs a) { idct_body<false>(a, blockIdx.x * kWavesPerWG); }
 __global__ __launch_bounds__(kWavesPerWG * 64) void idct_wide_dc_kernel(IdctArgs a) { idct_body<true>(a, blockIdx.x * kWavesPerWG); }
 // The measuring instantiation: decode and compare, no pixel written (tic_distortion_dev, tic_rd_points_dev, tic_compress_to_psnr_dev).
-__global__ __launch_bounds__(kWavesPerWG * 64) void idct_sse_kernel(IdctArgs a, SseArgs m) { idct_body<false, true>(a, blockIdx.x * kWavesPerWG, &m); }
+__global__ __launch_bounds__(kWavesPerWG * 64) void idct_sse_kernel(IdctArgs a, SseArgs m) {
+    SseAcc acc;
+    idct_body<false, true>(a, blockIdx.x * kWavesPerWG, &m, &acc);
+    sse_reduce_add(acc, m.res);
+}
 // The descriptor form: the frames of a chunk in one launch (tic_decompress_batch_adaptive).  Workgroup g transforms the kWavesPerWG tiles from
 // wgs[g].y on of frame wgs[g].x, whose arguments are args[wgs[g].x]; a frame has ceil(ntiles / kWavesPerWG) workgroups.
 __global__ __launch_bounds__(kWavesPerWG * 64) void idct_batch_kernel(const IdctArgs *__restrict__ args, const uint2 *__restrict__ wgs) {
     const uint2 e = wgs[blockIdx.x];
     const IdctArgs a = args[e.x];
     idct_body<false>(a, (int)e.y);
+}
+// The measuring kernel's descriptor form: up to kSseMaxProbes PROBES - a frame's coefficients at one quality against that frame's pixels,
+// any block counts - in ONE launch (tic_rd_points_v, tic_compress_batch_to_psnr, tic_distortion_v_dev).  A workgroup finds its probe as
+// stream_size_kernel_v does: lane l loads first_group[l] (0xffffffff behind the last probe), the wave counts the entries <= blockIdx.x; the
+// count is a scalar, so the record comes by scalar loads and is uniform across the workgroup.  Group g of a probe walks the probe's
+// workgroup-tiles g, g + ngroups, ... - the stride is the probe's own group count (capped on the host: tic_rd_plan.h), never the grid's -
+// sums in registers across the walk (SseAcc: 64-bit lane sums, no bound on the walk) and ends in one atomic per non-zero sum on the probe's
+// own result: a 4096^2 probe issues at most 1,024 atomics per sum, where idct_sse_kernel issues 8,192.
+// LDS across the walk: a wave's region of lds_all is reused by every tile.  All of it is wave-private and one wave's DS instructions execute
+// in order, so what is needed between the last transposing read of one tile and the first scatter of the next is a compiler-level fence:
+// transpose8x8_dwords ends in one behind its reads, and the loop closes with another.  No workgroup barrier inside the walk: the trip count
+// is uniform across the workgroup (it depends on blockIdx.x and the record alone), so every wave reaches the barrier of sse_reduce_add.
+static_assert(kWavesPerWG == kSseWavesPerWG, "tic_rd_plan.h counts a probe's workgroups by this workgroup");
+__global__ __launch_bounds__(kWavesPerWG * 64) void idct_sse_kernel_v(const SseProbeTable *__restrict__ pt, DistortionResult *__restrict__ res) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t first = pt->first_group[lane];
+    const int probe = __builtin_amdgcn_readfirstlane(__popcll(__ballot(first <= blockIdx.x)) - 1);
+    const SseProbeRec &r = pt->rec[probe];
+    IdctArgs a;
+    a.coeffs = r.coeffs;
+    a.out = nullptr;
+    a.h = r.h, a.w = r.w;
+    a.stride = 0;
+    a.bw = r.bw, a.tiles_x = r.tiles_x, a.ntiles = r.ntiles;
+    a.aligned8 = 0;
+    a.consts = static_cast<const DctqConsts *>(r.consts);
+    SseArgs m;
+    m.img = r.img;
+    m.stride = (long)r.stride;
+    m.aligned8 = r.aligned8;
+    m.res = res + r.result;
+    const uint32_t wg_tiles = ((uint32_t)r.ntiles + kWavesPerWG - 1) / kWavesPerWG, ngroups = r.ngroups;
+    SseAcc acc;
+    for (uint32_t t = blockIdx.x - r.first_group; t < wg_tiles; t += ngroups) {
+        idct_body<false, true>(a, (int)(t * kWavesPerWG), &m, &acc);
+        wave_lds_fence();
+    }
+    sse_reduce_add(acc, m.res);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1257,6 +1335,13 @@ hipError_t launch_idct_batch(const IdctArgs *d_args, const uint2 *d_wgs, size_t 
 hipError_t launch_idct_sse(const IdctArgs &a, const SseArgs &m, hipStream_t stream) {
     if (a.ntiles <= 0) return hipSuccess;
     hipLaunchKernelGGL(idct_sse_kernel, dim3(grid_for(a.ntiles)), dim3(kWavesPerWG * 64), 0, stream, a, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_idct_sse_v(const SseProbeTable *d_probes, size_t ngroups, DistortionResult *d_res, hipStream_t stream) {
+    if (ngroups == 0) return hipSuccess;
+    if (!d_probes || !d_res || ngroups > (size_t)kSseMaxProbes * kSseMaxGroups) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(idct_sse_kernel_v, dim3((unsigned)ngroups), dim3(kWavesPerWG * 64), 0, stream, d_probes, d_res);
     return hipGetLastError();
 }
 
