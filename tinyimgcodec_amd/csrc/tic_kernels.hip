@@ -28,6 +28,7 @@
 #include "tic_kernels.h"
 #include "tic_rd_plan.h"
 #include "tic_strip_plan.h"
+#include "tic_strip_lds.h"
 #include "tic_math.h"
 
 namespace tic {
@@ -258,8 +259,9 @@ __global__ __launch_bounds__(kWavesPerWG * 64) void dctq_exact_kernel(DctqArgs a
 //   pass 1 : float32 AAN DOWN the pixel column held by the lane - the reference's pass order (utils.py:33-37: axis -2 first).  Outputs
 //            0 and 4 are the column's sum and alternating sum: exact integers, the very numbers the reference's float64 row pass
 //            starts from for the four rational coefficients (0,0) (0,4) (4,0) (4,4).  The level shift is folded into output 0.
-//   xpose 1: 8x8 dword transpose per block through wave-private LDS (conflict-free slot layout); lane 8*b + u then holds frequency
-//            row u.
+//   xpose 1: 8x8 dword transpose per block through wave-private LDS: eight lane-linear planes, one per output of pass 1, written with
+//            ds_write_addtid_b32 (no address register) and read back 32 contiguous bytes per lane, conflict-free (tic_strip_lds.h);
+//            lane 8*b + u then holds frequency row u.
 //   pass 2 : float32 AAN along that row; quantise with the magic-number rounding trick; the guard test is the largest distance
 //            to the rounded value per lane against three per-row thresholds.
 //   ties   : if one of the four rational coefficients tripped anywhere in the strip (an exact .5 tie: 2.2 % of random blocks at q = 50,
@@ -267,14 +269,18 @@ __global__ __launch_bounds__(kWavesPerWG * 64) void dctq_exact_kernel(DctqArgs a
 //            reference's float64 operation order by the 64 lanes at once (rational_quad: column sums re-read from xpose 1's buffer,
 //            two DPP exchanges, one division) and written over the fast path's values in the zig-zag staging.  ~40 instructions;
 //            rounds 2-4 took the pixels through a byte transpose, v_sad_u8 and three DPP butterflies per tie block after the loop.
-//   store  : int16 results scattered to zig-zag order in LDS, read back 16 B per lane, 1 KiB contiguous per wave.
+//   store  : int16 results packed two to a dword, four lane-linear stores into staging planes, the lane that stores chunk k of the
+//            block gathers its eight scan positions with eight ds_read_u16 (rows first: scattered to zig-zag order in LDS, read back
+//            16 B per lane); 16 B per lane, 1 KiB contiguous per wave.
 //   trips  : blocks in which one of the 60 irrational coefficients tripped its guard band (0.2 % of random blocks at q = 50, 0.9 % at
 //            q = 90) join the wave's batch and are settled after the loop in float64.
 // ---------------------------------------------------------------------------------------------------------
-constexpr int kTWaveBytes = kLdsWaveBytes;        // 2176 B: transpose buffer, two halves of 256 dwords 272 dwords apart
-constexpr int kTHalfDw = 272;                     // dword offset of the half that holds columns 4..7 (272 = 16 mod 32: the two halves of a
-                                                  // 32-lane write group fall into different banks)
-constexpr int kZzWaveBytes = 8 * kZzStrideB;      // 1152 B zig-zag staging per wave; its first 640 B double as the byte-transpose buffer
+constexpr int kTWaveBytes = kTPlaneWaveBytes;     // 2448 B: transpose buffer.  Columns first: eight lane-linear planes (tic_strip_lds.h);
+                                                  // rows first: two halves of 256 dwords; the rare paths behind the loop: 8 x 68 dwords
+static_assert(kTWaveBytes >= kLdsWaveBytes && kTWaveBytes % 16 == 0, "transpose8x8_dwords keeps its own layout in the same buffer");
+constexpr int kZzWaveBytes = 8 * kZzStrideB;      // 1152 B zig-zag staging per wave (columns first: four planes, 1052 B; store_zigzag behind the
+                                                  // loop: 8 x 144 B); its first 640 B double as the byte-transpose buffer
+static_assert(kZPlaneWaveBytes <= kZzWaveBytes, "the staging planes fit the zig-zag buffer");
 constexpr int kPxBlkBytes = 80;                   // byte-transpose buffer: 64 pixel bytes per block + 16 (bank spread of the b64 writes)
 constexpr int kChunkStrips = 8;                   // chunked schedule: strips per wave (a workgroup streams 32 adjacent strips).  With the
                                                   // sc1 nt stores 8 beats round 2's 16: 256 x 1080p 270 against 288 us, 8192^2 37.3 against
@@ -334,9 +340,9 @@ __device__ __forceinline__ int rational_quad(const uint32_t *ldsT, int b, int i,
 #pragma clang fp contract(off)
     const int w = i >> 2, k = i & 3;
     const uint32_t ca = (0x05010300u >> (8 * k)) & 0xffu, cb = (0x06020407u >> (8 * k)) & 0xffu;
-    const uint32_t *row = ldsT + w * 128 + 4 * b; // frequency row u = 4w of block b (rows 0 and 4 are not swizzled)
-    const float fa = __uint_as_float(row[(ca >> 2) * kTHalfDw + (ca & 3)]);
-    const float fb = __uint_as_float(row[(cb >> 2) * kTHalfDw + (cb & 3)]);
+    const uint32_t *row = ldsT + w * (4 * kTPlaneQ[4]) + 8 * b; // frequency row u = 4w of block b: plane 4w, eight contiguous dwords
+    const float fa = __uint_as_float(row[ca]);                  // (planes 0 and 4 share banks: these two reads are 2-way conflicted)
+    const float fb = __uint_as_float(row[cb]);
     const double K = w ? (kTW3 * 0.5) : (kSq2h * 0.5);
     const double ya = (double)fa * K, yb = (double)fb * K;
     const double p = ya + yb;                                   // y0+y7 | y3+y4 | y1+y2 | y5+y6
@@ -579,6 +585,24 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
     // v[R] (which keeps the strip's bytes until the pair is loaded again, two strips later: the batch fetches the raw words from
     // there, raw_words) to the byte-transpose buffer
 #define TIC_TAKE_COLS(R, N) asm volatile("s_waitcnt vmcnt(" #N ")\n\tds_write_b64 %0, v[" R "]" : : "v"(px_wr) : TIC_RSV_CLOBBER)
+    // columns first, dword transpose: pass 1's eight outputs go to the eight lane-linear planes with ds_write_addtid_b32 (address =
+    // m0 + offset + 4 * lane: no address register to move, 2 cycles a store against 6 for a ds_write2_b32 of two of them).  m0 belongs to
+    // nobody between statements: it is set here, in front of its eight readers (one wait state between an SALU write of m0 and an
+    // add-TID access), and csrc/lint_strip_kernel.py checks that nothing else in the kernel writes or reads it.  The stores stand
+    // ahead of the compiler's reads in program order, which is all a wave's own LDS traffic needs (as TIC_TAKE_COLS).
+#define TIC_PUT_PLANES(D0, D1, D2, D3, D4, D5, D6, D7)                                                                            \
+    asm volatile("s_mov_b32 m0, %8\n\ts_nop 0\n\tds_write_addtid_b32 %0 offset:%9\n\tds_write_addtid_b32 %1 offset:%10\n\t"         \
+                 "ds_write_addtid_b32 %2 offset:%11\n\tds_write_addtid_b32 %3 offset:%12\n\tds_write_addtid_b32 %4 offset:%13\n\t" \
+                 "ds_write_addtid_b32 %5 offset:%14\n\tds_write_addtid_b32 %6 offset:%15\n\tds_write_addtid_b32 %7 offset:%16"     \
+                 : : "v"(D0), "v"(D1), "v"(D2), "v"(D3), "v"(D4), "v"(D5), "v"(D6), "v"(D7), "s"(t_base),                          \
+                     "n"(16 * kTPlaneQ[0]), "n"(16 * kTPlaneQ[1]), "n"(16 * kTPlaneQ[2]), "n"(16 * kTPlaneQ[3]),                   \
+                     "n"(16 * kTPlaneQ[4]), "n"(16 * kTPlaneQ[5]), "n"(16 * kTPlaneQ[6]), "n"(16 * kTPlaneQ[7]) : TIC_RSV_CLOBBER)
+    // columns first, zig-zag staging: the lane's four packed dwords to the four staging planes, same form
+#define TIC_PUT_ZPLANES(W0, W1, W2, W3)                                                                                           \
+    asm volatile("s_mov_b32 m0, %4\n\ts_nop 0\n\tds_write_addtid_b32 %0 offset:%5\n\tds_write_addtid_b32 %1 offset:%6\n\t"          \
+                 "ds_write_addtid_b32 %2 offset:%7\n\tds_write_addtid_b32 %3 offset:%8"                                            \
+                 : : "v"(W0), "v"(W1), "v"(W2), "v"(W3), "s"(z_base),                                                              \
+                     "n"(4 * kZPlaneDw[0]), "n"(4 * kZPlaneDw[1]), "n"(4 * kZPlaneDw[2]), "n"(4 * kZPlaneDw[3]) : TIC_RSV_CLOBBER)
     // rows first: waits, then converts the strip's eight pixels straight out of the landing registers v[R0], v[R1]
 #define TIC_TAKE_ROWS(D, R0, R1, N)                                                                          \
     asm volatile("s_waitcnt vmcnt(" #N ")\n\tv_cvt_f32_ubyte0 %0, v" #R0 "\n\tv_cvt_f32_ubyte1 %1, v" #R0 "\n\tv_cvt_f32_ubyte2 %2, v" #R0 \
@@ -604,21 +628,32 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
         // values in front of the wait - statements of this kind keep their order; left alone, the compiler computes them behind the barrier.)
         // LDS layouts of the loop (conflict-free: tools/lds_bank_model.py)
         //   byte transpose : block lb's pixel row lr at lb*80 + lr*8; lane (b, c) reads byte r*8 + c of block b, r = 0..7
-        //   dword transpose: value (u, c) of block b at dword (c>>2)*272 + u*32 + 4*(b ^ s(u)) + (c&3), s(u) = 4 for u in {2,3,6,7}
-        //   zig-zag staging: scan position p of block b at byte (p>>3)*128 + 16*(b ^ f(p>>3)) + 2*(p&7), f(c) = bit 1 of c | 4 * bit 2 of c
-        // (pass 1 runs in the compute layout - lane 8*b + c - columns first, in the load layout - lane 8*r + b - rows first; the half
-        //  offset of 272 dwords keeps the compute layout's 32-lane write groups conflict-free, the load layout needs none: 256)
-        constexpr int kHalf = kCols ? kTHalfDw : 256;
-        const int p1a = kCols ? i : lr, p1b = kCols ? b : lb;
+        //   dword transpose, columns first: value (u, c) of block b at dword 4*kTPlaneQ[u] + 8*b + c (tic_strip_lds.h): the writer's
+        //                    own lane index inside plane u, stored without an address register (TIC_PUT_PLANES); the reader's eight
+        //                    dwords are 32 contiguous bytes
+        //   dword transpose, rows first: value (v, r) of block b at dword (r>>2)*256 + v*32 + 4*(b ^ s(v)) + (r&3), s(v) = 4 for v in {2,3,6,7}
+        //   zig-zag staging, columns first: value (u, v) of block b is a halfword of dword kZPlaneDw[p] + 8*b + u, p the plane of v's pair
+        //                    (tic_strip_lds.h): four packed dwords per lane, stored like the transpose's (TIC_PUT_ZPLANES); the lane that
+        //                    stores chunk k gathers its eight scan positions with eight ds_read_u16 (8 conflict cycles per strip remain)
+        //   zig-zag staging, rows first: scan position p of block b at byte (p>>3)*128 + 16*(b ^ f(p>>3)) + 2*(p&7), f(c) = 4 * bit 1 of c:
+        //                    eight ds_write_b16, one ds_read_b128
+        // (pass 1 runs in the compute layout - lane 8*b + c - columns first, in the load layout - lane 8*r + b - rows first)
+        constexpr int kHalf = 256; // rows first: dword offset of the half that holds rows 4..7
         uint32_t px_wr = lds_addr(ldsZ + lb * kPxBlkBytes + lr * 8);
         uint32_t o_px_rd = lds_addr(ldsZ + b * kPxBlkBytes + i);
-        uint32_t o_twA = lds_addr(ldsT + (p1a >> 2) * kHalf + (p1a & 3) + 4 * p1b);       // outputs {0,1,4,5}: + k*32 dwords
-        uint32_t o_twB = lds_addr(ldsT + (p1a >> 2) * kHalf + (p1a & 3) + 4 * (p1b ^ 4)); // outputs {2,3,6,7}
+        uint32_t o_twA = lds_addr(ldsT + (lr >> 2) * kHalf + (lr & 3) + 4 * lb);       // rows first, outputs {0,1,4,5}: + k*32 dwords
+        uint32_t o_twB = lds_addr(ldsT + (lr >> 2) * kHalf + (lr & 3) + 4 * (lb ^ 4)); // rows first, outputs {2,3,6,7}
+        const uint32_t t_base = lds_addr(ldsT);                                        // columns first: the planes' base (wave-uniform)
         // (the two 16-byte reads are pinned as indices of 16-byte pieces: the pointers keep the alignment ds_read_b128 needs)
-        uint32_t q_tr = (uint32_t)(i * 8 + (b ^ (4 * ((i >> 1) & 1))));                    // first half; the second kHalf dwords on
-        uint32_t q_zr = (uint32_t)(i * 8 + (b ^ (kCols ? (((i >> 1) & 1) | (i & 4)) : (4 * ((i >> 1) & 1)))));
-        uint32_t o_zb = lds_addr(ldsZ); // (zz_ptr's base)
-        asm volatile("; addresses of the loop" : "+v"(px_wr), "+v"(o_px_rd), "+v"(o_twA), "+v"(o_twB), "+v"(q_tr), "+v"(q_zr), "+v"(o_zb), "+v"(st_off) : : TIC_RSV_CLOBBER);
+        uint32_t q_tr = kCols ? (uint32_t)(kTPlaneStepQ * (i >> 1) + kTPlaneOddQ * (i & 1) + 2 * b)   // plane u = i, block b; the second piece follows
+                              : (uint32_t)(i * 8 + (b ^ (4 * ((i >> 1) & 1))));                      // first half; the second kHalf dwords on
+        uint32_t q_zr = (uint32_t)(i * 8 + (b ^ (4 * ((i >> 1) & 1)))); // rows first: the lane's chunk of the staging
+        uint32_t o_zb = lds_addr(ldsZ); // the staging's base
+        const uint32_t z_base = lds_addr(ldsZ); // columns first: the staging planes' base (wave-uniform)
+        if constexpr (kCols)
+            asm volatile("; addresses of the loop" : "+v"(px_wr), "+v"(o_px_rd), "+v"(q_tr), "+v"(o_zb), "+v"(st_off) : : TIC_RSV_CLOBBER);
+        else
+            asm volatile("; addresses of the loop" : "+v"(px_wr), "+v"(o_px_rd), "+v"(o_twA), "+v"(o_twB), "+v"(q_tr), "+v"(q_zr), "+v"(o_zb), "+v"(st_off) : : TIC_RSV_CLOBBER);
         const uint8_t *px_rd = lds_ptr<const uint8_t>(o_px_rd);
         uint32_t *twA = lds_ptr<uint32_t>(o_twA), *twB = lds_ptr<uint32_t>(o_twB);
         const uint4 *tr = reinterpret_cast<const uint4 *>(__builtin_assume_aligned(ldsT, 16)) + q_tr;
@@ -639,13 +674,31 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
         m1 = *reinterpret_cast<const f32x4 *>(cst_blk + (kCols ? kBlkMul : kBlkMulT) + i * 32 + 16);
         thr = *reinterpret_cast<const f32x4 *>(cst_blk + (kCols ? kBlkThr : kBlkThrT) + i * 16);
         zzv = *reinterpret_cast<const u32x4 *>(cst_blk + (kCols ? kBlkZz : kBlkZzT) + i * 16);
+        // rows first: the eight scatter addresses of the lane's coefficients in the zig-zag staging
         auto zz_ptr = [&](uint32_t ofs) { // ofs = 2 * scan position of the coefficient
-            const uint32_t c = ofs >> 4; // (the chunk's swizzle: found by search for either lane mapping, tools/lds_bank_model.py)
-            return reinterpret_cast<int16_t *>(zb + c * 128 + (ofs & 15) + 16 * (b ^ (kCols ? (((c >> 1) & 1) | (c & 4)) : (4 * ((c >> 1) & 1)))));
+            const uint32_t c = ofs >> 4; // (the chunk's swizzle: found by search, tools/lds_bank_model.py)
+            return reinterpret_cast<int16_t *>(zb + c * 128 + (ofs & 15) + 16 * (b ^ (4 * ((c >> 1) & 1))));
         };
         int16_t *zp0 = zz_ptr(zzv.x & 0xffff), *zp1 = zz_ptr(zzv.x >> 16), *zp2 = zz_ptr(zzv.y & 0xffff), *zp3 = zz_ptr(zzv.y >> 16);
         int16_t *zp4 = zz_ptr(zzv.z & 0xffff), *zp5 = zz_ptr(zzv.z >> 16), *zp6 = zz_ptr(zzv.w & 0xffff), *zp7 = zz_ptr(zzv.w >> 16);
         wave_lds_fence();
+        // columns first: the lane that stores chunk i of block b gathers scan positions 8i .. 8i+7 out of the staging planes.  Where they sit
+        // is the inverse of zzv: lane (b, u = i) writes the staging offset of each of its (u, v) to an inverse table at the value's scan position
+        // (in the transpose buffer, free until the loop starts; the eight blocks write the same 128 bytes) and reads its chunk's eight back.
+        const uint16_t *zg0 = nullptr, *zg1 = nullptr, *zg2 = nullptr, *zg3 = nullptr, *zg4 = nullptr, *zg5 = nullptr, *zg6 = nullptr, *zg7 = nullptr;
+        if constexpr (kCols) {
+            char *inv = reinterpret_cast<char *>(ldsT);
+            auto put = [&](uint32_t ofs, int v) { *reinterpret_cast<uint16_t *>(inv + ofs) = (uint16_t)(strip_zstage_byte(0, v) + 4 * i); };
+            put(zzv.x & 0xffff, 0); put(zzv.x >> 16, 1); put(zzv.y & 0xffff, 2); put(zzv.y >> 16, 3);
+            put(zzv.z & 0xffff, 4); put(zzv.z >> 16, 5); put(zzv.w & 0xffff, 6); put(zzv.w >> 16, 7);
+            wave_lds_fence();
+            const uint4 gv = reinterpret_cast<const uint4 *>(__builtin_assume_aligned(ldsT, 16))[i];
+            wave_lds_fence();
+            const char *gb = zb + 32 * b;
+            auto at = [&](uint32_t ofs) { return reinterpret_cast<const uint16_t *>(gb + ofs); };
+            zg0 = at(gv.x & 0xffff); zg1 = at(gv.x >> 16); zg2 = at(gv.y & 0xffff); zg3 = at(gv.y >> 16);
+            zg4 = at(gv.z & 0xffff); zg5 = at(gv.z >> 16); zg6 = at(gv.w & 0xffff); zg7 = at(gv.w >> 16);
+        }
 
         int left = n_my;
         // raw pixel words of the strip in work, out of its landing registers (batch entries only)
@@ -667,11 +720,15 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
             // ---- pass 1: down the pixel column | along the pixel row -----------------------------------------------------
             dct8_aan(d0, d1, d2, d3, d4, d5, d6, d7);
             d0 -= 1024.0f;
-            twA[0 * 32] = __float_as_uint(d0); twA[1 * 32] = __float_as_uint(d1); twB[2 * 32] = __float_as_uint(d2);
-            twB[3 * 32] = __float_as_uint(d3); twA[4 * 32] = __float_as_uint(d4); twA[5 * 32] = __float_as_uint(d5);
-            twB[6 * 32] = __float_as_uint(d6); twB[7 * 32] = __float_as_uint(d7);
+            if constexpr (kCols) {
+                TIC_PUT_PLANES(d0, d1, d2, d3, d4, d5, d6, d7);
+            } else {
+                twA[0 * 32] = __float_as_uint(d0); twA[1 * 32] = __float_as_uint(d1); twB[2 * 32] = __float_as_uint(d2);
+                twB[3 * 32] = __float_as_uint(d3); twA[4 * 32] = __float_as_uint(d4); twA[5 * 32] = __float_as_uint(d5);
+                twB[6 * 32] = __float_as_uint(d6); twB[7 * 32] = __float_as_uint(d7);
+            }
             wave_lds_fence();
-            const uint4 ra = tr[0], rb = tr[kHalf / 4];
+            const uint4 ra = tr[0], rb = tr[kCols ? 1 : kHalf / 4];
             wave_lds_fence();
             float e0 = __uint_as_float(ra.x), e1 = __uint_as_float(ra.y), e2 = __uint_as_float(ra.z), e3 = __uint_as_float(ra.w);
             float e4 = __uint_as_float(rb.x), e5 = __uint_as_float(rb.y), e6 = __uint_as_float(rb.z), e7 = __uint_as_float(rb.w);
@@ -687,8 +744,15 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
             const float mB = fmaxf(fabsf(r0), fabsf(r4));
             const unsigned long long cA = __ballot(mA1 > thr.x) | __ballot(mA2 > thr.y); // lanes whose guard band tripped: v in 1,2,3,5,6,7
             const unsigned long long cB = __ballot(mB > thr.z);                           // ... v in 0,4
-            *zp0 = (int16_t)q0; *zp1 = (int16_t)q1; *zp2 = (int16_t)q2; *zp3 = (int16_t)q3;
-            *zp4 = (int16_t)q4; *zp5 = (int16_t)q5; *zp6 = (int16_t)q6; *zp7 = (int16_t)q7;
+            if constexpr (kCols) { // the low halves of the magic-number floats, two to a dword (v_perm_b32), four lane-linear stores
+                const uint32_t qq[8] = {q0, q1, q2, q3, q4, q5, q6, q7};
+                const uint32_t w0 = perm_b32(qq[kZPairHi[0]], qq[kZPairLo[0]], 0x05040100u), w1 = perm_b32(qq[kZPairHi[1]], qq[kZPairLo[1]], 0x05040100u);
+                const uint32_t w2 = perm_b32(qq[kZPairHi[2]], qq[kZPairLo[2]], 0x05040100u), w3 = perm_b32(qq[kZPairHi[3]], qq[kZPairLo[3]], 0x05040100u);
+                TIC_PUT_ZPLANES(w0, w1, w2, w3);
+            } else {
+                *zp0 = (int16_t)q0; *zp1 = (int16_t)q1; *zp2 = (int16_t)q2; *zp3 = (int16_t)q3;
+                *zp4 = (int16_t)q4; *zp5 = (int16_t)q5; *zp6 = (int16_t)q6; *zp7 = (int16_t)q7;
+            }
             const unsigned long long kRat = 0x1111111111111111ull; // lanes i in {0,4}: their coefficients 0 and 4 are the rational ones (either order)
             // ---- a rational coefficient sits on a tie somewhere in the strip (one strip in six at q = 50 on noise; every strip of
             //      posterised, two-level or flat content): the exact values of all 32, over the fast path's ------------------------
@@ -696,9 +760,10 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
                 n_quad++;
                 if constexpr (kCols) {
                     const int rq = rational_quad(ldsT, b, i, cst_rat);
-                    // scan positions 0, 14, 10, 39 of lanes i = 0, 1, 4, 5: byte offsets 0, 28, 20, 78 = 28 (i & 1) + 20 (i >> 2) + 30 (i & 1)(i >> 2), by
-                    // arithmetic (as nested selects the compiler built three exec-mask regions out of them, inside the tie path)
-                    if ((i & 2) == 0) *zz_ptr(28u * (uint32_t)(i & 1) + 20u * (uint32_t)(i >> 2) + 30u * (uint32_t)((i & 1) & (i >> 2))) = (int16_t)rq;
+                    // lanes i = 0, 1, 4, 5 hold (u, v) = (4 (i >> 2), 4 (i & 1)): its halfword in the staging planes of block b, by arithmetic
+                    // (as nested selects the compiler built three exec-mask regions out of the four offsets, inside the tie path)
+                    constexpr int kV0 = strip_zstage_byte(0, 0), kV4 = strip_zstage_byte(0, 4);
+                    if ((i & 2) == 0) *reinterpret_cast<int16_t *>(zb + kV0 + (kV4 - kV0) * (i & 1) + 16 * (i >> 2) + 32 * b) = (int16_t)rq;
                 } else { // rows first: no column sums at hand - from the pixels (load layout -> a row per lane of the block, through LDS)
                     uint32_t lo0, hi0;
                     raw_words(tag, lo0, hi0);
@@ -712,7 +777,12 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
                 }
             }
             wave_lds_fence();
-            const uint4 val = *zr;
+            uint4 val;
+            if constexpr (kCols) { // eight ds_read_u16 (zero-extending: not the d16 forms), two halves to a dword
+                const uint32_t h0 = *zg0, h1 = *zg1, h2 = *zg2, h3 = *zg3, h4 = *zg4, h5 = *zg5, h6 = *zg6, h7 = *zg7;
+                val = make_uint4(h0 | (h1 << 16), h2 | (h3 << 16), h4 | (h5 << 16), h6 | (h7 << 16));
+            } else
+                val = *zr;
             wave_lds_fence();
             const char *dst = reinterpret_cast<const char *>(out_f) + ((unsigned long long)ob << 7); // (scalar: the strip's 1 KiB)
             // ---- an irrational coefficient inside its guard band (one strip in seventy at q = 50, one in fourteen at q = 90) ------
@@ -777,6 +847,8 @@ __global__ __launch_bounds__(kWavesPerWG * 64, 6) __attribute__((amdgpu_num_vgpr
 #undef TIC_LOAD
 #undef TIC_LOAD_HEAD
 #undef TIC_TAKE_COLS
+#undef TIC_PUT_PLANES
+#undef TIC_PUT_ZPLANES
 #undef TIC_TAKE_ROWS
 #undef TIC_RSV_CLOBBER
     }
@@ -1265,7 +1337,7 @@ hipError_t launch_dctq(DctqArgs a, int variant, hipStream_t stream, hipEvent_t e
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dctq_strip_kernel<true>, kWavesPerWG * 64, 0) != hipSuccess || per_cu < 1)
             per_cu = 4;
-        // 80 VGPRs and 22 KiB of LDS allow 6 workgroups per CU (7 measured no better when the kernel still fitted them:
+        // 80 VGPRs and 23 KiB of LDS allow 6 workgroups per CU (7 measured no better when the kernel still fitted them:
         // a seventh lengthens the start ramp by as much as it hides, profiles/r02_ab_occupancy.txt)
         if (per_cu > 6) per_cu = 6;
         return cus * per_cu;
