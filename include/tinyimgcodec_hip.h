@@ -627,6 +627,37 @@ int tic_compress_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdif
 int tic_compress_scaled_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, int qf, void *d_out, size_t cap,
                             size_t *out_len);
 
+/* tic_compress_scaled of n frames of ANY sizes and settings in one call (the loop of the reference's tests/cbenchmark.py over image x
+ * setting): out_lens[i] bytes at outs[i] are byte for byte what tic_compress_scaled gives for frame i at qfs[i], whatever the order of the
+ * frames.  Semantics as tic_compress_batch_v: every argument is checked before any work - the first offender is named "frame i: ..." and
+ * nothing is written (TIC_E_ARG for a size that is no multiple of 8, a bad stride, a null image or buffer; TIC_E_QUALITY for a setting
+ * outside 0..3); a frame without blocks gets the host's 17-byte stream; tic_compress_scaled_bound(hs[i], ws[i]) always suffices as caps[i];
+ * a coefficient without a Huffman code fails the call with TIC_E_RANGE, a stream longer than caps[i] with TIC_E_SPACE naming frame i.
+ * Frames are ordered by (setting, width, height) and travel in chunks of up to 64 frames and 32 MB of pixels: per chunk one upload, ONE
+ * transform launch (the integer kernel's descriptor form), one packing and one placing launch, one read-back.  Frames a chunk cannot hold
+ * go through tic_compress_scaled behind the batch. */
+int tic_compress_batch_scaled_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                                const int *qfs, uint8_t *const *outs, const size_t *caps, size_t *out_lens);
+/* How the last tic_compress_batch_scaled_v went: frames through the batch kernels / frames coded one by one / chunks / transform launches
+ * (one per chunk).  Any pointer may be NULL. */
+int tic_last_compress_batch_scaled(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks, int *transform_launches);
+/* The integer kernel's descriptor form alone, synchronous, frames resident: d_images is a host array of n device pointers (rows
+ * row_strides[i] bytes apart, any alignment); the coefficients of all frames lie back to back at d_coeffs_zz (16-byte aligned, device
+ * layout, tic_num_blocks(hs[i], ws[i]) blocks each, in the caller's order).  One launch per 64 frames. */
+int tic_dctq_scaled_v_dev(tic_ctx *ctx, const void *const *d_images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                          const int *qfs, void *d_coeffs_zz);
+/* The table of tests/cbenchmark.py in one call: for frame i and setting qfs[j], sizes[i * nq + j] is the length of tic_compress_scaled's
+ * stream (-1 where a coefficient has no Huffman code; 17 for a frame without blocks) and sse[i * nq + j], sse_wrapped[i * nq + j] are the two
+ * sums of tic_roundtrip_sse_scaled (reported for a -1 entry too; 0 for a frame without blocks).  Any of the three may be NULL.  Argument
+ * checks as above.  Per chunk one upload, one memset of the results, and per 64 probes (a probe is a frame x setting pair) ONE transform
+ * launch - a record per probe, the nq records of a frame naming the same pixels -, one launch of the size kernel and one of the measuring
+ * kernel, then one read-back.  Frames a chunk cannot hold go through the single-frame calls behind the batch. */
+int tic_rd_points_scaled_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                           const int *qfs, int nq, long long *sizes, uint64_t *sse, uint64_t *sse_wrapped);
+/* How the last tic_rd_points_scaled_v went.  Any pointer may be NULL. */
+int tic_last_rd_scaled_batch(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks, int *transform_launches, int *size_launches,
+                             int *sse_launches);
+
 /* ---- multi-GPU (the reference has no counterpart: it is single-process, codec.py:133-164 runs one image
  *      at a time).  One process per GPU; a batch shards by independent frames (frame i -> rank i / ceil(B/G)) with no
  *      data-path collective.  The one exchange is an all-gather of per-frame compressed sizes, so that every rank knows every

@@ -2,7 +2,8 @@
 
 Mirrors tinyimgcodec/__init__.py:1-5 of the reference (same four names); see codec.py for the mapping, for compress_adaptive /
 decompress_adaptive and their batch forms compress_batch_adaptive / decompress_batch_adaptive (the reference's per-image Huffman tables) and for compress_scaled / dctq_scaled / entropy_encode_scaled (the
-reference's standalone integer encoder, c/img.c), and for rate control: compressed_size / compressed_sizes (the length of compress()'s
+reference's standalone integer encoder, c/img.c) with its batch forms compress_batch_scaled and rd_points_scaled_batch (a list of images at a
+setting each; the length and round-trip error of every image x setting pair), and for rate control: compressed_size / compressed_sizes (the length of compress()'s
 stream without producing it), compress_to_size (the best quality within a byte budget), their batch forms compressed_sizes_batch and
 compress_batch_to_size (a list of images of any shapes in one call, a byte budget per frame) and entropy_size; and for rate-distortion
 control: rd_points (size and exact round-trip error per quality), roundtrip_psnr, compress_to_psnr (the smallest stream at no less
@@ -10,9 +11,9 @@ than a PSNR), their batch forms rd_points_batch and compress_batch_to_psnr (a li
 frame), roundtrip_sse_scaled and psnr_from_sse.
 """
 from ._native import Context, NativeError, NativeUnavailable
-from .codec import (compress, compress_adaptive, compress_batch, compress_batch_adaptive, compress_batch_to_psnr, compress_batch_to_size, compress_scaled, compress_to_psnr, compress_to_size,
+from .codec import (compress, compress_adaptive, compress_batch, compress_batch_adaptive, compress_batch_to_psnr, compress_batch_scaled, compress_batch_to_size, compress_scaled, compress_to_psnr, compress_to_size,
                     compressed_size, compressed_sizes, compressed_sizes_batch, dctq, dctq_scaled, decode, decompress, decompress_adaptive, decompress_batch, decompress_batch_adaptive, encode, entropy_encode,
-                    entropy_encode_adaptive, entropy_encode_adaptive_batch, entropy_encode_scaled, entropy_size, max_sse_for_psnr, parse_header, psnr_from_sse, rd_points, rd_points_batch,
+                    entropy_encode_adaptive, entropy_encode_adaptive_batch, entropy_encode_scaled, entropy_size, max_sse_for_psnr, parse_header, psnr_from_sse, rd_points, rd_points_batch, rd_points_scaled_batch,
                     roundtrip_psnr, roundtrip_sse_scaled)
 
 __version__ = "0.1.0"

@@ -274,6 +274,25 @@ SIGNATURES = {
         C.c_int,
         [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
     ),
+    "tic_compress_batch_scaled_v": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ssize_t), C.POINTER(C.c_int),
+         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    ),
+    "tic_last_compress_batch_scaled": (C.c_int, [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tic_dctq_scaled_v_dev": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ssize_t), C.POINTER(C.c_int), C.c_void_p],
+    ),
+    "tic_rd_points_scaled_v": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ssize_t), C.c_void_p, C.c_int, C.c_void_p,
+         C.c_void_p, C.c_void_p],
+    ),
+    "tic_last_rd_scaled_batch": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    ),
     "tic_selftest_transpose": (C.c_int, [_ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "tic_comm_create": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]),
     "tic_comm_create_ex": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]),

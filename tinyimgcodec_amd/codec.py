@@ -744,6 +744,68 @@ def compress_scaled(image, quality="med", ctx=None):
         return out[: n.value].tobytes()
 
 
+def _per_frame_settings(quality, n):
+    """One setting (a name or 0..3) for all n frames, or a sequence with one per frame -> list of 0..3."""
+    if isinstance(quality, (str, bytes, int, np.integer, float, np.floating, bool, np.bool_)) or not hasattr(quality, "__len__"):
+        return [_scaled_setting(quality)] * n
+    if len(quality) != n:
+        raise ValueError("quality has %d entries for %d frames" % (len(quality), n))
+    return [_scaled_setting(q) for q in quality]
+
+
+def compress_batch_scaled(images, quality="med", ctx=None):
+    """compress_scaled(image, quality) of every image of a list, of any shapes (multiples of 8), in one call -> list of bytes in the
+    caller's order.  quality: one setting for all, or a sequence with one per frame - the loop over image x setting of the reference's
+    tests/cbenchmark.py is one call (tic_compress_batch_scaled_v): per chunk of up to 64 frames one upload, ONE transform launch whatever
+    the frames' sizes and settings, the device entropy stage, one read-back.  ValueError for a list of the wrong length, a bad setting or a
+    frame compress_scaled refuses, before any GPU work; KeyError when a coefficient of any frame has no Huffman code."""
+    frames = [_scaled_image(im) for im in images]
+    qs = _per_frame_settings(quality, len(frames))
+    if not frames:
+        return []
+    ctx = _ctx(ctx)
+    L = N.load()
+    n = len(frames)
+    caps_l = [L.tic_compress_scaled_bound(f[1], f[2]) for f in frames]
+    offs = np.concatenate(([0], np.cumsum([(c + 63) // 64 * 64 for c in caps_l]))).astype(np.int64)
+    with ctx.lock:
+        pool = getattr(ctx, "_mixed_pool", None)  # the mixed batch's landing pool
+        if pool is None or pool.size < offs[-1]:
+            pool = ctx._mixed_pool = np.empty(int(offs[-1]), dtype=np.uint8)
+        base = pool.ctypes.data
+        inp, hs, ws, strides = _frame_arrays(frames)
+        qa = (C.c_int * n)(*qs)
+        outp = (C.c_void_p * n)(*[base + int(o) for o in offs[:-1]])
+        caps = (C.c_size_t * n)(*caps_l)
+        lens = (C.c_size_t * n)()
+        rc = L.tic_compress_batch_scaled_v(ctx.handle, inp, n, hs, ws, strides, qa, outp, caps, lens)
+        if rc == N.TIC_E_RANGE:
+            raise KeyError("coefficient magnitude has no Huffman code")
+        ctx.check(rc)
+        return [pool[int(offs[i]): int(offs[i]) + lens[i]].tobytes() for i in range(n)]
+
+
+def rd_points_scaled_batch(images, qualities=SCALED_SETTINGS, ctx=None):
+    """The table of the reference's tests/cbenchmark.py in one call -> (sizes int64 (n, nq), sse uint64 (n, nq), sse_wrapped uint64 (n, nq)):
+    sizes[i, j] is len(compress_scaled(images[i], qualities[j])) (-1 where it would raise KeyError), the two sums are
+    roundtrip_sse_scaled's; psnr_from_sse turns them into dB.  Per chunk one upload, and per 64 image x setting pairs one launch each of
+    the transform, the size kernel and the measuring kernel (tic_rd_points_scaled_v).  Validation as compress_batch_scaled."""
+    frames = [_scaled_image(im) for im in images]
+    qs = [_scaled_setting(q) for q in qualities]
+    sizes = np.zeros((len(frames), len(qs)), dtype=np.int64)
+    sse = np.zeros((len(frames), len(qs)), dtype=np.uint64)
+    wrapped = np.zeros((len(frames), len(qs)), dtype=np.uint64)
+    if not frames or not qs:
+        return sizes, sse, wrapped
+    ctx = _ctx(ctx)
+    qarr = np.asarray(qs, dtype=np.intc)
+    inp, hs, ws, strides = _frame_arrays(frames)
+    with ctx.lock:
+        ctx.check(N.load().tic_rd_points_scaled_v(ctx.handle, inp, len(frames), hs, ws, strides, qarr.ctypes.data, len(qs), sizes.ctypes.data,
+                                                  sse.ctypes.data, wrapped.ctypes.data))
+    return sizes, sse, wrapped
+
+
 def entropy_encode_scaled(coeffs_zz, height, width, quality):
     """Host entropy stage of the integer encoder alone (no GPU needed): int16 [N, 64] zig-zag coefficients -> stream bytes."""
     L = N.load()

@@ -80,6 +80,8 @@ struct Slot {
     // and, for the read-back, where each stream lands in pin_out (pinned: the shader reads it where it lies)
     EntropyFrameTable *h_frames = nullptr, *d_frames = nullptr;
     unsigned long long *h_rb_off = nullptr;
+    // scaled batches (tic_compress_batch_scaled_v): the table of the chunk's ONE transform launch, pinned and on the device
+    ScaledFrameTable *h_sframes = nullptr, *d_sframes = nullptr;
     // adaptive batches (tic_compress_batch_adaptive_v): the chunk's statistics, tables, headers and bit counts, carved by adaptive_slot_layout
     // (tic_adaptive_frames.h), and the pinned mirror of their host-visible part.  Stream lengths are known only behind the statistics, so a
     // chunk may find d_streams or pin_out short and grow THIS slot's: streams_cap / pin_out_cap then say what it holds (0: what every slot holds)
@@ -297,6 +299,13 @@ struct tic_ctx {
     SseProbeTable *h_rd_tabs = nullptr, *d_rd_tabs = nullptr;
     size_t rd_tabs_host_bytes = 0, rd_tabs_dev_bytes = 0;
     int last_rbatch_sse_launches = 0;
+    // the integer encoder's batch forms (tic_compress_batch_scaled_v, tic_dctq_scaled_v_dev, tic_rd_points_scaled_v): the tables of the
+    // transform's descriptor form outside the batch slots, one per launch, and what the last calls did
+    ScaledFrameTable *h_scaled_tabs = nullptr, *d_scaled_tabs = nullptr;
+    size_t scaled_tabs_host_bytes = 0, scaled_tabs_dev_bytes = 0;
+    int last_sbatch_frames = 0, last_sbatch_single = 0, last_sbatch_chunks = 0, last_sbatch_launches = 0; // tic_last_compress_batch_scaled
+    int last_srd_frames = 0, last_srd_single = 0, last_srd_chunks = 0, last_srd_launches = 0, last_srd_size_launches = 0,
+        last_srd_sse_launches = 0; // tic_last_rd_scaled_batch
 };
 
 // NUMA node of a device (its PCI function's numa_node in sysfs) and the CPUs of that node within this process's affinity mask.
@@ -440,9 +449,9 @@ void DecWorkspace::release() {
 }
 
 void Slot::release() {
-    for (void *p : {(void *)pin_in, (void *)pin_out, (void *)h_lens, (void *)h_err, (void *)h_frames, (void *)h_rb_off, (void *)h_adapt})
+    for (void *p : {(void *)pin_in, (void *)pin_out, (void *)h_lens, (void *)h_err, (void *)h_frames, (void *)h_rb_off, (void *)h_adapt, (void *)h_sframes})
         if (p) (void)hipHostFree(p);
-    for (void *p : {d_img, d_coef, d_work, (void *)d_lens, (void *)d_err, d_streams, (void *)d_frames, (void *)d_adapt})
+    for (void *p : {d_img, d_coef, d_work, (void *)d_lens, (void *)d_err, d_streams, (void *)d_frames, (void *)d_adapt, (void *)d_sframes})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : {done, rb_done})
         if (e) (void)hipEventDestroy(e);
@@ -538,6 +547,8 @@ void tic_destroy(tic_ctx *ctx) {
     if (ctx->d_rate_tabs) (void)hipFree(ctx->d_rate_tabs);
     if (ctx->h_rd_tabs) (void)hipHostFree(ctx->h_rd_tabs);
     if (ctx->d_rd_tabs) (void)hipFree(ctx->d_rd_tabs);
+    if (ctx->h_scaled_tabs) (void)hipHostFree(ctx->h_scaled_tabs);
+    if (ctx->d_scaled_tabs) (void)hipFree(ctx->d_scaled_tabs);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -2248,7 +2259,9 @@ static int ensure_batch_slots(tic_ctx *ctx, tic_ctx::SlotNeed need) {
             (e = hipMalloc(&sl.d_streams, need.streams)) != hipSuccess ||
             (e = hipHostMalloc((void **)&sl.h_frames, sizeof(EntropyFrameTable), hipHostMallocDefault)) != hipSuccess ||
             (e = hipMalloc((void **)&sl.d_frames, sizeof(EntropyFrameTable))) != hipSuccess ||
-            (e = hipHostMalloc((void **)&sl.h_rb_off, kEntropyMaxFrames * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess)
+            (e = hipHostMalloc((void **)&sl.h_rb_off, kEntropyMaxFrames * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess ||
+            (e = hipHostMalloc((void **)&sl.h_sframes, sizeof(ScaledFrameTable), hipHostMallocDefault)) != hipSuccess ||
+            (e = hipMalloc((void **)&sl.d_sframes, sizeof(ScaledFrameTable))) != hipSuccess)
             return set_err(ctx, TIC_E_HIP, "batch entropy workspace allocation failed: %s", hipGetErrorString(e));
     }
     ctx->bslot_cap = need;
@@ -2785,6 +2798,25 @@ static hipError_t transform_chunk_v(tic_ctx *ctx, Slot &s, const MixedPlan &p, c
     return e;
 }
 
+// ... of a scaled chunk: ONE launch of the descriptor form, whatever the frames' widths and settings (the slot's table, uploaded in stream order)
+static hipError_t transform_chunk_scaled(Slot &s, const MixedPlan &p, const MixedChunk &c, hipStream_t stream, int *launches) {
+    unsigned long long off[kScaledMaxFrames], blk[kScaledMaxFrames];
+    long long pitch[kScaledMaxFrames];
+    int hs[kScaledMaxFrames], ws[kScaledMaxFrames], qfs[kScaledMaxFrames];
+    for (int k = 0; k < c.count; k++) {
+        const MixedFrame &f = p.frames[(size_t)(c.first + k)];
+        off[k] = f.img_off, blk[k] = f.first_block, pitch[k] = (long long)f.pitch;
+        hs[k] = f.h, ws[k] = f.w, qfs[k] = f.quality;
+    }
+    uint32_t strips = 0;
+    if (!fill_scaled_table(s.h_sframes, c.count, (unsigned long long)(uintptr_t)s.d_img, (unsigned long long)(uintptr_t)s.d_coef, off, pitch, hs, ws, qfs, blk, &strips))
+        return hipErrorInvalidValue;
+    hipError_t e = hipMemcpyAsync(s.d_sframes, s.h_sframes, sizeof(ScaledFrameTable), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = launch_fdctq_scaled_v(s.d_sframes, strips, stream);
+    (*launches)++;
+    return e;
+}
+
 static tic_ctx::SlotNeed mixed_slot_need(const MixedPlan &p) {
     tic_ctx::SlotNeed need;
     need.img = p.max_img;
@@ -2797,8 +2829,10 @@ static tic_ctx::SlotNeed mixed_slot_need(const MixedPlan &p) {
 }
 
 // One run of the pipeline over the plan's chunks.  kRetryEightLanes: a chunk that ran the lane-per-block kernel raised code 4; *retry_quality is
-// that chunk's lowest quality.
-static int batch_mixed_pipeline(tic_ctx *ctx, const MixedPlan &p, const MixedCall &io, int *retry_quality) {
+// that chunk's lowest quality.  scaled: the integer encoder's streams (the plan's qualities are its settings) - the descriptor-form transform,
+// the 8-lane packing kernel always (the bound learnt for the lane-per-block kernel is neither read nor written), header flag 1 << 30.
+// *launches_out: transform launches.
+static int batch_mixed_pipeline(tic_ctx *ctx, const MixedPlan &p, const MixedCall &io, int *retry_quality, bool scaled, int *launches_out) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int rc = ensure_batch_slots(ctx, mixed_slot_need(p));
     if (rc) return rc;
@@ -2811,17 +2845,17 @@ static int batch_mixed_pipeline(tic_ctx *ctx, const MixedPlan &p, const MixedCal
             const MixedFrame *fr = &p.frames[(size_t)c.first];
             // lane per block only when EVERY frame of the chunk may take it (the plan orders by quality: the first frame's is the lowest, the last
             // frame's the highest)
-            const int mode = fr[c.count - 1].quality <= ctx->ent_lane_max_quality ? kEntropyLanePerBlock : kEntropyEightLanes;
+            const int mode = !scaled && fr[c.count - 1].quality <= ctx->ent_lane_max_quality ? kEntropyLanePerBlock : kEntropyEightLanes;
             size_t nparts, ngroups, nplaces;
             if (!mixed_chunk_table(p, c, mode, s.h_frames, &nparts, &ngroups, &nplaces)) return set_err(ctx, TIC_E_ARG, "mixed batch: chunk %d has no table", ci);
             return enqueue_on_slot(
                 ctx, s, stream, c.first, c.count, [&](int *direct) { return upload_chunk_v(ctx, s, p, c, io, stream, direct); },
-                [&]() { return transform_chunk_v(ctx, s, p, c, stream, &launches); },
+                [&]() { return scaled ? transform_chunk_scaled(s, p, c, stream, &launches) : transform_chunk_v(ctx, s, p, c, stream, &launches); },
                 [&](Slot &sl, hipStream_t st) {
                     hipError_t e = hipMemcpyAsync(sl.d_frames, sl.h_frames, sizeof(EntropyFrameTable), hipMemcpyHostToDevice, st);
                     if (e == hipSuccess)
                         e = entropy_gpu_fused_v((const int16_t *)sl.d_coef, sl.h_frames, sl.d_frames, c.count, ctx->d_huff, sl.d_work, sl.work_bytes, sl.d_streams,
-                                                sl.d_lens, sl.d_err + par, sl.d_err + (par ^ 1), mode, st);
+                                                sl.d_lens, sl.d_err + par, sl.d_err + (par ^ 1), mode, st, scaled ? kFlagScaled : 0u);
                     if (e == hipSuccess) e = hipMemcpyAsync(sl.h_lens, sl.d_lens, c.count * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
                     if (e == hipSuccess) e = hipMemcpyAsync(sl.h_err, sl.d_err + par, sizeof(int), hipMemcpyDeviceToHost, st);
                     return e;
@@ -2834,7 +2868,7 @@ static int batch_mixed_pipeline(tic_ctx *ctx, const MixedPlan &p, const MixedCal
             return r;
         },
         [&](Slot &s) { return hand_out_chunk_v(ctx, p, s, io); });
-    ctx->last_vbatch_launches = launches;
+    *launches_out = launches;
     return result;
 }
 
@@ -2877,13 +2911,13 @@ int tic_compress_batch_v(tic_ctx *ctx, const uint8_t *const *images, int n, cons
     }
     if (!p.frames.empty()) {
         int retry_quality = 0;
-        int rc = batch_mixed_pipeline(ctx, p, io, &retry_quality);
+        int rc = batch_mixed_pipeline(ctx, p, io, &retry_quality, false, &ctx->last_vbatch_launches);
         if (rc == kRetryEightLanes) {
             // The flag does not say which frame of the chunk has the long block, so the bound drops below the chunk's LOWEST quality: this chunk and
             // every later one (qualities ascend) then run the 8-lane kernel, the chunks in front passed as they were - one more run settles it.
             ctx->ent_lane_max_quality = retry_quality - 1;
             retry_quality = 0;
-            rc = batch_mixed_pipeline(ctx, p, io, &retry_quality);
+            rc = batch_mixed_pipeline(ctx, p, io, &retry_quality, false, &ctx->last_vbatch_launches);
         }
         if (rc) return rc == kRetryEightLanes ? set_err(ctx, TIC_E_HIP, "mixed batch: the 8-lane packing kernel refused a block") : rc;
     }
@@ -2907,6 +2941,130 @@ int tic_last_compress_batch_v(tic_ctx *ctx, int *batch_frames, int *single_frame
     if (single_frames) *single_frames = ctx->last_vbatch_single;
     if (chunks) *chunks = ctx->last_vbatch_chunks;
     if (transform_launches) *transform_launches = ctx->last_vbatch_launches;
+    return TIC_OK;
+}
+
+// ---- the integer encoder for a batch (tic_compress_batch_scaled_v) --------------------------------------------------------------------------
+// The mixed batch's route with the settings 0..3 as the plan's qualities: frames ordered by (setting, width, height), the same chunks, slots,
+// upload, entropy stage in descriptor form, read-back and hand-out.  What differs: ONE transform launch per chunk (fdctq_scaled_kernel_v: a
+// table of records instead of a launch per run of equal-width frames), the 8-lane packing kernel always, header flag 1 << 30 with its flush
+// byte, and stream areas with room for that byte.  Nothing the float route learns (ent_lane_max_quality) is read or written.
+// Argument checks shared with tic_rd_points_scaled_v: every frame's geometry at every setting, its image pointer.
+static int check_scaled_frames(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides, const int *qfs,
+                               int nq_shared) {
+    for (int i = 0; i < n; i++) {
+        int rc = TIC_OK;
+        if (nq_shared < 0) rc = check_scaled_geometry(ctx, hs[i], ws[i], row_strides[i], qfs[i]);
+        for (int j = 0; j < nq_shared && rc == TIC_OK; j++) rc = check_scaled_geometry(ctx, hs[i], ws[i], row_strides[i], qfs[j]);
+        if (rc) {
+            const std::string why = ctx->err;
+            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
+        }
+        if (!images[i] && num_blocks(hs[i], ws[i]) != 0) return set_err(ctx, TIC_E_ARG, "frame %d: null image", i);
+    }
+    return TIC_OK;
+}
+
+int tic_compress_batch_scaled_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
+                                const int *qfs, uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    // every check before any work: nothing is written while a frame of the call is unacceptable
+    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
+    ctx->last_sbatch_frames = ctx->last_sbatch_single = ctx->last_sbatch_chunks = ctx->last_sbatch_launches = 0;
+    if (n == 0) return TIC_OK;
+    if (!images || !hs || !ws || !row_strides || !qfs || !outs || !caps || !out_lens) return set_err(ctx, TIC_E_ARG, "null array argument");
+    int rc = check_scaled_frames(ctx, images, n, hs, ws, row_strides, qfs, -1);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++)
+        if (!outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
+    int chunk_frames;
+    size_t chunk_bytes;
+    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
+    const MixedPlan p = plan_mixed_batch(hs, ws, qfs, n, chunk_frames, chunk_bytes, 1); // (+ 1: the flush byte)
+    for (const MixedFrame &f : p.frames)
+        if (f.bound < tic_compress_scaled_bound(f.h, f.w)) return set_err(ctx, TIC_E_ARG, "frame %d: stream area without room for the flush byte", f.index);
+    const MixedCall io = {images, row_strides, outs, caps, out_lens};
+    ctx->last_batch_direct_frames = ctx->last_batch_staged_frames = ctx->last_batch_autoreg_frames = ctx->last_batch_zero_copy = 0;
+    ctx->bt = BatchTrace();
+    for (int i : p.empty) { // frames without blocks: the host's 17-byte stream
+        rc = entropy_encode_scaled(nullptr, hs[i], ws[i], qfs[i], outs[i], caps[i], &out_lens[i]);
+        if (rc) return set_err(ctx, rc, "frame %d: output buffer too small for a header and the flush byte", i);
+    }
+    if (!p.frames.empty()) {
+        int retry_quality = 0;
+        rc = batch_mixed_pipeline(ctx, p, io, &retry_quality, true, &ctx->last_sbatch_launches);
+        if (rc) return rc == kRetryEightLanes ? set_err(ctx, TIC_E_HIP, "scaled batch: the 8-lane packing kernel refused a block") : rc;
+    }
+    ctx->last_sbatch_frames = (int)p.frames.size();
+    ctx->last_sbatch_chunks = (int)p.chunks.size();
+    for (int i : p.single) { // what the batch kernels do not take, behind the batch, frame by frame
+        rc = tic_compress_scaled(ctx, images[i], hs[i], ws[i], row_strides[i], qfs[i], outs[i], caps[i], &out_lens[i]);
+        if (rc) {
+            const std::string why = ctx->err;
+            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
+        }
+        ctx->last_sbatch_single++;
+    }
+    return TIC_OK;
+}
+
+int tic_last_compress_batch_scaled(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks, int *transform_launches) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (batch_frames) *batch_frames = ctx->last_sbatch_frames;
+    if (single_frames) *single_frames = ctx->last_sbatch_single;
+    if (chunks) *chunks = ctx->last_sbatch_chunks;
+    if (transform_launches) *transform_launches = ctx->last_sbatch_launches;
+    return TIC_OK;
+}
+
+// Room for `ntabs` tables of the transform's descriptor form outside the batch slots.  Nothing of an earlier call may be in flight.
+static int ensure_scaled_tabs(tic_ctx *ctx, size_t ntabs) {
+    const size_t bytes = ntabs * sizeof(ScaledFrameTable), alloc = align_up(bytes, 16384);
+    const int rc = grow_pinned(ctx, ctx->h_scaled_tabs, ctx->scaled_tabs_host_bytes, bytes, alloc);
+    return rc ? rc : grow_dev(ctx, ctx->d_scaled_tabs, ctx->scaled_tabs_dev_bytes, bytes, alloc);
+}
+
+// The kernel alone, synchronous: frames resident anywhere on the device, the coefficients of all of them back to back at d_coeffs_zz in the
+// caller's order (a frame without blocks takes none), one launch per kScaledMaxFrames frames.
+int tic_dctq_scaled_v_dev(tic_ctx *ctx, const void *const *d_images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides, const int *qfs,
+                          void *d_coeffs_zz) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
+    if (n == 0) return TIC_OK;
+    if (!d_images || !hs || !ws || !row_strides || !qfs) return set_err(ctx, TIC_E_ARG, "null array argument");
+    int rc = check_scaled_frames(ctx, (const uint8_t *const *)d_images, n, hs, ws, row_strides, qfs, -1);
+    if (rc) return rc;
+    std::vector<int> with_blocks;
+    for (int i = 0; i < n; i++)
+        if (num_blocks(hs[i], ws[i]) != 0) with_blocks.push_back(i);
+    if (with_blocks.empty()) return TIC_OK;
+    if (!d_coeffs_zz || ((uintptr_t)d_coeffs_zz & 15) != 0) return set_err(ctx, TIC_E_ARG, "coefficient buffer null or not 16-byte aligned");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t m = with_blocks.size(), ntabs = (m + kScaledMaxFrames - 1) / kScaledMaxFrames;
+    rc = ensure_scaled_tabs(ctx, ntabs);
+    if (rc) return rc;
+    std::vector<uint32_t> strips(ntabs);
+    unsigned long long block = 0;
+    for (size_t t = 0; t < ntabs; t++) {
+        unsigned long long off[kScaledMaxFrames], blk[kScaledMaxFrames];
+        long long pitch[kScaledMaxFrames];
+        int fh[kScaledMaxFrames], fw[kScaledMaxFrames], fq[kScaledMaxFrames];
+        const int cnt = (int)std::min<size_t>(kScaledMaxFrames, m - t * kScaledMaxFrames);
+        for (int k = 0; k < cnt; k++) {
+            const int i = with_blocks[t * kScaledMaxFrames + (size_t)k];
+            off[k] = (unsigned long long)(uintptr_t)d_images[i], blk[k] = block, pitch[k] = (long long)row_strides[i]; // (addresses: the table's base is 0)
+            fh[k] = hs[i], fw[k] = ws[i], fq[k] = qfs[i];
+            block += num_blocks(hs[i], ws[i]);
+        }
+        if (!fill_scaled_table(&ctx->h_scaled_tabs[t], cnt, 0ull, (unsigned long long)(uintptr_t)d_coeffs_zz, off, pitch, fh, fw, fq, blk, &strips[t]))
+            return set_err(ctx, TIC_E_ARG, "frames %d..: more strips than one launch walks", with_blocks[t * kScaledMaxFrames]);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_scaled_tabs, ctx->h_scaled_tabs, ntabs * sizeof(ScaledFrameTable), hipMemcpyHostToDevice, ctx->stream));
+    for (size_t t = 0; t < ntabs; t++) HIPCHK(ctx, launch_fdctq_scaled_v(ctx->d_scaled_tabs + t, strips[t], ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TIC_OK;
 }
 
@@ -3433,6 +3591,150 @@ int tic_last_rd_batch(tic_ctx *ctx, int *sse_launches) {
     TIC_LOCK(ctx);
     if (!ctx) return TIC_E_ARG;
     if (sse_launches) *sse_launches = ctx->last_rbatch_sse_launches;
+    return TIC_OK;
+}
+
+// ---- the table of the reference's tests/cbenchmark.py in one call (tic_rd_points_scaled_v) -----------------------------------------------------
+// Length and round-trip error of the integer encoder's stream for every frame x setting pair.  The chunks are the mixed plan's (frames ordered
+// by width and height), cut so that the coefficients of a chunk's probes - nq areas per frame - fit the rate workspace.  Per chunk: one
+// upload into the scratch image, one memset of the results, and per 64 probes ONE launch of the transform's descriptor form (a record per
+// probe: the nq records of a frame name the same pixels with their own setting and output area), one of the size kernel's and one of the
+// measuring kernel's (scaled branch per probe), then one read-back.  The probes are queued setting by setting, so a wave of the transform
+// meets a new setting - and reloads its table words - at most nq - 1 times.
+// Length of the integer encoder's stream: header, whole payload bytes, BB_flushBits' byte; -1: a coefficient without a code.
+static inline long long scaled_probe_size(const SizeResult &r) { return r.nocode ? -1ll : (long long)(16ull + (r.bits >> 3) + 1ull); }
+
+int tic_rd_points_scaled_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides, const int *qfs,
+                           int nq, long long *sizes, uint64_t *sse, uint64_t *sse_wrapped) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    // every check before any work
+    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
+    if (nq < 0 || (nq > 0 && !qfs)) return set_err(ctx, TIC_E_ARG, "bad setting list");
+    ctx->last_srd_frames = ctx->last_srd_single = ctx->last_srd_chunks = ctx->last_srd_launches = ctx->last_srd_size_launches = ctx->last_srd_sse_launches = 0;
+    if (n == 0 || nq == 0) return TIC_OK;
+    if (!images || !hs || !ws || !row_strides) return set_err(ctx, TIC_E_ARG, "null array argument");
+    for (int j = 0; j < nq; j++)
+        if (qfs[j] < 0 || qfs[j] > 3) return set_err(ctx, TIC_E_QUALITY, "scaled-DCT setting %d outside 0..3 (best, high, med, low)", qfs[j]);
+    int rc = check_scaled_frames(ctx, images, n, hs, ws, row_strides, qfs, nq);
+    if (rc) return rc;
+    auto put = [&](int i, int j, long long size, uint64_t s0, uint64_t s1) {
+        const size_t at = (size_t)i * (size_t)nq + (size_t)j;
+        if (sizes) sizes[at] = size;
+        if (sse) sse[at] = s0;
+        if (sse_wrapped) sse_wrapped[at] = s1;
+    };
+    int chunk_frames;
+    size_t chunk_bytes;
+    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
+    // (a block is 64 bytes of pixels and 128 of coefficients: a chunk's probes take 2 * nq times its pixels)
+    chunk_bytes = std::min(chunk_bytes, std::max<size_t>(kRateWorkspaceBytes / (2 * (size_t)nq), 64));
+    const std::vector<int> zeros((size_t)n, 0);
+    const MixedPlan p = plan_mixed_batch(hs, ws, zeros.data(), n, chunk_frames, chunk_bytes);
+    for (int i : p.empty)
+        for (int j = 0; j < nq; j++) put(i, j, 17, 0, 0);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const RateCall io = {images, hs, ws, row_strides};
+    const size_t sse_cap = sse_group_cap();
+    for (const MixedChunk &c : p.chunks) {
+        const int np = c.count * nq;
+        const size_t ntabs = ((size_t)np + kScaledMaxFrames - 1) / kScaledMaxFrames;
+        static_assert(kScaledMaxFrames == kSizeMaxProbes && kScaledMaxFrames == kSseMaxProbes, "one group of probes is one launch of each kernel");
+        rc = ensure_scratch(ctx, c.img_bytes, c.nblk * (size_t)nq * 128 + 16);
+        if (rc) return rc;
+        rc = ensure_rate(ctx, (size_t)np);
+        if (rc) return rc;
+        rc = ensure_scaled_tabs(ctx, ntabs);
+        if (rc) return rc;
+        const size_t size_bytes = ntabs * sizeof(SizeProbeTable), sse_bytes = ntabs * sizeof(SseProbeTable);
+        if ((rc = grow_pinned(ctx, ctx->h_rate_tabs, ctx->rate_tabs_host_bytes, size_bytes, align_up(size_bytes, 16384))) != TIC_OK ||
+            (rc = grow_dev(ctx, ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, size_bytes, align_up(size_bytes, 16384))) != TIC_OK ||
+            (rc = grow_pinned(ctx, ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, sse_bytes, align_up(sse_bytes, 16384))) != TIC_OK ||
+            (rc = grow_dev(ctx, ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, sse_bytes, align_up(sse_bytes, 16384))) != TIC_OK)
+            return rc;
+        rc = upload_rate_chunk(ctx, p, c, io);
+        if (rc) return rc;
+        // probe j * count + k: frame k of the chunk at setting j, its coefficients behind those of the probes in front
+        std::vector<size_t> size_groups(ntabs), sse_groups(ntabs), tab_first_block(ntabs);
+        std::vector<uint32_t> strips(ntabs);
+        size_t block = 0;
+        for (size_t t = 0; t < ntabs; t++) {
+            const int first = (int)t * kScaledMaxFrames, cnt = std::min(kScaledMaxFrames, np - first);
+            unsigned long long off[kScaledMaxFrames], blk[kScaledMaxFrames];
+            long long pitch[kScaledMaxFrames];
+            int fh[kScaledMaxFrames], fw[kScaledMaxFrames], fq[kScaledMaxFrames];
+            size_t nblk[kSizeMaxProbes], total = 0;
+            uint32_t result[kSizeMaxProbes];
+            SseProbeIn in[kSseMaxProbes];
+            tab_first_block[t] = block;
+            for (int k = 0; k < cnt; k++) {
+                const int pi = first + k, j = pi / c.count;
+                const MixedFrame &f = p.frames[(size_t)(c.first + pi % c.count)];
+                off[k] = f.img_off, blk[k] = block, pitch[k] = (long long)f.pitch, fh[k] = f.h, fw[k] = f.w, fq[k] = qfs[j];
+                nblk[k] = f.nblk, result[k] = (uint32_t)pi;
+                in[k] = SseProbeIn{(const int16_t *)ctx->d_coef + block * 64, (const uint8_t *)ctx->d_img + f.img_off, ctx->d_consts + 50, (long long)f.pitch,
+                                   f.h, f.w, (uint32_t)pi, qfs[j]};
+                block += f.nblk;
+            }
+            if (!fill_scaled_table(&ctx->h_scaled_tabs[t], cnt, (unsigned long long)(uintptr_t)ctx->d_img, (unsigned long long)(uintptr_t)ctx->d_coef, off, pitch, fh,
+                                   fw, fq, blk, &strips[t]) ||
+                !fill_size_probe_table(&ctx->h_rate_tabs[t], cnt, nblk, result, &size_groups[t], &total) ||
+                !fill_sse_probe_table(&ctx->h_rd_tabs[t], cnt, in, sse_cap, &sse_groups[t]))
+                return set_err(ctx, TIC_E_ARG, "scaled rate-distortion batch: probes %d.. have no table", first);
+        }
+        const size_t res_bytes = (size_t)np * (sizeof(SizeResult) + sizeof(DistortionResult));
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_rate, 0, res_bytes, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_scaled_tabs, ctx->h_scaled_tabs, ntabs * sizeof(ScaledFrameTable), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_rate_tabs, ctx->h_rate_tabs, size_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_rd_tabs, ctx->h_rd_tabs, sse_bytes, hipMemcpyHostToDevice, ctx->stream));
+        for (size_t t = 0; t < ntabs; t++) {
+            HIPCHK(ctx, launch_fdctq_scaled_v(ctx->d_scaled_tabs + t, strips[t], ctx->stream));
+            HIPCHK(ctx, stream_size_gpu_v((const int16_t *)ctx->d_coef + tab_first_block[t] * 64, ctx->d_rate_tabs + t, size_groups[t], ctx->d_size_tab, ctx->d_rate,
+                                          ctx->stream));
+            HIPCHK(ctx, launch_idct_sse_v(ctx->d_rd_tabs + t, sse_groups[t], dist_of(ctx->d_rate, np), ctx->stream, true));
+            ctx->last_srd_launches++, ctx->last_srd_size_launches++, ctx->last_srd_sse_launches++;
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_rate, ctx->d_rate, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, wait_stream(ctx));
+        const DistortionResult *dist = dist_of(ctx->h_rate, np);
+        for (int pi = 0; pi < np; pi++)
+            put(p.frames[(size_t)(c.first + pi % c.count)].index, pi / c.count, scaled_probe_size(ctx->h_rate[pi]), dist[pi].sse, dist[pi].sse_wrapped);
+    }
+    ctx->last_srd_frames = (int)p.frames.size();
+    ctx->last_srd_chunks = (int)p.chunks.size();
+    for (int i : p.single) { // what a chunk cannot hold, behind the batch, frame by frame and setting by setting
+        const size_t nblk = num_blocks(hs[i], ws[i]);
+        for (int j = 0; j < nq; j++) {
+            uint64_t sums[2] = {0, 0};
+            rc = tic_roundtrip_sse_scaled(ctx, images[i], hs[i], ws[i], row_strides[i], qfs[j], sums);
+            if (rc) {
+                const std::string why = ctx->err;
+                return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
+            }
+            // (its coefficients are still in the scratch buffer: the size kernel on them)
+            rc = ensure_rate(ctx, 1);
+            if (rc) return rc;
+            HIPCHK(ctx, hipMemsetAsync(ctx->d_rate, 0, sizeof(SizeResult), ctx->stream));
+            HIPCHK(ctx, stream_size_gpu((const int16_t *)ctx->d_coef, nblk, 1, ctx->d_size_tab, ctx->d_rate, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->h_rate, ctx->d_rate, sizeof(SizeResult), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, wait_stream(ctx));
+            put(i, j, scaled_probe_size(ctx->h_rate[0]), sums[0], sums[1]);
+        }
+        ctx->last_srd_single++;
+    }
+    return TIC_OK;
+}
+
+int tic_last_rd_scaled_batch(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks, int *transform_launches, int *size_launches,
+                             int *sse_launches) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (batch_frames) *batch_frames = ctx->last_srd_frames;
+    if (single_frames) *single_frames = ctx->last_srd_single;
+    if (chunks) *chunks = ctx->last_srd_chunks;
+    if (transform_launches) *transform_launches = ctx->last_srd_launches;
+    if (size_launches) *size_launches = ctx->last_srd_size_launches;
+    if (sse_launches) *sse_launches = ctx->last_srd_sse_launches;
     return TIC_OK;
 }
 

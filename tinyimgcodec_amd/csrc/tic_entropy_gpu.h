@@ -49,6 +49,7 @@ hipError_t entropy_gpu_fused(const int16_t *d_zz, size_t blocks_per_frame, int n
 size_t entropy_fused_work_bytes_v(size_t nblocks_total, size_t nframes);
 hipError_t entropy_gpu_fused_v(const int16_t *d_zz, const EntropyFrameTable *h_frames, const EntropyFrameTable *d_frames, int nframes,
                                const HuffDev *d_tab, void *d_work, size_t work_bytes, void *d_out, unsigned long long *d_lens, int *d_err,
-                               int *d_err_next, int mode, hipStream_t stream);
+                               int *d_err_next, int mode, hipStream_t stream, uint32_t flag = 0);
+// flag: as above, for every frame of the launch (1 << 30: rec[f].quality is the setting 0..3 and cap_words counts the flush byte's word).
 
 } // namespace tic

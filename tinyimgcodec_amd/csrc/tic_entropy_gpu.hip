@@ -958,19 +958,19 @@ __global__ __launch_bounds__(256) void entropy_place_kernel(const uint32_t *__re
                            frame * tiles_per_frame, tiles_per_frame, out + frame * out_frame_stride, cap_words, h, w, quality};
     entropy_place_body<ABL, kPlace, kGrp, kSlotWords, kHeads>(stage, nbits, gsum, tile_sum, fv, lens, err_flag, err_next, status, flag);
 }
-// ... in descriptor form: no tile sums (a frame has at most kEntropyMaxGroups groups), a default-table stream, no status block
+// ... in descriptor form: no tile sums (a frame has at most kEntropyMaxGroups groups), no status block
 template <int kPlace, int kGrp, int kSlotWords, bool kHeads, int kPartBlocks>
 __global__ __launch_bounds__(256) void entropy_place_kernel_v(const uint32_t *__restrict__ stage, const uint32_t *__restrict__ nbits,
                                                               const uint32_t *__restrict__ gsum, const EntropyFrameTable *__restrict__ frames,
                                                               unsigned char *__restrict__ out, unsigned long long *__restrict__ lens,
-                                                              int *__restrict__ err_flag, int *__restrict__ err_next) {
+                                                              int *__restrict__ err_flag, int *__restrict__ err_next, uint32_t flag) {
     const int f = find_frame(frames->first_place, blockIdx.x);
     const EntropyFrameRec &r = frames->rec[f];
     const unsigned long long parts = (r.nblocks + (unsigned long long)kPartBlocks - 1ull) / (unsigned long long)kPartBlocks;
     const PlaceFrame fv = {(unsigned long long)f, (unsigned long long)(blockIdx.x - r.first_place), (unsigned long long)r.first_part, parts,
                            (unsigned long long)r.first_group, (parts + (unsigned long long)kGrp - 1ull) / (unsigned long long)kGrp, 0ull, 0ull,
                            out + r.out_off, r.cap_words, r.h, r.w, r.quality};
-    entropy_place_body<0, kPlace, kGrp, kSlotWords, kHeads>(stage, nbits, gsum, nullptr, fv, lens, err_flag, err_next, nullptr, 0u);
+    entropy_place_body<0, kPlace, kGrp, kSlotWords, kHeads>(stage, nbits, gsum, nullptr, fv, lens, err_flag, err_next, nullptr, flag);
 }
 
 } // namespace
@@ -1106,7 +1106,7 @@ static_assert(kPB == 64 && kGroupL == 4 && kGroup == 16, "entropy_geom (tic_entr
 
 hipError_t entropy_gpu_fused_v(const int16_t *d_zz, const EntropyFrameTable *h_frames, const EntropyFrameTable *d_frames, int nframes,
                                const HuffDev *d_tab, void *d_work, size_t work_bytes, void *d_out, unsigned long long *d_lens, int *d_err,
-                               int *d_err_next, int mode, hipStream_t stream) {
+                               int *d_err_next, int mode, hipStream_t stream, uint32_t flag) {
     if (nframes <= 0) return hipSuccess;
     if (nframes > kEntropyMaxFrames || !h_frames || !d_frames) return hipErrorInvalidValue;
     const bool lane_form = mode == kEntropyLanePerBlock;
@@ -1140,10 +1140,10 @@ hipError_t entropy_gpu_fused_v(const int16_t *d_zz, const EntropyFrameTable *h_f
     if (e != hipSuccess) return e;
     if (lane_form)
         hipLaunchKernelGGL((entropy_place_kernel_v<8, kGroupL, PackL<kLaneW>::kStageWords, false, kPB>), dim3((unsigned)nplace), dim3(256), 0, stream, stage, nbits,
-                           gsum, d_frames, (unsigned char *)d_out, d_lens, d_err, d_err_next);
+                           gsum, d_frames, (unsigned char *)d_out, d_lens, d_err, d_err_next, flag);
     else
         hipLaunchKernelGGL((entropy_place_kernel_v<32, kGroup, kStageWords, true, 8>), dim3((unsigned)nplace), dim3(256), 0, stream, stage, nbits, gsum, d_frames,
-                           (unsigned char *)d_out, d_lens, d_err, d_err_next);
+                           (unsigned char *)d_out, d_lens, d_err, d_err_next, flag);
     return hipGetLastError();
 }
 

@@ -11,8 +11,8 @@
 //   TIC_DECODE_SHADOWS      device Huffman decoder: ranges in front of its own that a wave of the measure kernel shadows (1 ... 16; default 4, 8 below 544 bits per range)
 //   TIC_DECODE_ROUNDS       device Huffman decoder: hand-over rounds of the stitch (default 8)
 //   TIC_DECODE_NO_HOSTPIX   tic_decompress of small images through the device image buffer and a DMA copy, as large ones (not through host-mapped memory)
-//   TIC_BATCH_CHUNK         tic_compress_batch, tic_compress_batch_v, tic_compress_batch_adaptive_v, tic_stream_sizes_v, tic_compress_batch_to_size: frames per chunk instead of the choice by frame size
-//   TIC_BATCH_CHUNK_BYTES   tic_compress_batch_v, tic_compress_batch_adaptive_v, tic_stream_sizes_v, tic_compress_batch_to_size: staged pixels per chunk instead of 32 MB (a larger frame is coded alone, behind the batch)
+//   TIC_BATCH_CHUNK         tic_compress_batch, tic_compress_batch_v, tic_compress_batch_adaptive_v, tic_compress_batch_scaled_v, tic_rd_points_scaled_v, tic_stream_sizes_v, tic_compress_batch_to_size: frames per chunk instead of the choice by frame size
+//   TIC_BATCH_CHUNK_BYTES   tic_compress_batch_v, tic_compress_batch_adaptive_v, tic_compress_batch_scaled_v, tic_rd_points_scaled_v, tic_stream_sizes_v, tic_compress_batch_to_size: staged pixels per chunk instead of 32 MB (a larger frame is coded alone, behind the batch)
 //   TIC_DBATCH_CHUNK        tic_decompress_batch: frames per chunk instead of 1,024 (1 ... 1024; anything else is ignored)
 //   TIC_ADBATCH_CHUNK       tic_decompress_batch_adaptive: frames per chunk instead of 1,024 (1 ... 1024; anything else is ignored)
 //   TIC_DBATCH_WORK_CAP     tic_decompress_batch: at most this many bytes of work buffer are handed to the batch launcher (it refuses a chunk that needs more)
@@ -31,6 +31,7 @@
 //   TIC_ORDER               pass order of the strip kernel (0 rows first, 1 columns first) instead of the choice by grid
 //   TIC_BAND_BYTES          size from which a frame is transformed in bands of block rows (4 GiB in production)
 //   TIC_SSE_MAX_GROUPS      measuring kernel's descriptor form: workgroups per probe at most (1 ... 1024; default 1024), so that the walk runs on frames of a few blocks
+//   TIC_SCALED_V_GROUPS     integer transform's descriptor form: workgroups per launch at most (default 2,048), so that one wave walks strips of several frames
 // at every call (tests flip them inside one process).  tic_build_has_test_hooks() tells which build a process has loaded;
 // tests/test_gpu_parity.py::test_shipped_library_in_a_fresh_process runs the parity core on the product build.
 #pragma once

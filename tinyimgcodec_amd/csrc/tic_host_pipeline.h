@@ -130,7 +130,7 @@ struct MixedFrame {
     int index;                  // the caller's index
     int h, w, quality;
     size_t nblk, pitch, img_bytes; // img_bytes = pitch * h, a multiple of 8
-    size_t bound;               // bytes of the frame's stream area: compress_bound(h, w) rounded up to 16
+    size_t bound;               // bytes of the frame's stream area: compress_bound(h, w) (+ the plan's stream_extra) rounded up to 16
     size_t img_off, first_block, stream_off;
 };
 // A maximal run of neighbours the transform takes in ONE launch, as one tall frame: equal width and quality, every height a multiple of 8
@@ -155,8 +155,9 @@ struct MixedPlan {
 };
 
 // chunk_frames: frames per chunk (1..kMixedChunkFrames; anything else: kMixedChunkFrames); chunk_bytes: staged pixels per chunk.  A frame of
-// more than chunk_bytes goes to `single`.
-inline MixedPlan plan_mixed_batch(const int *hs, const int *ws, const int *qs, int n, int chunk_frames, size_t chunk_bytes) {
+// more than chunk_bytes goes to `single`.  stream_extra: bytes a stream may have beyond compress_bound() (1 for the scaled form's flush byte:
+// where the bound is a multiple of 16 the rounding alone leaves no room for it).
+inline MixedPlan plan_mixed_batch(const int *hs, const int *ws, const int *qs, int n, int chunk_frames, size_t chunk_bytes, size_t stream_extra = 0) {
     MixedPlan p;
     if (chunk_frames < 1 || chunk_frames > kMixedChunkFrames) chunk_frames = kMixedChunkFrames;
     const EntropyGeom g8 = entropy_geom(kEntropyEightLanes); // (the mode with more groups per block)
@@ -169,7 +170,7 @@ inline MixedPlan plan_mixed_batch(const int *hs, const int *ws, const int *qs, i
             continue;
         }
         f.pitch = batch_pitch(f.w), f.img_bytes = f.pitch * (size_t)f.h;
-        f.bound = (compress_bound(f.h, f.w) + 15) / 16 * 16;
+        f.bound = (compress_bound(f.h, f.w) + stream_extra + 15) / 16 * 16;
         f.img_off = f.first_block = f.stream_off = 0;
         const size_t parts = (f.nblk + g8.part_blocks - 1) / g8.part_blocks, groups = (parts + g8.group_parts - 1) / g8.group_parts;
         if (groups > kEntropyMaxGroups || f.img_bytes > chunk_bytes) {

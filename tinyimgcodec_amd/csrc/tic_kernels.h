@@ -112,9 +112,10 @@ int idct_batch_tiles_per_wg();
 hipError_t launch_idct_batch(const IdctArgs *d_args, const uint2 *d_wgs, size_t nwgs, hipStream_t stream);
 hipError_t launch_idct_sse(const IdctArgs &a, const SseArgs &m, hipStream_t stream);
 // The descriptor form: one launch for the probes of a table (device memory; fill_sse_probe_table, tic_rd_plan.h), `ngroups` workgroups, probe k
-// adding into d_res[its result index].
+// adding into d_res[its result index].  scaled_probes: the table may hold probes of the integer encoder (SseProbeRec::scaled_exp1 != 0); a launch
+// without it reads every probe as one of the float codec.
 struct SseProbeTable;
-hipError_t launch_idct_sse_v(const SseProbeTable *d_probes, size_t ngroups, DistortionResult *d_res, hipStream_t stream);
+hipError_t launch_idct_sse_v(const SseProbeTable *d_probes, size_t ngroups, DistortionResult *d_res, hipStream_t stream, bool scaled_probes = false);
 hipError_t launch_selftest_transpose(const void *in, void *out_dpp, void *out_ref, int nthreads, hipStream_t stream);
 
 } // namespace tic

@@ -1206,7 +1206,11 @@ __global__ __launch_bounds__(kWavesPerWG * 64) void idct_batch_kernel(const Idct
 // in order, so what is needed between the last transposing read of one tile and the first scatter of the next is a compiler-level fence:
 // transpose8x8_dwords ends in one behind its reads, and the loop closes with another.  No workgroup barrier inside the walk: the trip count
 // is uniform across the workgroup (it depends on blockIdx.x and the record alone), so every wave reaches the barrier of sse_reduce_add.
+// kScaledProbes: a table that may hold probes of the integer encoder (tic_rd_points_scaled_v) - the record's exponent word decides per probe,
+// and idct_body branches on a.scaled at run time.  A table of float probes alone takes the instantiation without the branch (measured: the
+// branch costs a 4096^2 float probe 1.6 of 40.4 us).
 static_assert(kWavesPerWG == kSseWavesPerWG, "tic_rd_plan.h counts a probe's workgroups by this workgroup");
+template <bool kScaledProbes>
 __global__ __launch_bounds__(kWavesPerWG * 64) void idct_sse_kernel_v(const SseProbeTable *__restrict__ pt, DistortionResult *__restrict__ res) {
     const int lane = threadIdx.x & 63;
     const uint32_t first = pt->first_group[lane];
@@ -1220,6 +1224,10 @@ __global__ __launch_bounds__(kWavesPerWG * 64) void idct_sse_kernel_v(const SseP
     a.bw = r.bw, a.tiles_x = r.tiles_x, a.ntiles = r.ntiles;
     a.aligned8 = 0;
     a.consts = static_cast<const DctqConsts *>(r.consts);
+    if constexpr (kScaledProbes) {
+        a.scaled = r.scaled_exp1 != 0u;
+        a.pow2 = __hiloint2double((int)((1022u + r.scaled_exp1) << 20), 0); // 2 ** (scaled_exp1 - 1); 0.5 for a float probe, which never reads it
+    }
     SseArgs m;
     m.img = r.img;
     m.stride = (long)r.stride;
@@ -1410,10 +1418,13 @@ hipError_t launch_idct_sse(const IdctArgs &a, const SseArgs &m, hipStream_t stre
     return hipGetLastError();
 }
 
-hipError_t launch_idct_sse_v(const SseProbeTable *d_probes, size_t ngroups, DistortionResult *d_res, hipStream_t stream) {
+hipError_t launch_idct_sse_v(const SseProbeTable *d_probes, size_t ngroups, DistortionResult *d_res, hipStream_t stream, bool scaled_probes) {
     if (ngroups == 0) return hipSuccess;
     if (!d_probes || !d_res || ngroups > (size_t)kSseMaxProbes * kSseMaxGroups) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(idct_sse_kernel_v, dim3((unsigned)ngroups), dim3(kWavesPerWG * 64), 0, stream, d_probes, d_res);
+    if (scaled_probes)
+        hipLaunchKernelGGL(idct_sse_kernel_v<true>, dim3((unsigned)ngroups), dim3(kWavesPerWG * 64), 0, stream, d_probes, d_res);
+    else
+        hipLaunchKernelGGL(idct_sse_kernel_v<false>, dim3((unsigned)ngroups), dim3(kWavesPerWG * 64), 0, stream, d_probes, d_res);
     return hipGetLastError();
 }
 

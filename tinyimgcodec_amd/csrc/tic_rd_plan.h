@@ -37,7 +37,8 @@ struct SseProbeRec {
     int aligned8;                   // img and stride are multiples of 8 -> 8-byte row loads
     uint32_t first_group, ngroups;  // its workgroups: [first_group, first_group + ngroups) of the grid
     uint32_t result;                // the DistortionResult entry it adds into
-    uint32_t pad[3];
+    uint32_t scaled_exp1;           // 0: a probe of the float codec; e + 1: decode()'s scaled_dct branch at exponent e (consts of quality 50)
+    uint32_t pad[2];
 };
 static_assert(sizeof(SseProbeRec) == 80, "a record is 80 bytes");
 // A workgroup finds its probe by ONE load per lane and a ballot: lane l compares first_group[l] with the workgroup's index; entries behind
@@ -54,6 +55,7 @@ struct SseProbeIn {
     long long stride;
     int h, w;        // at least one block: h, w >= 1
     uint32_t result;
+    int scaled_exp = -1; // >= 0: a stream of the integer encoder at this exponent (its setting); consts must be those of quality 50
 };
 // Fills `t` for n probes (1..kSseMaxProbes) with at most max_groups (1..kSseMaxGroups) workgroups each.  *ngroups: the launch's grid.
 // False when n, the cap or a frame size is out of range.
@@ -65,7 +67,7 @@ inline bool fill_sse_probe_table(SseProbeTable *t, int n, const SseProbeIn *in, 
     }
     size_t grp = 0;
     for (int k = 0; k < n; k++) {
-        if (in[k].h < 1 || in[k].w < 1) return false;
+        if (in[k].h < 1 || in[k].w < 1 || in[k].scaled_exp > 62) return false;
         SseProbeRec &r = t->rec[k];
         r.coeffs = in[k].coeffs, r.img = in[k].img, r.consts = in[k].consts, r.stride = in[k].stride;
         r.h = in[k].h, r.w = in[k].w;
@@ -75,6 +77,7 @@ inline bool fill_sse_probe_table(SseProbeTable *t, int n, const SseProbeIn *in, 
         r.aligned8 = ((((uintptr_t)in[k].img) | (uintptr_t)in[k].stride) & 7) == 0;
         const size_t groups = sse_probe_groups((size_t)r.ntiles, max_groups);
         r.first_group = (uint32_t)grp, r.ngroups = (uint32_t)groups, r.result = in[k].result;
+        r.scaled_exp1 = in[k].scaled_exp >= 0 ? (uint32_t)in[k].scaled_exp + 1u : 0u;
         t->first_group[k] = (uint32_t)grp;
         grp += groups;
     }

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tic_scaled_frames.h"
+
 namespace tic {
 
 constexpr uint32_t kFlagScaled = 1u << 30; // header flag word of a scaled-DCT stream (img.c:185, codec.py:127-128)
@@ -23,5 +25,11 @@ struct ScaledArgs {
 
 // ev_start / ev_stop (both or neither): bound to the kernel's own dispatch packet, as launch_dctq's.
 hipError_t launch_fdctq_scaled(const ScaledArgs &a, hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+
+// The descriptor form: the `total_strips` strips of the frames d_table names (fill_scaled_table, tic_scaled_frames.h; complete on the device
+// before `stream` reaches the launch) in ONE launch, whatever their sizes and settings.  The grid is sized as above, kMaxGroups workgroups
+// at most; the test-hooks build lowers it to TIC_SCALED_V_GROUPS (tic_hooks.h).
+hipError_t launch_fdctq_scaled_v(const ScaledFrameTable *d_table, uint32_t total_strips, hipStream_t stream, hipEvent_t ev_start = nullptr,
+                                 hipEvent_t ev_stop = nullptr);
 
 } // namespace tic

@@ -19,7 +19,8 @@ reading raw pixels; header flag 1 << 30); --quality is then ignored, and height 
 and "PSNR: <dB>" as third and fourth lines; the same restrictions, and not together with --max-bytes.
 
 --also INPUT OUTPUT (repeatable) codes further files in the same call: all images, of whatever sizes, go through ONE compress_batch() at --quality,
-and the two lines are printed per file.  Plain --quality only."""
+and the two lines are printed per file.  With --scaled SETTING they go through ONE compress_batch_scaled() at that setting instead.  Not
+with --max-bytes or --min-psnr."""
 import argparse
 import sys
 
@@ -50,22 +51,25 @@ def main(argv=None):
     target.add_argument("--min-psnr", type=float, metavar="DB", help="write the smallest stream whose round trip reaches DB decibels")
     ap.add_argument("--min-quality", type=int, default=None, help="with --max-bytes / --min-psnr: lowest quality tried (default 1)")
     ap.add_argument("--max-quality", type=int, default=None, help="with --max-bytes / --min-psnr: highest quality tried (default 99)")
-    ap.add_argument("--also", nargs=2, action="append", metavar=("INPUT", "OUTPUT"), help="a further file, coded in the same compress_batch() call (repeatable)")
+    ap.add_argument("--also", nargs=2, action="append", metavar=("INPUT", "OUTPUT"), help="a further file, coded in the same compress_batch() / compress_batch_scaled() call (repeatable)")
     args = ap.parse_args(argv)
     searching = args.max_bytes is not None or args.min_psnr is not None
     if searching and (args.scaled or args.quality is not None):
         ap.error("--max-bytes / --min-psnr cannot be combined with --scaled or --quality")
     if not searching and (args.min_quality is not None or args.max_quality is not None):
         ap.error("--min-quality / --max-quality need --max-bytes or --min-psnr")
-    if args.also and (searching or args.scaled):
-        ap.error("--also takes a plain --quality only")
-    from . import compress, compress_batch, compress_scaled, compress_to_psnr, compress_to_size
+    if args.also and searching:
+        ap.error("--also takes a plain --quality or --scaled only")
+    from . import compress, compress_batch, compress_batch_scaled, compress_scaled, compress_to_psnr, compress_to_size
 
     im = load_gray(args.input, args.shape)
     if args.also:
         paths = [(args.input, args.output)] + [tuple(p) for p in args.also]
         images = [im] + [load_gray(p[0], args.shape) for p in paths[1:]]
-        outs = compress_batch(images, [50 if args.quality is None else args.quality] * len(images))
+        if args.scaled:
+            outs = compress_batch_scaled(images, args.scaled)
+        else:
+            outs = compress_batch(images, [50 if args.quality is None else args.quality] * len(images))
         for (_, dst), a, out in zip(paths, images, outs):
             print(f"{len(out)} bytes")
             print(f"Compression Ratio: {a.shape[1] * a.shape[0] / len(out)}:1")
