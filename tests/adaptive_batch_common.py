@@ -46,16 +46,17 @@ def check_stream(out, e):
 class ACall:
     """One tic_compress_batch_adaptive_v call (or, with coeffs=True, tic_entropy_encode_adaptive_batch: `frames` are then int16 [N, 64] arrays and
     `shapes` their (h, w)).  outs[i] is a buffer of caps[i] + 64 bytes filled with 0xAB in front of the call, so that a test sees what the call
-    wrote, behind the capacity it gave away too."""
+    wrote, behind the capacity it gave away too.  `inputs`: (pointers, strides) of frames that lie elsewhere than in `frames`
+    (batch_inputs_common.Arena.inputs()), which then only give the shapes."""
 
-    def __init__(self, ctx, frames, quals, caps, coeffs=False, shapes=None):
+    def __init__(self, ctx, frames, quals, caps, coeffs=False, shapes=None, inputs=None):
         L = N.load()
         n = self.n = len(frames)
         self.keep = [np.ascontiguousarray(f) for f in frames]
         shapes = [f.shape for f in self.keep] if shapes is None else shapes
         self.caps = list(caps)
         self.outs = [np.full(c + 64, 0xAB, np.uint8) for c in self.caps]
-        inp = (C.c_void_p * n)(*[f.ctypes.data for f in self.keep])
+        inp = (C.c_void_p * n)(*([f.ctypes.data for f in self.keep] if inputs is None else [p or None for p in inputs[0]]))
         hs = (C.c_int * n)(*[s[0] for s in shapes])
         ws = (C.c_int * n)(*[s[1] for s in shapes])
         qa = (C.c_int * n)(*quals)
@@ -65,7 +66,7 @@ class ACall:
         if coeffs:
             self.rc = L.tic_entropy_encode_adaptive_batch(ctx.handle, inp, n, hs, ws, qa, outp, capa, self.lens)
         else:
-            strides = (C.c_ssize_t * n)(*[max(s[1], 1) for s in shapes])
+            strides = (C.c_ssize_t * n)(*([max(s[1], 1) for s in shapes] if inputs is None else inputs[1]))
             self.rc = L.tic_compress_batch_adaptive_v(ctx.handle, inp, n, hs, ws, strides, qa, outp, capa, self.lens)
         self.error = L.tic_last_error(ctx.handle).decode()
 

@@ -40,9 +40,10 @@ def small_frames():
 class VCall:
     """One tic_compress_batch_v call.  outs[i] is a buffer of caps[i] bytes filled with 0xAB in front of the call (so that a test sees what
     the call wrote); `null_images`: frames whose pixel pointer is null while their sizes stay; `caps`, `strides` override what the frames give;
-    `null_arrays`: arguments passed as null pointers; `n`: the count passed, if not len(frames)."""
+    `null_arrays`: arguments passed as null pointers; `n`: the count passed, if not len(frames); `inputs`: (pointers, strides) of frames that lie
+    elsewhere than in `frames` (batch_inputs_common.Arena.inputs(); a pointer of 0 is passed as null), which then only give the shapes."""
 
-    def __init__(self, ctx, frames, quals, caps=None, strides=None, null_arrays=(), null_images=(), n=None):
+    def __init__(self, ctx, frames, quals, caps=None, strides=None, null_arrays=(), null_images=(), n=None, inputs=None):
         L = self.L = N.load()
         count, n = n, len(frames)
         self.n = n
@@ -52,10 +53,11 @@ class VCall:
         self.caps = list(self.bounds if caps is None else caps)
         self.outs = [np.full(max(c, 1), 0xAB, np.uint8) for c in self.caps]
         arr = {
-            "images": (C.c_void_p * n)(*[None if i in null_images or f.size == 0 else f.ctypes.data for i, f in enumerate(self.keep)]),
+            "images": (C.c_void_p * n)(*[None if i in null_images or f.size == 0 else f.ctypes.data for i, f in enumerate(self.keep)])
+            if inputs is None else (C.c_void_p * n)(*[p or None for p in inputs[0]]),
             "hs": (C.c_int * n)(*[s[0] for s in shapes]),
             "ws": (C.c_int * n)(*[s[1] for s in shapes]),
-            "strides": (C.c_ssize_t * n)(*(strides if strides is not None else [max(s[1], 1) for s in shapes])),
+            "strides": (C.c_ssize_t * n)(*(strides if strides is not None else inputs[1] if inputs is not None else [max(s[1], 1) for s in shapes])),
             "quals": (C.c_int * n)(*quals),
             "outs": (C.c_void_p * n)(*[o.ctypes.data for o in self.outs]),
             "caps": (C.c_size_t * n)(*self.caps),

@@ -20,19 +20,21 @@ def small_frames():
     return [rand_frame(100 + i, h, w) for i, (h, w) in enumerate(SMALL_SHAPES)]
 
 
-def frame_arrays(frames):
+def frame_arrays(frames, inputs=None):
+    """`inputs`: (pointers, strides) of frames that lie elsewhere than in `frames` (batch_inputs_common.Arena.inputs(); a pointer of 0 is
+    passed as null), which then only give the shapes."""
     n = len(frames)
     frames = [np.ascontiguousarray(f) for f in frames]
-    inp = (C.c_void_p * n)(*[f.ctypes.data if f.size else None for f in frames])
+    inp = (C.c_void_p * n)(*([f.ctypes.data if f.size else None for f in frames] if inputs is None else [p or None for p in inputs[0]]))
     hs = (C.c_int * n)(*[f.shape[0] for f in frames])
     ws = (C.c_int * n)(*[f.shape[1] for f in frames])
-    strides = (C.c_ssize_t * n)(*[max(f.shape[1], 1) for f in frames])
+    strides = (C.c_ssize_t * n)(*([max(f.shape[1], 1) for f in frames] if inputs is None else inputs[1]))
     return frames, inp, hs, ws, strides
 
 
-def sizes_v(L, handle, frames, qs):
+def sizes_v(L, handle, frames, qs, inputs=None):
     """tic_stream_sizes_v -> (rc, int64 array (n, nq))."""
-    keep, inp, hs, ws, strides = frame_arrays(frames)
+    keep, inp, hs, ws, strides = frame_arrays(frames, inputs)
     qarr = (C.c_int * len(qs))(*qs)
     out = np.full((len(frames), len(qs)), -7, np.int64)
     rc = L.tic_stream_sizes_v(handle, inp, len(frames), hs, ws, strides, qarr, len(qs), out.ctypes.data)
@@ -50,9 +52,9 @@ class SearchCall:
     """One tic_compress_batch_to_size: every output a sentinel-filled buffer of caps[i] + 8 bytes.  run() -> rc; then status, lens, quals,
     stream(i), tail_intact(i) (the bytes behind the stream, or the whole buffer of a failed frame)."""
 
-    def __init__(self, L, handle, frames, budgets, qmin=1, qmax=99, caps=None):
+    def __init__(self, L, handle, frames, budgets, qmin=1, qmax=99, caps=None, inputs=None):
         self.L, self.handle, self.n = L, handle, len(frames)
-        self.keep, self.inp, self.hs, self.ws, self.strides = frame_arrays(frames)
+        self.keep, self.inp, self.hs, self.ws, self.strides = frame_arrays(frames, inputs)
         n = self.n
         caps = [L.tic_compress_bound(f.shape[0], f.shape[1]) for f in frames] if caps is None else list(caps)
         self.bufs = [np.full(c + 8, SENTINEL, np.uint8) for c in caps]

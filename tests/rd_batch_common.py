@@ -30,13 +30,14 @@ def bind(path):
     return L
 
 
-def rd_v(L, handle, frame_list, qs):
-    """tic_rd_points_v -> (rc, sizes, sse, wrapped), (n, nq) each, filled with markers the call must overwrite."""
-    keep, inp, hs, ws, strides = R.frame_arrays(frame_list)
+def rd_v(L, handle, frame_list, qs, inputs=None, scaled=False):
+    """tic_rd_points_v (scaled: tic_rd_points_scaled_v, `qs` its settings) -> (rc, sizes, sse, wrapped), (n, nq) each, filled with markers the
+    call must overwrite."""
+    keep, inp, hs, ws, strides = R.frame_arrays(frame_list, inputs)
     qarr = (C.c_int * len(qs))(*qs)
     shape = (len(frame_list), len(qs))
     sizes, sse, wrapped = np.full(shape, -7, np.int64), np.full(shape, 7, np.uint64), np.full(shape, 7, np.uint64)
-    rc = L.tic_rd_points_v(handle, inp, len(frame_list), hs, ws, strides, qarr, len(qs), sizes.ctypes.data, sse.ctypes.data, wrapped.ctypes.data)
+    rc = (L.tic_rd_points_scaled_v if scaled else L.tic_rd_points_v)(handle, inp, len(frame_list), hs, ws, strides, qarr, len(qs), sizes.ctypes.data, sse.ctypes.data, wrapped.ctypes.data)
     return rc, sizes, sse, wrapped
 
 
@@ -62,9 +63,9 @@ class PsnrCall:
     """One tic_compress_batch_to_psnr: every output a sentinel-filled buffer of caps[i] + 8 bytes.  run() -> rc; then status, lens, quals,
     sse, stream(i), tail_intact(i) (the bytes behind the stream, or the whole buffer of a failed frame)."""
 
-    def __init__(self, L, handle, frame_list, bounds, qmin=1, qmax=99, caps=None):
+    def __init__(self, L, handle, frame_list, bounds, qmin=1, qmax=99, caps=None, inputs=None):
         self.L, self.handle, self.n = L, handle, len(frame_list)
-        self.keep, self.inp, self.hs, self.ws, self.strides = R.frame_arrays(frame_list)
+        self.keep, self.inp, self.hs, self.ws, self.strides = R.frame_arrays(frame_list, inputs)
         n = self.n
         caps = [L.tic_compress_bound(f.shape[0], f.shape[1]) for f in frame_list] if caps is None else list(caps)
         self.bufs = [np.full(c + 8, SENTINEL, np.uint8) for c in caps]

@@ -67,9 +67,11 @@ def check_array(npz, man, key, suffix, sha_key, got):
 class SCall:
     """One tic_compress_batch_scaled_v call.  outs[i] is a buffer of caps[i] bytes with 64 sentinel bytes behind it, all filled with the
     sentinel in front of the call; `null_images`: frames whose pixel pointer is null while their sizes stay; `caps`, `strides`, `hs`, `ws`
-    override what the frames give; `null_arrays`: arguments passed as null pointers; `n`: the count passed, if not len(frames)."""
+    override what the frames give; `null_arrays`: arguments passed as null pointers; `n`: the count passed, if not len(frames); `inputs`: (pointers, strides) of
+    frames that lie elsewhere than in `frames` (batch_inputs_common.Arena.inputs(); a pointer of 0 is passed as null), which then only
+    give the shapes."""
 
-    def __init__(self, ctx, frames, qfs, null_images=(), caps=None, strides=None, hs=None, ws=None, null_arrays=(), n=None):
+    def __init__(self, ctx, frames, qfs, null_images=(), caps=None, strides=None, hs=None, ws=None, null_arrays=(), n=None, inputs=None):
         L = N.load()
         self.frames = [np.ascontiguousarray(f) for f in frames]
         m = len(frames)
@@ -77,7 +79,10 @@ class SCall:
         ws = [f.shape[1] for f in frames] if ws is None else ws
         self.caps = [L.tic_compress_scaled_bound(h, w) if h >= 0 and w >= 0 else 64 for h, w in zip(hs, ws)] if caps is None else list(caps)
         self.bufs = [np.full(c + 64, SENTINEL, np.uint8) for c in self.caps]
-        arr = {"images": (C.c_void_p * m)(*[None if (i in null_images or f.size == 0) else f.ctypes.data for i, f in enumerate(self.frames)]),
+        if inputs is not None and strides is None:
+            strides = inputs[1]
+        arr = {"images": (C.c_void_p * m)(*([None if (i in null_images or f.size == 0) else f.ctypes.data for i, f in enumerate(self.frames)]
+                                            if inputs is None else [p or None for p in inputs[0]])),
                "hs": (C.c_int * m)(*hs), "ws": (C.c_int * m)(*ws),
                "strides": (C.c_ssize_t * m)(*([max(w, 1) for w in ws] if strides is None else strides)), "quals": (C.c_int * m)(*qfs),
                "outs": (C.c_void_p * m)(*[b.ctypes.data for b in self.bufs]), "caps": (C.c_size_t * m)(*self.caps), "lens": (C.c_size_t * m)()}

@@ -2917,6 +2917,7 @@ int tic_compress_batch_v(tic_ctx *ctx, const uint8_t *const *images, int n, cons
             // every later one (qualities ascend) then run the 8-lane kernel, the chunks in front passed as they were - one more run settles it.
             ctx->ent_lane_max_quality = retry_quality - 1;
             retry_quality = 0;
+            ctx->last_batch_direct_frames = ctx->last_batch_staged_frames = 0; // (every chunk is uploaded again: the route's figures are the second run's)
             rc = batch_mixed_pipeline(ctx, p, io, &retry_quality, false, &ctx->last_vbatch_launches);
         }
         if (rc) return rc == kRetryEightLanes ? set_err(ctx, TIC_E_HIP, "mixed batch: the 8-lane packing kernel refused a block") : rc;
