@@ -119,6 +119,11 @@ int tic_memcpy_h2d(tic_ctx *ctx, void *dst, const void *src, size_t bytes);
 int tic_memcpy_d2h(tic_ctx *ctx, void *dst, const void *src, size_t bytes);
 int tic_memset_dev(tic_ctx *ctx, void *dst, int value, size_t bytes);
 int tic_sync(tic_ctx *ctx);
+/* Test hook of the hooks build (the shipped library returns TIC_E_ARG and touches nothing): waits for the context's streams and fills
+ * every buffer the context holds as scratch - any content is legal when a call begins - with `byte` (0..255); buffers that carry an
+ * invariant between calls are left alone; tic_last_error then says how many buffers and bytes it filled and how many it kept.
+ * TIC_E_BUSY while a tic_compress_dev_async or tic_decompress_dev_async ticket is open. */
+int tic_test_poison(tic_ctx *ctx, int byte);
 int tic_dctq_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, int quality,
                  void *d_coeffs_zz, int variant);
 /* Batch form: `nframes` equally sized frames in ONE launch (grid row per frame).  Frame f starts at

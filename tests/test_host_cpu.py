@@ -32,7 +32,8 @@ def test_library_loads_and_exports_every_declared_symbol():
         # variable name; the test-hooks build of the same sources says what it is
         assert lib.tic_build_has_test_hooks() == hooks
         blob = open(path, "rb").read()
-        for var in (b"TIC_SCHED", b"TIC_SPLIT", b"TIC_DECODE_HOST", b"TIC_DECODE_SERIAL", b"TIC_COMM_FORCE_RCCL", b"TIC_BAND_BYTES", b"TIC_DBATCH_WORK_CAP", b"TIC_TEST_HOOKS"):
+        for var in (b"TIC_SCHED", b"TIC_SPLIT", b"TIC_DECODE_HOST", b"TIC_DECODE_SERIAL", b"TIC_COMM_FORCE_RCCL", b"TIC_BAND_BYTES", b"TIC_DBATCH_WORK_CAP", b"TIC_POISON", b"TIC_DEC_EPOCH",
+                    b"TIC_TEST_HOOKS"):
             assert (var in blob) == bool(hooks) or var == b"TIC_TEST_HOOKS", (os.path.basename(path), var)
         assert b"TIC_TEST_HOOKS" not in blob  # (neither build reads that one: _native.py picks the build by it)
     assert declared == set(N.SIGNATURES), declared ^ set(N.SIGNATURES)

@@ -91,8 +91,23 @@ struct Slot {
     int first = 0, count = 0; // frames [first, first+count) are in flight in this slot
     int pending = 0;          // pieces of the chunk's work not yet finished (SlotGate); 0 = the slot is free
     size_t rb_row = 0;        // row pitch of the streams read back into pin_out (0: they went straight to the caller)
-    void release();           // frees everything the slot owns
+    void release(tic_ctx *ctx); // frees everything the slot owns
 };
+// What a context keeps between calls.  Hooks build only: every buffer a context owns is recorded when it is
+// allocated and dropped when it is freed, as SCRATCH - any content is legal when a public call begins - or STATE - it carries an
+// invariant from one call to the next.  TIC_POISON and tic_test_poison fill the scratch ones; nothing ever fills a state buffer
+// (a buffer that a kernel spin-waits on, the decoder's look-back words, is state by that rule alone).
+enum BufKind { kBufDev, kBufPinned, kBufMapped };
+enum BufClass { kBufScratch, kBufState };
+struct BufRec {
+    void *p;
+    size_t bytes;
+    int kind, cls;
+    const char *name;
+};
+static const char *const kDecWsNames[3] = {"dec_ws.work", "dec_ws.desc", "dec_ws.status"};
+static const char *const kDecSlotWsNames[3] = {"dec_slot.work", "dec_slot.desc", "dec_slot.status"};
+static const char *const kDecBatchWsNames[3] = {"dbat.work", "dbat.desc", "dbat.status"};
 // Workspace of the device Huffman decoder (tic_entropy_dec_gpu.hip), one per user: the single-frame calls, every asynchronous decode slot
 // and the batch.  Nothing of an earlier run may be in flight when it grows or a run begins.
 struct DecWorkspace {
@@ -100,6 +115,7 @@ struct DecWorkspace {
     size_t work_bytes = 0;
     unsigned long long *desc = nullptr; // look-back words of the decoder's scans: an array of their own, zero or stamped with a past epoch
     size_t desc_words = 0;
+    const char *const *names = kDecWsNames; // registry names of work, desc and status (buf_add): one set per user of a workspace
     uint32_t epoch = 0;                 // runs on these words (the single-launch scans tell their words by it)
     DecStatus *h_status = nullptr, *d_status = nullptr; // host-mapped, one entry per frame of a run
     size_t status_bytes = 0;
@@ -107,7 +123,9 @@ struct DecWorkspace {
     // grow: zeroed, epoch 0) and `status` status entries (`status_alloc`)
     int grow(tic_ctx *ctx, size_t work_need, size_t work_alloc, size_t desc_need, size_t status, size_t status_alloc);
     int begin(tic_ctx *ctx, hipStream_t stream, size_t status); // a run of `status` frames on `stream`
-    void release();
+    void release(tic_ctx *ctx);
+    DecWorkspace() = default;
+    explicit DecWorkspace(const char *const *registry_names) : names(registry_names) {}
 };
 } // namespace
 
@@ -188,7 +206,7 @@ struct tic_ctx {
         long long ticket = -1;
         hipStream_t stream = nullptr;
         hipEvent_t done = nullptr;
-        DecWorkspace ws;
+        DecWorkspace ws{kDecSlotWsNames};
         bool launched = false;   // false: the call ran synchronously (no guess to launch on): rc / h / w are its outcome
         int rc = TIC_OK, h = 0, w = 0;
         uint8_t head[16] = {0};  // the header the launch guessed
@@ -222,7 +240,7 @@ struct tic_ctx {
         size_t in_cap = 0;
         uint8_t *d_pix = nullptr, *h_pix = nullptr;
         size_t pix_cap = 0, hpix_cap = 0;
-        DecWorkspace ws;
+        DecWorkspace ws{kDecBatchWsNames};
     } dbat;
     int last_dbatch_frames = 0, last_dbatch_fallback = 0, last_dbatch_chunks = 0, last_dbatch_direct = 0;
     int last_dbatch_range = 0;                                 // tic_last_decompress_batch_work: the last chunk handed to the batch launcher -
@@ -259,6 +277,7 @@ struct tic_ctx {
     char pci[32] = {0};
     std::string err;
     char arch[128] = {0};
+    std::vector<BufRec> bufs; // hooks build: every buffer the context owns (buf_add, buf_drop)
     // per-image Huffman tables (tic_compress_adaptive): statistics, the frame's table and an error word in one allocation, the packing
     // workspace and the stream, kept across calls
     AdaptStats *d_adapt_stats = nullptr;
@@ -384,75 +403,127 @@ static int set_err(tic_ctx *ctx, int code, const char *fmt, ...) {
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The registry of the hooks build (BufRec above; folds away in the shipped library, where test_hooks_enabled() is a constant).
+// buf_fill: one byte value into a whole buffer, device memory by hipMemset - waited for, the context's streams do not wait for the
+// null stream by themselves - and pinned or host-mapped memory by the host.
+static hipError_t buf_fill(const BufRec &r, int byte) {
+    if (r.kind != kBufDev) {
+        memset(r.p, byte, r.bytes);
+        return hipSuccess;
+    }
+    const hipError_t e = hipMemset(r.p, byte, r.bytes);
+    return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
+// A buffer the context now owns.  Under TIC_POISON=<byte> a scratch buffer is filled with the byte at once, before anything the
+// allocation site clears itself.
+static hipError_t buf_add(tic_ctx *ctx, void *p, size_t bytes, int kind, int cls, const char *name) {
+    if (!test_hooks_enabled() || !ctx || !p) return hipSuccess;
+    const BufRec r = {p, bytes, kind, cls, name};
+    ctx->bufs.push_back(r);
+    const char *e = test_hook("TIC_POISON");
+    return e && cls == kBufScratch ? buf_fill(r, (int)(strtol(e, nullptr, 0) & 255)) : hipSuccess;
+}
+// ... and one it is about to free
+static void buf_drop(tic_ctx *ctx, const void *p) {
+    if (!test_hooks_enabled() || !ctx || !p) return;
+    for (size_t i = 0; i < ctx->bufs.size(); i++)
+        if (ctx->bufs[i].p == p) {
+            ctx->bufs.erase(ctx->bufs.begin() + (ptrdiff_t)i);
+            return;
+        }
+}
+// Allocation sites outside the grow helpers: `call` allocates `p`, which is then recorded (BUF_NEW: contexts that exist, through
+// HIPCHK).
+#define BUF_NEW(ctx, call, p, bytes, kind, cls, name)               \
+    do {                                                            \
+        HIPCHK(ctx, call);                                          \
+        HIPCHK(ctx, buf_add(ctx, p, bytes, kind, cls, name));       \
+    } while (0)
+
 // Buffers that grow on demand, one helper per kind of memory: when `need` bytes exceed `cap`, the buffer is freed and one of `alloc`
 // bytes (0: `need`) takes its place.  Nothing may be in flight on the old buffer.  A failed allocation leaves it null and `cap` 0.
-template <class T> static int grow_dev(tic_ctx *ctx, T *&p, size_t &cap, size_t need, size_t alloc = 0) {
+// `name` and `cls` are the buffer's entry in the registry above.
+template <class T> static int grow_dev(tic_ctx *ctx, const char *name, T *&p, size_t &cap, size_t need, size_t alloc = 0, int cls = kBufScratch) {
     if (need <= cap) return TIC_OK;
+    buf_drop(ctx, p);
     if (p) HIPCHK(ctx, hipFree(p));
     p = nullptr, cap = 0;
     alloc = alloc ? alloc : need;
     HIPCHK(ctx, hipMalloc((void **)&p, alloc));
     cap = alloc;
+    HIPCHK(ctx, buf_add(ctx, p, alloc, kBufDev, cls, name));
     return TIC_OK;
 }
-template <class T> static int grow_pinned(tic_ctx *ctx, T *&p, size_t &cap, size_t need, size_t alloc = 0) {
+template <class T> static int grow_pinned(tic_ctx *ctx, const char *name, T *&p, size_t &cap, size_t need, size_t alloc = 0) {
     if (need <= cap) return TIC_OK;
+    buf_drop(ctx, p);
     if (p) HIPCHK(ctx, hipHostFree(p));
     p = nullptr, cap = 0;
     alloc = alloc ? alloc : need;
     HIPCHK(ctx, hipHostMalloc((void **)&p, alloc, hipHostMallocDefault));
     cap = alloc;
+    HIPCHK(ctx, buf_add(ctx, p, alloc, kBufPinned, kBufScratch, name));
     return TIC_OK;
 }
 // ... host-mapped: `h` for the host, `d` for the kernels; coherent, because the host reads it behind a polled or drained stream
-template <class T> static int grow_mapped(tic_ctx *ctx, T *&h, T *&d, size_t &cap, size_t need, size_t alloc = 0) {
+template <class T> static int grow_mapped(tic_ctx *ctx, const char *name, T *&h, T *&d, size_t &cap, size_t need, size_t alloc = 0) {
     if (need <= cap) return TIC_OK;
+    buf_drop(ctx, h);
     if (h) HIPCHK(ctx, hipHostFree(h));
     h = d = nullptr, cap = 0;
     alloc = alloc ? alloc : need;
     HIPCHK(ctx, hipHostMalloc((void **)&h, alloc, hipHostMallocMapped | hipHostMallocCoherent));
     HIPCHK(ctx, hipHostGetDevicePointer((void **)&d, h, 0));
     cap = alloc;
+    HIPCHK(ctx, buf_add(ctx, h, alloc, kBufMapped, kBufScratch, name));
     return TIC_OK;
 }
 
 int DecWorkspace::grow(tic_ctx *ctx, size_t work_need, size_t work_alloc, size_t desc_need, size_t status, size_t status_alloc) {
-    int rc = grow_dev(ctx, work, work_bytes, work_need, work_alloc);
+    int rc = grow_dev(ctx, names[0], work, work_bytes, work_need, work_alloc);
     if (rc) return rc;
     if (desc_need > desc_words) {
         const size_t dw = desc_need < 8192 ? 8192 : 2 * desc_need;
         size_t bytes = desc_words * 8;
         desc_words = 0; // (counted only once the new words are zero)
-        rc = grow_dev(ctx, desc, bytes, desc_need * 8, dw * 8);
+        rc = grow_dev(ctx, names[1], desc, bytes, desc_need * 8, dw * 8, kBufState); // (state: wave_lookback spins on these words)
         if (rc) return rc;
         HIPCHK(ctx, hipMemset(desc, 0, dw * 8));
         desc_words = dw;
         epoch = 0;
     }
-    return grow_mapped(ctx, h_status, d_status, status_bytes, status * sizeof(DecStatus), status_alloc * sizeof(DecStatus));
+    return grow_mapped(ctx, names[2], h_status, d_status, status_bytes, status * sizeof(DecStatus), status_alloc * sizeof(DecStatus));
 }
 
 int DecWorkspace::begin(tic_ctx *ctx, hipStream_t stream, size_t status) {
+    if (const char *e = test_hook("TIC_DEC_EPOCH")) { // (tests: the wrap below within a few calls; forwards only - no word carries a later epoch)
+        const unsigned long v = strtoul(e, nullptr, 0);
+        if (v > epoch && v < (1ul << 22)) epoch = (uint32_t)v;
+    }
     if (++epoch >= (1u << 22)) { // (the scans carry 24 bits of 2 x epoch: start over on clean words long before a value could recur)
         HIPCHK(ctx, hipMemsetAsync(desc, 0, desc_words * 8, stream));
         epoch = 1;
     }
     memset(h_status, 0, status * sizeof(DecStatus)); // (host-mapped; nothing of an earlier run is in flight)
+    if (test_hooks_enabled()) set_err(ctx, TIC_OK, "decoder run on %s: epoch %u", names[0], epoch); // (hooks build: where a test can read it, tic_last_error)
     return TIC_OK;
 }
 
-void DecWorkspace::release() {
+void DecWorkspace::release(tic_ctx *ctx) {
+    for (const void *p : {(const void *)work, (const void *)desc, (const void *)h_status}) buf_drop(ctx, p);
     if (work) (void)hipFree(work);
     if (desc) (void)hipFree(desc);
     if (h_status) (void)hipHostFree(h_status);
+    const char *const *keep = names;
     *this = DecWorkspace();
+    names = keep;
 }
 
-void Slot::release() {
+void Slot::release(tic_ctx *ctx) {
     for (void *p : {(void *)pin_in, (void *)pin_out, (void *)h_lens, (void *)h_err, (void *)h_frames, (void *)h_rb_off, (void *)h_adapt, (void *)h_sframes})
-        if (p) (void)hipHostFree(p);
+        if (p) buf_drop(ctx, p), (void)hipHostFree(p);
     for (void *p : {d_img, d_coef, d_work, (void *)d_lens, (void *)d_err, d_streams, (void *)d_frames, (void *)d_adapt, (void *)d_sframes})
-        if (p) (void)hipFree(p);
+        if (p) buf_drop(ctx, p), (void)hipFree(p);
     for (hipEvent_t e : {done, rb_done})
         if (e) (void)hipEventDestroy(e);
     *this = Slot();
@@ -488,7 +559,7 @@ void tic_destroy(tic_ctx *ctx) {
             (void)hipStreamSynchronize(s);
             (void)hipStreamDestroy(s);
         }
-    for (auto &sl : ctx->bslots) sl.release();
+    for (auto &sl : ctx->bslots) sl.release(ctx);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->d_img) (void)hipFree(ctx->d_img);
@@ -517,20 +588,20 @@ void tic_destroy(tic_ctx *ctx) {
     if (ctx->d_stream_buf) (void)hipFree(ctx->d_stream_buf);
     if (ctx->d_dc32) (void)hipFree(ctx->d_dc32);
     if (ctx->d_dec_luts) (void)hipFree(ctx->d_dec_luts);
-    ctx->dec_ws.release();
+    ctx->dec_ws.release(ctx);
     if (ctx->h_dec_tail) (void)hipHostFree(ctx->h_dec_tail);
     if (ctx->h_small) (void)hipHostFree(ctx->h_small);
     for (auto &sl : ctx->dec_slots) {
         if (sl.stream) (void)hipStreamSynchronize(sl.stream);
         if (sl.done) (void)hipEventDestroy(sl.done);
-        sl.ws.release();
+        sl.ws.release(ctx);
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
     }
     if (ctx->dbat.h_in) (void)hipHostFree(ctx->dbat.h_in);
     if (ctx->dbat.d_in) (void)hipFree(ctx->dbat.d_in);
     if (ctx->dbat.d_pix) (void)hipFree(ctx->dbat.d_pix);
     if (ctx->dbat.h_pix) (void)hipHostFree(ctx->dbat.h_pix);
-    ctx->dbat.ws.release();
+    ctx->dbat.ws.release(ctx);
     if (ctx->dec_order) (void)hipEventDestroy(ctx->dec_order);
     if (ctx->d_adapt_stats) (void)hipFree(ctx->d_adapt_stats); // table and error word live in the same block
     if (ctx->d_adapt_work) (void)hipFree(ctx->d_adapt_work);
@@ -587,22 +658,27 @@ static int create_impl(tic_ctx *ctx, int device) {
     for (int q = 1; q <= 99; q++) build_consts(q, &all[q]);
     CK(hipMalloc((void **)&ctx->d_consts, all.size() * sizeof(DctqConsts)));
     CK(hipMemcpy(ctx->d_consts, all.data(), all.size() * sizeof(DctqConsts), hipMemcpyHostToDevice));
+    CK(buf_add(ctx, ctx->d_consts, all.size() * sizeof(DctqConsts), kBufDev, kBufState, "d_consts"));
     {
         HuffDev hd;
         build_huff_dev(&hd);
         CK(hipMalloc((void **)&ctx->d_huff, sizeof(HuffDev)));
         CK(hipMemcpy(ctx->d_huff, &hd, sizeof(HuffDev), hipMemcpyHostToDevice));
+        CK(buf_add(ctx, ctx->d_huff, sizeof(HuffDev), kBufDev, kBufState, "d_huff"));
         // one 32-byte status block: payload bits [2] of the device entropy stage, then its error flags [2]
         CK(hipMalloc((void **)&ctx->d_total_bits, 32));
         CK(hipMemset(ctx->d_total_bits, 0, 32));
+        CK(buf_add(ctx, ctx->d_total_bits, 32, kBufDev, kBufState, "d_total_bits"));
         ctx->d_err = reinterpret_cast<int *>(ctx->d_total_bits + 2);
         // the stage's last kernel writes {payload bits, error} straight into pinned host memory: no copy behind it
         CK(hipHostMalloc((void **)&ctx->h_stat, 64 + kAsyncSlots * 16, hipHostMallocMapped | hipHostMallocCoherent));
         memset(ctx->h_stat, 0, 64 + kAsyncSlots * 16);
+        CK(buf_add(ctx, ctx->h_stat, 64 + kAsyncSlots * 16, kBufMapped, kBufState, "h_stat"));
         CK(hipHostGetDevicePointer((void **)&ctx->d_stat, ctx->h_stat, 0));
     }
     CK(hipMalloc((void **)&ctx->d_fallback, 4 * sizeof(unsigned long long)));
     CK(hipMemset(ctx->d_fallback, 0, 4 * sizeof(unsigned long long)));
+    CK(buf_add(ctx, ctx->d_fallback, 4 * sizeof(unsigned long long), kBufDev, kBufState, "d_fallback"));
 #undef CK
     return TIC_OK;
 }
@@ -759,6 +835,34 @@ int tic_sync(tic_ctx *ctx) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (auto &sl : ctx->dec_slots) // (asynchronous decodes run on streams of their own)
         if (sl.stream) HIPCHK(ctx, hipStreamSynchronize(sl.stream));
+    return TIC_OK;
+}
+
+// Test hook (hooks build only; the shipped library returns TIC_E_ARG and touches nothing): fills every scratch buffer of the context's
+// registry with `byte`, behind everything its streams hold.  TIC_E_BUSY while a compress or decompress ticket is open - a frame in
+// flight owns its buffers.  State buffers are never touched.
+int tic_test_poison(tic_ctx *ctx, int byte) {
+    TIC_LOCK(ctx);
+    if (!test_hooks_enabled() || !ctx || byte < 0 || byte > 255) return TIC_E_ARG;
+    if (ctx->async_open > 0) return TIC_E_BUSY;
+    for (const auto &sl : ctx->dec_slots)
+        if (sl.ticket >= 0) return TIC_E_BUSY;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    for (hipStream_t s : {ctx->stream, ctx->bstream[0], ctx->bstream[1], ctx->rstream, ctx->lanes[0].stream, ctx->lanes[1].stream})
+        if (s) HIPCHK(ctx, hipStreamSynchronize(s));
+    for (auto &sl : ctx->dec_slots)
+        if (sl.stream) HIPCHK(ctx, hipStreamSynchronize(sl.stream));
+    size_t filled = 0, bytes = 0, kept = 0;
+    for (const BufRec &r : ctx->bufs) {
+        if (r.cls != kBufScratch) {
+            kept++;
+            continue;
+        }
+        HIPCHK(ctx, buf_fill(r, byte));
+        filled++, bytes += r.bytes;
+    }
+    // (what it did, where a test can read it: tic_last_error)
+    set_err(ctx, TIC_OK, "tic_test_poison: %zu scratch buffers and %zu bytes filled with 0x%02x, %zu state buffers kept", filled, bytes, byte, kept);
     return TIC_OK;
 }
 
@@ -1036,11 +1140,11 @@ int tic_last_fallback_blocks(tic_ctx *ctx, unsigned long long *count) {
 
 constexpr size_t kDecHostPixBytes = 1u << 20; // tic_decompress: images of at most this many bytes leave through tic_ctx::h_small as well
 constexpr size_t kSmallHostBytes = 2u << 20; // tic_compress: frames whose stream bound is at most this go through tic_ctx::h_small
-static int ensure_small(tic_ctx *ctx, size_t bytes) { return grow_mapped(ctx, ctx->h_small, ctx->d_small, ctx->small_cap, bytes); }
+static int ensure_small(tic_ctx *ctx, size_t bytes) { return grow_mapped(ctx, "h_small", ctx->h_small, ctx->d_small, ctx->small_cap, bytes); }
 
 static int ensure_scratch(tic_ctx *ctx, size_t img_bytes, size_t coef_bytes) {
-    const int rc = grow_dev(ctx, ctx->d_img, ctx->d_img_cap, img_bytes);
-    return rc ? rc : grow_dev(ctx, ctx->d_coef, ctx->d_coef_cap, coef_bytes);
+    const int rc = grow_dev(ctx, "d_img", ctx->d_img, ctx->d_img_cap, img_bytes);
+    return rc ? rc : grow_dev(ctx, "d_coef", ctx->d_coef, ctx->d_coef_cap, coef_bytes);
 }
 
 // Every host-image entry point brings its frame to the device here: the n blocks' uint8 pixels into the context's scratch image, rows
@@ -1218,7 +1322,7 @@ static int entropy_encode_dev_impl(tic_ctx *ctx, const void *d_coeffs_zz, int h,
         return TIC_OK;
     }
     if (!d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "null coefficient pointer");
-    rc = grow_dev(ctx, ctx->d_ent_work, ctx->ent_work_bytes, entropy_fused_work_bytes(n));
+    rc = grow_dev(ctx, "d_ent_work", ctx->d_ent_work, ctx->ent_work_bytes, entropy_fused_work_bytes(n));
     if (rc) return rc;
     StreamStatus st = {0, 0};
     for (int attempt = 0; attempt < 2; attempt++) {
@@ -1259,7 +1363,7 @@ static int ensure_lane(tic_ctx *ctx, tic_ctx::AsyncLane &ln, size_t n) {
         HIPCHK(ctx, hipEventCreateWithFlags(&ln.packed, hipEventDisableTiming));
         HIPCHK(ctx, hipEventCreateWithFlags(&ln.placed[0], hipEventDisableTiming));
         HIPCHK(ctx, hipEventCreateWithFlags(&ln.placed[1], hipEventDisableTiming));
-        HIPCHK(ctx, hipMalloc((void **)&ln.d_err, 4 * sizeof(int)));
+        BUF_NEW(ctx, hipMalloc((void **)&ln.d_err, 4 * sizeof(int)), ln.d_err, 4 * sizeof(int), kBufDev, kBufState, "lane.d_err");
         HIPCHK(ctx, hipMemset(ln.d_err, 0, 4 * sizeof(int)));
     }
     if (!ctx->lane_order) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->lane_order, hipEventDisableTiming));
@@ -1268,16 +1372,17 @@ static int ensure_lane(tic_ctx *ctx, tic_ctx::AsyncLane &ln, size_t n) {
     // (grows only between bursts of one geometry: frames in flight still use the old buffers)
     HIPCHK(ctx, hipStreamSynchronize(ln.stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const int rc = grow_dev(ctx, ln.d_coef, ln.coef_cap, coef_bytes);
+    const int rc = grow_dev(ctx, "lane.d_coef", ln.d_coef, ln.coef_cap, coef_bytes);
     if (rc) return rc;
     if (wb > ln.work_bytes) {
         for (int k = 0; k < 2; k++) {
+            buf_drop(ctx, ln.d_work[k]);
             if (ln.d_work[k]) HIPCHK(ctx, hipFree(ln.d_work[k]));
             ln.d_work[k] = nullptr;
         }
         ln.work_bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ln.d_work[0], wb));
-        HIPCHK(ctx, hipMalloc(&ln.d_work[1], wb));
+        BUF_NEW(ctx, hipMalloc(&ln.d_work[0], wb), ln.d_work[0], wb, kBufDev, kBufScratch, "lane.d_work");
+        BUF_NEW(ctx, hipMalloc(&ln.d_work[1], wb), ln.d_work[1], wb, kBufDev, kBufScratch, "lane.d_work");
         ln.work_bytes = wb;
     }
     return TIC_OK;
@@ -1388,7 +1493,7 @@ int tic_compress(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row
     // image -> HBM, transform stage, entropy stage, all on the device; only the finished stream returns
     const size_t need = compress_bound(h, w);
     const bool small = need <= kSmallHostBytes && !test_hook("TIC_NO_SMALL_PATH"); // the placing kernel writes the stream into host memory itself
-    rc = small ? ensure_small(ctx, kSmallHostBytes) : grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, need);
+    rc = small ? ensure_small(ctx, kSmallHostBytes) : grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, need);
     if (rc) return rc;
     size_t pitch = 0, len = 0;
     rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
@@ -1422,11 +1527,12 @@ static int ensure_rate(tic_ctx *ctx, size_t nres) {
         if (e != hipSuccess) (void)hipFree(d);
         HIPCHK(ctx, e);
         ctx->d_size_tab = d;
+        HIPCHK(ctx, buf_add(ctx, d, sizeof t, kBufDev, kBufState, "d_size_tab"));
     }
     // (a DistortionResult per probe as well, behind the nres SizeResults: dist_of)
     const size_t need = nres * (sizeof(SizeResult) + sizeof(DistortionResult)), alloc = align_up(need, 4096);
-    const int rc = grow_dev(ctx, ctx->d_rate, ctx->rate_dev_bytes, need, alloc);
-    return rc ? rc : grow_pinned(ctx, ctx->h_rate, ctx->rate_host_bytes, need, alloc);
+    const int rc = grow_dev(ctx, "d_rate", ctx->d_rate, ctx->rate_dev_bytes, need, alloc);
+    return rc ? rc : grow_pinned(ctx, "h_rate", ctx->h_rate, ctx->rate_host_bytes, need, alloc);
 }
 
 // The distortion results of a submission of nq probes lie behind its nq size results, in the device buffer and in its landing buffer alike:
@@ -1577,9 +1683,9 @@ static int chosen_stream(tic_ctx *ctx, const void *d_image, int h, int w, ptrdif
         *out_len = len;
         return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", len, cap);
     }
-    int rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, compress_bound(h, w));
+    int rc = grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, compress_bound(h, w));
     if (rc) return rc;
-    rc = grow_dev(ctx, ctx->d_ent_work, ctx->ent_work_bytes, entropy_fused_work_bytes(n));
+    rc = grow_dev(ctx, "d_ent_work", ctx->d_ent_work, ctx->ent_work_bytes, entropy_fused_work_bytes(n));
     if (rc) return rc;
     DctqArgs a = make_args(ctx, d_image, h, w, row_stride, q, ctx->d_coef);
     HIPCHK(ctx, launch_dctq(a, dctq_kernel_id(TIC_KERNEL_HYBRID), ctx->stream));
@@ -2053,7 +2159,7 @@ int tic_compress_scaled_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptr
     if (rc) return rc;
     const size_t bound = tic_compress_scaled_bound(h, w);
     if (cap >= bound || n == 0) return entropy_encode_dev_impl(ctx, ctx->d_coef, h, w, qf, d_out, cap, out_len, true);
-    rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, bound);
+    rc = grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, bound);
     if (rc) return rc;
     size_t len = 0;
     rc = entropy_encode_dev_impl(ctx, ctx->d_coef, h, w, qf, ctx->d_stream_buf, ctx->d_stream_cap, &len, true);
@@ -2075,7 +2181,7 @@ int tic_compress_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdif
     if (n == 0) return entropy_encode_scaled(nullptr, h, w, qf, out, cap, out_len);
     if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, tic_compress_scaled_bound(h, w));
+    rc = grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, tic_compress_scaled_bound(h, w));
     if (rc) return rc;
     size_t pitch = 0, len = 0;
     rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
@@ -2238,7 +2344,7 @@ static int ensure_batch_slots(tic_ctx *ctx, tic_ctx::SlotNeed need) {
     const tic_ctx::SlotNeed &old = ctx->bslot_cap;
     need.img = std::max(need.img, old.img), need.coef = std::max(need.coef, old.coef), need.pin_out = std::max(need.pin_out, old.pin_out);
     need.streams = std::max(need.streams, old.streams), need.work = std::max(need.work, old.work), need.frames = std::max(need.frames, old.frames);
-    for (auto &sl : ctx->bslots) sl.release();
+    for (auto &sl : ctx->bslots) sl.release(ctx);
     ctx->bslots.assign(kBatchSlots, Slot());
     ctx->bslot_cap = tic_ctx::SlotNeed();
     const size_t nf = (size_t)need.frames;
@@ -2263,6 +2369,27 @@ static int ensure_batch_slots(tic_ctx *ctx, tic_ctx::SlotNeed need) {
             (e = hipHostMalloc((void **)&sl.h_sframes, sizeof(ScaledFrameTable), hipHostMallocDefault)) != hipSuccess ||
             (e = hipMalloc((void **)&sl.d_sframes, sizeof(ScaledFrameTable))) != hipSuccess)
             return set_err(ctx, TIC_E_HIP, "batch entropy workspace allocation failed: %s", hipGetErrorString(e));
+        // (the registry of the hooks build; d_err - two flags used in turn, state - was cleared above and stays clear)
+        const struct { void *p; size_t bytes; int kind, cls; const char *name; } recs[] = {
+            {sl.pin_in, need.img, kBufPinned, kBufScratch, "bslot.pin_in"},
+            {sl.pin_out, need.pin_out, kBufPinned, kBufScratch, "bslot.pin_out"},
+            {sl.d_img, need.img, kBufDev, kBufScratch, "bslot.d_img"},
+            {sl.d_coef, need.coef, kBufDev, kBufScratch, "bslot.d_coef"},
+            {sl.d_work, sl.work_bytes, kBufDev, kBufScratch, "bslot.d_work"},
+            {sl.d_lens, nf * sizeof(unsigned long long), kBufDev, kBufScratch, "bslot.d_lens"},
+            {sl.h_lens, nf * sizeof(unsigned long long), kBufPinned, kBufScratch, "bslot.h_lens"},
+            {sl.d_err, 2 * sizeof(int), kBufDev, kBufState, "bslot.d_err"},
+            {sl.h_err, sizeof(int), kBufPinned, kBufScratch, "bslot.h_err"},
+            {sl.d_streams, need.streams, kBufDev, kBufScratch, "bslot.d_streams"},
+            {sl.h_frames, sizeof(EntropyFrameTable), kBufPinned, kBufScratch, "bslot.h_frames"},
+            {sl.d_frames, sizeof(EntropyFrameTable), kBufDev, kBufScratch, "bslot.d_frames"},
+            {sl.h_rb_off, kEntropyMaxFrames * sizeof(unsigned long long), kBufPinned, kBufScratch, "bslot.h_rb_off"},
+            {sl.h_sframes, sizeof(ScaledFrameTable), kBufPinned, kBufScratch, "bslot.h_sframes"},
+            {sl.d_sframes, sizeof(ScaledFrameTable), kBufDev, kBufScratch, "bslot.d_sframes"},
+        };
+        for (const auto &r : recs)
+            if ((e = buf_add(ctx, r.p, r.bytes, r.kind, r.cls, r.name)) != hipSuccess)
+                return set_err(ctx, TIC_E_HIP, "batch buffer poisoning failed: %s", hipGetErrorString(e));
     }
     ctx->bslot_cap = need;
     return TIC_OK;
@@ -3023,8 +3150,8 @@ int tic_last_compress_batch_scaled(tic_ctx *ctx, int *batch_frames, int *single_
 // Room for `ntabs` tables of the transform's descriptor form outside the batch slots.  Nothing of an earlier call may be in flight.
 static int ensure_scaled_tabs(tic_ctx *ctx, size_t ntabs) {
     const size_t bytes = ntabs * sizeof(ScaledFrameTable), alloc = align_up(bytes, 16384);
-    const int rc = grow_pinned(ctx, ctx->h_scaled_tabs, ctx->scaled_tabs_host_bytes, bytes, alloc);
-    return rc ? rc : grow_dev(ctx, ctx->d_scaled_tabs, ctx->scaled_tabs_dev_bytes, bytes, alloc);
+    const int rc = grow_pinned(ctx, "h_scaled_tabs", ctx->h_scaled_tabs, ctx->scaled_tabs_host_bytes, bytes, alloc);
+    return rc ? rc : grow_dev(ctx, "d_scaled_tabs", ctx->d_scaled_tabs, ctx->scaled_tabs_dev_bytes, bytes, alloc);
 }
 
 // The kernel alone, synchronous: frames resident anywhere on the device, the coefficients of all of them back to back at d_coeffs_zz in the
@@ -3099,7 +3226,7 @@ static int check_rate_frames(tic_ctx *ctx, const RateCall &io, int n, int qualit
 static int upload_rate_chunk(tic_ctx *ctx, const MixedPlan &p, const MixedChunk &c, const RateCall &io) {
     int rc = ensure_scratch(ctx, c.img_bytes, 0);
     if (rc) return rc;
-    rc = grow_pinned(ctx, ctx->h_rate_pix, ctx->rate_pix_cap, c.img_bytes);
+    rc = grow_pinned(ctx, "h_rate_pix", ctx->h_rate_pix, ctx->rate_pix_cap, c.img_bytes);
     if (rc) return rc;
     const MixedFrame *fr = &p.frames[(size_t)c.first];
     uint8_t *pin = ctx->h_rate_pix;
@@ -3133,14 +3260,14 @@ static int submit_rate_probes(tic_ctx *ctx, const RatePlan &p, RateSubmission &s
     size_t ntabs = 0;
     for (size_t i = 0; i + 1 < s.pass_first.size(); i++) ntabs += (size_t)(s.pass_first[i + 1] - s.pass_first[i] + kSizeMaxProbes - 1) / kSizeMaxProbes;
     const size_t tab_bytes = ntabs * sizeof(SizeProbeTable), tab_alloc = align_up(tab_bytes, 16384);
-    rc = grow_pinned(ctx, ctx->h_rate_tabs, ctx->rate_tabs_host_bytes, tab_bytes, tab_alloc);
+    rc = grow_pinned(ctx, "h_rate_tabs", ctx->h_rate_tabs, ctx->rate_tabs_host_bytes, tab_bytes, tab_alloc);
     if (rc) return rc;
-    rc = grow_dev(ctx, ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, tab_bytes, tab_alloc);
+    rc = grow_dev(ctx, "d_rate_tabs", ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, tab_bytes, tab_alloc);
     if (rc) return rc;
     const size_t sse_tab_bytes = distortion ? ntabs * sizeof(SseProbeTable) : 0, sse_tab_alloc = align_up(sse_tab_bytes, 16384);
-    rc = grow_pinned(ctx, ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, sse_tab_bytes, sse_tab_alloc);
+    rc = grow_pinned(ctx, "h_rd_tabs", ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, sse_tab_bytes, sse_tab_alloc);
     if (rc) return rc;
-    rc = grow_dev(ctx, ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, sse_tab_bytes, sse_tab_alloc);
+    rc = grow_dev(ctx, "d_rd_tabs", ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, sse_tab_bytes, sse_tab_alloc);
     if (rc) return rc;
     const size_t sse_cap = sse_group_cap();
     // the tables of every size launch (and of the measuring launch behind it), in launch order
@@ -3648,10 +3775,10 @@ int tic_rd_points_scaled_v(tic_ctx *ctx, const uint8_t *const *images, int n, co
         rc = ensure_scaled_tabs(ctx, ntabs);
         if (rc) return rc;
         const size_t size_bytes = ntabs * sizeof(SizeProbeTable), sse_bytes = ntabs * sizeof(SseProbeTable);
-        if ((rc = grow_pinned(ctx, ctx->h_rate_tabs, ctx->rate_tabs_host_bytes, size_bytes, align_up(size_bytes, 16384))) != TIC_OK ||
-            (rc = grow_dev(ctx, ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, size_bytes, align_up(size_bytes, 16384))) != TIC_OK ||
-            (rc = grow_pinned(ctx, ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, sse_bytes, align_up(sse_bytes, 16384))) != TIC_OK ||
-            (rc = grow_dev(ctx, ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, sse_bytes, align_up(sse_bytes, 16384))) != TIC_OK)
+        if ((rc = grow_pinned(ctx, "h_rate_tabs", ctx->h_rate_tabs, ctx->rate_tabs_host_bytes, size_bytes, align_up(size_bytes, 16384))) != TIC_OK ||
+            (rc = grow_dev(ctx, "d_rate_tabs", ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, size_bytes, align_up(size_bytes, 16384))) != TIC_OK ||
+            (rc = grow_pinned(ctx, "h_rd_tabs", ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, sse_bytes, align_up(sse_bytes, 16384))) != TIC_OK ||
+            (rc = grow_dev(ctx, "d_rd_tabs", ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, sse_bytes, align_up(sse_bytes, 16384))) != TIC_OK)
             return rc;
         rc = upload_rate_chunk(ctx, p, c, io);
         if (rc) return rc;
@@ -3747,9 +3874,9 @@ static int queue_distortion_v(tic_ctx *ctx, const void *d_coeffs_zz, const void 
     if (rc) return rc;
     const size_t ntabs = ((size_t)n + kSseMaxProbes - 1) / kSseMaxProbes; // (an upper bound: probes without blocks take no entry)
     const size_t tab_bytes = ntabs * sizeof(SseProbeTable), tab_alloc = align_up(tab_bytes, 16384);
-    rc = grow_pinned(ctx, ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, tab_bytes, tab_alloc);
+    rc = grow_pinned(ctx, "h_rd_tabs", ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, tab_bytes, tab_alloc);
     if (rc) return rc;
-    rc = grow_dev(ctx, ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, tab_bytes, tab_alloc);
+    rc = grow_dev(ctx, "d_rd_tabs", ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, tab_bytes, tab_alloc);
     if (rc) return rc;
     const size_t cap = sse_group_cap();
     launches.clear();
@@ -3921,6 +4048,7 @@ static int ensure_dec_tables(tic_ctx *ctx) {
     }
     if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "device decoder set-up failed: %s", hipGetErrorString(e));
     ctx->d_dec_luts = d;
+    HIPCHK(ctx, buf_add(ctx, d, sizeof(DecLutsDev), kBufDev, kBufState, "d_dec_luts"));
     return TIC_OK;
 }
 
@@ -4056,12 +4184,13 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
     // its end themselves); a host stream, or an odd address, goes through the context's stream buffer.
     const bool in_place = src_on_device && ((uintptr_t)data & 3u) == 0;
     if (!in_place) {
-        rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, align_up(len, 4) + 16);
+        rc = grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, align_up(len, 4) + 16);
         if (rc) return rc;
     }
     const void *d_stream = in_place ? (const void *)data : (const void *)ctx->d_stream_buf;
     if (!ctx->h_dec_tail) { // pinned: the stream's last bytes on their way down (device source), the tail's coefficients on their way up
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_dec_tail, kDecTailEnd + kDecTailCoef, hipHostMallocDefault));
+        BUF_NEW(ctx, hipHostMalloc((void **)&ctx->h_dec_tail, kDecTailEnd + kDecTailCoef, hipHostMallocDefault), ctx->h_dec_tail, kDecTailEnd + kDecTailCoef,
+                kBufPinned, kBufScratch, "h_dec_tail");
     }
     DecWorkspace &ws = ctx->dec_ws;
     const size_t wb = entropy_decode_gpu_work_bytes(len, n);
@@ -4243,7 +4372,7 @@ static int decode_on_host(tic_ctx *ctx, const uint8_t *data, size_t len, const S
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // coefficients land in a pinned buffer kept on the context: no page faults on a fresh 32 MB vector per call, and the upload
     // runs at PCIe speed instead of through the runtime's staging of pageable memory
-    int rc = grow_pinned(ctx, ctx->h_zz, ctx->h_zz_bytes, n * 128);
+    int rc = grow_pinned(ctx, "h_zz", ctx->h_zz, ctx->h_zz_bytes, n * 128);
     if (rc) return rc;
     std::vector<DcWide> wide;
     entropy_decode(data, len, sh.h, sh.w, ctx->h_zz, &wide);
@@ -4259,7 +4388,7 @@ static int decode_on_host(tic_ctx *ctx, const uint8_t *data, size_t len, const S
         std::vector<int32_t> dc32(n);
         for (size_t b = 0; b < n; b++) dc32[b] = ctx->h_zz[b * 64];
         for (const DcWide &x : wide) dc32[x.block] = x.dc;
-        rc = grow_dev(ctx, ctx->d_dc32, ctx->d_dc32_cap, n * sizeof(int32_t));
+        rc = grow_dev(ctx, "d_dc32", ctx->d_dc32, ctx->d_dc32_cap, n * sizeof(int32_t));
         if (rc) return rc;
         HIPCHK(ctx, hipMemcpy(ctx->d_dc32, dc32.data(), n * sizeof(int32_t), hipMemcpyHostToDevice)); // (pageable, synchronous: dc32 dies with this scope)
         d_dc32 = ctx->d_dc32;
@@ -4301,13 +4430,13 @@ static int dbatch_grow(tic_ctx *ctx, size_t up_bytes, size_t pix_bytes) {
     if (up_bytes > B.in_cap) {
         size_t hcap = B.in_cap, dcap = B.in_cap;
         B.in_cap = 0;
-        int rc = grow_pinned(ctx, B.h_in, hcap, up_bytes, up_bytes + up_bytes / 4);
+        int rc = grow_pinned(ctx, "dbat.h_in", B.h_in, hcap, up_bytes, up_bytes + up_bytes / 4);
         if (rc) return rc;
-        rc = grow_dev(ctx, B.d_in, dcap, up_bytes, up_bytes + up_bytes / 4);
+        rc = grow_dev(ctx, "dbat.d_in", B.d_in, dcap, up_bytes, up_bytes + up_bytes / 4);
         if (rc) return rc;
         B.in_cap = dcap;
     }
-    return grow_dev(ctx, B.d_pix, B.pix_cap, pix_bytes, pix_bytes + pix_bytes / 4);
+    return grow_dev(ctx, "dbat.d_pix", B.d_pix, B.pix_cap, pix_bytes, pix_bytes + pix_bytes / 4);
 }
 
 // Descriptors, buffers, ONE upload - descriptors, the frame of every measure wave, the frame of every fused workgroup, the streams - and the two
@@ -4402,7 +4531,7 @@ extern "C++" template <class Frame> static int dbatch_pixels_down(tic_ctx *ctx, 
         if (reg && hipHostUnregister(reg) != hipSuccess) (void)hipGetLastError();
     }
     if (!*direct) {
-        const int rc = grow_pinned(ctx, B.h_pix, B.hpix_cap, pix_bytes, pix_bytes + pix_bytes / 4);
+        const int rc = grow_pinned(ctx, "dbat.h_pix", B.h_pix, B.hpix_cap, pix_bytes, pix_bytes + pix_bytes / 4);
         if (rc) return rc;
         HIPCHK(ctx, hipMemcpyAsync(B.h_pix, B.d_pix, pix_bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -4723,6 +4852,9 @@ int tic_decompress_async_result(tic_ctx *ctx, long long ticket, int wait, int *h
     sl.ticket = -1;
     if (h_out) *h_out = sl.h;
     if (w_out) *w_out = sl.w;
+    if (test_hooks_enabled() && sl.rc == TIC_OK) // (hooks build: what became of the ticket, where a test can read it)
+        set_err(ctx, TIC_OK, "decode ticket %lld: slot %d, launched %d, guess held %d, epoch %u", ticket, (int)(ticket % kDecSlots), sl.launched ? 1 : 0,
+                sl.launched && ctx->last_decode_guess == 1 ? 1 : 0, sl.ws.epoch);
     return sl.rc;
 }
 
@@ -4773,8 +4905,9 @@ static int adaptive_encode_dev(tic_ctx *ctx, size_t n, int h, int w, int quality
         ctx->d_adapt_stats = (AdaptStats *)p;
         ctx->d_adapt_tab = (HuffWide *)(p + a);
         ctx->d_adapt_err = (uint32_t *)(p + a + b);
+        HIPCHK(ctx, buf_add(ctx, p, a + b + 256, kBufDev, kBufScratch, "d_adapt_stats")); // (all three rewritten per call; the context owns the block first)
     }
-    int rc = grow_dev(ctx, ctx->d_adapt_work, ctx->adapt_work_bytes, adaptive_work_bytes(n));
+    int rc = grow_dev(ctx, "d_adapt_work", ctx->d_adapt_work, ctx->adapt_work_bytes, adaptive_work_bytes(n));
     if (rc) return rc;
     AdaptStats *st = ctx->d_adapt_stats;
     HIPCHK(ctx, hipMemsetAsync(st, 0, sizeof(AdaptStats), ctx->stream));
@@ -4809,7 +4942,7 @@ static int adaptive_encode_dev(tic_ctx *ctx, size_t n, int h, int w, int quality
         *out_len = bytes;
         return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", bytes, cap);
     }
-    rc = grow_dev(ctx, ctx->d_adapt_out, ctx->adapt_out_bytes, words * 4);
+    rc = grow_dev(ctx, "d_adapt_out", ctx->d_adapt_out, ctx->adapt_out_bytes, words * 4);
     if (rc) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_adapt_out, 0, words * 4, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_adapt_out, head.data(), (size_t)((base + 7) / 8), hipMemcpyHostToDevice, ctx->stream));
@@ -4901,8 +5034,8 @@ static AdaptSlotView adapt_view(const Slot &s, size_t count, size_t nblk, size_t
 static int ensure_adapt_slots(tic_ctx *ctx, const MixedPlan &p) {
     const AdaptSlotLayout l = adaptive_slot_layout((size_t)p.max_count, p.max_nblk, p.max_nblk / kAdaptGroupBlocks + (size_t)p.max_count);
     for (auto &sl : ctx->bslots) {
-        int rc = grow_dev(ctx, sl.d_adapt, sl.adapt_bytes, l.end);
-        if (rc == TIC_OK) rc = grow_pinned(ctx, sl.h_adapt, sl.h_adapt_bytes, l.upload_end);
+        int rc = grow_dev(ctx, "bslot.d_adapt", sl.d_adapt, sl.adapt_bytes, l.end);
+        if (rc == TIC_OK) rc = grow_pinned(ctx, "bslot.h_adapt", sl.h_adapt, sl.h_adapt_bytes, l.upload_end);
         if (rc) return rc;
     }
     return TIC_OK;
@@ -4966,8 +5099,8 @@ static int adaptive_pack_chunk(tic_ctx *ctx, const MixedPlan &p, Slot &s, hipStr
     // (nothing is in flight on this slot's buffers: its previous chunk was handed out before this one claimed it)
     if (!s.streams_cap) s.streams_cap = ctx->bslot_cap.streams;
     if (!s.pin_out_cap) s.pin_out_cap = ctx->bslot_cap.pin_out;
-    int rc = grow_dev(ctx, s.d_streams, s.streams_cap, stream_bytes, stream_bytes + stream_bytes / 4);
-    if (rc == TIC_OK) rc = grow_pinned(ctx, s.pin_out, s.pin_out_cap, landing, landing + landing / 4);
+    int rc = grow_dev(ctx, "bslot.d_streams", s.d_streams, s.streams_cap, stream_bytes, stream_bytes + stream_bytes / 4);
+    if (rc == TIC_OK) rc = grow_pinned(ctx, "bslot.pin_out", s.pin_out, s.pin_out_cap, landing, landing + landing / 4);
     if (rc) return rc;
     *v.h_err = 0u;
     hipError_t e = stream_bytes ? hipMemsetAsync(s.d_streams, 0, stream_bytes, st) : hipSuccess;
@@ -5137,7 +5270,7 @@ static int adaptive_decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t l
     const bool in_place = src_on_device && ((uintptr_t)data & 3u) == 0;
     int rc = TIC_OK;
     if (!in_place) {
-        rc = grow_dev(ctx, ctx->d_stream_buf, ctx->d_stream_cap, align_up(len, 4) + 16);
+        rc = grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, align_up(len, 4) + 16);
         if (rc) return rc;
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_stream_buf, data, len, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
     }
@@ -5148,10 +5281,11 @@ static int adaptive_decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t l
         HIPCHK(ctx, hipMalloc((void **)&p, a + align_up(sizeof(AdaptDecStatus), 256)));
         ctx->d_adec_tab = (AdaptDecTab *)p;
         ctx->d_adec_status = (AdaptDecStatus *)(p + a);
+        HIPCHK(ctx, buf_add(ctx, p, a + align_up(sizeof(AdaptDecStatus), 256), kBufDev, kBufScratch, "d_adec_tab")); // (the table is uploaded per call)
     }
     const int range = adaptive_dec_range_bits(len, t.payload_bit, n);
     const size_t wb = adaptive_dec_work_bytes(len, t.payload_bit, n, range);
-    rc = grow_dev(ctx, ctx->d_adec_work, ctx->adec_work_bytes, wb, wb + wb / 8); // (room for a longer stream of the same geometry)
+    rc = grow_dev(ctx, "d_adec_work", ctx->d_adec_work, ctx->adec_work_bytes, wb, wb + wb / 8); // (room for a longer stream of the same geometry)
     if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_adec_tab, &ctx->adec_tab, sizeof ctx->adec_tab, hipMemcpyHostToDevice, ctx->stream));
     // Three launches of the stitch settle nearly every stream (the last one only proves it), so the passes behind them are launched
@@ -5229,7 +5363,7 @@ static int decompress_adaptive_impl(tic_ctx *ctx, const uint8_t *data, size_t le
     } else if (!src_on_device) {
         head = data;
     }
-    rc = grow_pinned(ctx, ctx->h_zz, ctx->h_zz_bytes, n * 128); // (the landing buffer of decode_on_host)
+    rc = grow_pinned(ctx, "h_zz", ctx->h_zz, ctx->h_zz_bytes, n * 128); // (the landing buffer of decode_on_host)
     if (rc) return rc;
     const char *why = "";
     rc = adaptive_decode(head, len, h, w, ctx->h_zz, &why);
@@ -5297,9 +5431,9 @@ static int adbatch_decode(tic_ctx *ctx, const DecBatchIO &io, const AdaptDecPlan
     const AdaptDecWorkLayout wl(c);
     int rc = dbatch_grow(ctx, up.up_bytes, c.pix_bytes);
     if (rc) return rc;
-    rc = grow_dev(ctx, A.d_work, A.work_cap, wl.bytes, wl.bytes + wl.bytes / 4);
+    rc = grow_dev(ctx, "adbat.d_work", A.d_work, A.work_cap, wl.bytes, wl.bytes + wl.bytes / 4);
     if (rc) return rc;
-    rc = grow_pinned(ctx, A.h_status, A.status_cap, wl.status_bytes, 2 * wl.status_bytes);
+    rc = grow_pinned(ctx, "adbat.h_status", A.h_status, A.status_cap, wl.status_bytes, 2 * wl.status_bytes);
     if (rc) return rc;
     BT_START();
     AdaptDecFrame *hf = (AdaptDecFrame *)(B.h_in + up.o_frames);

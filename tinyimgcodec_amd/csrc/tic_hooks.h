@@ -32,6 +32,10 @@
 //   TIC_BAND_BYTES          size from which a frame is transformed in bands of block rows (4 GiB in production)
 //   TIC_SSE_MAX_GROUPS      measuring kernel's descriptor form: workgroups per probe at most (1 ... 1024; default 1024), so that the walk runs on frames of a few blocks
 //   TIC_SCALED_V_GROUPS     integer transform's descriptor form: workgroups per launch at most (default 2,048), so that one wave walks strips of several frames
+//   TIC_POISON              every scratch buffer of a context is filled with this byte value (0 ... 255, 0x.. too) right after it is
+//                           allocated, before anything the allocation site clears itself; tic_test_poison fills them again between calls
+//   TIC_DEC_EPOCH           device Huffman decoder: the next run on a workspace continues from this epoch when it is ahead of the workspace's own
+//                           (below 2^22: the wrap - the look-back words cleared, epoch 1 - within a few calls)
 // at every call (tests flip them inside one process).  tic_build_has_test_hooks() tells which build a process has loaded;
 // tests/test_gpu_parity.py::test_shipped_library_in_a_fresh_process runs the parity core on the product build.
 #pragma once
