@@ -165,6 +165,12 @@ int tic_last_fallback_blocks(tic_ctx *ctx, unsigned long long *count);
  * (0,0) (0,4) (4,0) (4,4) somewhere in the strip), [2] = strips redone as a whole in the exact operation order (batch full, or all
  * eight blocks tripped), [3] = the largest batch any wave carried.  Diagnostics: no counterpart in the reference. */
 int tic_last_rare_path_stats(tic_ctx *ctx, unsigned long long stats[4]);
+/* What the launcher decided for the last transform launch through tic_dctq_dev / tic_dctq_dev_frames on this context: info[0] = 0 when the
+ * strip kernel did not run (the exact kernel took the whole frame), 1 when it ran rows first, 2 columns first; [1] = schedule kind (0 rows
+ * form: strided or team, 1 chunked, 2 round-interleaved); [2] = team count (0: no team schedule); [3], [4] = grid x, y; [5] = strips a
+ * wave advances by; [6], [7] = the fast rectangle in strips, x and y.  Host bookkeeping, no device work.  Diagnostics: no counterpart
+ * in the reference. */
+int tic_last_strip_launch(tic_ctx *ctx, int info[8]);
 
 /* ---- entropy stage (host): replaces the per-block loops of compress() codec.py:133-164:
  *      DC DPCM codec.py:34-35, encode_run_length huffman.py:12-33, encode_huffman huffman.py:41-63,

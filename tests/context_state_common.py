@@ -676,7 +676,9 @@ BY_NAME = {f.name: f for f in FAMILIES}
 # Entry points that take a context and belong to no family, with the reason each.
 EXEMPT = {
     "tic_destroy": "lifecycle: ends the context",
-    # (tic_last_*: getters of the last call's figures, exempt by their prefix)
+    # (tic_last_*: getters of the last call's figures, exempt by their prefix - test_context_state_cpu.py wants every call in exactly one of
+    #  {a family, this table, the prefix}.  tic_last_strip_launch among them: host bookkeeping of the last tic_dctq_dev / tic_dctq_dev_frames
+    #  launch - order, schedule kind, teams, grid, fast rectangle - that reads no context buffer and queues nothing.)
     "tic_device_arch": "getter", "tic_numa_info": "getter", "tic_pci_bus_id": "getter", "tic_get_stage_threads": "getter",
     "tic_set_custom_quality": "setter (writes slot 0 of d_consts, which no family reads)", "tic_set_numa_binding": "setter", "tic_set_auto_register": "setter",
     "tic_set_stats": "setter", "tic_set_entropy_lane_kernel": "setter (the after-an-error tests turn it on)", "tic_set_stage_threads": "setter",

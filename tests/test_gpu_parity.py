@@ -3,6 +3,7 @@
 Bar: bit-exact (integer coefficients, byte streams, decoded pixels).  Run with `-m gpu` on an MI355X."""
 import ctypes as C
 import hashlib
+import json
 import os
 
 import numpy as np
@@ -78,6 +79,14 @@ class DevFrame:
     def free(self):
         self.L.tic_dev_free(self.ctx.handle, self.d_img)
         self.L.tic_dev_free(self.ctx.handle, self.d_out)
+
+
+def strip_launch(ctx):
+    """What the launcher decided for the last tic_dctq_dev launch (tic_last_strip_launch): order (0 no strip launch, 1 rows first, 2 columns
+    first), schedule kind (0 rows form, 1 chunked, 2 round-interleaved), team count, grid x, grid y, tstep, fast_tx, fast_ty."""
+    info = (C.c_int * 8)()
+    ctx.check(N.load().tic_last_strip_launch(ctx.handle, info))
+    return dict(zip(("order", "kind", "team_count", "grid_x", "grid_y", "tstep", "fast_tx", "fast_ty"), info))
 
 
 def zz_to_dc_ac(zz):
@@ -351,7 +360,10 @@ def test_config2_4096_coefficient_digest(ctx, manifest, q):
     N.load().tic_set_stats(ctx.handle, 1)
     f.fallbacks()
     zz_h = f.run(q, N.KERNEL_HYBRID)
-    fb = f.fallbacks()
+    rare = (C.c_ulonglong * 4)()
+    ctx.check(N.load().tic_last_rare_path_stats(ctx.handle, rare))
+    rare, fb = list(rare), rare[0]
+    launch = strip_launch(ctx)
     N.load().tic_set_stats(ctx.handle, 0)
     zz_e = f.run(q, N.KERNEL_EXACT)
     f.free()
@@ -360,6 +372,12 @@ def test_config2_4096_coefficient_digest(ctx, manifest, q):
     assert sha(dc.astype("<i4").tobytes()) == m["dc_i4_sha256"]
     assert sha(ac.astype("<i4").tobytes()) == m["ac_i4_sha256"]
     assert 0 < fb < 0.08 * 262144, fb  # guard band trips on a small fraction of blocks only
+    # strips with a rational tie: a property of the frame, the quality and the pass order, whatever the schedule - the host model's count
+    # (tests/native/strip_decisions_model.cpp; recomputed on the CPU by tests/test_strip_decisions_cpu.py), exactly
+    with open(os.path.join(os.path.dirname(__file__), "golden", "strip_decisions.json")) as fh:
+        ties = json.load(fh)["config2_tie_strips"][str(q)]
+    assert launch["order"] in (1, 2) and (launch["fast_tx"], launch["fast_ty"]) == (64, 512), launch
+    assert rare[1] == ties[str(launch["order"] - 1)], (rare, ties, launch)
 
 
 def _true_tie_block():
@@ -413,6 +431,7 @@ def test_rare_paths_of_the_strip_kernel(ctx, oracle, golden, monkeypatch):
         "posterised noise, 4096 x 4096 (team schedule)": ((rand_frame(14, 4096, 4096) // 8 * 8 + 1).astype(np.uint8), (50, 99)),
     }
     monkeypatch.setenv("TIC_TUNE", "1")  # re-read the knobs at every launch
+    hooks = N.load().tic_build_has_test_hooks() == 1
     for name, (img, quals) in frames.items():
         f = DevFrame(ctx, img)
         for q in quals:
@@ -421,8 +440,14 @@ def test_rare_paths_of_the_strip_kernel(ctx, oracle, golden, monkeypatch):
             for order in ("1", "0"):  # both instantiations of the strip kernel: columns first, rows first (TIC_ORDER: csrc/tic_hooks.h)
                 monkeypatch.setenv("TIC_ORDER", order)
                 assert np.array_equal(f.run(q, N.KERNEL_HYBRID), want), (name, q, "production kernel", "columns first" if order == "1" else "rows first")
+                if hooks:  # the order forced is the order launched (the shipped library, which also runs this test, reads no knob)
+                    assert strip_launch(ctx)["order"] == (2 if order == "1" else 1), (name, q, order, strip_launch(ctx))
             monkeypatch.delenv("TIC_ORDER")
             assert np.array_equal(f.run(q, N.KERNEL_HYBRID), want), (name, q, "production kernel, order by grid")
+            by_grid = strip_launch(ctx)
+            assert by_grid["order"] in (1, 2) and by_grid["kind"] == 0, (name, by_grid)  # (none of these frames is larger than the chip)
+            if "team schedule" in name:
+                assert by_grid["team_count"] > 0 and by_grid["grid_y"] > 1 and by_grid["order"] == 2, (name, by_grid)
         f.free()
 
 
@@ -436,6 +461,7 @@ def test_strip_schedules_are_equivalent(ctx, monkeypatch):
     for name, img in frames.items():
         f = DevFrame(ctx, img)
         ref = f.run(50, N.KERNEL_EXACT)
+        seen = set()
         for knobs in ({}, {"TIC_SPLIT": "0"}, {"TIC_SPLIT": "1,1,1,1,1"}, {"TIC_SCHED": "0"}, {"TIC_SCHED": "1", "TIC_CHUNK": "5"},
                       {"TIC_SCHED": "2"}, {"TIC_MAX_WGS": "512"}, {"TIC_ORDER": "0"}, {"TIC_ORDER": "1"}, {"TIC_ORDER": "0", "TIC_SCHED": "0"},
                       {"TIC_ORDER": "1", "TIC_SCHED": "1", "TIC_CHUNK": "3"}):
@@ -444,7 +470,26 @@ def test_strip_schedules_are_equivalent(ctx, monkeypatch):
             for k, v in knobs.items():
                 monkeypatch.setenv(k, v)
             assert np.array_equal(f.run(50, N.KERNEL_HYBRID), ref), (name, knobs)
+            got = strip_launch(ctx)
+            assert got["order"] in (1, 2), (name, knobs, got)
+            if "TIC_ORDER" in knobs:
+                assert got["order"] == (2 if knobs["TIC_ORDER"] == "1" else 1), (name, knobs, got)  # the order forced is the order launched
+            if knobs.get("TIC_SCHED") == "0":
+                assert got["kind"] == 0, (name, knobs, got)  # strided (or teams): the rows form
+            if knobs.get("TIC_SPLIT") == "0":
+                assert (got["team_count"], got["grid_y"]) == (0, 1), (name, knobs, got)
+            if knobs.get("TIC_MAX_WGS") == "512":  # larger than the chip where 512 workgroups' waves would walk more than 16 strips: chunked, 8 per wave
+                large = (got["fast_tx"] * got["fast_ty"] + 63) // 64 > 512
+                assert got["kind"] == (1 if large else 0) and (not large or (got["team_count"], got["tstep"]) == (0, 4)), (name, knobs, got)
+            if name.startswith("team schedule, 65") and knobs in ({}, {"TIC_SPLIT": "1,1,1,1,1"}, {"TIC_ORDER": "0"}, {"TIC_ORDER": "1"}):
+                assert got["kind"] == 0 and got["team_count"] > 0 and got["grid_y"] > 1 and got["fast_tx"] == 65, (name, knobs, got)
+            seen.add((got["kind"], got["team_count"] > 0))
         f.free()
+        # the schedules a frame was built for did occur over its knob list
+        if name == "large grid":
+            assert {(0, False), (1, False)} <= seen, (name, seen)
+        if name.startswith("team schedule"):
+            assert {(0, True), (0, False)} <= seen if "65" in name else (0, False) in seen, (name, seen)
 
 
 @pytest.mark.parametrize("q", [10, 50, 90])

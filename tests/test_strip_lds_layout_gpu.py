@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(64, 8), (64, 16), (128, 8), (256, 72)]  # width x height
 QUALITIES = (50, 90)
 ABI = ("tic_build_has_test_hooks", "tic_create", "tic_destroy", "tic_num_blocks", "tic_dev_alloc", "tic_dev_free", "tic_memcpy_h2d",
-       "tic_memcpy_d2h", "tic_memset_dev", "tic_dctq_dev")
+       "tic_memcpy_d2h", "tic_memset_dev", "tic_dctq_dev", "tic_last_strip_launch")
 
 
 def bind(path):
@@ -109,5 +109,10 @@ def test_small_frames_through_the_plane_layout(builds, wanted, monkeypatch, shap
                 monkeypatch.setenv("TIC_ORDER", "1")  # columns first (read by the hooks build only)
                 got = f.run(q, N.KERNEL_HYBRID)
                 monkeypatch.delenv("TIC_ORDER")
+                # the launcher's report: columns first (forced on the hooks build, the grid's own choice on the product), one strided round of
+                # ceil(strips / 4) workgroups over the whole frame
+                info, wgs = (C.c_int * 8)(), ((w // 64) * (h // 8) + 3) // 4
+                assert L.tic_last_strip_launch(ctx, info) == 0
+                assert list(info) == [2, 0, 0, wgs, 1, 4 * wgs, w // 64, h // 8], (name, q, build, list(info))
                 assert np.array_equal(got, want[q]), (name, q, build, "strip kernel", int((got != want[q]).any(axis=1).sum()), "blocks differ")
             f.free()

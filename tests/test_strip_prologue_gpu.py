@@ -2,6 +2,7 @@
 on the frames that reach its branches (tests/strip_prologue_common.py; the same list is walked on the CPU by tests/native/strip_plan_selftest.cpp):
 the shipped library in a fresh process, and the test-hooks build under both pass orders and the forced schedules.  Everywhere the strip kernel
 is compared with the exact kernel and with the oracle, coefficient for coefficient."""
+import ctypes as C
 import os
 import subprocess
 import sys
@@ -89,6 +90,28 @@ def test_hooks_build_schedules_and_orders(cases, monkeypatch, knobs, order):
         monkeypatch.setenv(k, v)
     if order != "by grid":
         monkeypatch.setenv("TIC_ORDER", order)
+    ctx = cases[0][1].ctx
     for name, d, want in cases:
         got = d.run(N.KERNEL_HYBRID)
         assert np.array_equal(got, want), (name, knobs, order, int((got != want).any(axis=2).sum()), "blocks differ")
+        # what the launcher decided (tic_last_strip_launch): the order forced is the order launched, and the frames built for a schedule got it
+        info = (C.c_int * 8)()
+        ctx.check(N.load().tic_last_strip_launch(ctx.handle, info))
+        launched, kind, teams = info[0], info[1], info[2]
+        if "no fast rectangle" in name:
+            assert list(info) == [0] * 8, (name, list(info))
+            continue
+        assert launched == ({"1": 2, "0": 1}[order] if order != "by grid" else launched) and launched in (1, 2), (name, knobs, order, list(info))
+        cap, sched = knobs.get("TIC_MAX_WGS"), int(knobs.get("TIC_SCHED", "1"))
+        if name.startswith("512x512"):
+            assert (kind, teams, info[4]) == (0, 0, 1), (name, knobs, list(info))  # strided under every cap here
+        if name.startswith("2048x1536") and cap in ("64", "16"):
+            assert (kind, teams) == (sched, 0), (name, knobs, list(info))  # larger than the chip: strided, chunked, round-interleaved as asked
+        if name.startswith("1920x1080") and cap == "16":
+            assert (kind, teams) == (sched, 0), (name, knobs, list(info))
+        if kind == 1:
+            assert info[5] == 4, (name, knobs, list(info))
+        if name.startswith("2048x1536") and cap is None:  # the smallest team schedule - unless the weights are off
+            assert (teams > 0 and info[4] > 1) == (knobs.get("TIC_SPLIT") != "0") and kind == 0, (name, knobs, list(info))
+        if name.startswith("2048x1528") and cap is None:
+            assert teams == 0 and kind == 0, (name, knobs, list(info))

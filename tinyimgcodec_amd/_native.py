@@ -103,6 +103,7 @@ SIGNATURES = {
     "tic_compress_dev_async": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_longlong)]),
     "tic_async_result": (C.c_int, [_ctxp, C.c_longlong, C.c_int, C.POINTER(C.c_size_t)]),
     "tic_last_rare_path_stats": (C.c_int, [_ctxp, C.POINTER(C.c_ulonglong)]),
+    "tic_last_strip_launch": (C.c_int, [_ctxp, C.POINTER(C.c_int)]),
     "tic_entropy_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tic_entropy_encode_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tic_compress_dev": (

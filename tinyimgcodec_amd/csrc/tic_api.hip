@@ -143,6 +143,7 @@ struct tic_ctx {
     DctqConsts *d_consts = nullptr;   // [100], index = quality; slot 0 = the custom (non-integral) quality of tic_set_custom_quality
     double custom_quality = 0.0;      // what slot 0 holds (0: nothing yet)
     unsigned long long *d_fallback = nullptr;
+    StripLaunchInfo last_strip{}; // what the last tic_dctq_dev / tic_dctq_dev_frames launch decided (tic_last_strip_launch)
     bool stats = false; // count guard-band fallbacks with a global atomic (diagnostic; serialises at ~12 ns per wave)
     hipEvent_t ev0 = nullptr, ev1 = nullptr; // the interval of the timed entry points (timed_launches)
     // scratch for the host-buffer entry points
@@ -942,7 +943,7 @@ int tic_dctq_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_
     if (v < 0) return set_err(ctx, TIC_E_ARG, "unknown kernel variant %d", variant);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DctqArgs a = make_args(ctx, d_image, h, w, row_stride, quality, d_coeffs_zz);
-    HIPCHK(ctx, launch_dctq(a, v, ctx->stream));
+    HIPCHK(ctx, launch_dctq(a, v, ctx->stream, nullptr, nullptr, &ctx->last_strip));
     return TIC_OK;
 }
 
@@ -977,7 +978,7 @@ int tic_dctq_dev_frames(tic_ctx *ctx, const void *d_images, int nframes, int h, 
     const int v = dctq_kernel_id(variant);
     if (v < 0) return set_err(ctx, TIC_E_ARG, "unknown kernel variant %d", variant);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, launch_dctq(a, v, ctx->stream));
+    HIPCHK(ctx, launch_dctq(a, v, ctx->stream, nullptr, nullptr, &ctx->last_strip));
     return TIC_OK;
 }
 
@@ -1127,6 +1128,17 @@ int tic_last_rare_path_stats(tic_ctx *ctx, unsigned long long stats[4]) {
     HIPCHK(ctx, hipMemcpyAsync(stats, ctx->d_fallback, 4 * sizeof *stats, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_fallback, 0, 4 * sizeof *stats, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TIC_OK;
+}
+
+// What the launcher decided for the last transform launch through tic_dctq_dev / tic_dctq_dev_frames on this context (no other entry point
+// updates it; the report of a call that returned before its launch is the call's before).  Host bookkeeping: no device work, no wait.
+int tic_last_strip_launch(tic_ctx *ctx, int info[8]) {
+    TIC_LOCK(ctx);
+    if (!ctx || !info) return TIC_E_ARG;
+    const StripLaunchInfo &s = ctx->last_strip;
+    info[0] = s.order, info[1] = s.kind, info[2] = s.team_count, info[3] = s.grid_x;
+    info[4] = s.grid_y, info[5] = s.tstep, info[6] = s.fast_tx, info[7] = s.fast_ty;
     return TIC_OK;
 }
 

@@ -27,7 +27,9 @@
 //   TIC_DECODE_HOST         Huffman decoder: never the device decoder (host parallel / serial as the stream's length says)
 //   TIC_DECODE_THREADS      host Huffman decoder: threads of the parallel decoder
 //   TIC_COMM_FORCE_RCCL     a single rank goes through RCCL too (the only way to exercise tic_comm.hip on a one-GPU box)
-//   TIC_TUNE, TIC_SPLIT, TIC_SCHED, TIC_CHUNK, TIC_MAX_WGS   schedule knobs of the strip kernel's launcher
+//   TIC_TUNE, TIC_SPLIT, TIC_SCHED, TIC_CHUNK, TIC_MAX_WGS   schedule knobs of the strip kernel's launcher.  TIC_TUNE itself is looked up at every
+//                           launch: while it is set, the others (and TIC_ORDER) are read again at every launch; while it is not, the launcher uses
+//                           what they held at the first strip launch of the process.  tic_last_strip_launch reports what a launch used.
 //   TIC_ORDER               pass order of the strip kernel (0 rows first, 1 columns first) instead of the choice by grid
 //   TIC_BAND_BYTES          size from which a frame is transformed in bands of block rows (4 GiB in production)
 //   TIC_SSE_MAX_GROUPS      measuring kernel's descriptor form: workgroups per probe at most (1 ... 1024; default 1024), so that the walk runs on frames of a few blocks

@@ -102,7 +102,16 @@ struct SseArgs {           // idct_sse_kernel, beside its IdctArgs (whose out / 
 int dctq_kernel_id(int abi_variant);
 // ev_start / ev_stop (both or neither): bound to the strip kernel's own dispatch packet (hipExtLaunchKernelGGL) - its start and end
 // time stamps, without a marker packet in the queue; ignored for the exact kernel and for banded frames
-hipError_t launch_dctq(DctqArgs a, int variant, hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+// info (may be null): what the launcher decided for the strip kernel - host bookkeeping, nothing of it reaches the kernel.  All zero when
+// the strip kernel did not run (the exact kernel took the whole frame); of a banded frame, the last band's.
+struct StripLaunchInfo {
+    int order;      // 0: no strip launch, 1: rows first (dctq_strip_kernel<false>), 2: columns first (dctq_strip_kernel<true>)
+    int kind;       // kStripRows / kStripChunk / kStripRound (tic_strip_plan.h)
+    int team_count; // > 0: the team schedule
+    int grid_x, grid_y, tstep, fast_tx, fast_ty;
+};
+hipError_t launch_dctq(DctqArgs a, int variant, hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
+                       StripLaunchInfo *info = nullptr);
 hipError_t launch_dctq_wide(const WideArgs &a, hipStream_t stream);
 hipError_t launch_idct(const IdctArgs &a, hipStream_t stream);
 // One launch for the frames of a chunk: d_args[f] (device memory; whole-frame form, no dc32) and a table of nwgs workgroups, {frame, first

@@ -1262,7 +1262,7 @@ static inline int grid_for(int ntiles) { return (ntiles + kWavesPerWG - 1) / kWa
 
 // Schedule knobs of the strip kernel's launcher.  The product uses the defaults below; the environment is consulted only behind
 // the test-hook gate (tic_hooks.h, TIC_TEST_HOOKS=1: tests/test_gpu_parity.py::test_strip_schedules_are_equivalent drives every
-// schedule against the exact kernel) - read once, or at every launch when TIC_TUNE is set too.
+// schedule against the exact kernel) - read once, or at every launch while TIC_TUNE is set too (it may be set at any time).
 struct Tunables {
     int max_wgs, sched, chunk, order;
     int split[8];
@@ -1288,9 +1288,11 @@ static Tunables read_tunables() {
     return t;
 }
 static Tunables tunables() {
-    static const bool live = test_hook("TIC_TUNE") != nullptr;
+    // TIC_TUNE is looked up at every launch (rounds 1-6 latched it with the first launch of the process: a test that set it later - every
+    // one of the suite's, behind an earlier test's launch - forced nothing).  The shipped build reads no environment: test_hook is a
+    // constant nullptr there and this is `once`.
     static const Tunables once = read_tunables();
-    return live ? read_tunables() : once;
+    return test_hook("TIC_TUNE") != nullptr ? read_tunables() : once;
 }
 
 int dctq_kernel_id(int abi_variant) { // (TIC_KERNEL_AUTO 0, TIC_KERNEL_EXACT 1, TIC_KERNEL_HYBRID 2: include/tinyimgcodec_hip.h)
@@ -1299,7 +1301,8 @@ int dctq_kernel_id(int abi_variant) { // (TIC_KERNEL_AUTO 0, TIC_KERNEL_EXACT 1,
 
 // variant 1: the exact kernel for every block; variant 2: the strip kernel on the rectangle of complete 64x8 strips with 8-byte
 // aligned rows, the exact kernel on what is left (right / bottom padding).
-hipError_t launch_dctq(DctqArgs a, int variant, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop) {
+hipError_t launch_dctq(DctqArgs a, int variant, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, StripLaunchInfo *info) {
+    if (info) *info = StripLaunchInfo{};
     if (a.ntiles <= 0) return hipSuccess;
     if (variant != 1 && variant != 2) return hipErrorInvalidValue;
     dim3 block(kWavesPerWG * 64);
@@ -1327,7 +1330,7 @@ hipError_t launch_dctq(DctqArgs a, int variant, hipStream_t stream, hipEvent_t e
                     b.img = a.img + y0 * a.stride;
                     b.out = a.out + (y0 / 8) * (long)a.bw * 64;
                     b.ntiles = ((b.h + 7) / 8) * b.tiles_x;
-                    const hipError_t e = launch_dctq(b, variant, stream);
+                    const hipError_t e = launch_dctq(b, variant, stream, nullptr, nullptr, info); // (the report: the last band's)
                     if (e != hipSuccess) return e;
                 }
                 return hipSuccess;
@@ -1375,6 +1378,10 @@ hipError_t launch_dctq(DctqArgs a, int variant, hipStream_t stream, hipEvent_t e
         // of several rounds (dynamic dispatch: the average cost per strip decides); TIC_ORDER (test hook) forces one
         const bool cols = tune.order < 0 ? !pl.multi_round : tune.order == 1;
         auto *kern = cols ? dctq_strip_kernel<true> : dctq_strip_kernel<false>;
+        if (info) {
+            info->order = cols ? 2 : 1, info->kind = (int)(hd.misc & 0xffu), info->team_count = pl.team_count;
+            info->grid_x = (int)pl.grid_x, info->grid_y = (int)pl.grid_y, info->tstep = pl.tstep, info->fast_tx = pl.fast_tx, info->fast_ty = pl.fast_ty;
+        }
         if (ev_start && ev_stop) // the dispatch packet's own time stamps (tic_dctq_dev_timed_warm's per-launch times)
             hipExtLaunchKernelGGL(kern, grid, block, 0, stream, ev_start, ev_stop, 0, a.img, a.consts, hd.split, hd.stride, hd.misc, hd.tstep, hd.nfast,
                                   hd.fast_tx, hd.magic_fast_tx, hd.in_step32, hd.step_tx, wm, a);
