@@ -186,3 +186,60 @@ def test_the_rounds_cases_have_the_figures_of_k_25_26_and_29():
     assert figs["rounds_early"] == (5049, 213325, 2527, [1, 30, 0])
     assert figs["rounds_late"][:3] == (21386, 903317, 10705) and figs["rounds_late"][3].index(0) == 42
     assert 10 <= figs["rounds_mid"][3].index(0) <= 18
+
+
+def test_host_half_of_the_decoder_under_sanitizers(cases, streams, tmp_path):
+    """tests/native/adaptive_host_selftest.cpp: tic_adaptive.cpp (adaptive_parse_table, adaptive_decode, adaptive_dec_tab_build) and
+    tic_entropy.cpp compiled as HOST code with AddressSanitizer + UBSan - the parser of an embedded table from untrusted bytes and the
+    builder of the look-up table device lanes index, which only tests marked gpu reached.  Per case the program gets the stream,
+    decode_model's coefficients (or that it raises) and lut_model's tables, works on exact-size heap copies and checks (a) adaptive_decode
+    against the model, (b) the parsed and built tables against lut_model, and adaptive_dec_tab_buildable against the build, (c) on boundary
+    and max_table every single-bit flip of the table region and every cut from 16 bytes to the payload's first byte: parser and decoder
+    agree about the table, a table that parses is a prefix code (brute force), a built look-up table names only its entries.
+    too_wide is the one case where the product refuses what the model reads: a symbol of 65 bits with its value, beyond the 64 the
+    header documents - written as an error, with no tables."""
+    import shutil
+    import struct
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    if shutil.which("g++") is None:
+        pytest.skip("no host compiler")
+    if not os.path.exists(os.path.join(rocm, "include", "hip", "hip_runtime.h")):
+        pytest.skip("hip/hip_runtime.h is absent: tic_adaptive.h includes it")
+    path = tmp_path / "cases.bin"
+    with open(path, "wb") as f:
+        f.write(b"TICA" + struct.pack("<I", len(cases)))
+        for name, c in cases.items():
+            s = streams[name]
+            f.write(struct.pack("<I", len(name)) + name.encode() + struct.pack("<I", len(s)) + s)
+            refused = name == "too_wide"
+            try:
+                zz = AT.decode_model(s)
+            except ValueError:  # (NoCode is one)
+                zz = None
+            assert (zz is None) == (name == "damaged_chain"), name
+            if zz is None or refused:
+                f.write(b"\0")
+            else:
+                f.write(b"\1" + struct.pack("<I", len(zz)) + np.ascontiguousarray(zz, dtype="<i2").tobytes())
+            if refused:
+                f.write(b"\0")
+            else:
+                lut = AT.lut_model(AT.parse(s)[3])
+                f.write(b"\1")
+                for key in ("DC", "AC"):
+                    t = lut[key]
+                    f.write(np.array([0 if e is None else (e[0] << 8) | e[1] for e in t["prim"]], "<u2").tobytes())
+                    f.write(struct.pack("<I", len(t["codes"])) + np.array(t["codes"], "<u8").tobytes() + np.array([(n << 8) | y for n, y in t["ls"]], "<u2").tobytes())
+            f.write(b"\1" if name in ("boundary", "max_table") else b"\0")
+    exe = tmp_path / "adaptive_host_selftest"
+    csrc = os.path.join(root, "tinyimgcodec_amd", "csrc")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__",
+                    "-I" + os.path.join(rocm, "include"), "-o", str(exe), os.path.join(root, "tests", "native", "adaptive_host_selftest.cpp"),
+                    os.path.join(csrc, "tic_adaptive.cpp"), os.path.join(csrc, "tic_entropy.cpp"), "-lpthread"], check=True)
+    r = subprocess.run([str(exe), str(path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert ("adaptive_host_selftest ok %d cases" % len(cases)) in r.stdout and not r.stderr, r.stdout + r.stderr
+    print(r.stdout.strip())
