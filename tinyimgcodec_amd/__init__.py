@@ -8,13 +8,17 @@ stream without producing it), compress_to_size (the best quality within a byte b
 compress_batch_to_size (a list of images of any shapes in one call, a byte budget per frame) and entropy_size; and for rate-distortion
 control: rd_points (size and exact round-trip error per quality), roundtrip_psnr, compress_to_psnr (the smallest stream at no less
 than a PSNR), their batch forms rd_points_batch and compress_batch_to_psnr (a list of images of any shapes in one call, a PSNR target per
-frame), roundtrip_sse_scaled and psnr_from_sse.
+frame), roundtrip_sse_scaled and psnr_from_sse; and for rate control of the adaptive family: compressed_size_adaptive /
+compressed_sizes_adaptive (the length of compress_adaptive()'s stream without producing it), compress_adaptive_to_size (the best quality
+within a byte budget, with the image's own tables), compressed_sizes_adaptive_batch (a list of images of any shapes in one call) and
+entropy_size_adaptive (the same length from coefficients, on the host).
 """
 from ._native import Context, NativeError, NativeUnavailable
 from .codec import (compress, compress_adaptive, compress_batch, compress_batch_adaptive, compress_batch_to_psnr, compress_batch_scaled, compress_batch_to_size, compress_scaled, compress_to_psnr, compress_to_size,
                     compressed_size, compressed_sizes, compressed_sizes_batch, dctq, dctq_scaled, decode, decompress, decompress_adaptive, decompress_batch, decompress_batch_adaptive, encode, entropy_encode,
                     entropy_encode_adaptive, entropy_encode_adaptive_batch, entropy_encode_scaled, entropy_size, max_sse_for_psnr, parse_header, psnr_from_sse, rd_points, rd_points_batch, rd_points_scaled_batch,
                     roundtrip_psnr, roundtrip_sse_scaled)
+from .codec import compress_adaptive_to_size, compressed_size_adaptive, compressed_sizes_adaptive, compressed_sizes_adaptive_batch, entropy_size_adaptive
 
 __version__ = "0.1.0"
 __all__ = ["encode", "decode", "compress", "decompress"]

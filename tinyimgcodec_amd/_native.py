@@ -309,6 +309,33 @@ SIGNATURES = {
     "tic_rdv_wait": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64]),
 }
 
+# ... and exactly the symbols include/tinyimgcodec_hip_adaptive_rate.h declares: rate control for the adaptive family, a header and a table of
+# its own beside the main ones, bound by the same load()
+RATE_ADAPTIVE_SIGNATURES = {
+    "tic_adaptive_stream_size": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "tic_entropy_size_adaptive": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "tic_adaptive_stats_v_dev": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "tic_adaptive_stats_v_dev_timed": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)],
+    ),
+    "tic_adaptive_sizes_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "tic_adaptive_sizes": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "tic_compress_adaptive_to_size": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+         C.POINTER(C.c_int)],
+    ),
+    "tic_adaptive_sizes_v": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ssize_t), C.c_void_p, C.c_int, C.c_void_p],
+    ),
+    "tic_last_adaptive_rate": (C.c_int, [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+}
+
 _lib = None
 _lock = threading.RLock()  # re-entrant: default_context() creates a Context (which calls load()) under it
 
@@ -328,7 +355,7 @@ def load():
                 L = C.CDLL(path)
             except OSError as e:  # missing ROCm runtime etc.
                 raise NativeUnavailable("cannot load %s: %s" % (path, e)) from e
-            for name, (res, args) in SIGNATURES.items():
+            for name, (res, args) in list(SIGNATURES.items()) + list(RATE_ADAPTIVE_SIGNATURES.items()):
                 fn = getattr(L, name)
                 fn.restype = res
                 fn.argtypes = args

@@ -983,6 +983,118 @@ def entropy_encode_adaptive_batch(coeffs_list, shapes, qualities, ctx=None):
     return _adaptive_batch(ctx, call, frames, [L.tic_compress_bound(f[1], f[2]) + 4096 for f in frames])
 
 
+def _no_blocks_adaptive(L, h, w):
+    if L.tic_num_blocks(h, w) == 0:
+        raise IndexError("index -1 is out of bounds for axis 0 with size 0")  # calc_huffman_table on an empty symbol list, as compress_adaptive
+
+
+def entropy_size_adaptive(coeffs_zz, height, width):
+    """len(entropy_encode_adaptive(coeffs_zz, height, width, q)) for any quality, from a host walk of the symbols and the table they give
+    (no GPU needed): the length of an adaptive stream is a function of its symbol statistics alone.  IndexError for a frame without
+    blocks, OverflowError where the encoder raises it (a DC category or AC size above 15, a code and its value bits beyond 64 bits)."""
+    L = N.load()
+    height, width = int(height), int(width)
+    zz = np.ascontiguousarray(coeffs_zz, dtype=np.int16)
+    if height < 0 or width < 0:
+        raise ValueError("negative image size")
+    nb = L.tic_num_blocks(height, width)
+    if zz.size != nb * 64:
+        raise ValueError("coefficients of shape %r do not match %d blocks of 64" % (zz.shape, nb))
+    _no_blocks_adaptive(L, height, width)
+    n = C.c_size_t(0)
+    rc = L.tic_entropy_size_adaptive(zz.ctypes.data, height, width, C.byref(n))
+    if rc == N.TIC_E_RANGE:
+        raise OverflowError("a DC category or AC size above 15, or a Huffman code and its value bits beyond 64 bits")
+    if rc != N.TIC_OK:
+        raise N.NativeError(rc, "tic_entropy_size_adaptive failed")
+    return int(n.value)
+
+
+def compressed_sizes_adaptive(image, qualities, ctx=None):
+    """len(compress_adaptive(image, q)) for every q of `qualities` -> int64 array, -1 where compress_adaptive() would raise
+    OverflowError.  No stream is produced: per quality the transform, one statistics launch for up to 64 qualities, one read-back of the
+    symbol statistics, the tables and lengths on the host.  Validation as compressed_sizes; a frame without blocks raises IndexError, as
+    compress_adaptive."""
+    img, h, w = _as_u8_image(image)
+    qs = [_check_quality(q, packs_header=True) for q in qualities]
+    L = N.load()
+    _no_blocks_adaptive(L, h, w)
+    sizes = np.zeros(len(qs), dtype=np.int64)
+    if not qs:
+        return sizes
+    ctx = _ctx(ctx)
+    qarr = np.asarray(qs, dtype=np.intc)
+    with ctx.lock:
+        ctx.check(L.tic_adaptive_sizes(ctx.handle, img.ctypes.data, h, w, img.strides[0], qarr.ctypes.data, len(qs), sizes.ctypes.data))
+    return sizes
+
+
+def compressed_size_adaptive(image, quality=50, ctx=None):
+    """len(compress_adaptive(image, quality)) without producing the stream; the same exceptions for the same arguments."""
+    size = int(compressed_sizes_adaptive(image, [quality], ctx=ctx)[0])
+    if size < 0:
+        raise OverflowError("a DC category or AC size above 15, or a Huffman code and its value bits beyond 64 bits")  # as compress_adaptive
+    return size
+
+
+def compress_adaptive_to_size(image, max_bytes, min_quality=1, max_quality=99, ctx=None):
+    """compress_to_size with per-image Huffman tables -> (bytes, quality): compress_adaptive(image, quality) of the quality at which
+    compress_to_size's bisection over min_quality..max_quality ends, with "compress_adaptive() succeeds and len(...) <= max_bytes" as its
+    test.  The adaptive stream is the smallest at any quality, so the same budget buys a higher quality.  Probes are compressed_sizes_adaptive's,
+    several steps ahead per submission.  ValueError naming the size at min_quality when even that exceeds the budget, OverflowError when
+    min_quality has no adaptive stream, IndexError for a frame without blocks; 8-bit images only."""
+    img, h, w = _as_u8_image(image)
+    qmin = _check_quality(min_quality, packs_header=True)
+    qmax = _check_quality(max_quality, packs_header=True)
+    if qmin > qmax:
+        raise ValueError("min_quality %d above max_quality %d" % (qmin, qmax))
+    max_bytes = int(max_bytes)
+    if max_bytes < 0:
+        raise ValueError("max_bytes must not be negative")
+    L = N.load()
+    _no_blocks_adaptive(L, h, w)
+    ctx = _ctx(ctx)
+    cap = L.tic_compress_bound(h, w) + 4096
+    with ctx.lock:
+        for _ in range(2):
+            out = getattr(ctx, "_adapt_buf", None)  # compress_adaptive's landing buffer
+            if out is None or out.size < cap:
+                out = ctx._adapt_buf = np.empty(cap, dtype=np.uint8)
+            n, q = C.c_size_t(0), C.c_int(0)
+            rc = L.tic_compress_adaptive_to_size(ctx.handle, img.ctypes.data, h, w, img.strides[0], max_bytes, qmin, qmax, out.ctypes.data, cap,
+                                                 C.byref(n), C.byref(q))
+            if rc == N.TIC_E_SPACE and n.value > cap and n.value <= max_bytes:  # the first guess of the stream's size was short
+                cap = n.value
+                continue
+            break
+        if rc == N.TIC_E_RANGE:
+            raise OverflowError(L.tic_last_error(ctx.handle).decode())
+        if rc == N.TIC_E_SPACE:
+            raise ValueError("%d bytes at quality %d exceed max_bytes = %d" % (n.value, qmin, max_bytes))
+        ctx.check(rc)
+        return out[: n.value].tobytes(), int(q.value)
+
+
+def compressed_sizes_adaptive_batch(images, qualities, ctx=None):
+    """compressed_sizes_adaptive(image, qualities) of every image of a list, of any shapes, in one call -> int64 array (n, nq); -1 where
+    compress_adaptive() would raise OverflowError.  Per chunk of up to 64 frames one upload, every probe queued, one statistics launch per
+    64 probes, one read-back (tic_adaptive_sizes_v).  Validation as compressed_sizes_batch; a frame without blocks raises IndexError."""
+    frames = [_as_u8_image(im) for im in images]
+    qs = [_check_quality(q, packs_header=True) for q in qualities]
+    L = N.load()
+    for _, h, w in frames:
+        _no_blocks_adaptive(L, h, w)
+    sizes = np.zeros((len(frames), len(qs)), dtype=np.int64)
+    if not frames or not qs:
+        return sizes
+    ctx = _ctx(ctx)
+    qarr = np.asarray(qs, dtype=np.intc)
+    inp, hs, ws, strides = _frame_arrays(frames)
+    with ctx.lock:
+        ctx.check(L.tic_adaptive_sizes_v(ctx.handle, inp, len(frames), hs, ws, strides, qarr.ctypes.data, len(qs), sizes.ctypes.data))
+    return sizes
+
+
 def decompress_adaptive(data, ctx=None):
     """Reads a stream of compress_adaptive() (or of the reference's compress(..., auto_generate_huffman_table=True)) as written:
     Huffman decode with the embedded table (on the GPU for streams of 16,384 blocks, or 1,024 blocks and 32 KB of payload, and more;

@@ -225,6 +225,75 @@ int huffman_table_build(const unsigned long long *dc_count, const unsigned long 
     return TIC_OK;
 }
 
+unsigned long long adaptive_stream_bits(const unsigned long long *dc_count, const unsigned long long *ac_count, const uint8_t *dc_len,
+                                        const uint8_t *ac_len, size_t table_bits) {
+    unsigned long long bits = 128ull + table_bits;
+    for (int rs = 0; rs < 256; rs++) bits += ac_count[rs] * (unsigned long long)(ac_len[rs] + (unsigned)(rs & 15));
+    for (int c = 0; c < 16; c++) bits += dc_count[c] * (unsigned long long)(dc_len[c] + (unsigned)c);
+    return bits;
+}
+
+int adaptive_stream_size(const unsigned long long *dc_count, const unsigned long long *dc_first, const unsigned long long *ac_count,
+                         const unsigned long long *ac_first, size_t *bytes) {
+    if (!bytes) return TIC_E_ARG;
+    unsigned long long dc_code[16], ac_code[256];
+    uint8_t dc_len[16], ac_len[256], table[kAdaptMaxTableBytes];
+    size_t tbits = 0;
+    const int rc = huffman_table_build(dc_count, dc_first, ac_count, ac_first, dc_code, dc_len, ac_code, ac_len, table, sizeof table, &tbits);
+    if (rc) return rc;
+    *bytes = (size_t)((adaptive_stream_bits(dc_count, ac_count, dc_len, ac_len, tbits) + 7) / 8);
+    return TIC_OK;
+}
+
+void adaptive_host_stats(const int16_t *zz, size_t n, AdaptStats *st) {
+    for (int i = 0; i < kAdaptBins; i++) st->count[i] = 0ull, st->first[i] = ~0ull;
+    st->err = 0u;
+    auto bit_len = [](int v) {
+        unsigned a = (unsigned)(v < 0 ? -v : v);
+        int s = 0;
+        for (; a; a >>= 1) s++;
+        return s;
+    };
+    auto hit = [&](int bin, unsigned long long key) {
+        st->count[bin]++;
+        if (key < st->first[bin]) st->first[bin] = key;
+    };
+    int prev_dc = 0;
+    for (size_t b = 0; b < n; b++) {
+        const int16_t *c = zz + b * 64;
+        const int dsz = bit_len((int)c[0] - prev_dc); // codec.py:34-35: the first block raw
+        prev_dc = c[0];
+        if (dsz > 15) st->err = 1u;
+        hit(kAdaptDcBin + (dsz & 15), b);
+        int last = 63;
+        while (last > 0 && c[last] == 0) last--; // trailing zeros: no symbols (huffman.py:16-17)
+        int run = 0;
+        unsigned long long ord = 0;
+        for (int k = 1; k <= last; k++) {
+            if (c[k] == 0) {
+                run++;
+                continue;
+            }
+            for (; run >= 16; run -= 16) hit(0xF0, b * 64ull + ord++); // ZRL (huffman.py:24-28)
+            const int sz = bit_len(c[k]);
+            if (sz > 15) st->err = 1u;
+            hit((run << 4) | (sz & 15), b * 64ull + ord++);
+            run = 0;
+        }
+        hit(0, b * 64ull + ord); // EOB (huffman.py:33)
+    }
+}
+
+int entropy_size_adaptive(const int16_t *zz, int h, int w, size_t *bytes) {
+    if (!bytes || h < 0 || w < 0) return TIC_E_ARG;
+    const size_t n = num_blocks(h, w);
+    if (n == 0 || !zz) return TIC_E_ARG; // no blocks: no symbol to build a table from (the reference raises IndexError)
+    AdaptStats st;
+    adaptive_host_stats(zz, n, &st);
+    if (st.err) return TIC_E_RANGE;
+    return adaptive_stream_size(st.count + kAdaptDcBin, st.first + kAdaptDcBin, st.count, st.first, bytes);
+}
+
 // The header's flag and read_huffman_table (codec.py:87-99): the tries of the host decoder, the entries for the device decoder's
 // tables (t may be null); r is left at the payload's first bit.
 static int parse_table(const uint8_t *data, size_t len, BitIn &r, Trie &dc, Trie &ac, AdaptTable *t, const char **why) {

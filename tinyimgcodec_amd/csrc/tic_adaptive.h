@@ -20,6 +20,24 @@ int huffman_table_build(const unsigned long long *dc_count, const unsigned long 
                         const unsigned long long *ac_first, unsigned long long *dc_code, uint8_t *dc_len, unsigned long long *ac_code,
                         uint8_t *ac_len, uint8_t *table, size_t table_cap, size_t *table_bits);
 
+// The length of an adaptive stream is a function of the symbol statistics alone: the table comes from counts and first-occurrence keys,
+// the payload is counts x (code length + value bits).  adaptive_stream_bits: header (128), table and payload bits of a stream whose
+// table huffman_table_build made (dc_len / ac_len) from these counts - the ONE expression every encoder and every size entry takes its
+// length from.  adaptive_stream_size: the table build and that sum, *bytes = the bits rounded up to a byte (bitbuffer.py:17-18); TIC_E_ARG
+// and TIC_E_RANGE exactly where huffman_table_build returns them.
+unsigned long long adaptive_stream_bits(const unsigned long long *dc_count, const unsigned long long *ac_count, const uint8_t *dc_len,
+                                        const uint8_t *ac_len, size_t table_bits);
+int adaptive_stream_size(const unsigned long long *dc_count, const unsigned long long *dc_first, const unsigned long long *ac_count,
+                         const unsigned long long *ac_first, size_t *bytes);
+// The statistics adaptive_stats_kernel leaves for the n blocks of zz (int16 [n][64] zig-zag, absolute DC), walked on the host with
+// block_symbols' definition (tic_adaptive_gpu.hip): DPCM against the block before (the first against 0), run lengths, a ZRL per 16 zeros,
+// an EOB behind every block, trailing zeros silent.  st->err = 1 for a DC category or AC size above 15 (counted in bin size & 15, as the
+// kernel does).
+void adaptive_host_stats(const int16_t *zz, size_t n, AdaptStats *st);
+// The adaptive twin of entropy_size: adaptive_host_stats, then adaptive_stream_size.  A frame without blocks TIC_E_ARG (no symbol to build
+// a table from), a category or size above 15 TIC_E_RANGE.
+int entropy_size_adaptive(const int16_t *zz, int h, int w, size_t *bytes);
+
 // decompress()'s Huffman + run-length part (codec.py:167-189, huffman.py:36-38,66-98) for a stream with an embedded table, read
 // as written (flag 1 << 31 most significant bit first): zz = int16 [N][64] zig-zag with the DC integrated.  Strict: TIC_E_STREAM for
 // a malformed table (not a prefix code, a code the stream then meets without a symbol, counts out of range), a truncated stream,

@@ -18,7 +18,9 @@
 #include <vector>
 
 #include "../../include/tinyimgcodec_hip.h"
+#include "../../include/tinyimgcodec_hip_adaptive_rate.h"
 #include "tic_adaptive.h"
+#include "tic_adaptive_stats_gpu.h"
 #include "tic_decode_plan.h"
 #include "tic_entropy.h"
 #include "tic_entropy_dec_gpu.h"
@@ -326,6 +328,14 @@ struct tic_ctx {
     int last_sbatch_frames = 0, last_sbatch_single = 0, last_sbatch_chunks = 0, last_sbatch_launches = 0; // tic_last_compress_batch_scaled
     int last_srd_frames = 0, last_srd_single = 0, last_srd_chunks = 0, last_srd_launches = 0, last_srd_size_launches = 0,
         last_srd_sse_launches = 0; // tic_last_rd_scaled_batch
+    // rate control of the adaptive family (tic_adaptive_sizes, tic_compress_adaptive_to_size, tic_adaptive_sizes_v): the statistics of a
+    // submission's probes on the device and their pinned landing buffer, the frame tables of adaptive_stats_v_kernel where that kernel is
+    // asked for (the probe kernel's tables are h_rate_tabs / d_rate_tabs), and what the last call did.  All grow on demand.
+    AdaptStats *d_arate_stats = nullptr, *h_arate_stats = nullptr;
+    size_t arate_dev_bytes = 0, arate_host_bytes = 0;
+    AdaptFrameTable *h_arate_frames = nullptr, *d_arate_frames = nullptr;
+    size_t arate_frames_host_bytes = 0, arate_frames_dev_bytes = 0;
+    int last_arate_probes = 0, last_arate_waits = 0, last_arate_launches = 0;
 };
 
 // NUMA node of a device (its PCI function's numa_node in sysfs) and the CPUs of that node within this process's affinity mask.
@@ -621,6 +631,10 @@ void tic_destroy(tic_ctx *ctx) {
     if (ctx->d_rd_tabs) (void)hipFree(ctx->d_rd_tabs);
     if (ctx->h_scaled_tabs) (void)hipHostFree(ctx->h_scaled_tabs);
     if (ctx->d_scaled_tabs) (void)hipFree(ctx->d_scaled_tabs);
+    if (ctx->d_arate_stats) (void)hipFree(ctx->d_arate_stats);
+    if (ctx->h_arate_stats) (void)hipHostFree(ctx->h_arate_stats);
+    if (ctx->h_arate_frames) (void)hipHostFree(ctx->h_arate_frames);
+    if (ctx->d_arate_frames) (void)hipFree(ctx->d_arate_frames);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -4941,14 +4955,12 @@ static int adaptive_encode_dev(tic_ctx *ctx, size_t n, int h, int w, int quality
         return set_err(ctx, rc, "a Huffman code of this frame and its value bits exceed %d bits", kAdaptMaxSymbolBits);
     if (rc) return set_err(ctx, rc, "Huffman table build failed");
     HuffWide tab;
-    unsigned long long payload = 0;
     for (int i = 0; i < kAdaptBins; i++) {
         const bool dc = i >= kAdaptDcBin;
         tab.code[i] = dc ? dc_code[i - kAdaptDcBin] : ac_code[i];
         tab.len[i] = dc ? dc_len[i - kAdaptDcBin] : ac_len[i];
-        payload += hs.count[i] * (tab.len[i] + (unsigned)(dc ? i - kAdaptDcBin : i & 15));
     }
-    const unsigned long long base = 128 + tbits, total = base + payload;
+    const unsigned long long base = 128 + tbits, total = adaptive_stream_bits(hs.count + kAdaptDcBin, hs.count, dc_len, ac_len, tbits);
     const size_t bytes = (size_t)((total + 7) / 8), words = (size_t)((total + 31) / 32);
     if (bytes > cap) {
         *out_len = bytes;
@@ -5084,15 +5096,13 @@ static int adaptive_pack_chunk(tic_ctx *ctx, const MixedPlan &p, Slot &s, hipStr
         if (rc == TIC_E_RANGE) return set_err(ctx, rc, "frame %d: a Huffman code of this frame and its value bits exceed %d bits", f.index, kAdaptMaxSymbolBits);
         if (rc) return set_err(ctx, rc, "frame %d: Huffman table build failed", f.index);
         HuffWide &tab = v.h_tabs[k];
-        unsigned long long payload = 0;
         for (int i = 0; i < kAdaptBins; i++) {
             const bool dc = i >= kAdaptDcBin;
             tab.code[i] = dc ? dc_code[i - kAdaptDcBin] : ac_code[i];
             tab.len[i] = dc ? dc_len[i - kAdaptDcBin] : ac_len[i];
-            payload += hs.count[i] * (tab.len[i] + (unsigned)(dc ? i - kAdaptDcBin : i & 15));
         }
         base_bits[k] = (uint32_t)(128 + tbits);
-        const unsigned long long total = 128ull + tbits + payload;
+        const unsigned long long total = adaptive_stream_bits(hs.count + kAdaptDcBin, hs.count, dc_len, ac_len, tbits);
         const size_t bytes = (size_t)((total + 7) / 8);
         call.io.out_lens[f.index] = bytes;
         const bool fits = bytes <= call.io.caps[f.index];
@@ -5649,6 +5659,372 @@ int tic_decompress_adaptive_dev(tic_ctx *ctx, const void *d_stream, size_t len, 
         if (!d_out || (size_t)(h - 1) * (size_t)out_stride + (size_t)w > out_cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
     }
     return decompress_adaptive_impl(ctx, (const uint8_t *)d_stream, len, true, head, head_len, h, w, q, (uint8_t *)d_out, true, (size_t)out_stride);
+}
+
+// ---- rate control of the adaptive family (include/tinyimgcodec_hip_adaptive_rate.h) ------------------------------------------------------------
+// The length of an adaptive stream is a function of its symbol statistics alone (adaptive_stream_size, tic_adaptive.cpp), so a PROBE here is
+// the transform into the coefficient workspace and the statistics of what it left: the probes of a submission lie back to back in the
+// workspace (layout_rate_submission: passes where they exceed it), one statistics launch takes up to kSizeMaxProbes of them, ONE read-back
+// brings all their statistics, and the host builds a table and a length per probe.  Plan, chunks, uploads, transform runs and the bisection
+// are rate control's (tic_rate_plan.h); a single frame is a plan of one frame.
+int tic_adaptive_stream_size(const uint64_t *dc_count, const uint64_t *dc_first, const uint64_t *ac_count, const uint64_t *ac_first, size_t *bytes) {
+    return adaptive_stream_size((const unsigned long long *)dc_count, (const unsigned long long *)dc_first, (const unsigned long long *)ac_count,
+                                (const unsigned long long *)ac_first, bytes);
+}
+
+int tic_entropy_size_adaptive(const int16_t *coeffs_zz, int h, int w, size_t *bytes) { return entropy_size_adaptive(coeffs_zz, h, w, bytes); }
+
+// The statistics kernel of the size and search routes: 0 = adaptive_stats_probe_kernel_v, 1 = adaptive_stats_v_kernel (profiles/adaptive_rate.txt).
+static constexpr int kAdaptRateKernel = 0;
+
+// One statistics launch: probes [first, first + count) of a submission, back to back from block `first_block` of the coefficients.
+struct AdaptStatsLaunch {
+    size_t first_block;
+    int first, count;
+};
+
+// Buffers and tables of a submission of np probes (nblk[i] blocks each) cut into `launches`, queued on the context's stream: the statistics
+// reset (kernel 0; adaptive_stats_v resets its own), ONE upload of every launch's table.  groups[t]: launch t's grid.  Nothing of an
+// earlier submission may be in flight: the buffers may grow.
+static int prepare_adaptive_stats(tic_ctx *ctx, const std::vector<AdaptStatsLaunch> &launches, const size_t *nblk, int np, int kernel, int max_groups,
+                                  std::vector<size_t> &groups) {
+    const size_t st_bytes = (size_t)np * sizeof(AdaptStats), st_alloc = align_up(st_bytes, 65536);
+    int rc = grow_dev(ctx, "d_arate_stats", ctx->d_arate_stats, ctx->arate_dev_bytes, st_bytes, st_alloc);
+    if (rc) return rc;
+    rc = grow_pinned(ctx, "h_arate_stats", ctx->h_arate_stats, ctx->arate_host_bytes, st_bytes, st_alloc);
+    if (rc) return rc;
+    const size_t nt = launches.size();
+    groups.assign(nt, 0);
+    if (kernel == 0) {
+        const size_t tab_bytes = nt * sizeof(SizeProbeTable), tab_alloc = align_up(tab_bytes, 16384);
+        rc = grow_pinned(ctx, "h_rate_tabs", ctx->h_rate_tabs, ctx->rate_tabs_host_bytes, tab_bytes, tab_alloc);
+        if (rc) return rc;
+        rc = grow_dev(ctx, "d_rate_tabs", ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, tab_bytes, tab_alloc);
+        if (rc) return rc;
+        for (size_t t = 0; t < nt; t++) {
+            const AdaptStatsLaunch &l = launches[t];
+            uint32_t result[kSizeMaxProbes];
+            size_t total = 0;
+            for (int k = 0; k < l.count && k < kSizeMaxProbes; k++) result[k] = (uint32_t)(l.first + k);
+            if (!fill_size_probe_table(&ctx->h_rate_tabs[t], l.count, nblk + l.first, result, &groups[t], &total) ||
+                !cap_probe_groups(&ctx->h_rate_tabs[t], l.count, max_groups, &groups[t]))
+                return set_err(ctx, TIC_E_ARG, "adaptive statistics: probes %d.. have no table", l.first);
+        }
+        HIPCHK(ctx, adaptive_stats_probe_reset(ctx->d_arate_stats, np, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_rate_tabs, ctx->h_rate_tabs, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        const size_t tab_bytes = nt * sizeof(AdaptFrameTable), tab_alloc = align_up(tab_bytes, 16384);
+        rc = grow_pinned(ctx, "h_arate_frames", ctx->h_arate_frames, ctx->arate_frames_host_bytes, tab_bytes, tab_alloc);
+        if (rc) return rc;
+        rc = grow_dev(ctx, "d_arate_frames", ctx->d_arate_frames, ctx->arate_frames_dev_bytes, tab_bytes, tab_alloc);
+        if (rc) return rc;
+        for (size_t t = 0; t < nt; t++) {
+            size_t total = 0;
+            if (!fill_adaptive_table(&ctx->h_arate_frames[t], launches[t].count, nblk + launches[t].first, &total, &groups[t]))
+                return set_err(ctx, TIC_E_ARG, "adaptive statistics: probes %d.. have no table", launches[t].first);
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_arate_frames, ctx->h_arate_frames, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return TIC_OK;
+}
+
+// Launch t of a prepared submission on the coefficients at d_zz (block 0 of the submission's layout).
+static hipError_t launch_adaptive_stats(tic_ctx *ctx, const int16_t *d_zz, const AdaptStatsLaunch &l, size_t t, int kernel, size_t groups) {
+    ctx->last_arate_launches++;
+    if (kernel == 0) return adaptive_stats_probe_v(d_zz + l.first_block * 64, ctx->d_rate_tabs + t, groups, ctx->d_arate_stats, ctx->stream);
+    return adaptive_stats_v(d_zz + l.first_block * 64, ctx->d_arate_frames + t, l.count, groups, ctx->d_arate_stats + l.first, ctx->stream);
+}
+
+static int check_stats_v_args(tic_ctx *ctx, const void *d_coeffs_zz, int nprobes, const size_t *nblocks, int kernel, int max_groups) {
+    if (nprobes < 1 || nprobes > kSizeMaxProbes) return set_err(ctx, TIC_E_ARG, "probe count %d outside 1..%d", nprobes, kSizeMaxProbes);
+    if (!d_coeffs_zz || !nblocks) return set_err(ctx, TIC_E_ARG, "null coefficient pointer or block counts");
+    if (kernel != 0 && kernel != 1) return set_err(ctx, TIC_E_ARG, "kernel %d is neither 0 (probe kernel) nor 1 (adaptive_stats_v_kernel)", kernel);
+    if (max_groups < 0) return set_err(ctx, TIC_E_ARG, "negative workgroup cap %d", max_groups);
+    for (int k = 0; k < nprobes; k++)
+        if (nblocks[k] == 0) return set_err(ctx, TIC_E_ARG, "probe %d has no blocks", k);
+    return TIC_OK;
+}
+
+int tic_adaptive_stats_v_dev(tic_ctx *ctx, const void *d_coeffs_zz, int nprobes, const size_t *nblocks, int kernel, int max_groups, uint64_t *count,
+                             uint64_t *first, uint32_t *err) {
+    TIC_LOCK(ctx);
+    if (!ctx || !count || !first || !err) return TIC_E_ARG;
+    int rc = check_stats_v_args(ctx, d_coeffs_zz, nprobes, nblocks, kernel, max_groups);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const std::vector<AdaptStatsLaunch> launches{{0, 0, nprobes}};
+    std::vector<size_t> groups;
+    rc = prepare_adaptive_stats(ctx, launches, nblocks, nprobes, kernel, max_groups, groups);
+    if (rc) return rc;
+    HIPCHK(ctx, launch_adaptive_stats(ctx, (const int16_t *)d_coeffs_zz, launches[0], 0, kernel, groups[0]));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_arate_stats, ctx->d_arate_stats, (size_t)nprobes * sizeof(AdaptStats), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, wait_stream(ctx));
+    for (int k = 0; k < nprobes; k++) {
+        const AdaptStats &s = ctx->h_arate_stats[k];
+        memcpy(count + (size_t)k * kAdaptBins, s.count, sizeof s.count);
+        memcpy(first + (size_t)k * kAdaptBins, s.first, sizeof s.first);
+        err[k] = s.err;
+    }
+    return TIC_OK;
+}
+
+int tic_adaptive_stats_v_dev_timed(tic_ctx *ctx, const void *d_coeffs_zz, int nprobes, const size_t *nblocks, int kernel, int max_groups, int warm,
+                                   int iters, float *ms_total) {
+    TIC_LOCK(ctx);
+    if (!ctx || !ms_total || warm < 0 || iters <= 0) return TIC_E_ARG;
+    int rc = check_stats_v_args(ctx, d_coeffs_zz, nprobes, nblocks, kernel, max_groups);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const std::vector<AdaptStatsLaunch> launches{{0, 0, nprobes}};
+    std::vector<size_t> groups;
+    rc = prepare_adaptive_stats(ctx, launches, nblocks, nprobes, kernel, max_groups, groups);
+    if (rc) return rc;
+    return timed_launches(ctx, warm, iters, ms_total, nullptr, [&](int, hipEvent_t, hipEvent_t) {
+        if (kernel == 0) {
+            const hipError_t e = adaptive_stats_probe_reset(ctx->d_arate_stats, nprobes, ctx->stream);
+            if (e != hipSuccess) return e;
+        }
+        return launch_adaptive_stats(ctx, (const int16_t *)d_coeffs_zz, launches[0], 0, kernel, groups[0]);
+    });
+}
+
+// Stream length from a probe's statistics: -1 where tic_compress_adaptive returns TIC_E_RANGE (a category or size above 15, or a code
+// and its value bits beyond kAdaptMaxSymbolBits); any other failure of the table build is the call's.
+static int adaptive_probe_size(tic_ctx *ctx, const AdaptStats &st, long long *size) {
+    if (st.err) {
+        *size = -1;
+        return TIC_OK;
+    }
+    size_t bytes = 0;
+    const int rc = adaptive_stream_size(st.count + kAdaptDcBin, st.first + kAdaptDcBin, st.count, st.first, &bytes);
+    if (rc == TIC_E_RANGE) {
+        *size = -1;
+        return TIC_OK;
+    }
+    if (rc) return set_err(ctx, rc, "Huffman table build failed");
+    *size = (long long)bytes;
+    return TIC_OK;
+}
+
+// Queues the probes of `s` - frames of plan `p`, their pixels at img_base + MixedFrame::img_off - and the copy of their statistics into
+// ctx->h_arate_stats, entry i for probe i; the caller waits for the stream.  No host wait in here.
+static int submit_adaptive_probes(tic_ctx *ctx, const RatePlan &p, RateSubmission &s, const void *img_base) {
+    const int np = (int)s.probes.size();
+    layout_rate_submission(p.mixed, s, kRateWorkspaceBytes / 128);
+    int rc = ensure_scratch(ctx, 0, s.max_pass_blocks * 128 + 16);
+    if (rc) return rc;
+    std::vector<size_t> nblk((size_t)np);
+    for (int i = 0; i < np; i++) nblk[(size_t)i] = p.mixed.frames[(size_t)s.probes[(size_t)i].frame].nblk;
+    std::vector<AdaptStatsLaunch> launches;
+    for (size_t i = 0; i + 1 < s.pass_first.size(); i++)
+        for (int first = s.pass_first[i]; first < s.pass_first[i + 1]; first += kSizeMaxProbes)
+            launches.push_back(AdaptStatsLaunch{s.first_block[(size_t)first], first, std::min(kSizeMaxProbes, s.pass_first[i + 1] - first)});
+    std::vector<size_t> groups;
+    rc = prepare_adaptive_stats(ctx, launches, nblk.data(), np, kAdaptRateKernel, 0, groups);
+    if (rc) return rc;
+    size_t t = 0;
+    for (size_t i = 0; i + 1 < s.pass_first.size(); i++) {
+        const int end = s.pass_first[i + 1];
+        for (int k = s.pass_first[i]; k < end;) {
+            int h_total = 0;
+            const int m = rate_transform_run(p, s, k, end, &h_total);
+            const MixedFrame &f = p.mixed.frames[(size_t)s.probes[(size_t)k].frame];
+            DctqArgs a = make_args(ctx, (const char *)img_base + f.img_off, h_total, f.w, (ptrdiff_t)f.pitch, s.probes[(size_t)k].quality,
+                                   (int16_t *)ctx->d_coef + s.first_block[(size_t)k] * 64);
+            a.fallback_count = nullptr;
+            HIPCHK(ctx, launch_dctq(a, 2, ctx->stream));
+            k += m;
+        }
+        for (int first = s.pass_first[i]; first < end; first += kSizeMaxProbes, t++)
+            HIPCHK(ctx, launch_adaptive_stats(ctx, (const int16_t *)ctx->d_coef, launches[t], t, kAdaptRateKernel, groups[t]));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_arate_stats, ctx->d_arate_stats, (size_t)np * sizeof(AdaptStats), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->last_arate_probes += np;
+    return TIC_OK;
+}
+
+// A plan of ONE frame whose pixels lie at the submission's img_base with their own row stride.
+static RatePlan single_frame_rate_plan(int h, int w, ptrdiff_t row_stride, size_t n) {
+    RatePlan p;
+    MixedFrame f = MixedFrame();
+    f.index = 0, f.h = h, f.w = w, f.quality = 0;
+    f.nblk = n, f.pitch = (size_t)row_stride, f.img_bytes = (size_t)row_stride * (size_t)h;
+    p.mixed.frames.push_back(f);
+    p.run_of.push_back(0);
+    p.depth.push_back(rate_depth(n));
+    return p;
+}
+
+static void reset_adaptive_rate(tic_ctx *ctx) { ctx->last_arate_probes = ctx->last_arate_waits = ctx->last_arate_launches = 0; }
+
+static const char *const kAdaptNoBlocks = "an image without blocks has no symbols to build a table from (the reference raises IndexError)";
+
+// The probes of q[0 .. nq) on one resident frame: sizes[i], -1 where the encoder returns TIC_E_RANGE.  One submission, one wait.
+static int adaptive_sizes_impl(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, size_t n, const int *q, int nq, long long *sizes) {
+    const RatePlan p = single_frame_rate_plan(h, w, row_stride, n);
+    RateSubmission s;
+    for (int i = 0; i < nq; i++) s.probes.push_back(RateProbe{0, q[i]});
+    int rc = submit_adaptive_probes(ctx, p, s, d_image);
+    if (rc) return rc;
+    HIPCHK(ctx, wait_stream(ctx));
+    ctx->last_arate_waits++;
+    for (int i = 0; i < nq; i++) {
+        rc = adaptive_probe_size(ctx, ctx->h_arate_stats[i], &sizes[i]);
+        if (rc) return rc;
+    }
+    return TIC_OK;
+}
+
+int tic_adaptive_sizes_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq, long long *sizes) {
+    TIC_LOCK(ctx);
+    int rc = check_size_args(ctx, h, w, row_stride, qualities, nq, sizes); // (a bad quality fails here: nothing has been queued)
+    if (rc) return rc;
+    reset_adaptive_rate(ctx);
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return set_err(ctx, TIC_E_ARG, "%s", kAdaptNoBlocks);
+    if (nq == 0) return TIC_OK;
+    if (!d_image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return adaptive_sizes_impl(ctx, d_image, h, w, row_stride, n, qualities, nq, sizes);
+}
+
+int tic_adaptive_sizes(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, const int *qualities, int nq, long long *sizes) {
+    TIC_LOCK(ctx);
+    int rc = check_size_args(ctx, h, w, row_stride, qualities, nq, sizes);
+    if (rc) return rc;
+    reset_adaptive_rate(ctx);
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return set_err(ctx, TIC_E_ARG, "%s", kAdaptNoBlocks);
+    if (nq == 0) return TIC_OK;
+    if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    size_t pitch = 0;
+    rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
+    if (rc) return rc;
+    return adaptive_sizes_impl(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, n, qualities, nq, sizes);
+}
+
+int tic_compress_adaptive_to_size(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_stride, size_t max_bytes, int qmin, int qmax,
+                                  uint8_t *out, size_t cap, size_t *out_len, int *quality) {
+    TIC_LOCK(ctx);
+    int rc = check_search_args(ctx, h, w, row_stride, qmin, qmax, out, cap, out_len, quality);
+    if (rc) return rc;
+    reset_adaptive_rate(ctx);
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return set_err(ctx, TIC_E_ARG, "%s", kAdaptNoBlocks);
+    if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
+    size_t pitch = 0;
+    rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
+    if (rc) return rc;
+    const RatePlan p = single_frame_rate_plan(h, w, (ptrdiff_t)pitch, n);
+    RateSearch rs;
+    rate_search_begin(rs, qmin, qmax, (unsigned long long)max_bytes);
+    RateSubmission s;
+    for (;;) {
+        int cand[kRateMaxCandidates];
+        const int nc = rate_search_round(rs, p.depth[0], cand);
+        if (nc == 0) break;
+        s.probes.clear();
+        for (int i = 0; i < nc; i++) s.probes.push_back(RateProbe{0, cand[i]});
+        rc = submit_adaptive_probes(ctx, p, s, ctx->d_img);
+        if (rc) return rc;
+        HIPCHK(ctx, wait_stream(ctx));
+        ctx->last_arate_waits++;
+        for (int i = 0; i < nc; i++) {
+            rc = adaptive_probe_size(ctx, ctx->h_arate_stats[i], &rs.known[cand[i]]);
+            if (rc) return rc;
+        }
+        rate_search_replay(rs);
+    }
+    if (rs.state == kRateNoCode)
+        return set_err(ctx, TIC_E_RANGE, "no adaptive stream at quality %d: a DC category or AC size above 15, or a code and its value bits beyond %d bits",
+                       qmin, kAdaptMaxSymbolBits);
+    if (rs.state == kRateTooLarge) {
+        *out_len = (size_t)rs.known[qmin];
+        return set_err(ctx, TIC_E_SPACE, "%lld bytes at quality %d exceed the budget of %zu", rs.known[qmin], qmin, max_bytes);
+    }
+    // the stream: the adaptive encoder itself at the quality found (its own statistics, table and length: independent of the probe's)
+    const int q = rs.lo;
+    const size_t len = (size_t)rs.known[q];
+    if (len > cap) {
+        *out_len = len;
+        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", len, cap);
+    }
+    DctqArgs a = make_args(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, q, ctx->d_coef);
+    HIPCHK(ctx, launch_dctq(a, 2, ctx->stream));
+    size_t packed = 0;
+    rc = adaptive_encode_dev(ctx, n, h, w, q, out, cap, &packed);
+    ctx->last_arate_waits++;
+    if (rc) return rc;
+    if (packed != len) return set_err(ctx, TIC_E_HIP, "the encoded stream (%zu bytes) contradicts its probe (%zu bytes)", packed, len);
+    *out_len = len;
+    *quality = q;
+    return TIC_OK;
+}
+
+int tic_adaptive_sizes_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides, const int *qualities,
+                         int nq, long long *sizes) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    // every check before any work
+    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
+    if (nq < 0 || (nq > 0 && !qualities)) return set_err(ctx, TIC_E_ARG, "bad quality list");
+    reset_adaptive_rate(ctx);
+    if (n == 0) return TIC_OK;
+    if (!images || !hs || !ws || !row_strides || (nq > 0 && !sizes)) return set_err(ctx, TIC_E_ARG, "null array argument");
+    const RateCall io = {images, hs, ws, row_strides};
+    for (int j = 0; j < std::max(nq, 1); j++) {
+        const int rc = check_rate_frames(ctx, io, n, nq ? qualities[j] : 50);
+        if (rc) return rc;
+    }
+    for (int i = 0; i < n; i++)
+        if (num_blocks(hs[i], ws[i]) == 0) return set_err(ctx, TIC_E_ARG, "frame %d: %s", i, kAdaptNoBlocks);
+    if (nq == 0) return TIC_OK;
+    int chunk_frames;
+    size_t chunk_bytes;
+    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
+    const RatePlan p = plan_rate_batch(hs, ws, n, chunk_frames, chunk_bytes);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RateSubmission s;
+    int probes = 0, waits = 0, launches = 0;
+    for (const MixedChunk &c : p.mixed.chunks) {
+        int rc = upload_rate_chunk(ctx, p.mixed, c, io);
+        if (rc) return rc;
+        s.probes.clear();
+        for (int j = 0; j < nq; j++) // quality by quality: the frames of a transform run are neighbours in the queue
+            for (int k = 0; k < c.count; k++) s.probes.push_back(RateProbe{c.first + k, qualities[j]});
+        rc = submit_adaptive_probes(ctx, p, s, ctx->d_img);
+        if (rc) return rc;
+        HIPCHK(ctx, wait_stream(ctx));
+        ctx->last_arate_waits++;
+        for (int j = 0; j < nq; j++)
+            for (int k = 0; k < c.count; k++) {
+                rc = adaptive_probe_size(ctx, ctx->h_arate_stats[(size_t)j * c.count + k], &sizes[(size_t)p.mixed.frames[(size_t)(c.first + k)].index * nq + j]);
+                if (rc) {
+                    const std::string why = ctx->err;
+                    return set_err(ctx, rc, "frame %d: %s", p.mixed.frames[(size_t)(c.first + k)].index, why.c_str());
+                }
+            }
+    }
+    probes = ctx->last_arate_probes, waits = ctx->last_arate_waits, launches = ctx->last_arate_launches;
+    for (int i : p.mixed.single) { // what the batch does not take, behind it, frame by frame
+        const int rc = tic_adaptive_sizes(ctx, images[i], hs[i], ws[i], row_strides[i], qualities, nq, sizes + (size_t)i * nq);
+        probes += ctx->last_arate_probes, waits += ctx->last_arate_waits, launches += ctx->last_arate_launches;
+        if (rc) {
+            const std::string why = ctx->err;
+            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
+        }
+    }
+    ctx->last_arate_probes = probes, ctx->last_arate_waits = waits, ctx->last_arate_launches = launches;
+    return TIC_OK;
+}
+
+int tic_last_adaptive_rate(tic_ctx *ctx, int *probes, int *host_waits, int *stats_launches) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (probes) *probes = ctx->last_arate_probes;
+    if (host_waits) *host_waits = ctx->last_arate_waits;
+    if (stats_launches) *stats_launches = ctx->last_arate_launches;
+    return TIC_OK;
 }
 
 } // extern "C"

@@ -2,7 +2,7 @@
 """Command-line counterpart of the reference's encode.py (encode.py:1-19): image in, .img stream out.
 
     python -m tinyimgcodec_amd.encode_cli input.(gif|png|jpg|npy|raw) output.img [--quality 50] [--shape H W] [--scaled {best,high,med,low}]
-                                         [--max-bytes N | --min-psnr DB [--min-quality 1] [--max-quality 99]]
+                                         [--adaptive] [--max-bytes N | --min-psnr DB [--min-quality 1] [--max-quality 99]]
                                          [--also INPUT OUTPUT]...
 
 Prints "<n> bytes" and "Compression Ratio: <w*h/n>:1" exactly as the reference does.  Inputs: anything Pillow
@@ -14,6 +14,10 @@ reading raw pixels; header flag 1 << 30); --quality is then ignored, and height 
 
 --max-bytes N writes the stream of the best quality in --min-quality .. --max-quality that fits N bytes (compress_to_size) and prints
 "Quality: <q>" as a third line; it cannot be combined with --scaled or an explicit --quality.
+
+--adaptive writes the stream with the image's own Huffman tables (compress_adaptive: the reference's compress(...,
+auto_generate_huffman_table=True)); with --max-bytes N the stream of compress_adaptive_to_size - the same search over the smaller
+streams, so the same budget buys a higher quality.  Not with --scaled, --min-psnr or --also.
 
 --min-psnr DB writes the smallest stream of that range whose round trip reaches DB decibels (compress_to_psnr) and prints "Quality: <q>"
 and "PSNR: <dB>" as third and fourth lines; the same restrictions, and not together with --max-bytes.
@@ -46,6 +50,7 @@ def main(argv=None):
     ap.add_argument("--quality", type=int, default=None, help="default 50")
     ap.add_argument("--shape", type=int, nargs=2, metavar=("H", "W"))
     ap.add_argument("--scaled", choices=("best", "high", "med", "low"), help="write the integer encoder's stream (c/encode.c) at this setting")
+    ap.add_argument("--adaptive", action="store_true", help="write the stream with the image's own Huffman tables (compress_adaptive)")
     target = ap.add_mutually_exclusive_group()
     target.add_argument("--max-bytes", type=int, metavar="N", help="write the best quality whose stream fits N bytes")
     target.add_argument("--min-psnr", type=float, metavar="DB", help="write the smallest stream whose round trip reaches DB decibels")
@@ -60,7 +65,10 @@ def main(argv=None):
         ap.error("--min-quality / --max-quality need --max-bytes or --min-psnr")
     if args.also and searching:
         ap.error("--also takes a plain --quality or --scaled only")
-    from . import compress, compress_batch, compress_batch_scaled, compress_scaled, compress_to_psnr, compress_to_size
+    if args.adaptive and (args.scaled or args.min_psnr is not None or args.also):
+        ap.error("--adaptive cannot be combined with --scaled, --min-psnr or --also")
+    from . import (compress, compress_adaptive, compress_adaptive_to_size, compress_batch, compress_batch_scaled, compress_scaled, compress_to_psnr,
+                   compress_to_size)
 
     im = load_gray(args.input, args.shape)
     if args.also:
@@ -78,7 +86,11 @@ def main(argv=None):
         return 0
     chosen = reached = None
     qrange = (1 if args.min_quality is None else args.min_quality, 99 if args.max_quality is None else args.max_quality)
-    if args.max_bytes is not None:
+    if args.adaptive and args.max_bytes is not None:
+        out, chosen = compress_adaptive_to_size(im, args.max_bytes, *qrange)
+    elif args.adaptive:
+        out = compress_adaptive(im, 50 if args.quality is None else args.quality)
+    elif args.max_bytes is not None:
         out, chosen = compress_to_size(im, args.max_bytes, *qrange)
     elif args.min_psnr is not None:
         out, chosen, reached = compress_to_psnr(im, args.min_psnr, *qrange)
