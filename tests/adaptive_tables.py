@@ -23,6 +23,8 @@ order with the ABSOLUTE DC in column 0.
 
 Families (build_cases): boundary, all_long, order, incomplete, widest_eob / widest_zrl, max_table, max_distinct_table, too_wide, damaged_chain and rounds_*;
 the docstrings of the builders say what each reaches, census() counts it from the tables and coefficients alone.
+DAMAGED tables and payloads - one seeded corpus through every decoder route, pinned on the reference's own reader - are
+tests/damaged_adaptive.py's (it takes its bases `incomplete` and `all_long` and its stream writer from here); damaged_chain is the one case of that kind kept here.
 
 max_table: kAdaptMaxTableBytes (2,610) is 32 + 16 x 23 + 256 x 80 bits, an AC entry of 16 + 64 bits 256 times.  The parser asks for a prefix
 code and for code + value bits of at most 64; it does not ask for distinct symbols.  So a table reaches that length with entries of size
