@@ -10,7 +10,8 @@
 //   - entries behind the last probe are 0xffffffff; coefficient areas tile the launch's blocks; every probe names its result entry.
 // The lockstep search, on synthetic size tables (monotone, null-topped, saw-toothed, all-fit, none-fit) at depths 1..3 and random
 // (qmin, qmax, budget): the result is the plain bisection's, or its failure kind; no quality is probed twice; every quality the plain
-// bisection tests is probed; rounds are at most ceil(ceil(log2(qmax - qmin + 1)) / depth), exactly 1 when qmin == qmax.
+// bisection tests is probed; rounds are at most ceil(ceil(log2(qmax - qmin + 1)) / depth), exactly 1 when qmin == qmax.  And against the
+// hand-rolled loop the single-frame search once was (inline_size_search): the same candidates round by round, the same end.
 // The plan and a submission's layout, on random frame lists: every frame exactly once; passes hold at most the workspace (or one probe);
 // probes of a pass lie back to back; a merged transform launch covers neighbours of one run at one quality, contiguous in pixels and
 // coefficients; the depth of a chunk keeps blocks x 128 B x 2^depth within kRateWorkspaceBytes.
@@ -132,8 +133,42 @@ static Plain plain_bisection(const long long *size, int qmin, int qmax, unsigned
     return r;
 }
 
+// The single-frame search as tic_compress_to_size ran it before it drove a RateSearch, kept as the model of "the same probes in the same
+// order": a hand-rolled loop over known[], lo, hi and a first-round flag.  rounds: the candidates of every round, in queue order.
+struct Inline {
+    int state, q;
+    std::vector<std::vector<int>> rounds;
+};
+static Inline inline_size_search(const long long *size, int qmin, int qmax, unsigned long long budget, int depth) {
+    Inline r;
+    long long known[100];
+    for (auto &k : known) k = kRateUnknown;
+    auto fits = [&](int q) { return known[q] >= 0 && (unsigned long long)known[q] <= budget; };
+    int lo = qmin, hi = qmax;
+    for (bool first = true;; first = false) {
+        int cand[8], nc = 0;
+        if (first) cand[nc++] = qmin;
+        rate_candidates(lo, hi, depth, known, cand, &nc);
+        if (nc == 0) break;
+        r.rounds.push_back(std::vector<int>(cand, cand + nc));
+        for (int i = 0; i < nc; i++) known[cand[i]] = size[cand[i]];
+        if (first && !fits(qmin)) {
+            r.state = known[qmin] < 0 ? kRateNoCode : kRateTooLarge, r.q = qmin;
+            return r;
+        }
+        while (lo < hi) { // the bisection, as far as the known sizes carry it
+            const int mid = (lo + hi + 1) / 2;
+            if (known[mid] == kRateUnknown) break;
+            if (fits(mid)) lo = mid; else hi = mid - 1;
+        }
+    }
+    r.state = kRateFits, r.q = lo;
+    return r;
+}
+
 static void check_search(const long long *size, int qmin, int qmax, unsigned long long budget, int depth) {
     const Plain want = plain_bisection(size, qmin, qmax, budget);
+    const Inline model = inline_size_search(size, qmin, qmax, budget, depth);
     RateSearch s;
     rate_search_begin(s, qmin, qmax, budget);
     std::set<int> probed;
@@ -143,6 +178,7 @@ static void check_search(const long long *size, int qmin, int qmax, unsigned lon
         const int nc = rate_search_round(s, depth, cand);
         if (nc == 0) break;
         CHECK(nc <= (1 << depth) && s.state == kRateSearching);
+        CHECK((size_t)rounds < model.rounds.size() && model.rounds[(size_t)rounds] == std::vector<int>(cand, cand + nc)); // the same probes, in order
         rounds++;
         for (int i = 0; i < nc; i++) {
             CHECK(cand[i] >= qmin && cand[i] <= qmax);
@@ -152,6 +188,7 @@ static void check_search(const long long *size, int qmin, int qmax, unsigned lon
         rate_search_replay(s);
         CHECK(rounds <= 8);
     }
+    CHECK((size_t)rounds == model.rounds.size() && s.state == model.state && (s.state == kRateFits ? s.lo : s.qmin) == model.q);
     CHECK(s.state == want.state);
     if (want.state == kRateFits) CHECK(s.lo == want.q && s.known[s.lo] == size[want.q]);
     else CHECK(s.known[qmin] == size[qmin]);
@@ -256,7 +293,7 @@ static void check_plan(const std::vector<int> &hs, const std::vector<int> &ws, i
         std::vector<RateSearch> search(p.mixed.frames.size());
         for (auto &r : search) rate_search_begin(r, 1, 99, 1000);
         std::vector<RateProbe> probes;
-        rate_round_probes(c, search.data(), d, probes);
+        round_probes(c, search.data(), d, probes);
         CHECK(probes.size() == (size_t)c.count << d);
         for (size_t i = 0; i < probes.size(); i++) CHECK(probes[i].frame == c.first + (int)(i % (size_t)c.count) && probes[i].quality == probes[i - i % (size_t)c.count].quality);
     }
@@ -281,6 +318,8 @@ static void check_plans() {
         check_plan(hs, ws, rnd(0, 70), it % 3 ? kMixedChunkBytes : (size_t)rnd(1000, 2000000), rnd(1, 7), it % 2 ? kRateWorkspaceBytes / 128 : (size_t)rnd(1, 20000));
     }
     CHECK(rate_depth(1) == 3 && rate_depth(131072) == 3 && rate_depth(131073) == 2 && rate_depth(262144) == 2 && rate_depth(262145) == 1);
+    CHECK(single_frame_depth(1) == 3 && single_frame_depth(16384) == 3 && single_frame_depth(16385) == 2 && single_frame_depth(262144) == 2 &&
+          single_frame_depth(262145) == 1);
 }
 
 int main() {

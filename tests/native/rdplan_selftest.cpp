@@ -1,7 +1,7 @@
 // rdplan_selftest - the host plan of the batch forms of rate-distortion control (tinyimgcodec_amd/csrc/tic_rd_plan.h: fill_sse_probe_table,
 // the lockstep search by distortion) on the CPU.  tests/test_rd_batch_cpu.py builds it with the address and undefined-behaviour sanitizers
 // (with tic_entropy.cpp for num_blocks) and runs it.
-//   rdplan_selftest   -> "rdplan_selftest ok: <n> tables, <m> searches", exit 0; the first failed check is printed, exit 1
+//   rdplan_selftest   -> "rdplan_selftest ok: <n> tables, <m> searches, <p> lockstep rounds", exit 0; the first failed check is printed, exit 1
 // The probe table, on random probe lists with 1..64 probes of 1..300,000 blocks at group caps 1, 2, 3 and 1,024:
 //   - groups tile the grid without gap or overlap, no group spans two probes: every workgroup index finds - by the kernel's rule, the
 //     number of entries <= index, minus one - the probe whose groups contain it;
@@ -12,7 +12,8 @@
 // SseAcc); what is checked is that the longest walk the sweep meets times a tile's largest sum still fits the 64 bits many times over.
 // The lockstep search, on synthetic error tables (monotone, saw-toothed, null-topped, never reaching the bound, reaching it everywhere) at
 // depths 1..3 and random (qmin, qmax, bound): the result is the plain bisection's, or its failure kind with qmax's error; no quality is
-// probed twice; every quality the plain bisection tests is probed; rounds are at most 1 + ceil(7 / depth), exactly 1 when qmin == qmax.
+// probed twice; every quality the plain bisection tests is probed; rounds are at most 1 + ceil(7 / depth), exactly 1 when qmin == qmax.  And
+// against the hand-rolled loop the single-frame search once was (inline_psnr_search): the same candidates round by round, the same end.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -31,7 +32,7 @@ using namespace tic;
     } while (0)
 
 static std::mt19937_64 rng(20261019);
-static int tables = 0, searches = 0;
+static int tables = 0, searches = 0, lockstep_rounds = 0;
 static size_t longest_walk = 0;
 static int rnd(int lo, int hi) { return lo + (int)(rng() % (uint64_t)(hi - lo + 1)); }
 
@@ -157,8 +158,43 @@ static Plain plain_bisection(const long long *size, const uint64_t *err, int qmi
     return r;
 }
 
+// The single-frame search as tic_compress_to_psnr ran it before it drove a PsnrSearch, kept as the model of "the same probes in the same
+// order": a hand-rolled loop over known[], known_sse[], lo, hi and a first-round flag.  rounds: the candidates of every round, in queue order.
+struct Inline {
+    int state, q;
+    std::vector<std::vector<int>> rounds;
+};
+static Inline inline_psnr_search(const long long *size, const uint64_t *err, int qmin, int qmax, uint64_t max_sse, int depth) {
+    Inline r;
+    long long known[100];
+    uint64_t known_sse[100];
+    for (auto &k : known) k = kRateUnknown;
+    auto meets = [&](int q) { return known[q] >= 0 && known_sse[q] <= max_sse; };
+    int lo = qmin, hi = qmax;
+    for (bool first = true;; first = false) {
+        int cand[8], nc = 0;
+        if (first) cand[nc++] = qmax; // (never a middle: mid < hi <= qmax)
+        psnr_candidates(lo, hi, depth, known, cand, &nc);
+        if (nc == 0) break;
+        r.rounds.push_back(std::vector<int>(cand, cand + nc));
+        for (int i = 0; i < nc; i++) known[cand[i]] = size[cand[i]], known_sse[cand[i]] = err[cand[i]];
+        if (first && !meets(qmax)) {
+            r.state = known[qmax] < 0 ? kPsnrNoCode : kPsnrOutOfReach, r.q = qmax;
+            return r;
+        }
+        while (lo < hi) { // the bisection, as far as the known results carry it
+            const int mid = (lo + hi) / 2;
+            if (known[mid] == kRateUnknown) break;
+            if (meets(mid)) hi = mid; else lo = mid + 1;
+        }
+    }
+    r.state = kPsnrMeets, r.q = lo;
+    return r;
+}
+
 static void check_search(const long long *size, const uint64_t *err, int qmin, int qmax, uint64_t max_sse, int depth) {
     const Plain want = plain_bisection(size, err, qmin, qmax, max_sse);
+    const Inline model = inline_psnr_search(size, err, qmin, qmax, max_sse, depth);
     PsnrSearch s;
     psnr_search_begin(s, qmin, qmax, max_sse);
     std::set<int> probed;
@@ -169,6 +205,7 @@ static void check_search(const long long *size, const uint64_t *err, int qmin, i
         if (nc == 0) break;
         CHECK(nc <= (rounds == 0 ? 1 << depth : (1 << depth) - 1) && nc <= kRateMaxCandidates && s.state == kPsnrSearching);
         if (rounds == 0) CHECK(cand[0] == qmax);
+        CHECK((size_t)rounds < model.rounds.size() && model.rounds[(size_t)rounds] == std::vector<int>(cand, cand + nc)); // the same probes, in order
         rounds++;
         for (int i = 0; i < nc; i++) {
             CHECK(cand[i] >= qmin && cand[i] <= qmax);
@@ -179,6 +216,7 @@ static void check_search(const long long *size, const uint64_t *err, int qmin, i
         psnr_search_replay(s);
         CHECK(rounds <= 8);
     }
+    CHECK((size_t)rounds == model.rounds.size() && s.state == model.state && (s.state == kPsnrMeets ? s.lo : s.qmax) == model.q);
     CHECK(s.state == want.state);
     if (want.state == kPsnrMeets) CHECK(s.lo == want.q && s.hi == want.q && s.known[s.lo] == size[want.q] && s.known_sse[s.lo] == err[want.q]);
     else CHECK(s.known[qmax] == size[qmax] && s.known_sse[qmax] == err[qmax] && rounds == 1); // settled after the first round
@@ -212,9 +250,38 @@ static void check_searches() {
     }
 }
 
+// The lockstep queue (round_probes, tic_rate_plan.h) on searches by distortion, as rateplan_selftest checks it on searches by size: in the
+// first round every frame of a chunk asks for the same qualities - count << depth probes, queued candidate by candidate in chunk order.
+static void check_round_probes() {
+    const int shapes[][2] = {{1, 1}, {8, 8}, {7, 9}, {15, 17}, {24, 8}, {72, 8}, {128, 8}, {136, 8}, {40, 52}, {203, 317}, {0, 8}, {8, 0}};
+    std::vector<int> hs, ws;
+    for (auto &s : shapes) hs.push_back(s[0]), ws.push_back(s[1]);
+    for (int chunk_frames : {64, 5, 1}) {
+        const RatePlan p = plan_rate_batch(hs.data(), ws.data(), (int)hs.size(), chunk_frames, kMixedChunkBytes);
+        CHECK(!p.mixed.chunks.empty());
+        for (const MixedChunk &c : p.mixed.chunks)
+            for (int d = 1; d <= 3; d++) {
+                std::vector<PsnrSearch> search(p.mixed.frames.size());
+                for (auto &r : search) psnr_search_begin(r, 1, 99, 1000);
+                std::vector<RateProbe> probes;
+                round_probes(c, search.data(), d, probes);
+                CHECK(probes.size() == (size_t)c.count << d && probes[0].quality == 99);
+                for (size_t i = 0; i < probes.size(); i++)
+                    CHECK(probes[i].frame == c.first + (int)(i % (size_t)c.count) && probes[i].quality == probes[i - i % (size_t)c.count].quality);
+                // a settled frame asks for nothing more: the others keep their order
+                search[(size_t)c.first].state = kPsnrMeets;
+                round_probes(c, search.data(), d, probes);
+                CHECK(probes.size() == (size_t)(c.count - 1) << d);
+                for (const RateProbe &pr : probes) CHECK(pr.frame != c.first);
+                lockstep_rounds++;
+            }
+    }
+}
+
 int main() {
     check_tables();
     check_searches();
-    printf("rdplan_selftest ok: %d tables, %d searches\n", tables, searches);
+    check_round_probes();
+    printf("rdplan_selftest ok: %d tables, %d searches, %d lockstep rounds\n", tables, searches, lockstep_rounds);
     return 0;
 }

@@ -17,6 +17,7 @@ from distortion_common import SETTINGS, load_distortion, oracle_sums, scaled_ima
 from test_rate_control_cpu import IMAGES, fixture_image, load_fixture
 from test_rate_control_gpu import Dev
 from test_rate_control_gpu import bisect as bisect_size
+from test_rate_control_gpu import single_frame_depth
 
 pytestmark = pytest.mark.gpu
 
@@ -92,6 +93,42 @@ def bisect_psnr(sse, max_sse, qmin, qmax):
         else:
             lo = mid + 1
     return lo
+
+
+def schedule_psnr(sse, max_sse, qmin, qmax, depth):
+    """The documented schedule of tic_compress_to_psnr, replayed on errors (index q - 1; None = no code): (probes, host waits) - the mirror
+    of test_rate_control_gpu.schedule.  A round probes every middle the bisection can reach within `depth` further steps and has not
+    probed yet - the first round qmax as well - behind one wait; then the bisection goes as far as the probed errors carry it.  The stream
+    is one more wait; a qmax that does not meet the bound ends the search after the first round, without a stream."""
+    def meets(q):
+        return sse[q - 1] is not None and sse[q - 1] <= max_sse
+
+    def middles(lo, hi, d, out):
+        if lo < hi and d > 0:
+            mid = (lo + hi) // 2
+            if mid not in probed:
+                out.append(mid)
+            middles(lo, mid, d - 1, out)
+            middles(mid + 1, hi, d - 1, out)
+
+    probed, rounds = set(), 0
+    lo, hi = qmin, qmax
+    while True:
+        cand = [] if rounds else [qmax]
+        middles(lo, hi, depth, cand)
+        assert len(cand) == len(set(cand))
+        if not cand:
+            return len(probed), rounds + 1
+        probed.update(cand)
+        rounds += 1
+        if not meets(qmax):
+            return len(probed), rounds
+        while lo < hi and (lo + hi) // 2 in probed:
+            mid = (lo + hi) // 2
+            if meets(mid):
+                hi = mid
+            else:
+                lo = mid + 1
 
 
 @pytest.mark.parametrize("name", IMAGES)
@@ -317,7 +354,8 @@ def test_compress_to_psnr_is_the_bisection(ctx, shipped, fx, rate, name):
 
 def check_search_dev(L, handle, oracle, sse, sizes, img):
     """tic_compress_to_psnr_dev into a sentinel-filled buffer: untouched on every failure, untouched past out_len on success; quality and
-    error reported with TIC_E_SPACE / TIC_E_RANGE; fewer host waits than probes over 1..97."""
+    error reported with TIC_E_SPACE / TIC_E_RANGE; fewer host waits than probes over 1..97, and tic_last_rate_search reports exactly the
+    probes and waits of the replayed schedule."""
     h, w = img.shape
     d = Dev(L, handle)
     try:
@@ -332,9 +370,15 @@ def check_search_dev(L, handle, oracle, sse, sizes, img):
                     (2 ** 63, 1, 100, cap, N.TIC_E_QUALITY, -7, 7),
                     (2 ** 63, 1, 97, 15, N.TIC_E_SPACE, -7, 7),                  # cap below a header
                     (sse[49], 1, 97, sizes[49] - 1, N.TIC_E_SPACE, None, None))  # the chosen stream does not fit cap
+        depth = single_frame_depth(L.tic_num_blocks(h, w))
+        probes, waits = C.c_int(0), C.c_int(0)
         for max_sse, qmin, qmax, c, want_rc, want_q, want_sse in failures:
             rc, n, q, s = search_dev(L, handle, d_img, h, w, max_sse, qmin, qmax, d_out, c)
             assert rc == want_rc, (max_sse, qmin, qmax, c, rc)
+            if c == cap and want_rc in (N.TIC_E_SPACE, N.TIC_E_RANGE):  # the failing first probe: its round (qmax and the middles), no stream
+                assert L.tic_last_rate_search(handle, C.byref(probes), C.byref(waits)) == 0
+                print("max_sse", max_sse, "range", qmin, qmax, "fails; probes", probes.value, "host waits", waits.value)
+                assert (probes.value, waits.value) == schedule_psnr(sse, max_sse, qmin, qmax, depth) and waits.value == 1
             assert (want_q is None or q == want_q) and (want_sse is None or s == want_sse), (max_sse, qmin, qmax, q, s)
             if want_rc == N.TIC_E_SPACE and want_q is not None and want_q > 0:
                 assert n == 0  # (what tells "out of reach" from "does not fit cap", which reports the stream's length)
@@ -349,7 +393,6 @@ def check_search_dev(L, handle, oracle, sse, sizes, img):
             got = d.download(d_out, cap + 64)
             assert got[:n].tobytes() == oracle.compress(img, q)
             assert np.array_equal(got[n:], untouched[n:]), "bytes behind the stream were written"
-            probes, waits = C.c_int(0), C.c_int(0)
             assert L.tic_last_rate_search(handle, C.byref(probes), C.byref(waits)) == 0
             print("max_sse", max_sse, "range", qmin, qmax, "-> q", q, n, "bytes; probes", probes.value, "host waits", waits.value)
             assert 1 <= waits.value <= 8 and waits.value <= probes.value + 1 and probes.value <= 99
@@ -357,6 +400,7 @@ def check_search_dev(L, handle, oracle, sse, sizes, img):
                 assert (probes.value, waits.value) == (1, 2)
             elif (qmin, qmax) == (1, 97) and h * w >= 512 * 512:
                 assert waits.value < probes.value
+            assert (probes.value, waits.value) == schedule_psnr(sse, max_sse, qmin, qmax, depth), (max_sse, qmin, qmax)
     finally:
         d.close()
 

@@ -49,6 +49,47 @@ def bisect(sizes, budget, qmin, qmax):
     return lo
 
 
+def single_frame_depth(nblocks):
+    """The look-ahead of a single-frame search, by the frame's block count (csrc/tic_rate_plan.h; not the batch search's rate_depth)."""
+    return 3 if nblocks <= 16384 else 2 if nblocks <= 262144 else 1
+
+
+def schedule(sizes, budget, qmin, qmax, depth):
+    """The documented schedule of tic_compress_to_size, replayed on sizes (index q - 1; None = no code): (probes, host waits).  A round
+    probes every middle the bisection can reach within `depth` further steps from where it stands and has not probed yet - the first round
+    qmin as well - behind one wait; then the bisection goes as far as the probed sizes carry it.  The stream is one more wait; a qmin
+    that does not fit ends the search after the first round, without a stream."""
+    def fits(q):
+        return sizes[q - 1] is not None and sizes[q - 1] <= budget
+
+    def middles(lo, hi, d, out):
+        if lo < hi and d > 0:
+            mid = (lo + hi + 1) // 2
+            if mid not in probed:
+                out.append(mid)
+            middles(mid, hi, d - 1, out)
+            middles(lo, mid - 1, d - 1, out)
+
+    probed, rounds = set(), 0
+    lo, hi = qmin, qmax
+    while True:
+        cand = [] if rounds else [qmin]
+        middles(lo, hi, depth, cand)
+        assert len(cand) == len(set(cand))
+        if not cand:
+            return len(probed), rounds + 1
+        probed.update(cand)
+        rounds += 1
+        if not fits(qmin):
+            return len(probed), rounds
+        while lo < hi and (lo + hi + 1) // 2 in probed:
+            mid = (lo + hi + 1) // 2
+            if fits(mid):
+                lo = mid
+            else:
+                hi = mid - 1
+
+
 class Dev:
     """Device buffers through the C-ABI of library L; freed by close()."""
 
@@ -200,7 +241,7 @@ def search_dev(L, handle, d_img, h, w, budget, qmin, qmax, d_out, cap):
 
 def check_search_dev(L, handle, oracle, sizes, img):
     """tic_compress_to_size_dev into a sentinel-filled buffer: untouched on every failure, untouched past out_len on success; the host
-    waits at most 8 times for the range 1..99."""
+    waits at most 8 times for the range 1..99, and tic_last_rate_search reports exactly the probes and waits of the replayed schedule."""
     h, w = img.shape
     d = Dev(L, handle)
     try:
@@ -215,11 +256,19 @@ def check_search_dev(L, handle, oracle, sizes, img):
                     (10 ** 9, 1, 100, cap, N.TIC_E_QUALITY, None),
                     (10 ** 9, 1, 99, 15, N.TIC_E_SPACE, None),                            # cap below a header
                     (sizes[49], 1, 99, sizes[49] - 1, N.TIC_E_SPACE, sizes[49]))          # the chosen stream does not fit cap
-        for budget, qmin, qmax, c, want_rc, want_len in failures:
+        depth = single_frame_depth(L.tic_num_blocks(h, w))
+        probes, waits = C.c_int(0), C.c_int(0)
+        for budget, qmin, qmax, c, want_rc, want_len in failures + ((sizes[0] - 1, 1, 1, cap, N.TIC_E_SPACE, sizes[0]),):
             rc, n, q = search_dev(L, handle, d_img, h, w, budget, qmin, qmax, d_out, c)
             assert rc == want_rc, (budget, qmin, qmax, c, rc)
             assert want_len is None or n == want_len
             assert np.array_equal(d.download(d_out, cap + 64), untouched), (budget, qmin, qmax, c)
+            if c == cap and want_rc in (N.TIC_E_SPACE, N.TIC_E_RANGE):  # the failing first probe: its round (qmin and the middles), no stream
+                assert L.tic_last_rate_search(handle, C.byref(probes), C.byref(waits)) == 0
+                print("budget", budget, "range", qmin, qmax, "fails; probes", probes.value, "host waits", waits.value)
+                assert (probes.value, waits.value) == schedule(sizes, budget, qmin, qmax, depth) and waits.value == 1
+                if qmin == qmax:
+                    assert (probes.value, waits.value) == (1, 1)
         for budget, qmin, qmax, c in ((sizes[49], 1, 99, cap), (sizes[49], 1, 99, sizes[49]), (sizes[29] - 1, 1, 99, cap), (10 ** 9, 1, 99, cap),
                                       (sizes[39], 20, 60, cap), (sizes[0], 1, 1, cap)):
             assert L.tic_memset_dev(handle, d_out, SENTINEL, cap + 64) == 0
@@ -229,12 +278,12 @@ def check_search_dev(L, handle, oracle, sizes, img):
             got = d.download(d_out, cap + 64)
             assert got[:n].tobytes() == oracle.compress(img, q)
             assert np.array_equal(got[n:], untouched[n:]), "bytes behind the stream were written"
-            probes, waits = C.c_int(0), C.c_int(0)
             assert L.tic_last_rate_search(handle, C.byref(probes), C.byref(waits)) == 0
             print("budget", budget, "range", qmin, qmax, "-> q", q, n, "bytes; probes", probes.value, "host waits", waits.value)
             assert 1 <= waits.value <= 8 and waits.value <= probes.value + 1 and probes.value <= 99
             if qmin == qmax:
                 assert (probes.value, waits.value) == (1, 2)
+            assert (probes.value, waits.value) == schedule(sizes, budget, qmin, qmax, depth), (budget, qmin, qmax)
     finally:
         d.close()
 
@@ -267,6 +316,34 @@ def test_search_dev_waits_on_a_large_frame(ctx, dev):
         nxt = (C.c_int * 1)(q + 1)
         ctx.check(L.tic_stream_sizes_dev(ctx.handle, d_img, 4096, 4096, 4096, nxt, 1, sz))
         assert sz[0] < 0 or sz[0] > budget
+
+
+def test_search_dev_at_depth_two(ctx, dev):
+    """A 1024 x 1032 frame has 16512 blocks, just past the 16384 up to which a single-frame search looks three steps ahead - and far below
+    the 131072 at which the batch search's rate_depth leaves three: the one size at which the two depths disagree.  Range 1..99, the budget
+    its own size at q = 50: the counters are the replay's at depth 2 (not at depth 3) on the sizes of one tic_stream_sizes_dev call, the
+    stream is tic_compress_dev's at the quality found."""
+    L = N.load()
+    h, w = 1024, 1032
+    assert L.tic_num_blocks(h, w) == 16512 and single_frame_depth(16512) == 2 and single_frame_depth(16384) == 3
+    d_img = dev.upload(rand_frame(1234, h, w))
+    cap = L.tic_compress_bound(h, w)
+    d_out, d_ref = dev.alloc(cap), dev.alloc(cap)
+    qs, sz = (C.c_int * 99)(*range(1, 100)), (C.c_longlong * 99)()
+    ctx.check(L.tic_stream_sizes_dev(ctx.handle, d_img, h, w, w, qs, 99, sz))
+    sizes = [None if v < 0 else v for v in sz]
+    budget = sizes[49]
+    want = bisect(sizes, budget, 1, 99)
+    rc, n, q = search_dev(L, ctx.handle, d_img, h, w, budget, 1, 99, d_out, cap)
+    probes, waits = C.c_int(0), C.c_int(0)
+    assert L.tic_last_rate_search(ctx.handle, C.byref(probes), C.byref(waits)) == 0
+    two, three = schedule(sizes, budget, 1, 99, 2), schedule(sizes, budget, 1, 99, 3)
+    print("1024x1032: q", q, n, "bytes; probes", probes.value, "host waits", waits.value, "replay at depth 2:", two, "at depth 3:", three)
+    assert (rc, q, n) == (N.TIC_OK, want, sizes[want - 1])
+    assert two != three and (probes.value, waits.value) == two
+    ref = C.c_size_t(0)
+    ctx.check(L.tic_compress_dev(ctx.handle, d_img, h, w, w, q, d_ref, cap, C.byref(ref)))
+    assert ref.value == n and np.array_equal(dev.download(d_out, n), dev.download(d_ref, n))
 
 
 def test_stream_sizes_dev_produces_no_stream(ctx, dev, fx):

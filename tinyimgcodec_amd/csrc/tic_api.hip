@@ -400,6 +400,12 @@ static int set_err(tic_ctx *ctx, int code, const char *fmt, ...) {
     return code;
 }
 
+// A batch call's failure in frame i: the message the failing step left, behind "frame i: ".
+static int frame_err(tic_ctx *ctx, int code, int i) {
+    const std::string why = ctx->err;
+    return set_err(ctx, code, "frame %d: %s", i, why.c_str());
+}
+
 #define HIPCHK(ctx, call)                                                                                    \
     do {                                                                                                     \
         hipError_t e_ = (call);                                                                              \
@@ -1695,10 +1701,10 @@ int tic_stream_sizes(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t
     return tic_stream_sizes_dev(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, qualities, nq, sizes);
 }
 
-// The search.  Its contract is the bisection of the header (tic_compress_to_size_dev); what is free is WHEN a quality is probed:
-// rate_candidates (tic_rate_plan.h, shared with the batch form) names the middles reachable within `depth` further steps.  A wait costs
-// about what a probe of a 4096^2 frame does (some 15 us), a probe of a small frame a fraction of that: deep look-ahead for small frames,
-// none for frames beyond 4096^2.
+// The search.  Its contract is the bisection of the header (tic_compress_to_size_dev); what is free is WHEN a quality is probed.  The
+// bisection and its look-ahead are RateSearch's (tic_rate_plan.h, which the batch form drives for a chunk of frames at once): a round is
+// one queue of the candidates it names, one wait, and its replay.  A wait costs about what a probe of a 4096^2 frame does (some 15 us), a
+// probe of a small frame a fraction of that: deep look-ahead for small frames, none for frames beyond 4096^2 (single_frame_depth).
 
 // The last step of a search (by size or by distortion) that ended at quality q, whose probe said `len` bytes: transform, pack and place
 // into the context's own buffer, then exactly its bytes into the caller's - the length is known from the probe, so the copy is queued
@@ -1750,34 +1756,24 @@ static int compress_to_size_impl(tic_ctx *ctx, const void *d_image, int h, int w
     }
     int rc = ensure_rate(ctx, 8);
     if (rc) return rc;
-    const int depth = n <= 16384 ? 3 : (n <= 262144 ? 2 : 1);
-    long long known[100];
-    for (auto &k : known) k = kRateUnknown;
-    auto fits = [&](int q) { return known[q] >= 0 && (unsigned long long)known[q] <= (unsigned long long)max_bytes; };
-    int lo = qmin, hi = qmax;
-    for (bool first = true;; first = false) {
-        int cand[8], nc = 0;
-        if (first) cand[nc++] = qmin;
-        rate_candidates(lo, hi, depth, known, cand, &nc);
-        if (nc == 0) break;
+    RateSearch rs;
+    rate_search_begin(rs, qmin, qmax, (unsigned long long)max_bytes);
+    int cand[kRateMaxCandidates];
+    while (const int nc = rate_search_round(rs, single_frame_depth(n), cand)) {
         rc = queue_probes(ctx, d_image, h, w, row_stride, n, cand, nc);
         if (rc) return rc;
         HIPCHK(ctx, wait_stream(ctx));
         ctx->last_rate_probes += nc;
         ctx->last_rate_waits++;
-        for (int i = 0; i < nc; i++) known[cand[i]] = probe_size(ctx->h_rate[i]);
-        if (first && !fits(qmin)) {
-            if (known[qmin] < 0) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code at quality %d (reference raises KeyError)", qmin);
-            *out_len = (size_t)known[qmin];
-            return set_err(ctx, TIC_E_SPACE, "%lld bytes at quality %d exceed the budget of %zu", known[qmin], qmin, max_bytes);
-        }
-        while (lo < hi) { // the bisection, as far as the known sizes carry it
-            const int mid = (lo + hi + 1) / 2;
-            if (known[mid] == kRateUnknown) break;
-            if (fits(mid)) lo = mid; else hi = mid - 1;
-        }
+        for (int i = 0; i < nc; i++) rs.known[cand[i]] = probe_size(ctx->h_rate[i]);
+        rate_search_replay(rs);
     }
-    return chosen_stream(ctx, d_image, h, w, row_stride, n, lo, (size_t)known[lo], out, out_on_host, cap, out_len, quality);
+    if (rs.state == kRateNoCode) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code at quality %d (reference raises KeyError)", qmin);
+    if (rs.state == kRateTooLarge) {
+        *out_len = (size_t)rs.known[qmin];
+        return set_err(ctx, TIC_E_SPACE, "%lld bytes at quality %d exceed the budget of %zu", rs.known[qmin], qmin, max_bytes);
+    }
+    return chosen_stream(ctx, d_image, h, w, row_stride, n, rs.lo, (size_t)rs.known[rs.lo], out, out_on_host, cap, out_len, quality);
 }
 
 static int check_search_args(tic_ctx *ctx, int h, int w, ptrdiff_t row_stride, int qmin, int qmax, const void *out, size_t cap, size_t *out_len,
@@ -1960,9 +1956,9 @@ int tic_rd_points(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t ro
     return tic_rd_points_dev(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, qualities, nq, sizes, sse, sse_wrapped);
 }
 
-// The search by distortion: the mirror of compress_to_size_impl.  Contract (header, tic_compress_to_psnr_dev): lo, hi = qmin, qmax;
-// while lo < hi: mid = (lo + hi) / 2; meets(mid) ? hi = mid : lo = mid + 1 - the first probe is qmax as well, the look-ahead and its depth
-// per frame size are the size search's; psnr_candidates (tic_rd_plan.h, shared with the batch form) names the middles.
+// The search by distortion: the mirror of compress_to_size_impl.  Contract (header, tic_compress_to_psnr_dev):
+// bisect downwards to the smallest quality that meets the bound, behind a first test of qmax - as PsnrSearch (tic_rd_plan.h, shared with the
+// batch form) runs it; the depth of the look-ahead per frame size is the size search's.
 
 static int compress_to_psnr_impl(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, uint64_t max_sse, int qmin, int qmax,
                                  void *out, bool out_on_host, size_t cap, size_t *out_len, int *quality, uint64_t *sse) {
@@ -1983,17 +1979,10 @@ static int compress_to_psnr_impl(tic_ctx *ctx, const void *d_image, int h, int w
     }
     int rc = ensure_rate(ctx, 8);
     if (rc) return rc;
-    const int depth = n <= 16384 ? 3 : (n <= 262144 ? 2 : 1);
-    long long known[100];
-    uint64_t known_sse[100];
-    for (auto &k : known) k = kRateUnknown;
-    auto meets = [&](int q) { return known[q] >= 0 && known_sse[q] <= max_sse; };
-    int lo = qmin, hi = qmax;
-    for (bool first = true;; first = false) {
-        int cand[8], nc = 0;
-        if (first) cand[nc++] = qmax; // (never a middle: mid < hi <= qmax)
-        psnr_candidates(lo, hi, depth, known, cand, &nc);
-        if (nc == 0) break;
+    PsnrSearch ps;
+    psnr_search_begin(ps, qmin, qmax, max_sse);
+    int cand[kRateMaxCandidates];
+    while (const int nc = psnr_search_round(ps, single_frame_depth(n), cand)) {
         rc = queue_probes(ctx, d_image, h, w, row_stride, n, cand, nc, true);
         if (rc) return rc;
         HIPCHK(ctx, wait_stream(ctx));
@@ -2001,25 +1990,21 @@ static int compress_to_psnr_impl(tic_ctx *ctx, const void *d_image, int h, int w
         ctx->last_rate_waits++;
         const DistortionResult *d = dist_of(ctx->h_rate, nc);
         for (int i = 0; i < nc; i++) {
-            known[cand[i]] = probe_size(ctx->h_rate[i]);
-            known_sse[cand[i]] = d[i].sse;
+            ps.known[cand[i]] = probe_size(ctx->h_rate[i]);
+            ps.known_sse[cand[i]] = d[i].sse;
         }
-        if (first && !meets(qmax)) {
-            *quality = qmax;
-            *sse = known_sse[qmax];
-            *out_len = 0; // (tells this TIC_E_SPACE from the one of a stream that does not fit cap, which reports its length)
-            if (known[qmax] < 0) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code at quality %d (reference raises KeyError)", qmax);
-            return set_err(ctx, TIC_E_SPACE, "squared error %llu at quality %d exceeds the bound of %llu", (unsigned long long)known_sse[qmax], qmax,
-                           (unsigned long long)max_sse);
-        }
-        while (lo < hi) { // the bisection, as far as the known results carry it
-            const int mid = (lo + hi) / 2;
-            if (known[mid] == kRateUnknown) break;
-            if (meets(mid)) hi = mid; else lo = mid + 1;
-        }
+        psnr_search_replay(ps);
     }
-    *sse = known_sse[lo];
-    return chosen_stream(ctx, d_image, h, w, row_stride, n, lo, (size_t)known[lo], out, out_on_host, cap, out_len, quality);
+    if (ps.state != kPsnrMeets) {
+        *quality = qmax;
+        *sse = ps.known_sse[qmax];
+        *out_len = 0; // (tells this TIC_E_SPACE from the one of a stream that does not fit cap, which reports its length)
+        if (ps.state == kPsnrNoCode) return set_err(ctx, TIC_E_RANGE, "coefficient without a Huffman code at quality %d (reference raises KeyError)", qmax);
+        return set_err(ctx, TIC_E_SPACE, "squared error %llu at quality %d exceeds the bound of %llu", (unsigned long long)ps.known_sse[qmax], qmax,
+                       (unsigned long long)max_sse);
+    }
+    *sse = ps.known_sse[ps.lo];
+    return chosen_stream(ctx, d_image, h, w, row_stride, n, ps.lo, (size_t)ps.known[ps.lo], out, out_on_host, cap, out_len, quality);
 }
 
 int tic_compress_to_psnr_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, uint64_t max_sse, int qmin, int qmax,
@@ -3026,11 +3011,15 @@ static int batch_mixed_pipeline(tic_ctx *ctx, const MixedPlan &p, const MixedCal
 }
 
 // The chunk limits of the calls that go by plan_mixed_batch: 64 frames and 32 MB of staged pixels, or what the test hooks say.
-static void mixed_chunk_limits(int *chunk_frames, size_t *chunk_bytes) {
-    *chunk_frames = kMixedChunkFrames;
-    *chunk_bytes = kMixedChunkBytes;
-    if (const char *e = test_hook("TIC_BATCH_CHUNK")) *chunk_frames = atoi(e); // (out of range: the default)
-    if (const char *e = test_hook("TIC_BATCH_CHUNK_BYTES")) *chunk_bytes = strtoull(e, nullptr, 10) ? (size_t)strtoull(e, nullptr, 10) : *chunk_bytes;
+struct ChunkLimits {
+    int frames;
+    size_t bytes;
+};
+static ChunkLimits mixed_chunk_limits() {
+    ChunkLimits lim = {kMixedChunkFrames, kMixedChunkBytes};
+    if (const char *e = test_hook("TIC_BATCH_CHUNK")) lim.frames = atoi(e); // (out of range: the default)
+    if (const char *e = test_hook("TIC_BATCH_CHUNK_BYTES")) lim.bytes = strtoull(e, nullptr, 10) ? (size_t)strtoull(e, nullptr, 10) : lim.bytes;
+    return lim;
 }
 
 int tic_compress_batch_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
@@ -3044,17 +3033,12 @@ int tic_compress_batch_v(tic_ctx *ctx, const uint8_t *const *images, int n, cons
     if (!images || !hs || !ws || !row_strides || !qualities || !outs || !caps || !out_lens) return set_err(ctx, TIC_E_ARG, "null array argument");
     for (int i = 0; i < n; i++) {
         const int rc = check_stream_geometry(ctx, hs[i], ws[i], row_strides[i], qualities[i]);
-        if (rc) {
-            const std::string why = ctx->err;
-            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
-        }
+        if (rc) return frame_err(ctx, rc, i);
         if (!outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
         if (!images[i] && num_blocks(hs[i], ws[i]) != 0) return set_err(ctx, TIC_E_ARG, "frame %d: null image", i);
     }
-    int chunk_frames;
-    size_t chunk_bytes;
-    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
-    const MixedPlan p = plan_mixed_batch(hs, ws, qualities, n, chunk_frames, chunk_bytes);
+    const ChunkLimits lim = mixed_chunk_limits();
+    const MixedPlan p = plan_mixed_batch(hs, ws, qualities, n, lim.frames, lim.bytes);
     const MixedCall io = {images, row_strides, outs, caps, out_lens};
     ctx->last_batch_direct_frames = ctx->last_batch_staged_frames = ctx->last_batch_autoreg_frames = ctx->last_batch_zero_copy = 0;
     ctx->bt = BatchTrace();
@@ -3079,10 +3063,7 @@ int tic_compress_batch_v(tic_ctx *ctx, const uint8_t *const *images, int n, cons
     ctx->last_vbatch_chunks = (int)p.chunks.size();
     for (int i : p.single) { // what the batch kernels do not take, behind the batch, frame by frame
         const int rc = tic_compress(ctx, images[i], hs[i], ws[i], row_strides[i], qualities[i], outs[i], caps[i], &out_lens[i]);
-        if (rc) {
-            const std::string why = ctx->err;
-            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
-        }
+        if (rc) return frame_err(ctx, rc, i);
         ctx->last_vbatch_single++;
     }
     return TIC_OK;
@@ -3110,10 +3091,7 @@ static int check_scaled_frames(tic_ctx *ctx, const uint8_t *const *images, int n
         int rc = TIC_OK;
         if (nq_shared < 0) rc = check_scaled_geometry(ctx, hs[i], ws[i], row_strides[i], qfs[i]);
         for (int j = 0; j < nq_shared && rc == TIC_OK; j++) rc = check_scaled_geometry(ctx, hs[i], ws[i], row_strides[i], qfs[j]);
-        if (rc) {
-            const std::string why = ctx->err;
-            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
-        }
+        if (rc) return frame_err(ctx, rc, i);
         if (!images[i] && num_blocks(hs[i], ws[i]) != 0) return set_err(ctx, TIC_E_ARG, "frame %d: null image", i);
     }
     return TIC_OK;
@@ -3132,10 +3110,8 @@ int tic_compress_batch_scaled_v(tic_ctx *ctx, const uint8_t *const *images, int 
     if (rc) return rc;
     for (int i = 0; i < n; i++)
         if (!outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
-    int chunk_frames;
-    size_t chunk_bytes;
-    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
-    const MixedPlan p = plan_mixed_batch(hs, ws, qfs, n, chunk_frames, chunk_bytes, 1); // (+ 1: the flush byte)
+    const ChunkLimits lim = mixed_chunk_limits();
+    const MixedPlan p = plan_mixed_batch(hs, ws, qfs, n, lim.frames, lim.bytes, 1); // (+ 1: the flush byte)
     for (const MixedFrame &f : p.frames)
         if (f.bound < tic_compress_scaled_bound(f.h, f.w)) return set_err(ctx, TIC_E_ARG, "frame %d: stream area without room for the flush byte", f.index);
     const MixedCall io = {images, row_strides, outs, caps, out_lens};
@@ -3154,10 +3130,7 @@ int tic_compress_batch_scaled_v(tic_ctx *ctx, const uint8_t *const *images, int 
     ctx->last_sbatch_chunks = (int)p.chunks.size();
     for (int i : p.single) { // what the batch kernels do not take, behind the batch, frame by frame
         rc = tic_compress_scaled(ctx, images[i], hs[i], ws[i], row_strides[i], qfs[i], outs[i], caps[i], &out_lens[i]);
-        if (rc) {
-            const std::string why = ctx->err;
-            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
-        }
+        if (rc) return frame_err(ctx, rc, i);
         ctx->last_sbatch_single++;
     }
     return TIC_OK;
@@ -3239,10 +3212,7 @@ struct RateCall {
 static int check_rate_frames(tic_ctx *ctx, const RateCall &io, int n, int quality) {
     for (int i = 0; i < n; i++) {
         const int rc = check_stream_geometry(ctx, io.hs[i], io.ws[i], io.row_strides[i], quality);
-        if (rc) {
-            const std::string why = ctx->err;
-            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
-        }
+        if (rc) return frame_err(ctx, rc, i);
         if (!io.images[i] && num_blocks(io.hs[i], io.ws[i]) != 0) return set_err(ctx, TIC_E_ARG, "frame %d: null image", i);
     }
     return TIC_OK;
@@ -3276,6 +3246,33 @@ static size_t sse_group_cap() { // (TIC_SSE_MAX_GROUPS, a test hook, lowers the 
     return kSseMaxGroups;
 }
 
+// Room for the probe tables of a submission, on the host and on the device: `size_tabs` of the size kernel's, `sse_tabs` of the measuring
+// kernel's (0: that kernel is not launched, its buffers stay as they are).  Nothing of an earlier submission may be in flight.
+static int ensure_probe_tabs(tic_ctx *ctx, size_t size_tabs, size_t sse_tabs) {
+    const size_t size_bytes = size_tabs * sizeof(SizeProbeTable), sse_bytes = sse_tabs * sizeof(SseProbeTable);
+    int rc = grow_pinned(ctx, "h_rate_tabs", ctx->h_rate_tabs, ctx->rate_tabs_host_bytes, size_bytes, align_up(size_bytes, 16384));
+    if (rc == TIC_OK) rc = grow_dev(ctx, "d_rate_tabs", ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, size_bytes, align_up(size_bytes, 16384));
+    if (rc == TIC_OK) rc = grow_pinned(ctx, "h_rd_tabs", ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, sse_bytes, align_up(sse_bytes, 16384));
+    if (rc == TIC_OK) rc = grow_dev(ctx, "d_rd_tabs", ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, sse_bytes, align_up(sse_bytes, 16384));
+    return rc;
+}
+
+// The transforms of probes [first, end) of `s` - one pass - into their areas of the coefficient workspace: a launch per transform run.  The
+// frames' pixels lie at img_base + MixedFrame::img_off.
+static int queue_rate_transforms(tic_ctx *ctx, const RatePlan &p, const RateSubmission &s, int first, int end, const void *img_base) {
+    for (int k = first; k < end;) {
+        int h_total = 0;
+        const int m = rate_transform_run(p, s, k, end, &h_total);
+        const MixedFrame &f = p.mixed.frames[(size_t)s.probes[(size_t)k].frame];
+        DctqArgs a = make_args(ctx, (const char *)img_base + f.img_off, h_total, f.w, (ptrdiff_t)f.pitch, s.probes[(size_t)k].quality,
+                               (int16_t *)ctx->d_coef + s.first_block[(size_t)k] * 64);
+        a.fallback_count = nullptr;
+        HIPCHK(ctx, launch_dctq(a, 2, ctx->stream));
+        k += m;
+    }
+    return TIC_OK;
+}
+
 static int submit_rate_probes(tic_ctx *ctx, const RatePlan &p, RateSubmission &s, bool distortion = false) {
     const int np = (int)s.probes.size();
     layout_rate_submission(p.mixed, s, kRateWorkspaceBytes / 128);
@@ -3285,16 +3282,9 @@ static int submit_rate_probes(tic_ctx *ctx, const RatePlan &p, RateSubmission &s
     if (rc) return rc;
     size_t ntabs = 0;
     for (size_t i = 0; i + 1 < s.pass_first.size(); i++) ntabs += (size_t)(s.pass_first[i + 1] - s.pass_first[i] + kSizeMaxProbes - 1) / kSizeMaxProbes;
-    const size_t tab_bytes = ntabs * sizeof(SizeProbeTable), tab_alloc = align_up(tab_bytes, 16384);
-    rc = grow_pinned(ctx, "h_rate_tabs", ctx->h_rate_tabs, ctx->rate_tabs_host_bytes, tab_bytes, tab_alloc);
+    rc = ensure_probe_tabs(ctx, ntabs, distortion ? ntabs : 0);
     if (rc) return rc;
-    rc = grow_dev(ctx, "d_rate_tabs", ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, tab_bytes, tab_alloc);
-    if (rc) return rc;
-    const size_t sse_tab_bytes = distortion ? ntabs * sizeof(SseProbeTable) : 0, sse_tab_alloc = align_up(sse_tab_bytes, 16384);
-    rc = grow_pinned(ctx, "h_rd_tabs", ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, sse_tab_bytes, sse_tab_alloc);
-    if (rc) return rc;
-    rc = grow_dev(ctx, "d_rd_tabs", ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, sse_tab_bytes, sse_tab_alloc);
-    if (rc) return rc;
+    const size_t tab_bytes = ntabs * sizeof(SizeProbeTable), sse_tab_bytes = distortion ? ntabs * sizeof(SseProbeTable) : 0;
     const size_t sse_cap = sse_group_cap();
     // the tables of every size launch (and of the measuring launch behind it), in launch order
     std::vector<size_t> tab_groups(ntabs), sse_groups(ntabs);
@@ -3326,16 +3316,8 @@ static int submit_rate_probes(tic_ctx *ctx, const RatePlan &p, RateSubmission &s
     t = 0;
     for (size_t i = 0; i + 1 < s.pass_first.size(); i++) {
         const int end = s.pass_first[i + 1];
-        for (int k = s.pass_first[i]; k < end;) {
-            int h_total = 0;
-            const int m = rate_transform_run(p, s, k, end, &h_total);
-            const MixedFrame &f = p.mixed.frames[(size_t)s.probes[(size_t)k].frame];
-            DctqArgs a = make_args(ctx, (const char *)ctx->d_img + f.img_off, h_total, f.w, (ptrdiff_t)f.pitch, s.probes[(size_t)k].quality,
-                                   (int16_t *)ctx->d_coef + s.first_block[(size_t)k] * 64);
-            a.fallback_count = nullptr;
-            HIPCHK(ctx, launch_dctq(a, 2, ctx->stream));
-            k += m;
-        }
+        rc = queue_rate_transforms(ctx, p, s, s.pass_first[i], end, ctx->d_img);
+        if (rc) return rc;
         for (int first = s.pass_first[i]; first < end; first += kSizeMaxProbes, t++) {
             HIPCHK(ctx, stream_size_gpu_v((const int16_t *)ctx->d_coef + s.first_block[(size_t)first] * 64, ctx->d_rate_tabs + t, tab_groups[t], ctx->d_size_tab,
                                           ctx->d_rate, ctx->stream));
@@ -3356,6 +3338,33 @@ static void reset_rate_batch(tic_ctx *ctx) {
     ctx->last_rbatch_probes = ctx->last_rbatch_waits = ctx->last_rbatch_launches = ctx->last_rbatch_sse_launches = 0;
 }
 
+// The chunk loop of the calls that probe every frame at every quality of a list (tic_stream_sizes_v, tic_rd_points_v, tic_adaptive_sizes_v).
+// Per chunk: its upload, ONE submission of np = count x nq probes - submit(s) - one wait, counted in *waits, and take(pr, np, at) for
+// every probe: probe pr of the submission's np is the result at = frame index x nq + j of the caller's tables.  A take that fails ends the call with
+// "frame i: " in front of its message.
+extern "C++" template <class Submit, class Take>
+static int probe_every_quality(tic_ctx *ctx, const RatePlan &p, const RateCall &io, const int *qualities, int nq, int *waits, Submit submit, Take take) {
+    RateSubmission s;
+    for (const MixedChunk &c : p.mixed.chunks) {
+        int rc = upload_rate_chunk(ctx, p.mixed, c, io);
+        if (rc) return rc;
+        s.probes.clear();
+        for (int j = 0; j < nq; j++) // quality by quality: the frames of a transform run are neighbours in the queue
+            for (int k = 0; k < c.count; k++) s.probes.push_back(RateProbe{c.first + k, qualities[j]});
+        rc = submit(s);
+        if (rc) return rc;
+        HIPCHK(ctx, wait_stream(ctx));
+        (*waits)++;
+        for (int j = 0; j < nq; j++)
+            for (int k = 0; k < c.count; k++) {
+                const int i = p.mixed.frames[(size_t)(c.first + k)].index;
+                rc = take((size_t)j * c.count + k, c.count * nq, (size_t)i * nq + j);
+                if (rc) return frame_err(ctx, rc, i);
+            }
+    }
+    return TIC_OK;
+}
+
 int tic_stream_sizes_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides, const int *qualities,
                        int nq, long long *sizes) {
     TIC_LOCK(ctx);
@@ -3371,58 +3380,149 @@ int tic_stream_sizes_v(tic_ctx *ctx, const uint8_t *const *images, int n, const 
         const int rc = check_rate_frames(ctx, io, n, qualities[j]);
         if (rc) return rc;
     }
-    int chunk_frames;
-    size_t chunk_bytes;
-    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
-    const RatePlan p = plan_rate_batch(hs, ws, n, chunk_frames, chunk_bytes);
+    const ChunkLimits lim = mixed_chunk_limits();
+    const RatePlan p = plan_rate_batch(hs, ws, n, lim.frames, lim.bytes);
     for (int i : p.mixed.empty) // header only (codec.py:151)
         for (int j = 0; j < nq; j++) sizes[(size_t)i * nq + j] = 16;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    RateSubmission s;
-    for (const MixedChunk &c : p.mixed.chunks) {
-        int rc = upload_rate_chunk(ctx, p.mixed, c, io);
-        if (rc) return rc;
-        s.probes.clear();
-        for (int j = 0; j < nq; j++) // quality by quality: the frames of a transform run are neighbours in the queue
-            for (int k = 0; k < c.count; k++) s.probes.push_back(RateProbe{c.first + k, qualities[j]});
-        rc = submit_rate_probes(ctx, p, s);
-        if (rc) return rc;
-        HIPCHK(ctx, wait_stream(ctx));
-        ctx->last_rbatch_waits++;
-        for (int j = 0; j < nq; j++)
-            for (int k = 0; k < c.count; k++)
-                sizes[(size_t)p.mixed.frames[(size_t)(c.first + k)].index * nq + j] = probe_size(ctx->h_rate[(size_t)j * c.count + k]);
-    }
+    const int rc = probe_every_quality(
+        ctx, p, io, qualities, nq, &ctx->last_rbatch_waits, [&](RateSubmission &s) { return submit_rate_probes(ctx, p, s); },
+        [&](size_t pr, int, size_t at) {
+            sizes[at] = probe_size(ctx->h_rate[pr]);
+            return TIC_OK;
+        });
+    if (rc) return rc;
     ctx->last_rbatch_frames = (int)p.mixed.frames.size();
     ctx->last_rbatch_chunks = (int)p.mixed.chunks.size();
     for (int i : p.mixed.single) { // what the batch does not take, behind it, frame by frame
         const int rc = tic_stream_sizes(ctx, images[i], hs[i], ws[i], row_strides[i], qualities, nq, sizes + (size_t)i * nq);
-        if (rc) {
-            const std::string why = ctx->err;
-            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
-        }
+        if (rc) return frame_err(ctx, rc, i);
         ctx->last_rbatch_single++;
     }
     return TIC_OK;
 }
 
-// Phase 1 of tic_compress_batch_to_size for one chunk: its upload, then the bisections of all its frames in lockstep - a round is one
-// submission of every unsettled frame's candidates, one read-back and one wait.  search[f]: plan frame f.
-static int search_rate_chunk(tic_ctx *ctx, const RatePlan &p, int ci, const RateCall &io, RateSearch *search) {
-    const MixedChunk &c = p.mixed.chunks[(size_t)ci];
-    int rc = upload_rate_chunk(ctx, p.mixed, c, io);
-    if (rc) return rc;
-    RateSubmission s;
-    for (;;) {
-        rate_round_probes(c, search, p.depth[(size_t)ci], s.probes);
-        if (s.probes.empty()) return TIC_OK;
-        rc = submit_rate_probes(ctx, p, s);
-        if (rc) return rc;
-        HIPCHK(ctx, wait_stream(ctx));
-        ctx->last_rbatch_waits++;
-        for (size_t i = 0; i < s.probes.size(); i++) search[s.probes[i].frame].known[s.probes[i].quality] = probe_size(ctx->h_rate[i]);
-        for (int k = 0; k < c.count; k++) rate_search_replay(search[c.first + k]);
+// ---- the two batch searches (tic_compress_batch_to_size, tic_compress_batch_to_psnr): what they share ----------------------------------------
+// A call is: the prologue (search_batch_begin), its own rule for block-less frames, phase 1 - the searches, chunk by chunk
+// (search_chunks) - its own classification of every finished search into a failure or a stream to pack, phase 2 - the streams
+// (search_batch_pack) - and the frames the batch does not take with the call's verdict behind them (search_batch_end).
+struct SearchBatch {
+    tic_ctx *ctx;
+    RateCall io;
+    int n;
+    uint8_t *const *outs;
+    const size_t *caps;
+    size_t *out_lens;
+    int *qualities, *status;
+    RatePlan plan;
+    std::string first_err; // the message of the first failing frame, in frame order
+    int first_bad;
+    // Frame i failed with `code`, its message in ctx->err; the call goes on.
+    void fail(int i, int code) {
+        status[i] = code;
+        if (i < first_bad) first_bad = i, first_err = ctx->err;
     }
+};
+// A plan frame whose search ended at `quality` with a probe of `len` bytes that fit its buffer: it gets a stream.
+struct SettledFrame {
+    int frame, quality;
+    size_t len;
+};
+
+// Every check before any work: nothing is written while an argument of the call is unacceptable.  arrays_ok: the call's own arrays are there.
+// Then the plan and status[] = TIC_OK.  The caller returns at once on a code, and on n == 0.
+static int search_batch_begin(SearchBatch &b, bool arrays_ok, int qmin, int qmax) {
+    tic_ctx *ctx = b.ctx;
+    const int n = b.n;
+    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
+    if (qmin < 1 || qmax > 99 || qmin > qmax) return set_err(ctx, TIC_E_QUALITY, "quality range %d..%d is not inside 1..99", qmin, qmax);
+    reset_rate_batch(ctx);
+    if (n == 0) return TIC_OK;
+    if (!b.io.images || !b.io.hs || !b.io.ws || !b.io.row_strides || !arrays_ok || !b.outs || !b.caps || !b.out_lens || !b.qualities || !b.status)
+        return set_err(ctx, TIC_E_ARG, "null array argument");
+    const int rc = check_rate_frames(ctx, b.io, n, qmin);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++)
+        if (!b.outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
+    const ChunkLimits lim = mixed_chunk_limits();
+    b.plan = plan_rate_batch(b.io.hs, b.io.ws, n, lim.frames, lim.bytes);
+    for (int i = 0; i < n; i++) b.status[i] = TIC_OK;
+    b.first_bad = n;
+    return TIC_OK;
+}
+
+// Phase 1: per chunk its upload, then the bisections of all its frames in lockstep - a round is one submission of every unsettled frame's
+// candidates (round_probes), one read-back, one wait and the replay.  search[f]: plan frame f, begun by the caller; store(r, q, i, np):
+// probe i of the round's np is what state r learns about quality q.
+extern "C++" template <class Search, class Store>
+static int search_chunks(tic_ctx *ctx, const RatePlan &p, const RateCall &io, Search *search, bool distortion, Store store) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RateSubmission s;
+    for (size_t ci = 0; ci < p.mixed.chunks.size(); ci++) {
+        const MixedChunk &c = p.mixed.chunks[ci];
+        int rc = upload_rate_chunk(ctx, p.mixed, c, io);
+        if (rc) return rc;
+        for (;;) {
+            round_probes(c, search, p.depth[ci], s.probes);
+            if (s.probes.empty()) break;
+            rc = submit_rate_probes(ctx, p, s, distortion);
+            if (rc) return rc;
+            HIPCHK(ctx, wait_stream(ctx));
+            ctx->last_rbatch_waits++;
+            for (size_t i = 0; i < s.probes.size(); i++) store(search[s.probes[i].frame], s.probes[i].quality, i, (int)s.probes.size());
+            for (int k = 0; k < c.count; k++) search_replay(search[c.first + k]);
+        }
+    }
+    ctx->last_rbatch_frames = (int)p.mixed.frames.size();
+    ctx->last_rbatch_chunks = (int)p.mixed.chunks.size();
+    return TIC_OK;
+}
+
+// Phase 2: the streams of the settled frames, at the qualities found, by the mixed batch (which uploads their pixels again); then their
+// out_lens and qualities.
+static int search_batch_pack(SearchBatch &b, const std::vector<SettledFrame> &sub) {
+    tic_ctx *ctx = b.ctx;
+    if (sub.empty()) return TIC_OK;
+    const size_t m = sub.size();
+    std::vector<const uint8_t *> im(m);
+    std::vector<int> sh(m), sw(m), sq(m);
+    std::vector<ptrdiff_t> ss(m);
+    std::vector<uint8_t *> so(m);
+    std::vector<size_t> sc(m), sl(m);
+    for (size_t k = 0; k < m; k++) {
+        const int i = b.plan.mixed.frames[(size_t)sub[k].frame].index;
+        im[k] = b.io.images[i], sh[k] = b.io.hs[i], sw[k] = b.io.ws[i], ss[k] = b.io.row_strides[i], sq[k] = sub[k].quality;
+        so[k] = b.outs[i], sc[k] = sub[k].len, sl[k] = 0; // (the capacity is the probe's length: a longer stream fails before it is written)
+    }
+    const int rc = tic_compress_batch_v(ctx, im.data(), (int)m, sh.data(), sw.data(), ss.data(), sq.data(), so.data(), sc.data(), sl.data());
+    if (rc == TIC_E_SPACE || rc == TIC_E_RANGE) { // (a stream longer than its probe, or no code where the probe found one)
+        const std::string why = ctx->err;
+        return set_err(ctx, TIC_E_HIP, "the packed streams contradict their probes: %s", why.c_str());
+    }
+    if (rc) return rc;
+    for (size_t k = 0; k < m; k++) {
+        const int i = b.plan.mixed.frames[(size_t)sub[k].frame].index;
+        if (sl[k] != sc[k]) // (two independent walks over the same coefficients: cannot differ)
+            return set_err(ctx, TIC_E_HIP, "frame %d: the packed stream (%zu bytes) contradicts its probe (%zu bytes)", i, sl[k], sc[k]);
+        b.out_lens[i] = sl[k], b.qualities[i] = sq[k];
+    }
+    return TIC_OK;
+}
+
+// What the batch does not take, behind it: the single-frame search one(i) of each such frame.  Then the call's code: the first failing
+// frame's, in frame order, with its message.
+extern "C++" template <class One> static int search_batch_end(SearchBatch &b, One one) {
+    tic_ctx *ctx = b.ctx;
+    for (int i : b.plan.mixed.single) {
+        const int rc = one(i);
+        if (rc) b.fail(i, frame_err(ctx, rc, i));
+        ctx->last_rbatch_single++;
+    }
+    if (b.first_bad < b.n) {
+        ctx->err = b.first_err;
+        return b.status[b.first_bad];
+    }
+    return TIC_OK;
 }
 
 int tic_compress_batch_to_size(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
@@ -3430,107 +3530,47 @@ int tic_compress_batch_to_size(tic_ctx *ctx, const uint8_t *const *images, int n
                                int *status) {
     TIC_LOCK(ctx);
     if (!ctx) return TIC_E_ARG;
-    // every check before any work: nothing is written while an argument of the call is unacceptable
-    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
-    if (qmin < 1 || qmax > 99 || qmin > qmax) return set_err(ctx, TIC_E_QUALITY, "quality range %d..%d is not inside 1..99", qmin, qmax);
-    reset_rate_batch(ctx);
-    if (n == 0) return TIC_OK;
-    if (!images || !hs || !ws || !row_strides || !max_bytes || !outs || !caps || !out_lens || !qualities || !status)
-        return set_err(ctx, TIC_E_ARG, "null array argument");
-    const RateCall io = {images, hs, ws, row_strides};
-    int rc = check_rate_frames(ctx, io, n, qmin);
-    if (rc) return rc;
-    for (int i = 0; i < n; i++)
-        if (!outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
-    int chunk_frames;
-    size_t chunk_bytes;
-    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
-    const RatePlan p = plan_rate_batch(hs, ws, n, chunk_frames, chunk_bytes);
-    for (int i = 0; i < n; i++) status[i] = TIC_OK;
-    std::string first_err; // the message of the first failing frame, in frame order
-    int first_bad = n;
-    auto fail = [&](int i, int code) {
-        status[i] = code;
-        if (i < first_bad) first_bad = i, first_err = ctx->err;
-    };
-    for (int i : p.mixed.empty) { // a header at every quality: the bisection ends at qmax
+    SearchBatch b = {ctx, {images, hs, ws, row_strides}, n, outs, caps, out_lens, qualities, status};
+    int rc = search_batch_begin(b, max_bytes != nullptr, qmin, qmax);
+    if (rc || n == 0) return rc;
+    const MixedPlan &mp = b.plan.mixed;
+    for (int i : mp.empty) { // a header at every quality: the bisection ends at qmax
         if (max_bytes[i] < 16) {
             out_lens[i] = 16;
-            fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: 16 bytes at quality %d exceed the budget of %zu", i, qmin, max_bytes[i]));
+            b.fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: 16 bytes at quality %d exceed the budget of %zu", i, qmin, max_bytes[i]));
         } else if (caps[i] < 16) {
             out_lens[i] = 16;
-            fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small (16 bytes needed, %zu given)", i, caps[i]));
+            b.fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small (16 bytes needed, %zu given)", i, caps[i]));
         } else {
             write_header(outs[i], hs[i], ws[i], qmax);
             out_lens[i] = 16, qualities[i] = qmax;
         }
     }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // phase 1: the searches, chunk by chunk
-    std::vector<RateSearch> search(p.mixed.frames.size());
-    for (size_t f = 0; f < search.size(); f++) rate_search_begin(search[f], qmin, qmax, (unsigned long long)max_bytes[p.mixed.frames[f].index]);
-    for (int ci = 0; ci < (int)p.mixed.chunks.size(); ci++) {
-        rc = search_rate_chunk(ctx, p, ci, io, search.data());
-        if (rc) return rc;
-    }
-    ctx->last_rbatch_frames = (int)p.mixed.frames.size();
-    ctx->last_rbatch_chunks = (int)p.mixed.chunks.size();
-    // phase 2: the streams of the fitting frames, at the qualities found, by the mixed batch (which uploads their pixels again)
-    std::vector<int> sub; // plan frames that get a stream
+    std::vector<RateSearch> search(mp.frames.size());
+    for (size_t f = 0; f < search.size(); f++) rate_search_begin(search[f], qmin, qmax, (unsigned long long)max_bytes[mp.frames[f].index]);
+    rc = search_chunks(ctx, b.plan, b.io, search.data(), false, [&](RateSearch &r, int q, size_t i, int) { r.known[q] = probe_size(ctx->h_rate[i]); });
+    if (rc) return rc;
+    std::vector<SettledFrame> sub;
     for (size_t f = 0; f < search.size(); f++) {
         const RateSearch &r = search[f];
-        const int i = p.mixed.frames[f].index;
+        const int i = mp.frames[f].index;
         if (r.state == kRateNoCode) {
-            fail(i, set_err(ctx, TIC_E_RANGE, "frame %d: coefficient without a Huffman code at quality %d (reference raises KeyError)", i, qmin));
+            b.fail(i, set_err(ctx, TIC_E_RANGE, "frame %d: coefficient without a Huffman code at quality %d (reference raises KeyError)", i, qmin));
         } else if (r.state == kRateTooLarge) {
             out_lens[i] = (size_t)r.known[qmin];
-            fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: %lld bytes at quality %d exceed the budget of %zu", i, r.known[qmin], qmin, max_bytes[i]));
+            b.fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: %lld bytes at quality %d exceed the budget of %zu", i, r.known[qmin], qmin, max_bytes[i]));
         } else if ((size_t)r.known[r.lo] > caps[i]) {
             out_lens[i] = (size_t)r.known[r.lo];
-            fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small (%lld bytes needed, %zu given)", i, r.known[r.lo], caps[i]));
+            b.fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small (%lld bytes needed, %zu given)", i, r.known[r.lo], caps[i]));
         } else {
-            sub.push_back((int)f);
+            sub.push_back(SettledFrame{(int)f, r.lo, (size_t)r.known[r.lo]});
         }
     }
-    if (!sub.empty()) {
-        const size_t m = sub.size();
-        std::vector<const uint8_t *> im(m);
-        std::vector<int> sh(m), sw(m), sq(m);
-        std::vector<ptrdiff_t> ss(m);
-        std::vector<uint8_t *> so(m);
-        std::vector<size_t> sc(m), sl(m);
-        for (size_t k = 0; k < m; k++) {
-            const RateSearch &r = search[(size_t)sub[k]];
-            const int i = p.mixed.frames[(size_t)sub[k]].index;
-            im[k] = images[i], sh[k] = hs[i], sw[k] = ws[i], ss[k] = row_strides[i], sq[k] = r.lo;
-            so[k] = outs[i], sc[k] = (size_t)r.known[r.lo], sl[k] = 0; // (the capacity is the probe's length: a longer stream fails before it is written)
-        }
-        rc = tic_compress_batch_v(ctx, im.data(), (int)m, sh.data(), sw.data(), ss.data(), sq.data(), so.data(), sc.data(), sl.data());
-        if (rc == TIC_E_SPACE || rc == TIC_E_RANGE) { // (a stream longer than its probe, or no code where the probe found one)
-            const std::string why = ctx->err;
-            return set_err(ctx, TIC_E_HIP, "the packed streams contradict their probes: %s", why.c_str());
-        }
-        if (rc) return rc;
-        for (size_t k = 0; k < m; k++) {
-            const int i = p.mixed.frames[(size_t)sub[k]].index;
-            if (sl[k] != sc[k]) // (two independent walks over the same coefficients: cannot differ)
-                return set_err(ctx, TIC_E_HIP, "frame %d: the packed stream (%zu bytes) contradicts its probe (%zu bytes)", i, sl[k], sc[k]);
-            out_lens[i] = sl[k], qualities[i] = sq[k];
-        }
-    }
-    for (int i : p.mixed.single) { // what the batch does not take, behind it: the single-frame search
-        rc = tic_compress_to_size(ctx, images[i], hs[i], ws[i], row_strides[i], max_bytes[i], qmin, qmax, outs[i], caps[i], &out_lens[i], &qualities[i]);
-        if (rc) {
-            const std::string why = ctx->err;
-            fail(i, set_err(ctx, rc, "frame %d: %s", i, why.c_str()));
-        }
-        ctx->last_rbatch_single++;
-    }
-    if (first_bad < n) {
-        ctx->err = first_err;
-        return status[first_bad];
-    }
-    return TIC_OK;
+    rc = search_batch_pack(b, sub);
+    if (rc) return rc;
+    return search_batch_end(b, [&](int i) {
+        return tic_compress_to_size(ctx, images[i], hs[i], ws[i], row_strides[i], max_bytes[i], qmin, qmax, outs[i], caps[i], &out_lens[i], &qualities[i]);
+    });
 }
 
 int tic_last_rate_batch(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks, int *probes, int *search_waits, int *size_launches) {
@@ -3565,72 +3605,33 @@ int tic_rd_points_v(tic_ctx *ctx, const uint8_t *const *images, int n, const int
         const int rc = check_rate_frames(ctx, io, n, qualities[j]);
         if (rc) return rc;
     }
-    int chunk_frames;
-    size_t chunk_bytes;
-    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
-    const RatePlan p = plan_rate_batch(hs, ws, n, chunk_frames, chunk_bytes);
+    const ChunkLimits lim = mixed_chunk_limits();
+    const RatePlan p = plan_rate_batch(hs, ws, n, lim.frames, lim.bytes);
     for (int i : p.mixed.empty) // header only (codec.py:151): no pixel, no error
         for (int j = 0; j < nq; j++) {
             sizes[(size_t)i * nq + j] = 16;
             sse[(size_t)i * nq + j] = sse_wrapped[(size_t)i * nq + j] = 0;
         }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    RateSubmission s;
-    for (const MixedChunk &c : p.mixed.chunks) {
-        int rc = upload_rate_chunk(ctx, p.mixed, c, io);
-        if (rc) return rc;
-        s.probes.clear();
-        for (int j = 0; j < nq; j++) // quality by quality: the frames of a transform run are neighbours in the queue
-            for (int k = 0; k < c.count; k++) s.probes.push_back(RateProbe{c.first + k, qualities[j]});
-        rc = submit_rate_probes(ctx, p, s, true);
-        if (rc) return rc;
-        HIPCHK(ctx, wait_stream(ctx));
-        ctx->last_rbatch_waits++;
-        const DistortionResult *d = dist_of(ctx->h_rate, (int)s.probes.size());
-        for (int j = 0; j < nq; j++)
-            for (int k = 0; k < c.count; k++) {
-                const size_t at = (size_t)p.mixed.frames[(size_t)(c.first + k)].index * nq + j, pr = (size_t)j * c.count + k;
-                sizes[at] = probe_size(ctx->h_rate[pr]);
-                sse[at] = d[pr].sse;
-                sse_wrapped[at] = d[pr].sse_wrapped;
-            }
-    }
+    const int rc = probe_every_quality(
+        ctx, p, io, qualities, nq, &ctx->last_rbatch_waits, [&](RateSubmission &s) { return submit_rate_probes(ctx, p, s, true); },
+        [&](size_t pr, int np, size_t at) {
+            const DistortionResult &d = dist_of(ctx->h_rate, np)[pr];
+            sizes[at] = probe_size(ctx->h_rate[pr]);
+            sse[at] = d.sse;
+            sse_wrapped[at] = d.sse_wrapped;
+            return TIC_OK;
+        });
+    if (rc) return rc;
     ctx->last_rbatch_frames = (int)p.mixed.frames.size();
     ctx->last_rbatch_chunks = (int)p.mixed.chunks.size();
     for (int i : p.mixed.single) { // what the batch does not take, behind it, frame by frame
         const int rc = tic_rd_points(ctx, images[i], hs[i], ws[i], row_strides[i], qualities, nq, sizes + (size_t)i * nq, sse + (size_t)i * nq,
                                      sse_wrapped + (size_t)i * nq);
-        if (rc) {
-            const std::string why = ctx->err;
-            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
-        }
+        if (rc) return frame_err(ctx, rc, i);
         ctx->last_rbatch_single++;
     }
     return TIC_OK;
-}
-
-// Phase 1 of tic_compress_batch_to_psnr for one chunk: its upload, then the bisections of all its frames in lockstep - a round is one
-// submission of every unsettled frame's candidates, one read-back and one wait.  search[f]: plan frame f.
-static int search_psnr_chunk(tic_ctx *ctx, const RatePlan &p, int ci, const RateCall &io, PsnrSearch *search) {
-    const MixedChunk &c = p.mixed.chunks[(size_t)ci];
-    int rc = upload_rate_chunk(ctx, p.mixed, c, io);
-    if (rc) return rc;
-    RateSubmission s;
-    for (;;) {
-        psnr_round_probes(c, search, p.depth[(size_t)ci], s.probes);
-        if (s.probes.empty()) return TIC_OK;
-        rc = submit_rate_probes(ctx, p, s, true);
-        if (rc) return rc;
-        HIPCHK(ctx, wait_stream(ctx));
-        ctx->last_rbatch_waits++;
-        const DistortionResult *d = dist_of(ctx->h_rate, (int)s.probes.size());
-        for (size_t i = 0; i < s.probes.size(); i++) {
-            PsnrSearch &r = search[s.probes[i].frame];
-            r.known[s.probes[i].quality] = probe_size(ctx->h_rate[i]);
-            r.known_sse[s.probes[i].quality] = d[i].sse;
-        }
-        for (int k = 0; k < c.count; k++) psnr_search_replay(search[c.first + k]);
-    }
 }
 
 int tic_compress_batch_to_psnr(tic_ctx *ctx, const uint8_t *const *images, int n, const int *hs, const int *ws, const ptrdiff_t *row_strides,
@@ -3638,107 +3639,50 @@ int tic_compress_batch_to_psnr(tic_ctx *ctx, const uint8_t *const *images, int n
                                uint64_t *sse, int *status) {
     TIC_LOCK(ctx);
     if (!ctx) return TIC_E_ARG;
-    // every check before any work: nothing is written while an argument of the call is unacceptable
-    if (n < 0) return set_err(ctx, TIC_E_ARG, "negative frame count %d", n);
-    if (qmin < 1 || qmax > 99 || qmin > qmax) return set_err(ctx, TIC_E_QUALITY, "quality range %d..%d is not inside 1..99", qmin, qmax);
-    reset_rate_batch(ctx);
-    if (n == 0) return TIC_OK;
-    if (!images || !hs || !ws || !row_strides || !max_sse || !outs || !caps || !out_lens || !qualities || !sse || !status)
-        return set_err(ctx, TIC_E_ARG, "null array argument");
-    const RateCall io = {images, hs, ws, row_strides};
-    int rc = check_rate_frames(ctx, io, n, qmin);
-    if (rc) return rc;
-    for (int i = 0; i < n; i++)
-        if (!outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
-    int chunk_frames;
-    size_t chunk_bytes;
-    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
-    const RatePlan p = plan_rate_batch(hs, ws, n, chunk_frames, chunk_bytes);
-    for (int i = 0; i < n; i++) status[i] = TIC_OK;
-    std::string first_err; // the message of the first failing frame, in frame order
-    int first_bad = n;
-    auto fail = [&](int i, int code) {
-        status[i] = code;
-        if (i < first_bad) first_bad = i, first_err = ctx->err;
-    };
-    for (int i : p.mixed.empty) { // a header and no error at every quality: the bisection ends at qmin
+    SearchBatch b = {ctx, {images, hs, ws, row_strides}, n, outs, caps, out_lens, qualities, status};
+    int rc = search_batch_begin(b, max_sse && sse, qmin, qmax);
+    if (rc || n == 0) return rc;
+    const MixedPlan &mp = b.plan.mixed;
+    for (int i : mp.empty) { // a header and no error at every quality: the bisection ends at qmin
         if (caps[i] < 16) {
             out_lens[i] = 16;
-            fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small (16 bytes needed, %zu given)", i, caps[i]));
+            b.fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small (16 bytes needed, %zu given)", i, caps[i]));
         } else {
             write_header(outs[i], hs[i], ws[i], qmin);
             out_lens[i] = 16, qualities[i] = qmin, sse[i] = 0;
         }
     }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // phase 1: the searches, chunk by chunk
-    std::vector<PsnrSearch> search(p.mixed.frames.size());
-    for (size_t f = 0; f < search.size(); f++) psnr_search_begin(search[f], qmin, qmax, max_sse[p.mixed.frames[f].index]);
-    for (int ci = 0; ci < (int)p.mixed.chunks.size(); ci++) {
-        rc = search_psnr_chunk(ctx, p, ci, io, search.data());
-        if (rc) return rc;
-    }
-    ctx->last_rbatch_frames = (int)p.mixed.frames.size();
-    ctx->last_rbatch_chunks = (int)p.mixed.chunks.size();
-    // phase 2: the streams of the frames that met their bound, at the qualities found, by the mixed batch (which uploads their pixels again)
-    std::vector<int> sub; // plan frames that get a stream
+    std::vector<PsnrSearch> search(mp.frames.size());
+    for (size_t f = 0; f < search.size(); f++) psnr_search_begin(search[f], qmin, qmax, max_sse[mp.frames[f].index]);
+    rc = search_chunks(ctx, b.plan, b.io, search.data(), true, [&](PsnrSearch &r, int q, size_t i, int np) {
+        r.known[q] = probe_size(ctx->h_rate[i]);
+        r.known_sse[q] = dist_of(ctx->h_rate, np)[i].sse;
+    });
+    if (rc) return rc;
+    std::vector<SettledFrame> sub;
     for (size_t f = 0; f < search.size(); f++) {
         const PsnrSearch &r = search[f];
-        const int i = p.mixed.frames[f].index;
+        const int i = mp.frames[f].index;
         if (r.state == kPsnrNoCode || r.state == kPsnrOutOfReach) { // the single call's side values: the quality and the error of qmax, no length
             qualities[i] = qmax, sse[i] = r.known_sse[qmax], out_lens[i] = 0;
             if (r.state == kPsnrNoCode)
-                fail(i, set_err(ctx, TIC_E_RANGE, "frame %d: coefficient without a Huffman code at quality %d (reference raises KeyError)", i, qmax));
+                b.fail(i, set_err(ctx, TIC_E_RANGE, "frame %d: coefficient without a Huffman code at quality %d (reference raises KeyError)", i, qmax));
             else
-                fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: squared error %llu at quality %d exceeds the bound of %llu", i,
-                                (unsigned long long)r.known_sse[qmax], qmax, (unsigned long long)max_sse[i]));
+                b.fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: squared error %llu at quality %d exceeds the bound of %llu", i,
+                                  (unsigned long long)r.known_sse[qmax], qmax, (unsigned long long)max_sse[i]));
         } else if ((size_t)r.known[r.lo] > caps[i]) {
             sse[i] = r.known_sse[r.lo], out_lens[i] = (size_t)r.known[r.lo];
-            fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small (%lld bytes needed, %zu given)", i, r.known[r.lo], caps[i]));
+            b.fail(i, set_err(ctx, TIC_E_SPACE, "frame %d: output buffer too small (%lld bytes needed, %zu given)", i, r.known[r.lo], caps[i]));
         } else {
-            sub.push_back((int)f);
+            sub.push_back(SettledFrame{(int)f, r.lo, (size_t)r.known[r.lo]});
         }
     }
-    if (!sub.empty()) {
-        const size_t m = sub.size();
-        std::vector<const uint8_t *> im(m);
-        std::vector<int> sh(m), sw(m), sq(m);
-        std::vector<ptrdiff_t> ss(m);
-        std::vector<uint8_t *> so(m);
-        std::vector<size_t> sc(m), sl(m);
-        for (size_t k = 0; k < m; k++) {
-            const PsnrSearch &r = search[(size_t)sub[k]];
-            const int i = p.mixed.frames[(size_t)sub[k]].index;
-            im[k] = images[i], sh[k] = hs[i], sw[k] = ws[i], ss[k] = row_strides[i], sq[k] = r.lo;
-            so[k] = outs[i], sc[k] = (size_t)r.known[r.lo], sl[k] = 0; // (the capacity is the probe's length: a longer stream fails before it is written)
-        }
-        rc = tic_compress_batch_v(ctx, im.data(), (int)m, sh.data(), sw.data(), ss.data(), sq.data(), so.data(), sc.data(), sl.data());
-        if (rc == TIC_E_SPACE || rc == TIC_E_RANGE) { // (a stream longer than its probe, or no code where the probe found one)
-            const std::string why = ctx->err;
-            return set_err(ctx, TIC_E_HIP, "the packed streams contradict their probes: %s", why.c_str());
-        }
-        if (rc) return rc;
-        for (size_t k = 0; k < m; k++) {
-            const PsnrSearch &r = search[(size_t)sub[k]];
-            const int i = p.mixed.frames[(size_t)sub[k]].index;
-            if (sl[k] != sc[k]) // (two independent walks over the same coefficients: cannot differ)
-                return set_err(ctx, TIC_E_HIP, "frame %d: the packed stream (%zu bytes) contradicts its probe (%zu bytes)", i, sl[k], sc[k]);
-            out_lens[i] = sl[k], qualities[i] = sq[k], sse[i] = r.known_sse[r.lo];
-        }
-    }
-    for (int i : p.mixed.single) { // what the batch does not take, behind it: the single-frame search
-        rc = tic_compress_to_psnr(ctx, images[i], hs[i], ws[i], row_strides[i], max_sse[i], qmin, qmax, outs[i], caps[i], &out_lens[i], &qualities[i], &sse[i]);
-        if (rc) {
-            const std::string why = ctx->err;
-            fail(i, set_err(ctx, rc, "frame %d: %s", i, why.c_str()));
-        }
-        ctx->last_rbatch_single++;
-    }
-    if (first_bad < n) {
-        ctx->err = first_err;
-        return status[first_bad];
-    }
-    return TIC_OK;
+    rc = search_batch_pack(b, sub);
+    if (rc) return rc;
+    for (const SettledFrame &t : sub) sse[mp.frames[(size_t)t.frame].index] = search[(size_t)t.frame].known_sse[t.quality];
+    return search_batch_end(b, [&](int i) {
+        return tic_compress_to_psnr(ctx, images[i], hs[i], ws[i], row_strides[i], max_sse[i], qmin, qmax, outs[i], caps[i], &out_lens[i], &qualities[i], &sse[i]);
+    });
 }
 
 int tic_last_rd_batch(tic_ctx *ctx, int *sse_launches) {
@@ -3778,13 +3722,11 @@ int tic_rd_points_scaled_v(tic_ctx *ctx, const uint8_t *const *images, int n, co
         if (sse) sse[at] = s0;
         if (sse_wrapped) sse_wrapped[at] = s1;
     };
-    int chunk_frames;
-    size_t chunk_bytes;
-    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
+    ChunkLimits lim = mixed_chunk_limits();
     // (a block is 64 bytes of pixels and 128 of coefficients: a chunk's probes take 2 * nq times its pixels)
-    chunk_bytes = std::min(chunk_bytes, std::max<size_t>(kRateWorkspaceBytes / (2 * (size_t)nq), 64));
+    lim.bytes = std::min(lim.bytes, std::max<size_t>(kRateWorkspaceBytes / (2 * (size_t)nq), 64));
     const std::vector<int> zeros((size_t)n, 0);
-    const MixedPlan p = plan_mixed_batch(hs, ws, zeros.data(), n, chunk_frames, chunk_bytes);
+    const MixedPlan p = plan_mixed_batch(hs, ws, zeros.data(), n, lim.frames, lim.bytes);
     for (int i : p.empty)
         for (int j = 0; j < nq; j++) put(i, j, 17, 0, 0);
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -3801,11 +3743,8 @@ int tic_rd_points_scaled_v(tic_ctx *ctx, const uint8_t *const *images, int n, co
         rc = ensure_scaled_tabs(ctx, ntabs);
         if (rc) return rc;
         const size_t size_bytes = ntabs * sizeof(SizeProbeTable), sse_bytes = ntabs * sizeof(SseProbeTable);
-        if ((rc = grow_pinned(ctx, "h_rate_tabs", ctx->h_rate_tabs, ctx->rate_tabs_host_bytes, size_bytes, align_up(size_bytes, 16384))) != TIC_OK ||
-            (rc = grow_dev(ctx, "d_rate_tabs", ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, size_bytes, align_up(size_bytes, 16384))) != TIC_OK ||
-            (rc = grow_pinned(ctx, "h_rd_tabs", ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, sse_bytes, align_up(sse_bytes, 16384))) != TIC_OK ||
-            (rc = grow_dev(ctx, "d_rd_tabs", ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, sse_bytes, align_up(sse_bytes, 16384))) != TIC_OK)
-            return rc;
+        rc = ensure_probe_tabs(ctx, ntabs, ntabs);
+        if (rc) return rc;
         rc = upload_rate_chunk(ctx, p, c, io);
         if (rc) return rc;
         // probe j * count + k: frame k of the chunk at setting j, its coefficients behind those of the probes in front
@@ -3861,10 +3800,7 @@ int tic_rd_points_scaled_v(tic_ctx *ctx, const uint8_t *const *images, int n, co
         for (int j = 0; j < nq; j++) {
             uint64_t sums[2] = {0, 0};
             rc = tic_roundtrip_sse_scaled(ctx, images[i], hs[i], ws[i], row_strides[i], qfs[j], sums);
-            if (rc) {
-                const std::string why = ctx->err;
-                return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
-            }
+            if (rc) return frame_err(ctx, rc, i);
             // (its coefficients are still in the scratch buffer: the size kernel on them)
             rc = ensure_rate(ctx, 1);
             if (rc) return rc;
@@ -3899,10 +3835,7 @@ static int queue_distortion_v(tic_ctx *ctx, const void *d_coeffs_zz, const void 
     int rc = ensure_rate(ctx, (size_t)n);
     if (rc) return rc;
     const size_t ntabs = ((size_t)n + kSseMaxProbes - 1) / kSseMaxProbes; // (an upper bound: probes without blocks take no entry)
-    const size_t tab_bytes = ntabs * sizeof(SseProbeTable), tab_alloc = align_up(tab_bytes, 16384);
-    rc = grow_pinned(ctx, "h_rd_tabs", ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, tab_bytes, tab_alloc);
-    if (rc) return rc;
-    rc = grow_dev(ctx, "d_rd_tabs", ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, tab_bytes, tab_alloc);
+    rc = ensure_probe_tabs(ctx, 0, ntabs); // (no size launch: the size kernel's tables are not touched)
     if (rc) return rc;
     const size_t cap = sse_group_cap();
     launches.clear();
@@ -5203,19 +5136,14 @@ static int compress_batch_adaptive_impl(tic_ctx *ctx, const uint8_t *const *imag
             rc = set_err(ctx, TIC_E_ARG, "negative image size");
         else if (qualities[i] < 1 || qualities[i] > 99)
             rc = set_err(ctx, TIC_E_QUALITY, "quality %d outside 1..99", qualities[i]);
-        if (rc) {
-            const std::string why = ctx->err;
-            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
-        }
+        if (rc) return frame_err(ctx, rc, i);
         if (num_blocks(hs[i], ws[i]) == 0)
             return set_err(ctx, TIC_E_ARG, "frame %d: an image without blocks has no symbols to build a table from (the reference raises IndexError)", i);
         if (!outs[i]) return set_err(ctx, TIC_E_ARG, "frame %d: null output buffer", i);
         if (images ? !images[i] : !coeffs[i]) return set_err(ctx, TIC_E_ARG, images ? "frame %d: null image" : "frame %d: null coefficient pointer", i);
     }
-    int chunk_frames;
-    size_t chunk_bytes;
-    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
-    const MixedPlan p = plan_mixed_batch(hs, ws, qualities, n, chunk_frames, chunk_bytes);
+    const ChunkLimits lim = mixed_chunk_limits();
+    const MixedPlan p = plan_mixed_batch(hs, ws, qualities, n, lim.frames, lim.bytes);
     AdaptCall call = {coeffs, {images, row_strides, outs, caps, out_lens}, 0};
     ctx->last_batch_direct_frames = ctx->last_batch_staged_frames = ctx->last_batch_autoreg_frames = ctx->last_batch_zero_copy = 0;
     ctx->bt = BatchTrace();
@@ -5233,10 +5161,7 @@ static int compress_batch_adaptive_impl(tic_ctx *ctx, const uint8_t *const *imag
             call.short_frames++;
             continue;
         }
-        if (rc) {
-            const std::string why = ctx->err;
-            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
-        }
+        if (rc) return frame_err(ctx, rc, i);
     }
     if (call.short_frames)
         return set_err(ctx, TIC_E_SPACE, "%d frame(s) not written: output buffer too small (out_lens holds the sizes needed)", call.short_frames);
@@ -5825,16 +5750,8 @@ static int submit_adaptive_probes(tic_ctx *ctx, const RatePlan &p, RateSubmissio
     size_t t = 0;
     for (size_t i = 0; i + 1 < s.pass_first.size(); i++) {
         const int end = s.pass_first[i + 1];
-        for (int k = s.pass_first[i]; k < end;) {
-            int h_total = 0;
-            const int m = rate_transform_run(p, s, k, end, &h_total);
-            const MixedFrame &f = p.mixed.frames[(size_t)s.probes[(size_t)k].frame];
-            DctqArgs a = make_args(ctx, (const char *)img_base + f.img_off, h_total, f.w, (ptrdiff_t)f.pitch, s.probes[(size_t)k].quality,
-                                   (int16_t *)ctx->d_coef + s.first_block[(size_t)k] * 64);
-            a.fallback_count = nullptr;
-            HIPCHK(ctx, launch_dctq(a, 2, ctx->stream));
-            k += m;
-        }
+        rc = queue_rate_transforms(ctx, p, s, s.pass_first[i], end, img_base);
+        if (rc) return rc;
         for (int first = s.pass_first[i]; first < end; first += kSizeMaxProbes, t++)
             HIPCHK(ctx, launch_adaptive_stats(ctx, (const int16_t *)ctx->d_coef, launches[t], t, kAdaptRateKernel, groups[t]));
     }
@@ -5979,40 +5896,18 @@ int tic_adaptive_sizes_v(tic_ctx *ctx, const uint8_t *const *images, int n, cons
     for (int i = 0; i < n; i++)
         if (num_blocks(hs[i], ws[i]) == 0) return set_err(ctx, TIC_E_ARG, "frame %d: %s", i, kAdaptNoBlocks);
     if (nq == 0) return TIC_OK;
-    int chunk_frames;
-    size_t chunk_bytes;
-    mixed_chunk_limits(&chunk_frames, &chunk_bytes);
-    const RatePlan p = plan_rate_batch(hs, ws, n, chunk_frames, chunk_bytes);
+    const ChunkLimits lim = mixed_chunk_limits();
+    const RatePlan p = plan_rate_batch(hs, ws, n, lim.frames, lim.bytes);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    RateSubmission s;
-    int probes = 0, waits = 0, launches = 0;
-    for (const MixedChunk &c : p.mixed.chunks) {
-        int rc = upload_rate_chunk(ctx, p.mixed, c, io);
-        if (rc) return rc;
-        s.probes.clear();
-        for (int j = 0; j < nq; j++) // quality by quality: the frames of a transform run are neighbours in the queue
-            for (int k = 0; k < c.count; k++) s.probes.push_back(RateProbe{c.first + k, qualities[j]});
-        rc = submit_adaptive_probes(ctx, p, s, ctx->d_img);
-        if (rc) return rc;
-        HIPCHK(ctx, wait_stream(ctx));
-        ctx->last_arate_waits++;
-        for (int j = 0; j < nq; j++)
-            for (int k = 0; k < c.count; k++) {
-                rc = adaptive_probe_size(ctx, ctx->h_arate_stats[(size_t)j * c.count + k], &sizes[(size_t)p.mixed.frames[(size_t)(c.first + k)].index * nq + j]);
-                if (rc) {
-                    const std::string why = ctx->err;
-                    return set_err(ctx, rc, "frame %d: %s", p.mixed.frames[(size_t)(c.first + k)].index, why.c_str());
-                }
-            }
-    }
-    probes = ctx->last_arate_probes, waits = ctx->last_arate_waits, launches = ctx->last_arate_launches;
+    const int brc = probe_every_quality(
+        ctx, p, io, qualities, nq, &ctx->last_arate_waits, [&](RateSubmission &s) { return submit_adaptive_probes(ctx, p, s, ctx->d_img); },
+        [&](size_t pr, int, size_t at) { return adaptive_probe_size(ctx, ctx->h_arate_stats[pr], &sizes[at]); });
+    if (brc) return brc;
+    int probes = ctx->last_arate_probes, waits = ctx->last_arate_waits, launches = ctx->last_arate_launches;
     for (int i : p.mixed.single) { // what the batch does not take, behind it, frame by frame
         const int rc = tic_adaptive_sizes(ctx, images[i], hs[i], ws[i], row_strides[i], qualities, nq, sizes + (size_t)i * nq);
         probes += ctx->last_arate_probes, waits += ctx->last_arate_waits, launches += ctx->last_arate_launches;
-        if (rc) {
-            const std::string why = ctx->err;
-            return set_err(ctx, rc, "frame %d: %s", i, why.c_str());
-        }
+        if (rc) return frame_err(ctx, rc, i);
     }
     ctx->last_arate_probes = probes, ctx->last_arate_waits = waits, ctx->last_arate_launches = launches;
     return TIC_OK;

@@ -1,6 +1,8 @@
-// tic_rate_plan.h - the host plan of the batch forms of rate control (tic_stream_sizes_v, tic_compress_batch_to_size), free of HIP and of
-// the context: the chunks of a call, the table the size kernel's descriptor form reads (stream_size_kernel_v, tic_size_gpu.hip), the layout
-// of one submission's probes in the coefficient workspace, and the bisection of every frame of a chunk run in lockstep.
+// tic_rate_plan.h - the host plan of rate control, free of HIP and of the context: the chunks of a batch call, the table the size kernel's
+// descriptor form reads (stream_size_kernel_v, tic_size_gpu.hip), the layout of one submission's probes in the coefficient workspace, and
+// the bisection by size as a state machine (RateSearch) that EVERY search by size drives - the single-frame ones (tic_compress_to_size,
+// tic_compress_adaptive_to_size) one frame at a time, tic_compress_batch_to_size every frame of a chunk in lockstep (round_probes, which
+// the search by distortion of tic_rd_plan.h shares).
 // tests/native/rateplan_selftest.cpp compiles it alone and sweeps it under the address and undefined-behaviour sanitizers.
 #pragma once
 #include <stddef.h>
@@ -80,6 +82,12 @@ inline int rate_depth(size_t chunk_blocks) {
     return 1;
 }
 
+// The look-ahead of a SINGLE-FRAME search of a frame of n blocks.  Not rate_depth: a probe of such a search takes the whole coefficient
+// workspace in its turn (the stream orders the probes), so no workspace bounds the look-ahead; what does is a host wait against a probe -
+// a wait costs about what a probe of a 4096^2 frame does (262144 blocks, some 15 us), a probe of a small frame a fraction of that: deep
+// look-ahead for small frames, none beyond 4096^2.
+inline int single_frame_depth(size_t n) { return n <= 16384 ? 3 : n <= 262144 ? 2 : 1; }
+
 struct RatePlan {
     MixedPlan mixed;
     std::vector<int> run_of; // per frame of mixed.frames
@@ -148,7 +156,7 @@ inline int rate_transform_run(const RatePlan &p, const RateSubmission &s, int i,
 }
 
 // ---- the search ------------------------------------------------------------------------------------------------------------------------------
-// Its contract is the bisection of tic_compress_to_size_dev; what is free is WHEN a quality is probed.  One submission probes every middle
+// The one copy of the bisection by size.  Its contract is that of tic_compress_to_size_dev; what is free is WHEN a quality is probed.  One submission probes every middle
 // the bisection can reach within `depth` further steps from where it stands (2^depth - 1 probes, the first one qmin as well), then the
 // bisection is replayed over the known sizes as far as they carry.  Sizes: -1 = no code, kRateUnknown = not probed.
 constexpr long long kRateUnknown = -2;
@@ -198,15 +206,19 @@ inline void rate_search_replay(RateSearch &s) {
     s.state = kRateFits;
 }
 
-// The probes every unsettled frame of chunk `c` wants, queued candidate by candidate: the frames' first candidates in chunk order, then
-// their second ones ... - in the first round every frame of a call asks for the same qualities, and neighbours of a transform run are
-// neighbours in the queue.  search[f]: the state of plan frame f.
-inline void rate_round_probes(const MixedChunk &c, const RateSearch *search, int depth, std::vector<RateProbe> &probes) {
+inline int search_round(const RateSearch &s, int depth, int *cand) { return rate_search_round(s, depth, cand); }
+inline void search_replay(RateSearch &s) { rate_search_replay(s); }
+
+// The probes every unsettled frame of chunk `c` wants - by size or by distortion: search_round / search_replay are overloaded for RateSearch
+// and for PsnrSearch (tic_rd_plan.h) - queued candidate by candidate: the frames' first candidates in chunk order, then their second
+// ones ... - in the first round every frame of a call asks for the same qualities, and neighbours of a transform run are neighbours in
+// the queue.  search[f]: the state of plan frame f.
+template <class Search> inline void round_probes(const MixedChunk &c, const Search *search, int depth, std::vector<RateProbe> &probes) {
     probes.clear();
     std::vector<int> cand((size_t)c.count * kRateMaxCandidates), nc((size_t)c.count);
     int most = 0;
     for (int k = 0; k < c.count; k++) {
-        nc[(size_t)k] = rate_search_round(search[c.first + k], depth, &cand[(size_t)k * kRateMaxCandidates]);
+        nc[(size_t)k] = search_round(search[c.first + k], depth, &cand[(size_t)k * kRateMaxCandidates]);
         most = std::max(most, nc[(size_t)k]);
     }
     for (int j = 0; j < most; j++)

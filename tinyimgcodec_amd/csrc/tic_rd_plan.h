@@ -1,7 +1,8 @@
-// tic_rd_plan.h - the host plan of the batch forms of rate-distortion control (tic_rd_points_v, tic_compress_batch_to_psnr,
-// tic_distortion_v_dev), free of HIP and of the context: the table the measuring kernel's descriptor form reads (idct_sse_kernel_v,
-// tic_kernels.hip) and the bisection by distortion of every frame of a chunk run in lockstep.  The chunks of a call, the layout of a
-// submission's probes in the coefficient workspace and the look-ahead depth are the rate plan's (tic_rate_plan.h).
+// tic_rd_plan.h - the host plan of rate-distortion control, free of HIP and of the context: the table the measuring kernel's descriptor
+// form reads (idct_sse_kernel_v, tic_kernels.hip) and the bisection by distortion as a state machine (PsnrSearch) that tic_compress_to_psnr
+// drives for one frame and tic_compress_batch_to_psnr for every frame of a chunk in lockstep.  The chunks of a call, the layout of a
+// submission's probes in the coefficient workspace, the look-ahead depths and the lockstep queue (round_probes) are the rate plan's
+// (tic_rate_plan.h).
 // tests/native/rdplan_selftest.cpp compiles it alone and sweeps it under the address and undefined-behaviour sanitizers.
 #pragma once
 #include <stddef.h>
@@ -86,7 +87,7 @@ inline bool fill_sse_probe_table(SseProbeTable *t, int n, const SseProbeIn *in, 
 }
 
 // ---- the search by distortion -------------------------------------------------------------------------------------------------------------------
-// Its contract is the bisection of tic_compress_to_psnr_dev: lo, hi = qmin, qmax; while lo < hi: mid = (lo + hi) / 2;
+// The one copy of the bisection by distortion.  Its contract is that of tic_compress_to_psnr_dev: lo, hi = qmin, qmax; while lo < hi: mid = (lo + hi) / 2;
 // meets(mid) ? hi = mid : lo = mid + 1, behind a first test of qmax.  What is free is WHEN a quality is probed: one submission probes every
 // middle the bisection can reach within `depth` further steps (2^depth - 1 probes, the first one qmax as well), then the bisection is
 // replayed over the known results as far as they carry.  known[]: stream lengths as the size search keeps them (-1 = no code,
@@ -139,19 +140,7 @@ inline void psnr_search_replay(PsnrSearch &s) {
     s.state = kPsnrMeets;
 }
 
-// The probes every unsettled frame of chunk `c` wants, queued candidate by candidate as rate_round_probes queues them: the frames' first
-// candidates in chunk order, then their second ones ...  search[f]: the state of plan frame f.
-inline void psnr_round_probes(const MixedChunk &c, const PsnrSearch *search, int depth, std::vector<RateProbe> &probes) {
-    probes.clear();
-    std::vector<int> cand((size_t)c.count * kRateMaxCandidates), nc((size_t)c.count);
-    int most = 0;
-    for (int k = 0; k < c.count; k++) {
-        nc[(size_t)k] = psnr_search_round(search[c.first + k], depth, &cand[(size_t)k * kRateMaxCandidates]);
-        most = std::max(most, nc[(size_t)k]);
-    }
-    for (int j = 0; j < most; j++)
-        for (int k = 0; k < c.count; k++)
-            if (j < nc[(size_t)k]) probes.push_back(RateProbe{c.first + k, cand[(size_t)k * kRateMaxCandidates + (size_t)j]});
-}
+inline int search_round(const PsnrSearch &s, int depth, int *cand) { return psnr_search_round(s, depth, cand); }
+inline void search_replay(PsnrSearch &s) { psnr_search_replay(s); }
 
 } // namespace tic
