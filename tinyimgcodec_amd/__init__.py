@@ -11,7 +11,9 @@ than a PSNR), their batch forms rd_points_batch and compress_batch_to_psnr (a li
 frame), roundtrip_sse_scaled and psnr_from_sse; and for rate control of the adaptive family: compressed_size_adaptive /
 compressed_sizes_adaptive (the length of compress_adaptive()'s stream without producing it), compress_adaptive_to_size (the best quality
 within a byte budget, with the image's own tables), compressed_sizes_adaptive_batch (a list of images of any shapes in one call) and
-entropy_size_adaptive (the same length from coefficients, on the host).
+entropy_size_adaptive (the same length from coefficients, on the host); and for the way back from a stream to its coefficients:
+entropy_decode (the dictionary the reference's decompress() hands to decode()), entropy_decode_zz (the int16 [N, 64] layout the entropy_*
+functions take), entropy_decode_adaptive, and lossless re-tabling of stored streams, retable_adaptive / retable_default.
 """
 from ._native import Context, NativeError, NativeUnavailable
 from .codec import (compress, compress_adaptive, compress_batch, compress_batch_adaptive, compress_batch_to_psnr, compress_batch_scaled, compress_batch_to_size, compress_scaled, compress_to_psnr, compress_to_size,
@@ -19,6 +21,7 @@ from .codec import (compress, compress_adaptive, compress_batch, compress_batch_
                     entropy_encode_adaptive, entropy_encode_adaptive_batch, entropy_encode_scaled, entropy_size, max_sse_for_psnr, parse_header, psnr_from_sse, rd_points, rd_points_batch, rd_points_scaled_batch,
                     roundtrip_psnr, roundtrip_sse_scaled)
 from .codec import compress_adaptive_to_size, compressed_size_adaptive, compressed_sizes_adaptive, compressed_sizes_adaptive_batch, entropy_size_adaptive
+from .codec import entropy_decode, entropy_decode_adaptive, entropy_decode_zz, retable_adaptive, retable_default
 
 __version__ = "0.1.0"
 __all__ = ["encode", "decode", "compress", "decompress"]

@@ -336,6 +336,29 @@ RATE_ADAPTIVE_SIGNATURES = {
     "tic_last_adaptive_rate": (C.c_int, [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
+# ... and exactly the symbols include/tinyimgcodec_hip_transcode.h declares: a stream's coefficients, and lossless re-tabling between the
+# two Huffman table families
+TRANSCODE_SIGNATURES = {
+    "tic_entropy_decode": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32)],
+    ),
+    "tic_entropy_decode_dev": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32)],
+    ),
+    "tic_entropy_decode_dev_timed": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float)],
+    ),
+    "tic_entropy_decode_adaptive": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    ),
+    "tic_retable_adaptive": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tic_retable_default": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+}
+
 _lib = None
 _lock = threading.RLock()  # re-entrant: default_context() creates a Context (which calls load()) under it
 
@@ -355,7 +378,7 @@ def load():
                 L = C.CDLL(path)
             except OSError as e:  # missing ROCm runtime etc.
                 raise NativeUnavailable("cannot load %s: %s" % (path, e)) from e
-            for name, (res, args) in list(SIGNATURES.items()) + list(RATE_ADAPTIVE_SIGNATURES.items()):
+            for name, (res, args) in list(SIGNATURES.items()) + list(RATE_ADAPTIVE_SIGNATURES.items()) + list(TRANSCODE_SIGNATURES.items()):
                 fn = getattr(L, name)
                 fn.restype = res
                 fn.argtypes = args

@@ -1225,6 +1225,141 @@ def decompress_batch(streams, ctx=None):
     return outs
 
 
+def _info_of(zz, hdr):
+    """The dictionary the reference's decompress() hands to decode() (codec.py:167-188), from zz16 rows: dc int32 DPCM differences with
+    the first one raw, ac int16 [N, 63]."""
+    dc = zz[:, 0].astype(np.int32)
+    info = dict(hdr)
+    info["dc"] = np.diff(dc, prepend=np.int32(0)).astype(np.int32) if dc.size else dc
+    info["ac"] = np.ascontiguousarray(zz[:, 1:])
+    return info
+
+
+def _default_header(buf):
+    """The header checks of decompress() that need no device, with its exceptions: struct.error below 16 bytes, ValueError for the
+    little-endian bit 31 and for a negative size (np.zeros in decompress()), the library's own error for a quality it refuses."""
+    hdr = parse_header(buf)
+    if hdr["flag"] & (1 << 31):
+        raise ValueError("stream carries an embedded Huffman table (little-endian flag bit 31): not supported")
+    if hdr["height"] < 0 or hdr["width"] < 0:
+        raise ValueError("negative dimensions are not allowed")
+    scaled = bool(hdr["flag"] & (1 << 30))
+    q = hdr["quality"]
+    if scaled and not 0 <= q <= 62:
+        raise N.NativeError(N.TIC_E_QUALITY, "scaled_dct exponent %d in header outside 0..62" % q)
+    if not scaled and not 1 <= q <= 99:
+        raise N.NativeError(N.TIC_E_QUALITY, "quality %d in header outside 1..99" % q)
+    return {"height": hdr["height"], "width": hdr["width"], "quality": q, "scaled_dct": scaled}
+
+
+def _adaptive_header(buf):
+    """decompress_adaptive()'s header checks that need no device, with its exceptions."""
+    if buf.size < 16:
+        raise ValueError("stream shorter than its 16-byte header")
+    hdr = parse_header(buf)
+    if hdr["height"] < 0 or hdr["width"] < 0:
+        raise ValueError("negative image size in the header")
+    if not 1 <= hdr["quality"] <= 99:
+        raise ValueError("quality %d in the header outside 1..99" % hdr["quality"])
+    return {"height": hdr["height"], "width": hdr["width"], "quality": hdr["quality"], "scaled_dct": False}
+
+
+def entropy_decode_zz(data, ctx=None):
+    """The mirror of entropy_encode(): a default-table or scaled_dct stream -> (coefficients int16 [N, 64] in zig-zag order with the
+    absolute DC - the layout entropy_encode, entropy_size and entropy_encode_adaptive take -, header dict with height, width, quality,
+    scaled_dct).  The reference's reading of the stream, as decompress() reads it (long streams on the GPU).  Exceptions as
+    decompress(); ValueError when the running DC leaves int16, which the layout cannot hold."""
+    buf = _as_bytes_view(data)
+    hdr = _default_header(buf)
+    L = N.load()
+    n = L.tic_num_blocks(hdr["height"], hdr["width"])
+    zz = np.empty((n, 64), dtype=np.int16)
+    ctx = _ctx(ctx)
+    with ctx.lock:
+        rc = L.tic_entropy_decode(ctx.handle, buf.ctypes.data, buf.size, zz.ctypes.data, n, None, None, None, None)
+        if rc == N.TIC_E_RANGE:
+            raise ValueError(L.tic_last_error(ctx.handle).decode())
+        ctx.check(rc)
+    return zz, hdr
+
+
+def entropy_decode(data, ctx=None):
+    """The first half of the reference's decompress() (codec.py:167-188): the dictionary it hands to decode() - height, width, quality,
+    scaled_dct, dc (int32 DPCM differences, the first one raw), ac (int16 [N, 63]).  decode(entropy_decode(s)) is decompress(s)."""
+    zz, hdr = entropy_decode_zz(data, ctx=ctx)
+    return _info_of(zz, hdr)
+
+
+def entropy_decode_adaptive(data, ctx=None):
+    """entropy_decode() for a stream with an embedded table (compress_adaptive): the same dictionary; strict, with
+    decompress_adaptive()'s exceptions."""
+    buf = _as_bytes_view(data)
+    hdr = _adaptive_header(buf)
+    L = N.load()
+    n = L.tic_num_blocks(hdr["height"], hdr["width"])
+    zz = np.empty((n, 64), dtype=np.int16)
+    ctx = _ctx(ctx)
+    with ctx.lock:
+        rc = L.tic_entropy_decode_adaptive(ctx.handle, buf.ctypes.data, buf.size, zz.ctypes.data, n, None, None, None)
+        if rc in (N.TIC_E_STREAM, N.TIC_E_SPACE):
+            raise ValueError(L.tic_last_error(ctx.handle).decode())
+        ctx.check(rc)
+    return _info_of(zz, hdr)
+
+
+def _retable(ctx, fn, buf, cap, missing_code):
+    """A re-tabling entry point under the context's lock: _adaptive_encode's retry and OverflowError, KeyError for a symbol without a
+    default code, ValueError for a refused stream or a DC outside int16."""
+    L = N.load()
+    with ctx.lock:
+        try:
+            return _adaptive_encode(ctx, fn, (buf.ctypes.data, buf.size), cap)
+        except OverflowError as e:
+            if "running DC" in str(e):
+                raise ValueError(str(e)) from None
+            if missing_code:
+                raise KeyError(str(e)) from None
+            raise
+        except N.NativeError as e:
+            if e.code == N.TIC_E_STREAM:
+                raise ValueError(L.tic_last_error(ctx.handle).decode()) from None
+            raise
+
+
+def retable_adaptive(data, ctx=None):
+    """A stored default-table stream rewritten with its image's own Huffman tables, losslessly: the reference's reader (codec.py:167-188)
+    followed by its writer with auto_generate_huffman_table=True (codec.py:133-164) on the same coefficients.  For a stream of
+    compress(image, q) the result is compress_adaptive(image, q), byte for byte.  ValueError for scaled_dct streams, refused headers and
+    a running DC outside int16; IndexError for a frame without blocks; OverflowError as compress_adaptive."""
+    buf = _as_bytes_view(data)
+    hdr = parse_header(buf)
+    if hdr["flag"] & (1 << 31):
+        raise ValueError("stream carries an embedded Huffman table already (little-endian flag bit 31)")
+    if hdr["flag"] & (1 << 30):
+        raise ValueError("a scaled_dct stream cannot carry an embedded table: the flag word has room for one family")
+    if hdr["height"] < 0 or hdr["width"] < 0:
+        raise ValueError("negative image size in the header")
+    if not 1 <= hdr["quality"] <= 99:
+        raise ValueError("quality %d in the header outside 1..99" % hdr["quality"])
+    L = N.load()
+    if L.tic_num_blocks(hdr["height"], hdr["width"]) == 0:
+        raise IndexError("index -1 is out of bounds for axis 0 with size 0")  # calc_huffman_table on an empty symbol list
+    ctx = _ctx(ctx)
+    return _retable(ctx, L.tic_retable_adaptive, buf, L.tic_compress_bound(hdr["height"], hdr["width"]) + 4096, False)
+
+
+def retable_default(data, ctx=None):
+    """The way back: a stream with an embedded table rewritten with the default tables.  KeyError where a symbol has no default code (as
+    compress() raises it); ValueError as decompress_adaptive()."""
+    buf = _as_bytes_view(data)
+    hdr = _adaptive_header(buf)
+    L = N.load()
+    ctx = _ctx(ctx)
+    # (the default stream is the longer one as a rule, by a few per cent at most qualities: one retry with the reported length otherwise)
+    cap = min(L.tic_compress_bound(hdr["height"], hdr["width"]), buf.size + buf.size // 2 + 4096)
+    return _retable(ctx, L.tic_retable_default, buf, cap, True)
+
+
 def decode(data, ctx=None):
     """decode() of the reference: dict with height, width, quality, scaled_dct, dc (DPCM'd), ac."""
     ctx = _ctx(ctx)

@@ -19,6 +19,7 @@
 
 #include "../../include/tinyimgcodec_hip.h"
 #include "../../include/tinyimgcodec_hip_adaptive_rate.h"
+#include "../../include/tinyimgcodec_hip_transcode.h"
 #include "tic_adaptive.h"
 #include "tic_adaptive_stats_gpu.h"
 #include "tic_decode_plan.h"
@@ -4097,6 +4098,13 @@ static int idctq_impl(tic_ctx *ctx, const int16_t *coeffs_zz, int h, int w, int 
 // up and the second run cost more than the host decoder.  Round 6: the stitch follows the chain over such ranges (tic_entropy_dec_gpu.hip,
 // the fix-up loop), every density is taken, and the bit floor is 1 KB (the benchmark set's sparsest stream at q = 5 has 4,071 bytes).
 // Hooks TIC_DECODE_MIN_BLOCKS / _BITS / _DENSITY move the lines for measurements.
+// The SINK (DecSink): pixels, as described - or the COEFFICIENTS themselves (tic_entropy_decode, tic_retable_adaptive): the same two launches with the
+// fused kernel's phase 1 alone (entropy_decode_coef_gpu), the same tries, and the blocks of the host-decoded tail copied behind block m instead of
+// transformed; `out`, ctx->d_img and ctx->h_small are not touched then.
+struct DecSink {
+    bool coef = false;          // false: pixels into `out`
+    int16_t *d_user = nullptr;  // coef: the caller's device buffer, int16 [n][64], 16-byte aligned; null: ctx->d_coef
+};
 constexpr size_t kDevDecodeMinBlocks = 1024, kDevDecodeMinBits = 1u << 13, kDevDecodeMinDensity = 0;
 static bool device_decoder_takes(size_t n, size_t len) {
     size_t min_blocks = kDevDecodeMinBlocks, min_bits = kDevDecodeMinBits, min_density = kDevDecodeMinDensity;
@@ -4125,7 +4133,7 @@ static int decode_range_bits(size_t len, size_t n, size_t mult = 2, size_t floor
 
 static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const StreamHead &sh, uint8_t *out, bool out_on_device, size_t out_stride,
                             bool *done, const uint8_t *head16 /* the 16 header bytes sh came from */, bool src_on_device = false,
-                            bool head_is_guess = false, bool *guess_held = nullptr) {
+                            bool head_is_guess = false, bool *guess_held = nullptr, DecSink sink = DecSink()) {
     *done = false;
     const int h = sh.h, w = sh.w;
     if (guess_held) *guess_held = false;
@@ -4137,8 +4145,9 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
     int rc = ensure_dec_tables(ctx);
     if (rc) return rc;
     const size_t pitch = align_up((size_t)w, 256);
-    rc = ensure_scratch(ctx, pitch * (size_t)h, n * 128);
+    rc = ensure_scratch(ctx, sink.coef ? 0 : pitch * (size_t)h, n * 128);
     if (rc) return rc;
+    int16_t *const d_sink = sink.coef ? (sink.d_user ? sink.d_user : (int16_t *)ctx->d_coef) : nullptr;
     // The stream is decoded where it lies when it is in device memory at a 4-byte aligned address (the kernels mask the bytes behind
     // its end themselves); a host stream, or an odd address, goes through the context's stream buffer.
     const bool in_place = src_on_device && ((uintptr_t)data & 3u) == 0;
@@ -4163,12 +4172,12 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
     bool tail_prefetched = false;
     // where the pixels go: a device destination whose rows are 8-byte aligned takes them straight from the kernels (row stores are
     // cropped to w); anything else gets them from the context's image buffer with one strided copy at the end
-    const bool direct = out_on_device && out_stride % 8 == 0 && (uintptr_t)out % 8 == 0;
+    const bool direct = !sink.coef && out_on_device && out_stride % 8 == 0 && (uintptr_t)out % 8 == 0;
     // a small image on its way to host memory: the kernels store its rows (8-byte aligned, back to back) into the context's host-mapped
     // buffer, and one memcpy behind the wait that reads the status takes them to the caller - no copy command, no second wait
     // (a 512 x 512 image: 30 us between the last kernel and the end of the read-back, profiles/r05_decoder.txt)
     const size_t pitch8 = dec_pix_pitch(w);
-    const bool host_pix = !out_on_device && pitch8 * (size_t)h <= kDecHostPixBytes && !test_hook("TIC_DECODE_NO_HOSTPIX");
+    const bool host_pix = !sink.coef && !out_on_device && pitch8 * (size_t)h <= kDecHostPixBytes && !test_hook("TIC_DECODE_NO_HOSTPIX");
     if (host_pix) {
         rc = ensure_small(ctx, kSmallHostBytes);
         if (rc) return rc;
@@ -4207,8 +4216,12 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
         if (rc) return rc;
         ctx->last_decode_tries++;
         ctx->last_decode_range = range_bits;
-        HIPCHK(ctx, entropy_decode_idct_gpu(d_stream, len, n, ctx->d_dec_luts, ws.work, ws.work_bytes, ws.desc, ws.desc_words, ws.epoch, ia,
-                                            ws.d_status, range_bits, margin_bits, ctx->stream, flat_grid));
+        if (sink.coef)
+            HIPCHK(ctx, entropy_decode_coef_gpu(d_stream, len, n, ctx->d_dec_luts, ws.work, ws.work_bytes, ws.desc, ws.desc_words, ws.epoch, head16, d_sink,
+                                                ws.d_status, range_bits, margin_bits, ctx->stream, flat_grid));
+        else
+            HIPCHK(ctx, entropy_decode_idct_gpu(d_stream, len, n, ctx->d_dec_luts, ws.work, ws.work_bytes, ws.desc, ws.desc_words, ws.epoch, ia,
+                                                ws.d_status, range_bits, margin_bits, ctx->stream, flat_grid));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         memcpy(&st, ws.h_status, sizeof st); // (host-mapped: the stream has drained)
         if (guessed_head) { // geometry and quality were a guess (tic_decompress_dev): what this run produced counts only if the stream's header is the guessed one
@@ -4257,6 +4270,12 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
             ctx->last_decode_giveup = kDecGiveupWideDc;
             return TIC_OK;
         }
+        if (sink.coef) { // nothing is transformed: the tail's rows go behind block m, and the call ends with a drained stream
+            HIPCHK(ctx, hipMemcpyAsync((char *)d_sink + (size_t)st.m * 128, tail, tail_bytes, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            *done = true;
+            return TIC_OK;
+        }
         HIPCHK(ctx, hipMemcpyAsync((char *)ctx->d_coef + (size_t)st.m * 128, tail, tail_bytes, hipMemcpyHostToDevice, ctx->stream));
         IdctArgs a = idct_args(ia, (const int16_t *)ctx->d_coef);
         a.first_block = (long)st.m;
@@ -4267,7 +4286,7 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
     }
     if (host_pix) { // (the stream has drained: the kernels' stores have arrived)
         copy_rows(out, (size_t)w, ctx->h_small, (ptrdiff_t)pitch8, h, w);
-    } else if (!direct) {
+    } else if (!direct && !sink.coef) { // (coefficient sink: every row is in place already)
         HIPCHK(ctx, hipMemcpy2DAsync(out, out_on_device ? out_stride : (size_t)w, ctx->d_img, pitch, (size_t)w, (size_t)h,
                                      out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -5278,11 +5297,15 @@ static int adaptive_decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t l
 // its first `head_len` bytes in host memory (all of it, or 16 + kAdaptMaxTableBytes: header and table).  Pixels as idct_from_device.
 // The host decoder runs for the streams the device decoder does not take, after a give-up, and whenever the table does not parse:
 // it alone decides between pixels and TIC_E_STREAM and words the message.
-static int decompress_adaptive_impl(tic_ctx *ctx, const uint8_t *data, size_t len, bool src_on_device, const uint8_t *head, size_t head_len, int h, int w,
-                                    int q, uint8_t *out, bool out_on_device, size_t out_stride) {
+// The front half, which the coefficient calls share (tic_entropy_decode_adaptive, tic_retable_default): the stream's coefficients into ctx->d_coef
+// (*in_h_zz = false: the device decoder wrote them) or into ctx->h_zz (*in_h_zz = true: the host decoder did; the caller uploads them where it needs
+// them on the device).  img_bytes: the scratch image provisioned beside the coefficients (0: none).
+static int adaptive_read_coefs(tic_ctx *ctx, const uint8_t *data, size_t len, bool src_on_device, const uint8_t *head, size_t head_len, int h, int w,
+                               size_t img_bytes, bool *in_h_zz) {
     const size_t n = num_blocks(h, w);
+    *in_h_zz = false;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc = n ? ensure_scratch(ctx, align_up((size_t)w, 256) * (size_t)h, n * 128) : TIC_OK;
+    int rc = n ? ensure_scratch(ctx, img_bytes, n * 128) : TIC_OK;
     if (rc) return rc;
     {
         AdaptTable t;
@@ -5293,7 +5316,7 @@ static int decompress_adaptive_impl(tic_ctx *ctx, const uint8_t *data, size_t le
             if (rc) return rc;
             if (done) {
                 ctx->last_decode_path = 1;
-                return idct_from_device(ctx, h, w, q, -1, out, out_on_device, out_stride);
+                return TIC_OK;
             }
         }
     }
@@ -5315,8 +5338,18 @@ static int decompress_adaptive_impl(tic_ctx *ctx, const uint8_t *data, size_t le
     const char *why = "";
     rc = adaptive_decode(head, len, h, w, ctx->h_zz, &why);
     if (rc) return set_err(ctx, rc, "adaptive stream: %s", why);
+    *in_h_zz = true;
+    return TIC_OK;
+}
+
+static int decompress_adaptive_impl(tic_ctx *ctx, const uint8_t *data, size_t len, bool src_on_device, const uint8_t *head, size_t head_len, int h, int w,
+                                    int q, uint8_t *out, bool out_on_device, size_t out_stride) {
+    const size_t n = num_blocks(h, w);
+    bool in_h_zz = false;
+    const int rc = adaptive_read_coefs(ctx, data, len, src_on_device, head, head_len, h, w, align_up((size_t)w, 256) * (size_t)h, &in_h_zz);
+    if (rc) return rc;
     if (n == 0) return TIC_OK;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, ctx->h_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
+    if (in_h_zz) HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, ctx->h_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
     return idct_from_device(ctx, h, w, q, -1, out, out_on_device, out_stride);
 }
 
@@ -5342,6 +5375,213 @@ int tic_decompress_adaptive(tic_ctx *ctx, const uint8_t *data, size_t len, uint8
     const int rc = check_adaptive_header(ctx, data, len, out, cap, &h, &w, &q);
     if (rc) return rc;
     return decompress_adaptive_impl(ctx, data, len, false, data, len, h, w, q, out, false, 0);
+}
+
+// ---- transcoding (tinyimgcodec_hip_transcode.h): a stream's coefficients, and the stream of the other table family from them -----------------------
+// The reader of default-table and scaled_dct streams: decode_on_device with the coefficient sink - *on_device = true, the n rows are at d_user (null:
+// ctx->d_coef) - or, for everything the device reader does not take or gives up on, the host decoder as in decode_on_host: *on_device = false, the
+// rows are in ctx->h_zz.  A running DC outside int16 (the device run's give-up bit 512 comes here too) is TIC_E_RANGE: the layout cannot hold it.
+// `data` in host or device memory; head16: the stream's own 16 header bytes, in host memory.
+static int read_default_coefs(tic_ctx *ctx, const uint8_t *data, size_t len, bool src_on_device, const StreamHead &sh, const uint8_t *head16,
+                              int16_t *d_user, bool *on_device) {
+    const size_t n = num_blocks(sh.h, sh.w);
+    DecSink sink;
+    sink.coef = true;
+    sink.d_user = d_user;
+    int rc = decode_on_device(ctx, data, len, sh, nullptr, false, 0, on_device, head16, src_on_device, false, nullptr, sink);
+    if (rc) return rc;
+    if (*on_device) {
+        ctx->last_decode_path = 1;
+        return TIC_OK;
+    }
+    std::vector<uint8_t> host;
+    if (src_on_device) {
+        try {
+            host.resize(len);
+        } catch (...) {
+            return set_err(ctx, TIC_E_ARG, "out of host memory for a stream of %zu bytes", len);
+        }
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        HIPCHK(ctx, hipMemcpy(host.data(), data, len, hipMemcpyDeviceToHost));
+        data = host.data();
+    }
+    rc = grow_pinned(ctx, "h_zz", ctx->h_zz, ctx->h_zz_bytes, n * 128);
+    if (rc) return rc;
+    std::vector<DcWide> wide;
+    entropy_decode(data, len, sh.h, sh.w, ctx->h_zz, &wide);
+    ctx->last_decode_path = 2;
+    if (!wide.empty())
+        return set_err(ctx, TIC_E_RANGE, "the running DC left int16 at block %zu (%d): the int16 coefficient layout cannot hold it", wide[0].block,
+                       (int)wide[0].dc);
+    return TIC_OK;
+}
+
+// the header's fields as the caller gets them (quality: the exponent of a scaled_dct stream)
+static void head_out(const StreamHead &sh, int *h, int *w, int *quality, uint32_t *flag) {
+    if (h) *h = sh.h;
+    if (w) *w = sh.w;
+    if (quality) *quality = sh.scaled_exp >= 0 ? sh.scaled_exp : sh.quality;
+    if (flag) *flag = sh.scaled_exp >= 0 ? kFlagScaled : 0u;
+}
+
+static int entropy_decode_impl(tic_ctx *ctx, const uint8_t *data, size_t len, bool on_device, void *coeffs_zz, size_t cap_blocks, int *h, int *w,
+                               int *quality, uint32_t *flag) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    ctx->last_decode_giveup = 0;
+    ctx->last_decode_tries = 0;
+    if (!data && len) return set_err(ctx, TIC_E_ARG, "null stream pointer");
+    uint8_t head[16] = {0};
+    if (on_device) {
+        if (len < 16) return set_err(ctx, TIC_E_STREAM, "stream shorter than the 16-byte header");
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        HIPCHK(ctx, hipMemcpy(head, data, 16, hipMemcpyDeviceToHost));
+    }
+    StreamHead sh;
+    int rc = check_header(ctx, on_device ? head : data, on_device ? 16 : len, &sh);
+    if (rc) return rc;
+    head_out(sh, h, w, quality, flag);
+    const size_t n = num_blocks(sh.h, sh.w);
+    if (n == 0) return TIC_OK;
+    if (!coeffs_zz || cap_blocks < n) return set_err(ctx, TIC_E_SPACE, "coefficient buffer too small (%zu blocks needed)", n);
+    if (on_device && ((uintptr_t)coeffs_zz & 15u)) return set_err(ctx, TIC_E_ARG, "device coefficient buffer must be 16-byte aligned");
+    bool dev = false;
+    rc = read_default_coefs(ctx, data, len, on_device, sh, on_device ? head : data, on_device ? (int16_t *)coeffs_zz : nullptr, &dev);
+    if (rc) return rc;
+    if (dev && on_device) return TIC_OK; // (the rows are where the caller wants them, behind a drained stream)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (dev) HIPCHK(ctx, hipMemcpyAsync(coeffs_zz, ctx->d_coef, n * 128, hipMemcpyDeviceToHost, ctx->stream));
+    else if (on_device) HIPCHK(ctx, hipMemcpyAsync(coeffs_zz, ctx->h_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
+    else memcpy(coeffs_zz, ctx->h_zz, n * 128);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TIC_OK;
+}
+
+int tic_entropy_decode(tic_ctx *ctx, const uint8_t *data, size_t len, int16_t *coeffs_zz, size_t cap_blocks, int *h, int *w, int *quality,
+                       uint32_t *flag) {
+    return entropy_decode_impl(ctx, data, len, false, coeffs_zz, cap_blocks, h, w, quality, flag);
+}
+
+int tic_entropy_decode_dev(tic_ctx *ctx, const void *d_stream, size_t len, void *d_coeffs_zz, size_t cap_blocks, int *h, int *w, int *quality,
+                           uint32_t *flag) {
+    return entropy_decode_impl(ctx, (const uint8_t *)d_stream, len, true, d_coeffs_zz, cap_blocks, h, w, quality, flag);
+}
+
+int tic_entropy_decode_dev_timed(tic_ctx *ctx, const void *d_stream, size_t len, void *d_coeffs_zz, size_t cap_blocks, int warm, int iters,
+                                 float *ms_total) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (!ms_total || warm < 0 || iters <= 0 || !d_stream || !d_coeffs_zz || len < 16) return set_err(ctx, TIC_E_ARG, "bad argument");
+    if (((uintptr_t)d_stream & 3u) || ((uintptr_t)d_coeffs_zz & 15u)) return set_err(ctx, TIC_E_ARG, "stream 4-byte, coefficients 16-byte aligned");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    uint8_t head[16];
+    HIPCHK(ctx, hipMemcpy(head, d_stream, 16, hipMemcpyDeviceToHost));
+    StreamHead sh;
+    int rc = check_header(ctx, head, 16, &sh);
+    if (rc) return rc;
+    const size_t n = num_blocks(sh.h, sh.w);
+    if (cap_blocks < n) return set_err(ctx, TIC_E_SPACE, "coefficient buffer too small (%zu blocks needed)", n);
+    if (!device_decoder_takes(n, len)) return set_err(ctx, TIC_E_ARG, "the device reader does not take this stream");
+    rc = ensure_dec_tables(ctx);
+    if (rc) return rc;
+    DecWorkspace &ws = ctx->dec_ws;
+    const size_t wb = entropy_decode_gpu_work_bytes(len, n);
+    rc = ws.grow(ctx, wb, wb, entropy_decode_gpu_desc_words(len, n), 1, 1);
+    if (rc) return rc;
+    const int range_bits = decode_range_bits(len, n);
+    rc = timed_launches(ctx, warm, iters, ms_total, nullptr, [&](int, hipEvent_t, hipEvent_t) {
+        if (ws.begin(ctx, ctx->stream, 1)) return hipErrorUnknown; // (a new epoch per run; the status words are the last run's when the stream has drained)
+        return entropy_decode_coef_gpu(d_stream, len, n, ctx->d_dec_luts, ws.work, ws.work_bytes, ws.desc, ws.desc_words, ws.epoch, head,
+                                       (int16_t *)d_coeffs_zz, ws.d_status, range_bits, 0, ctx->stream);
+    });
+    if (rc) return rc;
+    DecStatus st;
+    memcpy(&st, ws.h_status, sizeof st);
+    if (!dec_status_complete(st, head, n)) return set_err(ctx, TIC_E_ARG, "the device reader gave up on this stream (flags %d): nothing to time", st.giveup);
+    return TIC_OK;
+}
+
+int tic_entropy_decode_adaptive(tic_ctx *ctx, const uint8_t *data, size_t len, int16_t *coeffs_zz, size_t cap_blocks, int *h_out, int *w_out,
+                                int *quality) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    ctx->last_decode_giveup = 0;
+    int h = 0, w = 0, q = 0;
+    int rc = check_adaptive_header(ctx, data, len, data, ~(size_t)0 >> 1, &h, &w, &q); // (no pixels: the capacity that counts is cap_blocks, below)
+    if (rc) return rc;
+    if (h_out) *h_out = h;
+    if (w_out) *w_out = w;
+    if (quality) *quality = q;
+    const size_t n = num_blocks(h, w);
+    if (n && (!coeffs_zz || cap_blocks < n)) return set_err(ctx, TIC_E_SPACE, "coefficient buffer too small (%zu blocks needed)", n);
+    bool in_h_zz = false;
+    rc = adaptive_read_coefs(ctx, data, len, false, data, len, h, w, 0, &in_h_zz);
+    if (rc || n == 0) return rc;
+    if (in_h_zz) {
+        memcpy(coeffs_zz, ctx->h_zz, n * 128);
+        return TIC_OK;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(coeffs_zz, ctx->d_coef, n * 128, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TIC_OK;
+}
+
+int tic_retable_adaptive(tic_ctx *ctx, const uint8_t *data, size_t len, uint8_t *out, size_t cap, size_t *out_len) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    ctx->last_decode_giveup = 0;
+    ctx->last_decode_tries = 0;
+    if (!out || !out_len) return set_err(ctx, TIC_E_ARG, "null output pointer");
+    int h = 0, w = 0, q = 0;
+    uint32_t flag = 0;
+    if (parse_header(data, len, &h, &w, &q, &flag) != TIC_OK) return set_err(ctx, TIC_E_STREAM, "stream shorter than the 16-byte header");
+    if (flag & (1u << 31)) return set_err(ctx, TIC_E_STREAM, "the stream has an embedded Huffman table already");
+    if (flag & kFlagScaled) return set_err(ctx, TIC_E_STREAM, "a scaled_dct stream cannot carry an embedded table: the flag word has room for one family");
+    if (h < 0 || w < 0) return set_err(ctx, TIC_E_STREAM, "negative image size in the header");
+    if (q < 1 || q > 99) return set_err(ctx, TIC_E_STREAM, "quality %d in the header outside 1..99", q);
+    const size_t n = num_blocks(h, w);
+    if (n == 0) return set_err(ctx, TIC_E_ARG, "an image without blocks has no symbols to build a table from (the reference raises IndexError)");
+    const StreamHead sh = {h, w, q, -1};
+    bool dev = false;
+    int rc = read_default_coefs(ctx, data, len, false, sh, data, nullptr, &dev);
+    if (rc) return rc;
+    if (!dev) { // the host reader's rows go up; the device reader's never left
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        rc = ensure_scratch(ctx, 0, n * 128);
+        if (rc) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, ctx->h_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return adaptive_encode_dev(ctx, n, h, w, q, out, cap, out_len);
+}
+
+int tic_retable_default(tic_ctx *ctx, const uint8_t *data, size_t len, uint8_t *out, size_t cap, size_t *out_len) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    ctx->last_decode_giveup = 0;
+    if (!out || !out_len) return set_err(ctx, TIC_E_ARG, "null output pointer");
+    int h = 0, w = 0, q = 0;
+    int rc = check_adaptive_header(ctx, data, len, data, ~(size_t)0 >> 1, &h, &w, &q); // (no pixels: `cap` is the stream's, checked against its length)
+    if (rc) return rc;
+    const size_t n = num_blocks(h, w);
+    bool in_h_zz = false;
+    rc = adaptive_read_coefs(ctx, data, len, false, data, len, h, w, 0, &in_h_zz);
+    if (rc) return rc;
+    if (n == 0) return entropy_encode(nullptr, h, w, q, out, cap, out_len); // the header alone (codec.py:151)
+    if (in_h_zz) HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, ctx->h_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
+    // the default device entropy stage on the context's workspace; the input stream's copy in d_stream_buf (if the device reader made one) is done with
+    rc = grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, compress_bound(h, w));
+    if (rc) return rc;
+    size_t packed = 0;
+    rc = entropy_encode_dev_impl(ctx, ctx->d_coef, h, w, q, ctx->d_stream_buf, ctx->d_stream_cap, &packed, false);
+    if (rc) return rc;
+    if (packed > cap) {
+        *out_len = packed;
+        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", packed, cap);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_stream_buf, packed, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *out_len = packed;
+    return TIC_OK;
 }
 
 // ---- tic_decompress_batch_adaptive: decompress_adaptive() of MANY streams at once ---------------------------------------------------------------

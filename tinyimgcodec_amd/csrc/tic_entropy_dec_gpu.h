@@ -146,6 +146,14 @@ hipError_t entropy_decode_idct_gpu(const void *d_stream_words, size_t stream_byt
                                    size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, const DecIdctArgs &idct,
                                    DecStatus *d_status, int range_bits, int margin_bits, hipStream_t stream, int flat_grid = 4096);
 
+// The same two launches with a COEFFICIENT sink: the unchanged measure / stitch kernel, then the fused kernel's phase 1, which stores blocks [0, m) as
+// rows of the zz16 layout - int16 [nblocks][64], zig-zag order, absolute DC (saturated to int16: giveup bit kDecGiveupWideDc says that it was) -
+// at d_coef (16-byte aligned) instead of transforming them.  head16: the stream's own 16 header bytes (coefficients are stored only under them).
+// Work buffer, look-back words, epoch, range, margin and status as above.
+hipError_t entropy_decode_coef_gpu(const void *d_stream_words, size_t stream_bytes, size_t nblocks, const DecLutsDev *d_luts, void *d_work,
+                                   size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, const uint8_t head16[16], int16_t *d_coef,
+                                   DecStatus *d_status, int range_bits, int margin_bits, hipStream_t stream, int flat_grid = 4096);
+
 // The batch form: `nframes` whole streams in two launches.  d_frames / d_tile_frame / d_wg_frame: device copies of the descriptors, the frame of
 // every wave of the measure grid and of every workgroup of the fused grid; d_status: nframes entries, zeroed by the caller; the sums'
 // look-back words and the epoch as above; small_win: every stream has at most 240 bits per block on average.  A frame whose status comes back

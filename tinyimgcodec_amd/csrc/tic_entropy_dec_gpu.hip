@@ -619,11 +619,15 @@ __constant__ int kAnnScalesDec[64] = { // ANNSCALES of the reference's scaled_dc
 
 // kWinWords: stream words of the workgroup's window: 2048 (+ kOver) hold 256 blocks of up to 256 bits on average - three workgroups
 // per CU - 4096 of up to 512 - two; what lies behind the window is read from memory
-template <uint32_t kWinWords, bool kScaled>
+// kCoefSink: phase 1 only - the block's LDS image is kept in SCAN order (the zig-zag walk is not undone) and the wave copies its 64 images
+// to coef_out, a row of the zz16 layout per block, instead of transforming them (the copy-out below); `a` then carries the
+// stream's header and nothing else.
+template <uint32_t kWinWords, bool kScaled, bool kCoefSink = false>
 __device__ __forceinline__ void decode_idct_body(const uint32_t *__restrict__ gwords, uint32_t nwords, uint32_t last_mask, const DecLutsDev *__restrict__ L,
                                                  const uint32_t *__restrict__ bpos, unsigned long long *__restrict__ desc, uint32_t desc_half, uint32_t flat_grid, uint32_t epoch,
                                                  const long long *__restrict__ total_blocks, unsigned long long n_want, uint32_t stream_bits,
-                                                 const DecIdctArgs &a, DecStatus *__restrict__ st, const uint32_t wg /* this workgroup among the stream's `nwgs` */, const uint32_t nwgs) {
+                                                 const DecIdctArgs &a, DecStatus *__restrict__ st, const uint32_t wg /* this workgroup among the stream's `nwgs` */, const uint32_t nwgs,
+                                                 int16_t *__restrict__ coef_out = nullptr /* kCoefSink: int16 [n_want][64], 16-byte aligned */) {
     // tables + stream window
     constexpr uint32_t kBlkWin = kWinWords + kOver;
     constexpr uint32_t kBlkLds = kBlkWin + kBlkWin / 32 + 2;
@@ -645,7 +649,7 @@ __device__ __forceinline__ void decode_idct_body(const uint32_t *__restrict__ gw
     // geometry and quality came from a.head - possibly a guess (tic_decompress_dev): pixels are written only under the header the stream
     // really has (four words, the same for every lane: scalar loads; the measure kernel echoes them to the host, which decodes again)
     if (gwords[0] != a.head[0] || gwords[1] != a.head[1] || gwords[2] != a.head[2] || gwords[3] != a.head[3]) return;
-    if (threadIdx.x < 64) {
+    if (!kCoefSink && threadIdx.x < 64) {
         zznat[threadIdx.x] = a.consts->zznat[threadIdx.x];
         dq[threadIdx.x] = a.consts->div[threadIdx.x];
     }
@@ -718,14 +722,14 @@ __device__ __forceinline__ void decode_idct_body(const uint32_t *__restrict__ gw
                 const int len1 = (int)((e >> 8) & 31u), size1 = (int)(e & 15u);
                 const int k1 = k + (int)((e >> 4) & 15u);
                 const bool bad1 = nocode || (!none && !eob1 && k1 > 63);
-                if (!none && !eob1 && !bad1) c[zznat[k1]] = (int16_t)value_of(pk, len1, size1);
+                if (!none && !eob1 && !bad1) c[kCoefSink ? k1 : (int)zznat[k1]] = (int16_t)value_of(pk, len1, size1);
                 const bool has2 = ((e >> 13) & 1u) != 0u; // (never behind an EOB, never in a long codeword's step)
                 const uint32_t e2 = e >> 14;
                 const bool eob2 = has2 && (e2 & 0xffu) == 0u;
                 const int len2 = (int)((e2 >> 8) & 31u), size2 = (int)(e2 & 15u);
                 const int k2 = k1 + 1 + (int)((e2 >> 4) & 15u);
                 const bool bad2 = has2 && !bad1 && !eob2 && k2 > 63;
-                if (has2 && !eob2 && !bad1 && !bad2) c[zznat[k2]] = (int16_t)value_of(pk << (len1 + size1), len2, size2); // (at most 11 + 10 bits in front of and in it)
+                if (has2 && !eob2 && !bad1 && !bad2) c[kCoefSink ? k2 : (int)zznat[k2]] = (int16_t)value_of(pk << (len1 + size1), len2, size2); // (at most 11 + 10 bits in front of and in it)
                 advance(none ? 0u : e >> 27, wn); // (at most 26 bits)
                 k = none ? k : (has2 ? k2 + 1 : k1 + 1);
                 in_long = esc;
@@ -756,6 +760,40 @@ __device__ __forceinline__ void decode_idct_body(const uint32_t *__restrict__ gw
             if ((int32_t)c[0] != dc32) atomicOr(&st->giveup, kDecGiveupWideDc);
             if (b == m - 1) st->dc_out = (int)dc32; // running DC behind the last block produced here (the host's tail continues from it)
         }
+    }
+    // ---- the coefficient sink: no phase 2.  A wave's 64 blocks are 8 KiB contiguous in the output, and a lane that stored its own 128-byte row would
+    // issue eight 16-byte stores 128 bytes apart from its neighbours' (round 3's separate decode kernel was slow for that).  So the WAVE copies its own 64
+    // images out: eight rounds of eight images, lane j the 16-byte piece j & 7 of image 8 r + (j >> 3) - a wave-instruction stores 1 KiB contiguous.
+    // The images are the wave's own and a wave's DS operations execute in order: a compiler fence, no barrier (a wave whose blocks were short goes on
+    // while the others still decode, as in front of phase 2).  Lanes without a block (b >= m) copy their wave's other blocks; stores behind block m - 1
+    // are masked.
+    // Banks (MI355X: 4-byte accesses are served in lane groups {0-31}, {32-63}, bank = dword address mod 32).  The images stay 33 dwords apart - not
+    // 16-byte aligned, so a piece is read as four dwords:
+    //   phase 1's two-byte stores: lane l writes dword 33 l + k / 2 of the image array, bank (l + k / 2) mod 32 - lanes at the same k (the walk's first
+    //     steps) hit 32 different banks; at different k the banks are data-dependent, as in the pixel instantiations;
+    //   copy-out read d (0..3) of round r: lane j reads dword 33 (8 r + (j >> 3)) + 4 (j & 7) + d, bank ((j >> 3) + 4 (j & 7) + 8 r + d) mod 32 - inside a
+    //     group j >> 3 takes four consecutive values and 4 (j & 7) the multiples of 4 up to 28: 32 different banks, no conflict (the compiler
+    //     pairs the four reads into two ds_read2_b32, which are served as two dword reads each: the same banks).
+    if constexpr (kCoefSink) {
+        asm volatile("" ::: "memory"); // (the images' two-byte stores above are read back as dwords)
+        const uint32_t lane = threadIdx.x & 63u, wave0 = threadIdx.x & ~63u;
+        const unsigned long long wb0 = b0 + wave0; // the wave's first block
+        if (wb0 >= m) return;                      // (the whole wave)
+        const uint32_t *wimg = reinterpret_cast<const uint32_t *>(img) + (size_t)wave0 * (kImgStrideB / 4);
+        const uint32_t sub = lane >> 3, piece = lane & 7u;
+        uint4 v[8];
+#pragma unroll
+        for (uint32_t r = 0; r < 8u; r++) {
+            const uint32_t *p = wimg + (8u * r + sub) * (uint32_t)(kImgStrideB / 4) + 4u * piece;
+            v[r] = make_uint4(p[0], p[1], p[2], p[3]);
+        }
+        uint4 *o = reinterpret_cast<uint4 *>(coef_out);
+#pragma unroll
+        for (uint32_t r = 0; r < 8u; r++) {
+            const unsigned long long blk = wb0 + 8u * r + sub;
+            if (blk < m) o[blk * 8u + piece] = v[r];
+        }
+        return;
     }
     // ---- phase 2: the lane that decoded a block transforms it - all 64 coefficients in registers, no transposition, no barrier between
     // the phases (a wave whose blocks were short goes on while the others still decode), nothing but the lane's own image read back.
@@ -845,6 +883,14 @@ __global__ __launch_bounds__(kDecodeWG, kWinWords <= 2048u ? 3 : 2) void dec_dec
                                                                     DecIdctArgs a, DecStatus *__restrict__ st) {
     decode_idct_body<kWinWords, kScaled>(gwords, nwords, last_mask, L, bpos, desc, desc_half, flat_grid, epoch, total_blocks, n_want, stream_bits, a, st, blockIdx.x, gridDim.x);
 }
+// The coefficient sink's kernel (entropy_decode_coef_gpu): phase 1 and the copy-out.  The scaled flag changes nothing in the Huffman walk: no kScaled split.
+template <uint32_t kWinWords>
+__global__ __launch_bounds__(kDecodeWG, kWinWords <= 2048u ? 3 : 2) void dec_decode_coef_kernel(const uint32_t *__restrict__ gwords, uint32_t nwords, uint32_t last_mask, const DecLutsDev *__restrict__ L,
+                                                                    const uint32_t *__restrict__ bpos, unsigned long long *__restrict__ desc, uint32_t desc_half, uint32_t flat_grid, uint32_t epoch,
+                                                                    const long long *__restrict__ total_blocks, unsigned long long n_want, uint32_t stream_bits,
+                                                                    DecIdctArgs a, DecStatus *__restrict__ st, int16_t *__restrict__ coef_out) {
+    decode_idct_body<kWinWords, false, true>(gwords, nwords, last_mask, L, bpos, desc, desc_half, flat_grid, epoch, total_blocks, n_want, stream_bits, a, st, blockIdx.x, gridDim.x, coef_out);
+}
 // The batch form: workgroup g decodes 256 blocks of stream wg_frame[g] (a stream's blocks start a workgroup of their own: the DC sum
 // starts over with every frame, codec.py:53) and writes that frame's pixels through the frame's own DecIdctArgs.
 template <uint32_t kWinWords>
@@ -892,9 +938,10 @@ size_t entropy_decode_gpu_desc_words(size_t stream_bytes, size_t nblocks) { // l
     return 4 * (tr > tb ? tr : tb);
 }
 
-hipError_t entropy_decode_idct_gpu(const void *d_stream_words, size_t stream_bytes, size_t nblocks, const DecLutsDev *d_luts, void *d_work,
-                                   size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, const DecIdctArgs &idct,
-                                   DecStatus *d_status, int range_bits, int margin_bits, hipStream_t stream, int flat_grid) {
+// both sinks: d_coef == nullptr pixels through `idct`, else coefficients to d_coef (`idct` carries the header only)
+static hipError_t decode_launch(const void *d_stream_words, size_t stream_bytes, size_t nblocks, const DecLutsDev *d_luts, void *d_work,
+                                size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, const DecIdctArgs &idct, int16_t *d_coef,
+                                DecStatus *d_status, int range_bits, int margin_bits, hipStream_t stream, int flat_grid) {
     const size_t nbits = stream_bytes * 8;
     if (!entropy_decode_gpu_range_ok(range_bits)) return hipErrorInvalidValue;
     const uint32_t range = (uint32_t)range_bits;
@@ -944,11 +991,32 @@ hipError_t entropy_decode_idct_gpu(const void *d_stream_words, size_t stream_byt
                            (const long long *)totals, (unsigned long long)nblocks, (uint32_t)nbits, idct, d_status);
     };
     const bool small_win = nbits / nblocks <= 240; // sparse enough for the small window: one workgroup more per CU
-    if (idct.scaled) small_win ? fused(dec_decode_idct_kernel<2048, true>) : fused(dec_decode_idct_kernel<4096, true>);
+    if (d_coef) {
+        auto sink = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dgrid, dim3(kDecodeWG), 0, stream, words, nwords, last_mask, d_luts, (const uint32_t *)bpos, desc_b, desc_half, (uint32_t)flat_grid, 2u * epoch + 1u,
+                               (const long long *)totals, (unsigned long long)nblocks, (uint32_t)nbits, idct, d_status, d_coef);
+        };
+        small_win ? sink(dec_decode_coef_kernel<2048>) : sink(dec_decode_coef_kernel<4096>);
+    } else if (idct.scaled) small_win ? fused(dec_decode_idct_kernel<2048, true>) : fused(dec_decode_idct_kernel<4096, true>);
     else small_win ? fused(dec_decode_idct_kernel<2048, false>) : fused(dec_decode_idct_kernel<4096, false>);
     return hipGetLastError();
 }
 
+hipError_t entropy_decode_idct_gpu(const void *d_stream_words, size_t stream_bytes, size_t nblocks, const DecLutsDev *d_luts, void *d_work,
+                                   size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, const DecIdctArgs &idct,
+                                   DecStatus *d_status, int range_bits, int margin_bits, hipStream_t stream, int flat_grid) {
+    return decode_launch(d_stream_words, stream_bytes, nblocks, d_luts, d_work, work_bytes, d_desc, desc_words, epoch, idct, nullptr, d_status, range_bits, margin_bits, stream,
+                         flat_grid);
+}
+
+hipError_t entropy_decode_coef_gpu(const void *d_stream_words, size_t stream_bytes, size_t nblocks, const DecLutsDev *d_luts, void *d_work,
+                                   size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, const uint8_t head16[16], int16_t *d_coef,
+                                   DecStatus *d_status, int range_bits, int margin_bits, hipStream_t stream, int flat_grid) {
+    if (!d_coef || ((uintptr_t)d_coef & 15u) || !head16) return hipErrorInvalidValue;
+    DecIdctArgs a{};
+    memcpy(a.head, head16, 16);
+    return decode_launch(d_stream_words, stream_bytes, nblocks, d_luts, d_work, work_bytes, d_desc, desc_words, epoch, a, d_coef, d_status, range_bits, margin_bits, stream, flat_grid);
+}
 
 uint32_t entropy_decode_batch_tiles(uint32_t nranges, int range_bits) { const uint32_t owned = 64u - dec_shadows(range_bits); return (nranges + owned - 1u) / owned; }
 uint32_t entropy_decode_batch_wgs(size_t nblocks) { return (uint32_t)((nblocks + kDecodeWG - 1) / kDecodeWG); }
