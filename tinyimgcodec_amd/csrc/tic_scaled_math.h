@@ -7,8 +7,11 @@
 //   quant_scaled : IMG_quantize (img.c:194-205): sign(d) * (((QUANT >> 1) + |d|) * (65536 / (QUANT << qf)) >> 16).
 //   scaled_tab   : per natural index u*8+v one word: reciprocal (bits 0..15, at most 6,553) | QUANT >> 1 (bits 16..22) | scan
 //                  position (bits 24..29).
-// Ranges: pixels are int8 after the level shift, a row pass gives at most 8 * 128 = 1,024 in output 0 and ~1,340 elsewhere, a column
-// pass eight times that: every product below stays under 2^31 (12,871 * 334; (60 + 12,871) * 6,553).
+// Ranges: pixels are int8 after the level shift, a row pass gives at most 8 * 128 = 1,024 in output 0 and 1,282 elsewhere (exhaustive over the
+// 256 rows of extreme pixels), a column pass 12,871 at (1, 1) - the largest a greedy search over 0 / 255 blocks finds, not a proven
+// maximum (tests/scaled_blocks.py; tests/test_scaled_blocks_cpu.py holds both to these figures).  A pass gains a factor of about 10 (128 ->
+// 1,282), which keeps a column pass near 13,000 whatever the search misses: no int16 truncation changes a value, and every product
+// below stays under 2^31 (12,871 * 334; (60 + 12,871) * 6,553).
 #pragma once
 #include <stdint.h>
 
