@@ -124,6 +124,9 @@ int tic_sync(tic_ctx *ctx);
  * invariant between calls are left alone; tic_last_error then says how many buffers and bytes it filled and how many it kept.
  * TIC_E_BUSY while a tic_compress_dev_async or tic_decompress_dev_async ticket is open. */
 int tic_test_poison(tic_ctx *ctx, int byte);
+/* Test hook of the hooks build (the shipped library returns -1 and counts nothing): how many buffers the contexts of this process
+ * own at the moment - counted where one is allocated and where one is freed, so that a closed context must give all of its back. */
+int tic_test_live_buffers(void);
 int tic_dctq_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptrdiff_t row_stride, int quality,
                  void *d_coeffs_zz, int variant);
 /* Batch form: `nframes` equally sized frames in ONE launch (grid row per frame).  Frame f starts at

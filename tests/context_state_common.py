@@ -18,7 +18,7 @@ POISON_BYTES = (0x00, 0xFF, 0xA5)
 DEVICE_ROUTE = {"TIC_DECODE_MIN_BLOCKS": "1", "TIC_DECODE_MIN_BITS": "0"}
 HOST_ROUTE = {}
 
-# ---- the registry's names (tic_api.hip: buf_add and the grow helpers) ------------------------------------------------------------------
+# ---- the registry's names (tic_api.hip: each written once, where its Buf field is declared) ---------------------------------------------
 STATE = {
     "d_consts": "quantiser constants of qualities 1..99, written at creation; slot 0 by tic_set_custom_quality only",
     "d_huff": "the fixed Huffman table of the device entropy stage, written at creation",

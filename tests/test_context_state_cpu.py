@@ -2,6 +2,7 @@
 its callable, or a device-buffer form that the called one is built on: listed, not necessarily run) or exempt with a reason, every buffer name a record uses is one the library registers, and every expected result loads from the oracle or a fixture with
 the shape its case says.  Needs no GPU."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -42,12 +43,59 @@ def test_buffer_names_are_the_registry_s():
         src = f.read()
     with open(os.path.join(CS.ROOT, "DESIGN.md")) as f:
         design = f.read()
-    for name in list(CS.SCRATCH) + list(CS.STATE):
-        assert '"%s"' % name in src, name
+    for name in list(CS.SCRATCH) + list(CS.STATE):  # exactly once: where its field is declared (the decoder workspaces': in their name sets)
+        assert src.count('"%s"' % name) == 1, "%s is written %d times in tic_api.hip" % (name, src.count('"%s"' % name))
     for name in CS.STATE:
         assert "`%s`" % name in design, "DESIGN.md does not list the state buffer %s" % name
     used = {n for f in CS.FAMILIES for n in f.scratch}
     assert used == set(CS.SCRATCH), "scratch buffers no family touches: %s" % sorted(set(CS.SCRATCH) - used)
+
+
+def _regions(lines, starts):
+    """Line numbers inside the top-level definitions that begin on a line starting with one of `starts`: each up to its closing brace in
+    column 0."""
+    inside, on = set(), False
+    for n, line in enumerate(lines):
+        on = on or line.startswith(starts)
+        if on:
+            inside.add(n)
+        if on and line.startswith("}"):
+            on = False
+    return inside
+
+
+def test_only_the_buffer_type_allocates_and_frees():
+    """No leak by construction: in tic_api.hip every hipMalloc, hipHostMalloc, hipFree and hipHostFree stands inside the owning buffer type,
+    the four calls that hand memory to the user, or the transpose self-test (buffers of its own), and tic_destroy calls none of them."""
+    with open(os.path.join(CS.ROOT, "tinyimgcodec_amd", "csrc", "tic_api.hip")) as f:
+        lines = f.read().split("\n")
+    calls = ("hipMalloc(", "hipHostMalloc(", "hipFree(", "hipHostFree(")
+    allowed = _regions(lines, ("template <class T, BufKind K> struct Buf ", "template <class T, BufKind K> int Buf<T, K>::",
+                               "template <class T, BufKind K> void Buf<T, K>::", "int tic_dev_alloc(", "int tic_dev_free(",
+                               "int tic_host_alloc_pinned(", "int tic_host_free_pinned(", "int tic_selftest_transpose("))
+    destroy = _regions(lines, ("void tic_destroy(",))
+    assert 10 < len(destroy) < 60 and len(allowed) > 100 and not allowed & destroy  # (the definitions were found)
+    found = [n for n, line in enumerate(lines) if any(c in line.split("//")[0] for c in calls)]
+    assert len(found) >= 11, found  # (3 in the type, 4 in the user's calls, 6 in the self-test: several to a line at most)
+    for n in found:
+        assert n in allowed, "tic_api.hip:%d allocates or frees outside the buffer type, the user's calls and the self-test: %s" % (n + 1, lines[n].strip())
+    buf = _regions(lines, ("template <class T, BufKind K> struct Buf ",))
+    for kind in calls:  # (one allocating and one freeing function in the type)
+        assert sum(kind in lines[n] for n in found if n in buf) == 1, kind
+
+
+def test_release_names_every_buffer_member():
+    """Slot::release and DecWorkspace::release release member by member: every Buf field of the two structs is in its list (one left out
+    would be freed with the struct, but keep its registry record)."""
+    with open(os.path.join(CS.ROOT, "tinyimgcodec_amd", "csrc", "tic_api.hip")) as f:
+        lines = f.read().split("\n")
+    for struct, n_fields in (("Slot", 17), ("DecWorkspace", 3)):
+        decl = "\n".join(lines[n] for n in sorted(_regions(lines, ("struct %s {" % struct,))))
+        body = "\n".join(lines[n] for n in sorted(_regions(lines, ("void %s::release(" % struct,))))
+        fields = re.findall(r"^    (?:Dev|Pin|Mapped)Buf<[^>]+> (\w+)\{", decl, flags=re.M)
+        assert len(fields) == n_fields, (struct, fields)
+        for name in fields:
+            assert "%s.release(ctx)" % name in body, "%s::release does not release %s" % (struct, name)
 
 
 def _frames(f, which):

@@ -280,6 +280,91 @@ def test_decompress_tickets(ctx, monkeypatch):
     f.check(ctx, "small", monkeypatch, "(after the bursts and a poison)")
 
 
+# ---- ownership and teardown -------------------------------------------------------------------------------------------------------------------
+def _exact_8x8(ctx):
+    img, q = CS.SMALL[0]
+    s = T.compress(img, q, ctx=ctx)
+    assert s == CS.oracle().compress(img, q) and np.array_equal(T.decompress(s, ctx=ctx), CS.oracle().decompress(s))
+
+
+def test_registry_is_ownership(monkeypatch):
+    """What the registry records is what the context owns: after every family's dense case on a fresh context, the buffers
+    tic_test_poison walks are the buffers allocated since the context was made (other contexts of the process may be alive: base)."""
+    live = N.load().tic_test_live_buffers
+    base = live()
+    assert base >= 0
+    ctx = T.Context(0)
+    try:
+        assert live() - base == 5  # d_consts, d_huff, d_total_bits, h_stat, d_fallback
+        for f in CS.FAMILIES:
+            f.check(ctx, "dense", monkeypatch)
+        filled, _, kept = poison(ctx, 0x5A)
+        assert filled >= len(CS.SCRATCH) - 1 and kept >= len(CS.STATE), (filled, kept)
+        assert filled + kept == live() - base, (filled, kept, live(), base)
+    finally:
+        ctx.close()
+    assert live() == base
+
+
+def test_destroy_frees_everything(monkeypatch):
+    """Three contexts in turn: every family's small case, the batch families' dense cases (the slots grow, some one by one), close - and
+    the process owns what it owned before.  Then a new context is exact."""
+    live = N.load().tic_test_live_buffers
+    base = live()
+    for k in range(3):
+        ctx = T.Context(0)
+        try:
+            for f in CS.FAMILIES:
+                f.check(ctx, "small", monkeypatch, "(context %d)" % k)
+            for f in CS.FAMILIES:
+                if "batch" in f.name:
+                    f.check(ctx, "dense", monkeypatch, "(context %d)" % k)
+            assert live() - base > len(CS.SCRATCH)
+        finally:
+            ctx.close()
+        assert live() == base, "context %d left %d buffers behind" % (k, live() - base)
+    ctx = T.Context(0)
+    try:
+        _exact_8x8(ctx)
+    finally:
+        ctx.close()
+    assert live() == base
+
+
+def test_destroy_with_tickets_open(monkeypatch):
+    """Closing a context with a compress and a decode ticket issued and never collected is a supported call: tic_destroy waits for every
+    stream first.  Everything the context owned is freed, the frames' own device buffers outlive it, and a new context is exact."""
+    live = N.load().tic_test_live_buffers
+    base = live()
+    for k, v in CS.DEVICE_ROUTE.items():
+        monkeypatch.setenv(k, v)
+    ctx = T.Context(0)
+    try:
+        f = CS.BY_NAME["decompress_dev_async[device]"]
+        f.check(ctx, "dense", monkeypatch, "(warm-up: the next ticket is launched on a slot)")
+        (ct,) = CS.open_compress_tickets(ctx, CS.DENSE)
+        (dt,) = CS.open_decompress_tickets(ctx, CS.DENSE)
+        assert N.load().tic_test_poison(ctx.handle, 0xFF) == N.TIC_E_BUSY  # (both are open)
+    finally:
+        ctx.close()
+    assert live() == base
+    ctx = T.Context(0)
+    try:
+        # the closed context waited for both frames: their outputs, in the caller's buffers, are whole
+        ct[2].ctx = dt[2].ctx = ctx
+        want = CS.oracle().compress(*CS.DENSE[0])
+        assert ct[2].down(len(want)).tobytes() == want
+        h, w = CS.DENSE[0][0].shape
+        assert np.array_equal(dt[2].down(h * w).reshape(h, w), CS.oracle().decompress(want))  # (w is a multiple of 8: rows without a gap)
+        for d in (ct[1], ct[2], dt[1], dt[2]):
+            d.ctx = ctx
+            d.free()
+        _exact_8x8(ctx)
+    finally:
+        ctx.close()
+    assert live() == base
+
+
 # ---- epoch wrap ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["decompress[device]", "decompress_dev_async[device]", "decompress_batch[device]"])
 def test_epoch_wrap(name, ctx, monkeypatch):
@@ -312,7 +397,7 @@ def test_epoch_wrap(name, ctx, monkeypatch):
 # ---- the shipped library --------------------------------------------------------------------------------------------------------------------
 def test_shipped_library_dirty_then_small():
     """The pairs of test_dirty_then_small with nothing in between, on libtinyimgcodec_hip.so in a fresh child process; tic_test_poison is
-    TIC_E_ARG there.  The shipped library reads no hook variable, so the seven [device] decoder families - which exist by those variables
+    TIC_E_ARG there and tic_test_live_buffers -1.  The shipped library reads no hook variable, so the seven [device] decoder families - which exist by those variables
     - cannot run on it and are left out, with their pairs (541 of the 912 remain): there the decoder families take the host route, which
     is asserted."""
     code = r'''
@@ -328,6 +413,7 @@ class NoEnv:
     def delenv(self, k, raising=True): pass
 ctx = T.Context(0)
 assert L.tic_test_poison(ctx.handle, 0xA5) == N.TIC_E_ARG
+assert L.tic_test_live_buffers() == -1  # (no counter in the shipped library)
 fams = [f for f in CS.FAMILIES if not f.env]
 n = 0
 for a, b in CS.sharing_pairs():

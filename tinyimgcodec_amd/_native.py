@@ -73,6 +73,7 @@ SIGNATURES = {
     "tic_memset_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_size_t]),
     "tic_sync": (C.c_int, [_ctxp]),
     "tic_test_poison": (C.c_int, [_ctxp, C.c_int]),
+    "tic_test_live_buffers": (C.c_int, []),
     "tic_dctq_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_void_p, C.c_int]),
     "tic_dctq_dev_frames": (
         C.c_int,

@@ -7,6 +7,7 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <atomic>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -65,37 +66,6 @@ static inline int chunk_frames(int n, size_t img_bytes) {
     if (const char *e = test_hook("TIC_BATCH_CHUNK")) c = atoi(e) >= 1 && atoi(e) <= 64 ? (size_t)atoi(e) : c; // (tests: several chunks of small frames)
     return n < (int)c ? n : (int)c;
 }
-struct Slot {
-    uint8_t *pin_in = nullptr;
-    int16_t *pin_out = nullptr;
-    void *d_img = nullptr;
-    void *d_coef = nullptr;
-    hipEvent_t done = nullptr;
-    hipEvent_t rb_done = nullptr; // the chunk's streams have arrived in pin_out (recorded behind the read-back copy)
-    // device entropy stage of the chunk
-    void *d_work = nullptr;  // workspace of the fused entropy pass
-    size_t work_bytes = 0;
-    int parity = 0;          // which of the two descriptor arrays / error flags the next call uses
-    unsigned long long *d_lens = nullptr, *h_lens = nullptr; // stream length per frame (device / pinned host)
-    int *d_err = nullptr, *h_err = nullptr;
-    void *d_streams = nullptr;                                // finished streams, one compress_bound() apart
-    // mixed batches (tic_compress_batch_v): the entropy stage's table of the chunk - filled in pinned memory, uploaded in stream order -
-    // and, for the read-back, where each stream lands in pin_out (pinned: the shader reads it where it lies)
-    EntropyFrameTable *h_frames = nullptr, *d_frames = nullptr;
-    unsigned long long *h_rb_off = nullptr;
-    // scaled batches (tic_compress_batch_scaled_v): the table of the chunk's ONE transform launch, pinned and on the device
-    ScaledFrameTable *h_sframes = nullptr, *d_sframes = nullptr;
-    // adaptive batches (tic_compress_batch_adaptive_v): the chunk's statistics, tables, headers and bit counts, carved by adaptive_slot_layout
-    // (tic_adaptive_frames.h), and the pinned mirror of their host-visible part.  Stream lengths are known only behind the statistics, so a
-    // chunk may find d_streams or pin_out short and grow THIS slot's: streams_cap / pin_out_cap then say what it holds (0: what every slot holds)
-    char *d_adapt = nullptr, *h_adapt = nullptr;
-    size_t adapt_bytes = 0, h_adapt_bytes = 0;
-    size_t streams_cap = 0, pin_out_cap = 0;
-    int first = 0, count = 0; // frames [first, first+count) are in flight in this slot
-    int pending = 0;          // pieces of the chunk's work not yet finished (SlotGate); 0 = the slot is free
-    size_t rb_row = 0;        // row pitch of the streams read back into pin_out (0: they went straight to the caller)
-    void release(tic_ctx *ctx); // frees everything the slot owns
-};
 // What a context keeps between calls.  Hooks build only: every buffer a context owns is recorded when it is
 // allocated and dropped when it is freed, as SCRATCH - any content is legal when a public call begins - or STATE - it carries an
 // invariant from one call to the next.  TIC_POISON and tic_test_poison fill the scratch ones; nothing ever fills a state buffer
@@ -108,27 +78,113 @@ struct BufRec {
     int kind, cls;
     const char *name;
 };
+#ifdef TIC_TEST_HOOKS
+std::atomic<int> g_live_buffers{0}; // owned buffers allocated in this process (tic_test_live_buffers)
+#endif
+// A buffer a context owns: the pointer, its capacity in bytes, and its entry in the registry above - name and class, given once, where
+// the field is declared.  It converts to its pointer, so that it reads as one wherever it is used; it frees its memory when it is
+// released or destroyed, and nothing else does.  Not copied; a move leaves the source null.
+template <class T, BufKind K> struct Buf {
+    T *p = nullptr;
+    T *d = nullptr; // host-mapped memory only: the kernels' address of it (coherent: the host reads it behind a polled or drained stream)
+    size_t cap = 0;
+    const char *const name;
+    const BufClass cls;
+    Buf(const char *registry_name, BufClass c = kBufScratch) : name(registry_name), cls(c) {}
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    Buf(Buf &&o) noexcept : p(o.p), d(o.d), cap(o.cap), name(o.name), cls(o.cls) { o.p = o.d = nullptr, o.cap = 0; }
+    ~Buf() { (void)free_mem(); }
+    operator T *() const { return p; }
+    template <class U> explicit operator U *() const { return (U *)p; } // (a cast of the buffer is a cast of its pointer)
+    // When `need` bytes exceed the capacity, the buffer is freed and one of `alloc` bytes (0: `need`) takes its place.  Nothing may be
+    // in flight on the old buffer.  A failed allocation leaves it null with capacity 0.
+    int grow(tic_ctx *ctx, size_t need, size_t alloc = 0);
+    void release(tic_ctx *ctx);
+
+private:
+    hipError_t alloc_mem(size_t bytes) {
+        hipError_t e = K == kBufDev ? hipMalloc((void **)&p, bytes)
+                                    : hipHostMalloc((void **)&p, bytes, K == kBufPinned ? hipHostMallocDefault : hipHostMallocMapped | hipHostMallocCoherent);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return e;
+        }
+#ifdef TIC_TEST_HOOKS
+        g_live_buffers++;
+#endif
+        if (K == kBufMapped && (e = hipHostGetDevicePointer((void **)&d, p, 0)) != hipSuccess) {
+            (void)free_mem(); // (null again, as after any failed allocation)
+            return e;
+        }
+        cap = bytes;
+        return hipSuccess;
+    }
+    hipError_t free_mem() { // the one place a context's memory is freed
+        if (!p) return hipSuccess;
+#ifdef TIC_TEST_HOOKS
+        g_live_buffers--;
+#endif
+        void *const q = p;
+        p = d = nullptr, cap = 0;
+        return K == kBufDev ? hipFree(q) : hipHostFree(q);
+    }
+};
+template <class T> using DevBuf = Buf<T, kBufDev>;
+template <class T> using PinBuf = Buf<T, kBufPinned>;
+template <class T> using MappedBuf = Buf<T, kBufMapped>;
+
+struct Slot {
+    PinBuf<uint8_t> pin_in{"bslot.pin_in"};
+    PinBuf<int16_t> pin_out{"bslot.pin_out"};
+    DevBuf<void> d_img{"bslot.d_img"};
+    DevBuf<void> d_coef{"bslot.d_coef"};
+    hipEvent_t done = nullptr;
+    hipEvent_t rb_done = nullptr; // the chunk's streams have arrived in pin_out (recorded behind the read-back copy)
+    // device entropy stage of the chunk
+    DevBuf<void> d_work{"bslot.d_work"}; // workspace of the fused entropy pass
+    int parity = 0;                      // which of the two descriptor arrays / error flags the next call uses
+    DevBuf<unsigned long long> d_lens{"bslot.d_lens"}; // stream length per frame (device / pinned host)
+    PinBuf<unsigned long long> h_lens{"bslot.h_lens"};
+    DevBuf<int> d_err{"bslot.d_err", kBufState}; // two flags used in turn: zero when allocated, the chunk's last kernel clears the next one
+    PinBuf<int> h_err{"bslot.h_err"};
+    DevBuf<void> d_streams{"bslot.d_streams"}; // finished streams, one compress_bound() apart
+    // mixed batches (tic_compress_batch_v): the entropy stage's table of the chunk - filled in pinned memory, uploaded in stream order -
+    // and, for the read-back, where each stream lands in pin_out (pinned: the shader reads it where it lies)
+    PinBuf<EntropyFrameTable> h_frames{"bslot.h_frames"};
+    DevBuf<EntropyFrameTable> d_frames{"bslot.d_frames"};
+    PinBuf<unsigned long long> h_rb_off{"bslot.h_rb_off"};
+    // scaled batches (tic_compress_batch_scaled_v): the table of the chunk's ONE transform launch, pinned and on the device
+    PinBuf<ScaledFrameTable> h_sframes{"bslot.h_sframes"};
+    DevBuf<ScaledFrameTable> d_sframes{"bslot.d_sframes"};
+    // adaptive batches (tic_compress_batch_adaptive_v): the chunk's statistics, tables, headers and bit counts, carved by adaptive_slot_layout
+    // (tic_adaptive_frames.h), and the pinned mirror of their host-visible part.  Stream lengths are known only behind the statistics, so a
+    // chunk may find d_streams or pin_out short and grow THIS slot's
+    DevBuf<char> d_adapt{"bslot.d_adapt"};
+    PinBuf<char> h_adapt{"bslot.h_adapt"};
+    int first = 0, count = 0; // frames [first, first+count) are in flight in this slot
+    int pending = 0;          // pieces of the chunk's work not yet finished (SlotGate); 0 = the slot is free
+    size_t rb_row = 0;        // row pitch of the streams read back into pin_out (0: they went straight to the caller)
+    void release(tic_ctx *ctx); // frees everything the slot owns
+};
 static const char *const kDecWsNames[3] = {"dec_ws.work", "dec_ws.desc", "dec_ws.status"};
 static const char *const kDecSlotWsNames[3] = {"dec_slot.work", "dec_slot.desc", "dec_slot.status"};
 static const char *const kDecBatchWsNames[3] = {"dbat.work", "dbat.desc", "dbat.status"};
 // Workspace of the device Huffman decoder (tic_entropy_dec_gpu.hip), one per user: the single-frame calls, every asynchronous decode slot
 // and the batch.  Nothing of an earlier run may be in flight when it grows or a run begins.
 struct DecWorkspace {
-    void *work = nullptr;
-    size_t work_bytes = 0;
-    unsigned long long *desc = nullptr; // look-back words of the decoder's scans: an array of their own, zero or stamped with a past epoch
-    size_t desc_words = 0;
-    const char *const *names = kDecWsNames; // registry names of work, desc and status (buf_add): one set per user of a workspace
+    const char *const *names; // registry names of work, desc and status: one set per user of a workspace
+    DevBuf<void> work{names[0]};
+    DevBuf<unsigned long long> desc{names[1], kBufState}; // look-back words of the decoder's scans: an array of their own, zero or stamped
+    size_t desc_words = 0;                                // with a past epoch (state: wave_lookback spins on these words)
     uint32_t epoch = 0;                 // runs on these words (the single-launch scans tell their words by it)
-    DecStatus *h_status = nullptr, *d_status = nullptr; // host-mapped, one entry per frame of a run
-    size_t status_bytes = 0;
+    MappedBuf<DecStatus> h_status{names[2]}; // host-mapped, one entry per frame of a run
     // at least `work_need` bytes of work buffer (`work_alloc` when it grows), `desc_need` look-back words (max(8192, 2 x desc_need) when they
     // grow: zeroed, epoch 0) and `status` status entries (`status_alloc`)
     int grow(tic_ctx *ctx, size_t work_need, size_t work_alloc, size_t desc_need, size_t status, size_t status_alloc);
     int begin(tic_ctx *ctx, hipStream_t stream, size_t status); // a run of `status` frames on `stream`
     void release(tic_ctx *ctx);
-    DecWorkspace() = default;
-    explicit DecWorkspace(const char *const *registry_names) : names(registry_names) {}
+    explicit DecWorkspace(const char *const *registry_names = kDecWsNames) : names(registry_names) {}
 };
 } // namespace
 
@@ -141,26 +197,25 @@ struct tic_ctx {
     hipStream_t stream = nullptr;     // all single-frame work
     hipStream_t bstream[2] = {nullptr, nullptr}; // batch pipeline streams
     hipStream_t rstream = nullptr;               // read-back of finished streams: never queued behind a later chunk's work
-    int16_t *h_zz = nullptr;                     // pinned landing buffer of the host Huffman decoder (tic_decompress)
-    size_t h_zz_bytes = 0;
-    DctqConsts *d_consts = nullptr;   // [100], index = quality; slot 0 = the custom (non-integral) quality of tic_set_custom_quality
+    // The buffers below are Buf fields: each owns its memory, knows its capacity (.cap) and carries its registry name and class.
+    PinBuf<int16_t> h_zz{"h_zz"};                // pinned landing buffer of the host Huffman decoder (tic_decompress)
+    DevBuf<DctqConsts> d_consts{"d_consts", kBufState}; // [100], index = quality; slot 0 = the custom (non-integral) quality of tic_set_custom_quality
     double custom_quality = 0.0;      // what slot 0 holds (0: nothing yet)
-    unsigned long long *d_fallback = nullptr;
+    DevBuf<unsigned long long> d_fallback{"d_fallback", kBufState};
     StripLaunchInfo last_strip{}; // what the last tic_dctq_dev / tic_dctq_dev_frames launch decided (tic_last_strip_launch)
     bool stats = false; // count guard-band fallbacks with a global atomic (diagnostic; serialises at ~12 ns per wave)
     hipEvent_t ev0 = nullptr, ev1 = nullptr; // the interval of the timed entry points (timed_launches)
     // scratch for the host-buffer entry points
-    void *d_img = nullptr;
-    size_t d_img_cap = 0;
-    void *d_coef = nullptr;
-    size_t d_coef_cap = 0;
+    DevBuf<void> d_img{"d_img"};
+    DevBuf<void> d_coef{"d_coef"};
     std::vector<int16_t> h_coef;
     // device entropy stage workspace
-    HuffDev *d_huff = nullptr;
-    int *d_err = nullptr;
-    unsigned long long *d_total_bits = nullptr; // status block of the device entropy stage: payload bits [2], error flags [2] (used in turn)
-    unsigned long long *h_stat = nullptr, *d_stat = nullptr; // host-mapped status block of the device entropy stage (bits, error); behind
-                                                            // its first 64 bytes: the {bits, error} pairs of the asynchronous calls' tickets
+    DevBuf<HuffDev> d_huff{"d_huff", kBufState};
+    DevBuf<unsigned long long> d_total_bits{"d_total_bits", kBufState}; // status block of the device entropy stage: payload bits [2], error flags [2] (used in turn)
+    int *d_err = nullptr;                                               // ... the error flags: a view of d_total_bits
+    MappedBuf<unsigned long long> h_stat{"h_stat", kBufState}; // host-mapped status block of the device entropy stage (bits, error); behind
+    unsigned long long *d_stat = nullptr;                      // its first 64 bytes: the {bits, error} pairs of the asynchronous calls' tickets
+                                                               // (d_stat: the kernels' view of h_stat)
     // asynchronous device-resident calls (tic_compress_dev_async): ticket t lives in slot t % kAsyncSlots
     struct AsyncSlot { long long ticket = -1; size_t cap = 0; int early_rc = TIC_OK; hipEvent_t done = nullptr; bool empty_image = false; };
     AsyncSlot async_slots[kAsyncSlots];
@@ -170,11 +225,11 @@ struct tic_ctx {
     // frame t + 1 is transformed and packed beside the packing and placing of frame t (tic_compress_dev_async)
     struct AsyncLane {
         hipStream_t stream = nullptr;
-        void *d_coef = nullptr;
-        size_t coef_cap = 0;
-        void *d_work[2] = {nullptr, nullptr}; // two entropy workspaces used in turn: the lane packs its next frame while the placing kernel
-        size_t work_bytes = 0;                // of the frame before still reads the other one
-        int *d_err = nullptr; // [4], used in turn (a placing kernel zeroes the flag of the lane's frame three ahead: no packing in flight uses it)
+        static constexpr const char *kWorkName = "lane.d_work";
+        DevBuf<void> d_coef{"lane.d_coef"};
+        DevBuf<void> d_work[2] = {{kWorkName}, {kWorkName}}; // two entropy workspaces of one size used in turn: the lane packs its next frame
+                                                             // while the placing kernel of the frame before still reads the other one
+        DevBuf<int> d_err{"lane.d_err", kBufState}; // [4], used in turn (a placing kernel zeroes the flag of the lane's frame three ahead: no packing in flight uses it)
         unsigned long long frames = 0;        // frames this lane has taken
         hipEvent_t packed = nullptr, placed[2] = {nullptr, nullptr}; // the lane's last packing has run / the frame that used workspace k has been placed (on ctx->stream)
         bool placed_valid[2] = {false, false};
@@ -184,8 +239,7 @@ struct tic_ctx {
     hipEvent_t lane_order = nullptr; // a burst's lanes start behind what the context's stream held when the burst began
     int async_open = 0;              // tickets open
     unsigned long long lane_epoch = 0;
-    void *d_ent_work = nullptr;                 // workspace of the device entropy stage (tile sums, bit counts, staging slots)
-    size_t ent_work_bytes = 0;
+    DevBuf<void> d_ent_work{"d_ent_work"};      // workspace of the device entropy stage (tile sums, bit counts, staging slots)
     int ent_parity = 0;
     // Which packing kernel the device entropy stage starts with: the lane-per-block kernel up to this quality, the 8-lane kernel
     // above it.  -1 (the default): always the 8-lane kernel - round 3 built the lane-per-block kernel and measured it no faster
@@ -194,14 +248,12 @@ struct tic_ctx {
     // than 512 bits (noise at quality >= ~85) makes it raise error 4: the stage is run again with the 8-lane kernel and the limit
     // drops below that quality for the rest of the context's life.
     int ent_lane_max_quality = -1;
-    void *d_stream_buf = nullptr;
-    size_t d_stream_cap = 0;
-    int32_t *d_dc32 = nullptr;                   // int32 DC of every block of a frame whose running DC left int16 (decode_on_host; idct_kernel's wide-DC form)
-    size_t d_dc32_cap = 0;
+    DevBuf<void> d_stream_buf{"d_stream_buf"};
+    DevBuf<int32_t> d_dc32{"d_dc32"};            // int32 DC of every block of a frame whose running DC left int16 (decode_on_host; idct_kernel's wide-DC form)
     // device Huffman decoder (tic_decompress of long streams): tables, workspace, status
-    DecLutsDev *d_dec_luts = nullptr;
+    DevBuf<DecLutsDev> d_dec_luts{"d_dec_luts", kBufState};
     DecWorkspace dec_ws;
-    uint8_t *h_dec_tail = nullptr;                              // pinned: kDecTailEnd bytes of stream end + kDecTailCoef bytes of tail coefficients
+    PinBuf<uint8_t> h_dec_tail{"h_dec_tail"};                   // pinned: kDecTailEnd bytes of stream end + kDecTailCoef bytes of tail coefficients
     int last_decode_path = 0;                                  // 0 none, 1 device decoder, 2 host decoder (tic_last_decode_path)
     // asynchronous device-resident decodes (tic_decompress_dev_async): ticket t lives in slot t % kDecSlots; every slot has its own HIP
     // stream, workspace, look-back words and status words, so that the frames of a burst overlap (the measure kernel is one wave per
@@ -228,8 +280,7 @@ struct tic_ctx {
     // and the host copies it out with memcpy - no device-to-host DMA copy, whose submission and completion cost more than the transfer of a
     // 30 - 80 KB stream: compress() of a 512 x 512 image 54 us instead of 62 (profiles/r05_decoder.txt).  (The same for the PIXELS of a small
     // decompress(): measured, no gain - 262 KB written across PCIe by the kernel and copied again by the host cost what the DMA copy does.)
-    uint8_t *h_small = nullptr, *d_small = nullptr;
-    size_t small_cap = 0;
+    MappedBuf<uint8_t> h_small{"h_small"}; // (h_small.d: the placing kernel's address of it)
     uint8_t dec_head[16] = {0};                                  // header of the last stream tic_decompress_dev decoded on the device: the next call's guess
     bool dec_head_valid = false;
     int dec_head_streak = 0;   // device decodes in a row (before the last one) whose header was dec_head: a guess is made from 1 on, i.e. after two equal headers
@@ -240,10 +291,10 @@ struct tic_ctx {
     // batched decode (tic_decompress_batch): one pinned + one device buffer for a chunk's descriptors and streams, a device and a pinned
     // buffer for its pixels, workspace, look-back words and per-frame status words - kept across calls
     struct DecBatch {
-        uint8_t *h_in = nullptr, *d_in = nullptr;
-        size_t in_cap = 0;
-        uint8_t *d_pix = nullptr, *h_pix = nullptr;
-        size_t pix_cap = 0, hpix_cap = 0;
+        PinBuf<uint8_t> h_in{"dbat.h_in"};
+        DevBuf<uint8_t> d_in{"dbat.d_in"};
+        DevBuf<uint8_t> d_pix{"dbat.d_pix"};
+        PinBuf<uint8_t> h_pix{"dbat.h_pix"};
         DecWorkspace ws{kDecBatchWsNames};
     } dbat;
     int last_dbatch_frames = 0, last_dbatch_fallback = 0, last_dbatch_chunks = 0, last_dbatch_direct = 0;
@@ -284,58 +335,54 @@ struct tic_ctx {
     std::vector<BufRec> bufs; // hooks build: every buffer the context owns (buf_add, buf_drop)
     // per-image Huffman tables (tic_compress_adaptive): statistics, the frame's table and an error word in one allocation, the packing
     // workspace and the stream, kept across calls
-    AdaptStats *d_adapt_stats = nullptr;
-    HuffWide *d_adapt_tab = nullptr;
+    DevBuf<AdaptStats> d_adapt_stats{"d_adapt_stats"};
+    HuffWide *d_adapt_tab = nullptr; // views of d_adapt_stats: the table and the error word behind the statistics
     uint32_t *d_adapt_err = nullptr;
-    void *d_adapt_work = nullptr;
-    size_t adapt_work_bytes = 0;
-    uint32_t *d_adapt_out = nullptr;
-    size_t adapt_out_bytes = 0;
+    DevBuf<void> d_adapt_work{"d_adapt_work"};
+    DevBuf<uint32_t> d_adapt_out{"d_adapt_out"};
     // ... and their device decoder (tic_decompress_adaptive): look-up tables and status words in one allocation, the workspace
     AdaptDecTab adec_tab; // the host copy, built per call
-    AdaptDecTab *d_adec_tab = nullptr;
-    AdaptDecStatus *d_adec_status = nullptr;
-    void *d_adec_work = nullptr;
-    size_t adec_work_bytes = 0;
+    DevBuf<AdaptDecTab> d_adec_tab{"d_adec_tab"};
+    AdaptDecStatus *d_adec_status = nullptr; // a view of d_adec_tab: the status words behind the tables
+    DevBuf<void> d_adec_work{"d_adec_work"};
     // ... and its batch form (tic_decompress_batch_adaptive): a chunk's status words, work arrays and coefficients in one device buffer
     // (AdaptDecWorkLayout), the pinned landing buffer of the status words; upload and pixel buffers are the batched decode's (dbat)
     struct AdaptDecBatchBuf {
-        char *d_work = nullptr, *h_status = nullptr;
-        size_t work_cap = 0, status_cap = 0;
+        DevBuf<char> d_work{"adbat.d_work"};
+        PinBuf<char> h_status{"adbat.h_status"};
     } adbat;
     int last_adbatch_frames = 0, last_adbatch_single = 0, last_adbatch_chunks = 0, last_adbatch_direct = 0; // tic_last_decompress_batch_adaptive (_direct)
     // rate control (tic_stream_sizes_dev, tic_compress_to_size_dev): the size kernel's table, a result per probe on the device and its
     // pinned landing buffer, and what the last search did
-    SizeTabDev *d_size_tab = nullptr;
-    SizeResult *d_rate = nullptr, *h_rate = nullptr;
-    size_t rate_dev_bytes = 0, rate_host_bytes = 0;
+    DevBuf<SizeTabDev> d_size_tab{"d_size_tab", kBufState};
+    DevBuf<SizeResult> d_rate{"d_rate"};
+    PinBuf<SizeResult> h_rate{"h_rate"};
     int last_rate_probes = 0, last_rate_waits = 0;
     // ... their batch forms (tic_stream_sizes_v, tic_compress_batch_to_size): the pinned buffer a chunk's pixels are staged in (the chunk
     // itself and its probes' coefficients live in d_img / d_coef), the probe tables of one submission, and what the last call did
-    uint8_t *h_rate_pix = nullptr;
-    size_t rate_pix_cap = 0;
-    SizeProbeTable *h_rate_tabs = nullptr, *d_rate_tabs = nullptr;
-    size_t rate_tabs_host_bytes = 0, rate_tabs_dev_bytes = 0;
+    PinBuf<uint8_t> h_rate_pix{"h_rate_pix"};
+    PinBuf<SizeProbeTable> h_rate_tabs{"h_rate_tabs"};
+    DevBuf<SizeProbeTable> d_rate_tabs{"d_rate_tabs"};
     int last_rbatch_frames = 0, last_rbatch_single = 0, last_rbatch_chunks = 0, last_rbatch_probes = 0, last_rbatch_waits = 0, last_rbatch_launches = 0;
     // ... and of rate-distortion control (tic_rd_points_v, tic_compress_batch_to_psnr, tic_distortion_v_dev): the tables of the measuring
     // kernel's descriptor form, one per launch
-    SseProbeTable *h_rd_tabs = nullptr, *d_rd_tabs = nullptr;
-    size_t rd_tabs_host_bytes = 0, rd_tabs_dev_bytes = 0;
+    PinBuf<SseProbeTable> h_rd_tabs{"h_rd_tabs"};
+    DevBuf<SseProbeTable> d_rd_tabs{"d_rd_tabs"};
     int last_rbatch_sse_launches = 0;
     // the integer encoder's batch forms (tic_compress_batch_scaled_v, tic_dctq_scaled_v_dev, tic_rd_points_scaled_v): the tables of the
     // transform's descriptor form outside the batch slots, one per launch, and what the last calls did
-    ScaledFrameTable *h_scaled_tabs = nullptr, *d_scaled_tabs = nullptr;
-    size_t scaled_tabs_host_bytes = 0, scaled_tabs_dev_bytes = 0;
+    PinBuf<ScaledFrameTable> h_scaled_tabs{"h_scaled_tabs"};
+    DevBuf<ScaledFrameTable> d_scaled_tabs{"d_scaled_tabs"};
     int last_sbatch_frames = 0, last_sbatch_single = 0, last_sbatch_chunks = 0, last_sbatch_launches = 0; // tic_last_compress_batch_scaled
     int last_srd_frames = 0, last_srd_single = 0, last_srd_chunks = 0, last_srd_launches = 0, last_srd_size_launches = 0,
         last_srd_sse_launches = 0; // tic_last_rd_scaled_batch
     // rate control of the adaptive family (tic_adaptive_sizes, tic_compress_adaptive_to_size, tic_adaptive_sizes_v): the statistics of a
     // submission's probes on the device and their pinned landing buffer, the frame tables of adaptive_stats_v_kernel where that kernel is
     // asked for (the probe kernel's tables are h_rate_tabs / d_rate_tabs), and what the last call did.  All grow on demand.
-    AdaptStats *d_arate_stats = nullptr, *h_arate_stats = nullptr;
-    size_t arate_dev_bytes = 0, arate_host_bytes = 0;
-    AdaptFrameTable *h_arate_frames = nullptr, *d_arate_frames = nullptr;
-    size_t arate_frames_host_bytes = 0, arate_frames_dev_bytes = 0;
+    DevBuf<AdaptStats> d_arate_stats{"d_arate_stats"};
+    PinBuf<AdaptStats> h_arate_stats{"h_arate_stats"};
+    PinBuf<AdaptFrameTable> h_arate_frames{"h_arate_frames"};
+    DevBuf<AdaptFrameTable> d_arate_frames{"d_arate_frames"};
     int last_arate_probes = 0, last_arate_waits = 0, last_arate_launches = 0;
 };
 
@@ -450,67 +497,36 @@ static void buf_drop(tic_ctx *ctx, const void *p) {
             return;
         }
 }
-// Allocation sites outside the grow helpers: `call` allocates `p`, which is then recorded (BUF_NEW: contexts that exist, through
-// HIPCHK).
-#define BUF_NEW(ctx, call, p, bytes, kind, cls, name)               \
-    do {                                                            \
-        HIPCHK(ctx, call);                                          \
-        HIPCHK(ctx, buf_add(ctx, p, bytes, kind, cls, name));       \
-    } while (0)
 
-// Buffers that grow on demand, one helper per kind of memory: when `need` bytes exceed `cap`, the buffer is freed and one of `alloc`
-// bytes (0: `need`) takes its place.  Nothing may be in flight on the old buffer.  A failed allocation leaves it null and `cap` 0.
-// `name` and `cls` are the buffer's entry in the registry above.
-template <class T> static int grow_dev(tic_ctx *ctx, const char *name, T *&p, size_t &cap, size_t need, size_t alloc = 0, int cls = kBufScratch) {
+// Buf::grow and Buf::release: the only callers of buf_add and buf_drop (tic_test_poison reads the registry they keep).
+template <class T, BufKind K> int Buf<T, K>::grow(tic_ctx *ctx, size_t need, size_t alloc) {
     if (need <= cap) return TIC_OK;
     buf_drop(ctx, p);
-    if (p) HIPCHK(ctx, hipFree(p));
-    p = nullptr, cap = 0;
+    HIPCHK(ctx, free_mem());
     alloc = alloc ? alloc : need;
-    HIPCHK(ctx, hipMalloc((void **)&p, alloc));
-    cap = alloc;
-    HIPCHK(ctx, buf_add(ctx, p, alloc, kBufDev, cls, name));
+    if (const hipError_t e = alloc_mem(alloc); e != hipSuccess) // (HIPCHK's text; the buffer's name and size stand for the call's arguments)
+        return set_err(ctx, TIC_E_HIP, "%s(%s, %zu) failed: %s (%s:%d)", K == kBufDev ? "hipMalloc" : K == kBufPinned ? "hipHostMalloc" : "hipHostMalloc+GetDevicePointer",
+                       name, alloc, hipGetErrorString(e), __FILE__, __LINE__);
+    HIPCHK(ctx, buf_add(ctx, p, alloc, K, cls, name));
     return TIC_OK;
 }
-template <class T> static int grow_pinned(tic_ctx *ctx, const char *name, T *&p, size_t &cap, size_t need, size_t alloc = 0) {
-    if (need <= cap) return TIC_OK;
+template <class T, BufKind K> void Buf<T, K>::release(tic_ctx *ctx) {
     buf_drop(ctx, p);
-    if (p) HIPCHK(ctx, hipHostFree(p));
-    p = nullptr, cap = 0;
-    alloc = alloc ? alloc : need;
-    HIPCHK(ctx, hipHostMalloc((void **)&p, alloc, hipHostMallocDefault));
-    cap = alloc;
-    HIPCHK(ctx, buf_add(ctx, p, alloc, kBufPinned, kBufScratch, name));
-    return TIC_OK;
-}
-// ... host-mapped: `h` for the host, `d` for the kernels; coherent, because the host reads it behind a polled or drained stream
-template <class T> static int grow_mapped(tic_ctx *ctx, const char *name, T *&h, T *&d, size_t &cap, size_t need, size_t alloc = 0) {
-    if (need <= cap) return TIC_OK;
-    buf_drop(ctx, h);
-    if (h) HIPCHK(ctx, hipHostFree(h));
-    h = d = nullptr, cap = 0;
-    alloc = alloc ? alloc : need;
-    HIPCHK(ctx, hipHostMalloc((void **)&h, alloc, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(ctx, hipHostGetDevicePointer((void **)&d, h, 0));
-    cap = alloc;
-    HIPCHK(ctx, buf_add(ctx, h, alloc, kBufMapped, kBufScratch, name));
-    return TIC_OK;
+    (void)free_mem();
 }
 
 int DecWorkspace::grow(tic_ctx *ctx, size_t work_need, size_t work_alloc, size_t desc_need, size_t status, size_t status_alloc) {
-    int rc = grow_dev(ctx, names[0], work, work_bytes, work_need, work_alloc);
+    int rc = work.grow(ctx, work_need, work_alloc);
     if (rc) return rc;
     if (desc_need > desc_words) {
-        const size_t dw = desc_need < 8192 ? 8192 : 2 * desc_need;
-        size_t bytes = desc_words * 8;
         desc_words = 0; // (counted only once the new words are zero)
-        rc = grow_dev(ctx, names[1], desc, bytes, desc_need * 8, dw * 8, kBufState); // (state: wave_lookback spins on these words)
+        rc = desc.grow(ctx, desc_need * 8, (desc_need < 8192 ? 8192 : 2 * desc_need) * 8);
         if (rc) return rc;
-        HIPCHK(ctx, hipMemset(desc, 0, dw * 8));
-        desc_words = dw;
+        HIPCHK(ctx, hipMemset(desc, 0, desc.cap));
+        desc_words = desc.cap / 8;
         epoch = 0;
     }
-    return grow_mapped(ctx, names[2], h_status, d_status, status_bytes, status * sizeof(DecStatus), status_alloc * sizeof(DecStatus));
+    return h_status.grow(ctx, status * sizeof(DecStatus), status_alloc * sizeof(DecStatus));
 }
 
 int DecWorkspace::begin(tic_ctx *ctx, hipStream_t stream, size_t status) {
@@ -528,23 +544,20 @@ int DecWorkspace::begin(tic_ctx *ctx, hipStream_t stream, size_t status) {
 }
 
 void DecWorkspace::release(tic_ctx *ctx) {
-    for (const void *p : {(const void *)work, (const void *)desc, (const void *)h_status}) buf_drop(ctx, p);
-    if (work) (void)hipFree(work);
-    if (desc) (void)hipFree(desc);
-    if (h_status) (void)hipHostFree(h_status);
-    const char *const *keep = names;
-    *this = DecWorkspace();
-    names = keep;
+    work.release(ctx), desc.release(ctx), h_status.release(ctx);
+    desc_words = 0, epoch = 0;
 }
 
+// (every Buf member of Slot is named here: one left out would still be freed with the slot, but its registry record would stay behind
+// and tic_test_poison would fill freed memory - tests/test_context_state_cpu.py holds this list, and DecWorkspace's, against the fields)
 void Slot::release(tic_ctx *ctx) {
-    for (void *p : {(void *)pin_in, (void *)pin_out, (void *)h_lens, (void *)h_err, (void *)h_frames, (void *)h_rb_off, (void *)h_adapt, (void *)h_sframes})
-        if (p) buf_drop(ctx, p), (void)hipHostFree(p);
-    for (void *p : {d_img, d_coef, d_work, (void *)d_lens, (void *)d_err, d_streams, (void *)d_frames, (void *)d_adapt, (void *)d_sframes})
-        if (p) buf_drop(ctx, p), (void)hipFree(p);
+    pin_in.release(ctx), pin_out.release(ctx), d_img.release(ctx), d_coef.release(ctx), d_work.release(ctx), d_lens.release(ctx), h_lens.release(ctx);
+    d_err.release(ctx), h_err.release(ctx), d_streams.release(ctx), h_frames.release(ctx), d_frames.release(ctx), h_rb_off.release(ctx);
+    h_sframes.release(ctx), d_sframes.release(ctx), d_adapt.release(ctx), h_adapt.release(ctx);
     for (hipEvent_t e : {done, rb_done})
         if (e) (void)hipEventDestroy(e);
-    *this = Slot();
+    done = rb_done = nullptr;
+    parity = first = count = pending = 0, rb_row = 0;
 }
 
 extern "C" {
@@ -567,82 +580,28 @@ const char *tic_device_arch(const tic_ctx *ctx) { return ctx ? ctx->arch : ""; }
 size_t tic_num_blocks(int h, int w) { return num_blocks(h, w); }
 size_t tic_compress_bound(int h, int w) { return compress_bound(h, w); }
 
+// Drains and destroys every stream, destroys the events, and deletes the context: its buffers free themselves (Buf), behind the last
+// synchronisation.  Supported with tickets open.
 void tic_destroy(tic_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->rstream) (void)hipStreamDestroy(ctx->rstream);
-    for (auto &s : ctx->bstream)
+    std::vector<hipStream_t> streams = {ctx->rstream, ctx->bstream[0], ctx->bstream[1]};
+    for (const auto &ln : ctx->lanes) streams.push_back(ln.stream);
+    for (const auto &sl : ctx->dec_slots) streams.push_back(sl.stream);
+    for (hipStream_t s : streams)
         if (s) {
             (void)hipStreamSynchronize(s);
             (void)hipStreamDestroy(s);
         }
-    for (auto &sl : ctx->bslots) sl.release(ctx);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->d_img) (void)hipFree(ctx->d_img);
-    if (ctx->d_coef) (void)hipFree(ctx->d_coef);
-    if (ctx->d_consts) (void)hipFree(ctx->d_consts);
-    if (ctx->d_fallback) (void)hipFree(ctx->d_fallback);
-    if (ctx->d_huff) (void)hipFree(ctx->d_huff);
-    if (ctx->d_total_bits) (void)hipFree(ctx->d_total_bits); // d_err lives in the same block
-    if (ctx->d_ent_work) (void)hipFree(ctx->d_ent_work);
-    for (auto &sl : ctx->async_slots)
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    for (auto &ln : ctx->lanes) {
-        if (ln.stream) (void)hipStreamSynchronize(ln.stream);
-        if (ln.d_coef) (void)hipFree(ln.d_coef);
-        for (int k = 0; k < 2; k++) {
-            if (ln.d_work[k]) (void)hipFree(ln.d_work[k]);
-            if (ln.placed[k]) (void)hipEventDestroy(ln.placed[k]);
-        }
-        if (ln.d_err) (void)hipFree(ln.d_err);
-        if (ln.packed) (void)hipEventDestroy(ln.packed);
-        if (ln.stream) (void)hipStreamDestroy(ln.stream);
-    }
-    if (ctx->lane_order) (void)hipEventDestroy(ctx->lane_order);
-    if (ctx->h_stat) (void)hipHostFree(ctx->h_stat);
-    if (ctx->h_zz) (void)hipHostFree(ctx->h_zz);
-    if (ctx->d_stream_buf) (void)hipFree(ctx->d_stream_buf);
-    if (ctx->d_dc32) (void)hipFree(ctx->d_dc32);
-    if (ctx->d_dec_luts) (void)hipFree(ctx->d_dec_luts);
-    ctx->dec_ws.release(ctx);
-    if (ctx->h_dec_tail) (void)hipHostFree(ctx->h_dec_tail);
-    if (ctx->h_small) (void)hipHostFree(ctx->h_small);
-    for (auto &sl : ctx->dec_slots) {
-        if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        sl.ws.release(ctx);
-        if (sl.stream) (void)hipStreamDestroy(sl.stream);
-    }
-    if (ctx->dbat.h_in) (void)hipHostFree(ctx->dbat.h_in);
-    if (ctx->dbat.d_in) (void)hipFree(ctx->dbat.d_in);
-    if (ctx->dbat.d_pix) (void)hipFree(ctx->dbat.d_pix);
-    if (ctx->dbat.h_pix) (void)hipHostFree(ctx->dbat.h_pix);
-    ctx->dbat.ws.release(ctx);
-    if (ctx->dec_order) (void)hipEventDestroy(ctx->dec_order);
-    if (ctx->d_adapt_stats) (void)hipFree(ctx->d_adapt_stats); // table and error word live in the same block
-    if (ctx->d_adapt_work) (void)hipFree(ctx->d_adapt_work);
-    if (ctx->d_adapt_out) (void)hipFree(ctx->d_adapt_out);
-    if (ctx->d_adec_tab) (void)hipFree(ctx->d_adec_tab); // the status words live in the same block
-    if (ctx->d_adec_work) (void)hipFree(ctx->d_adec_work);
-    if (ctx->adbat.d_work) (void)hipFree(ctx->adbat.d_work);
-    if (ctx->adbat.h_status) (void)hipHostFree(ctx->adbat.h_status);
-    if (ctx->d_size_tab) (void)hipFree(ctx->d_size_tab);
-    if (ctx->d_rate) (void)hipFree(ctx->d_rate);
-    if (ctx->h_rate) (void)hipHostFree(ctx->h_rate);
-    if (ctx->h_rate_pix) (void)hipHostFree(ctx->h_rate_pix);
-    if (ctx->h_rate_tabs) (void)hipHostFree(ctx->h_rate_tabs);
-    if (ctx->d_rate_tabs) (void)hipFree(ctx->d_rate_tabs);
-    if (ctx->h_rd_tabs) (void)hipHostFree(ctx->h_rd_tabs);
-    if (ctx->d_rd_tabs) (void)hipFree(ctx->d_rd_tabs);
-    if (ctx->h_scaled_tabs) (void)hipHostFree(ctx->h_scaled_tabs);
-    if (ctx->d_scaled_tabs) (void)hipFree(ctx->d_scaled_tabs);
-    if (ctx->d_arate_stats) (void)hipFree(ctx->d_arate_stats);
-    if (ctx->h_arate_stats) (void)hipHostFree(ctx->h_arate_stats);
-    if (ctx->h_arate_frames) (void)hipHostFree(ctx->h_arate_frames);
-    if (ctx->d_arate_frames) (void)hipFree(ctx->d_arate_frames);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    std::vector<hipEvent_t> events = {ctx->ev0, ctx->ev1, ctx->lane_order, ctx->dec_order};
+    for (const auto &sl : ctx->bslots) events.insert(events.end(), {sl.done, sl.rb_done});
+    for (const auto &sl : ctx->async_slots) events.push_back(sl.done);
+    for (const auto &ln : ctx->lanes) events.insert(events.end(), {ln.packed, ln.placed[0], ln.placed[1]});
+    for (const auto &sl : ctx->dec_slots) events.push_back(sl.done);
+    for (hipEvent_t e : events)
+        if (e) (void)hipEventDestroy(e);
     delete ctx;
 }
 
@@ -678,29 +637,28 @@ static int create_impl(tic_ctx *ctx, int device) {
     std::vector<DctqConsts> all(100);
     memset(all.data(), 0, all.size() * sizeof(DctqConsts));
     for (int q = 1; q <= 99; q++) build_consts(q, &all[q]);
-    CK(hipMalloc((void **)&ctx->d_consts, all.size() * sizeof(DctqConsts)));
+    // (a buffer that does not come leaves its message in the context, which is about to go: handed on to tic_last_error(NULL))
+#define GROW(buf, bytes) \
+    if ((buf).grow(ctx, bytes) != TIC_OK) return set_err(nullptr, TIC_E_HIP, "%s", ctx->err.c_str());
+    GROW(ctx->d_consts, all.size() * sizeof(DctqConsts));
     CK(hipMemcpy(ctx->d_consts, all.data(), all.size() * sizeof(DctqConsts), hipMemcpyHostToDevice));
-    CK(buf_add(ctx, ctx->d_consts, all.size() * sizeof(DctqConsts), kBufDev, kBufState, "d_consts"));
     {
         HuffDev hd;
         build_huff_dev(&hd);
-        CK(hipMalloc((void **)&ctx->d_huff, sizeof(HuffDev)));
+        GROW(ctx->d_huff, sizeof(HuffDev));
         CK(hipMemcpy(ctx->d_huff, &hd, sizeof(HuffDev), hipMemcpyHostToDevice));
-        CK(buf_add(ctx, ctx->d_huff, sizeof(HuffDev), kBufDev, kBufState, "d_huff"));
         // one 32-byte status block: payload bits [2] of the device entropy stage, then its error flags [2]
-        CK(hipMalloc((void **)&ctx->d_total_bits, 32));
+        GROW(ctx->d_total_bits, 32);
         CK(hipMemset(ctx->d_total_bits, 0, 32));
-        CK(buf_add(ctx, ctx->d_total_bits, 32, kBufDev, kBufState, "d_total_bits"));
         ctx->d_err = reinterpret_cast<int *>(ctx->d_total_bits + 2);
         // the stage's last kernel writes {payload bits, error} straight into pinned host memory: no copy behind it
-        CK(hipHostMalloc((void **)&ctx->h_stat, 64 + kAsyncSlots * 16, hipHostMallocMapped | hipHostMallocCoherent));
+        GROW(ctx->h_stat, 64 + kAsyncSlots * 16);
         memset(ctx->h_stat, 0, 64 + kAsyncSlots * 16);
-        CK(buf_add(ctx, ctx->h_stat, 64 + kAsyncSlots * 16, kBufMapped, kBufState, "h_stat"));
-        CK(hipHostGetDevicePointer((void **)&ctx->d_stat, ctx->h_stat, 0));
+        ctx->d_stat = ctx->h_stat.d;
     }
-    CK(hipMalloc((void **)&ctx->d_fallback, 4 * sizeof(unsigned long long)));
+    GROW(ctx->d_fallback, 4 * sizeof(unsigned long long));
     CK(hipMemset(ctx->d_fallback, 0, 4 * sizeof(unsigned long long)));
-    CK(buf_add(ctx, ctx->d_fallback, 4 * sizeof(unsigned long long), kBufDev, kBufState, "d_fallback"));
+#undef GROW
 #undef CK
     return TIC_OK;
 }
@@ -887,6 +845,14 @@ int tic_test_poison(tic_ctx *ctx, int byte) {
     set_err(ctx, TIC_OK, "tic_test_poison: %zu scratch buffers and %zu bytes filled with 0x%02x, %zu state buffers kept", filled, bytes, byte, kept);
     return TIC_OK;
 }
+// Test hook (hooks build only; the shipped library returns -1 and has no counter): the buffers the contexts of this process own now.
+int tic_test_live_buffers(void) {
+#ifdef TIC_TEST_HOOKS
+    return g_live_buffers.load();
+#else
+    return -1;
+#endif
+}
 
 // ---- transform stage -----------------------------------------------------------------------------------
 // Waits for the context's stream.  A blocking hipStreamSynchronize wakes the thread some microseconds after the last kernel
@@ -929,7 +895,7 @@ static DctqArgs make_args(tic_ctx *ctx, const void *d_image, int h, int w, ptrdi
     a.aligned8 = ((((uintptr_t)d_image) | (uintptr_t)stride) & 7) == 0;
     a.consts = ctx->d_consts + quality;
     a.out = (int16_t *)d_out;
-    a.fallback_count = ctx->stats ? ctx->d_fallback : nullptr;
+    a.fallback_count = ctx->stats ? ctx->d_fallback.p : nullptr;
     a.nframes = 1;
     a.frame_stride_in = 0;
     a.frame_stride_out = 0;
@@ -1173,11 +1139,11 @@ int tic_last_fallback_blocks(tic_ctx *ctx, unsigned long long *count) {
 
 constexpr size_t kDecHostPixBytes = 1u << 20; // tic_decompress: images of at most this many bytes leave through tic_ctx::h_small as well
 constexpr size_t kSmallHostBytes = 2u << 20; // tic_compress: frames whose stream bound is at most this go through tic_ctx::h_small
-static int ensure_small(tic_ctx *ctx, size_t bytes) { return grow_mapped(ctx, "h_small", ctx->h_small, ctx->d_small, ctx->small_cap, bytes); }
+static int ensure_small(tic_ctx *ctx, size_t bytes) { return ctx->h_small.grow(ctx, bytes); }
 
 static int ensure_scratch(tic_ctx *ctx, size_t img_bytes, size_t coef_bytes) {
-    const int rc = grow_dev(ctx, "d_img", ctx->d_img, ctx->d_img_cap, img_bytes);
-    return rc ? rc : grow_dev(ctx, "d_coef", ctx->d_coef, ctx->d_coef_cap, coef_bytes);
+    const int rc = ctx->d_img.grow(ctx, img_bytes);
+    return rc ? rc : ctx->d_coef.grow(ctx, coef_bytes);
 }
 
 // Every host-image entry point brings its frame to the device here: the n blocks' uint8 pixels into the context's scratch image, rows
@@ -1308,7 +1274,7 @@ static hipError_t pack_and_place(tic_ctx *ctx, const void *d_zz, size_t n, int h
     const int par = ctx->ent_parity;
     ctx->ent_parity ^= 1;
     const size_t cap_words = ((cap - 16) / 16) * 4; // whole 16-byte units behind the header
-    return entropy_gpu_fused((const int16_t *)d_zz, n, 1, ctx->d_huff, ctx->d_ent_work, ctx->ent_work_bytes, d_out, 0, cap_words, h, w, quality,
+    return entropy_gpu_fused((const int16_t *)d_zz, n, 1, ctx->d_huff, ctx->d_ent_work, ctx->d_ent_work.cap, d_out, 0, cap_words, h, w, quality,
                              nullptr, ctx->d_stat, ctx->d_err + par, ctx->d_err + (par ^ 1), mode, ctx->stream, nullptr, nullptr, flag);
 }
 
@@ -1355,7 +1321,7 @@ static int entropy_encode_dev_impl(tic_ctx *ctx, const void *d_coeffs_zz, int h,
         return TIC_OK;
     }
     if (!d_coeffs_zz) return set_err(ctx, TIC_E_ARG, "null coefficient pointer");
-    rc = grow_dev(ctx, "d_ent_work", ctx->d_ent_work, ctx->ent_work_bytes, entropy_fused_work_bytes(n));
+    rc = ctx->d_ent_work.grow(ctx, entropy_fused_work_bytes(n));
     if (rc) return rc;
     StreamStatus st = {0, 0};
     for (int attempt = 0; attempt < 2; attempt++) {
@@ -1396,29 +1362,19 @@ static int ensure_lane(tic_ctx *ctx, tic_ctx::AsyncLane &ln, size_t n) {
         HIPCHK(ctx, hipEventCreateWithFlags(&ln.packed, hipEventDisableTiming));
         HIPCHK(ctx, hipEventCreateWithFlags(&ln.placed[0], hipEventDisableTiming));
         HIPCHK(ctx, hipEventCreateWithFlags(&ln.placed[1], hipEventDisableTiming));
-        BUF_NEW(ctx, hipMalloc((void **)&ln.d_err, 4 * sizeof(int)), ln.d_err, 4 * sizeof(int), kBufDev, kBufState, "lane.d_err");
+        const int rc = ln.d_err.grow(ctx, 4 * sizeof(int));
+        if (rc) return rc;
         HIPCHK(ctx, hipMemset(ln.d_err, 0, 4 * sizeof(int)));
     }
     if (!ctx->lane_order) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->lane_order, hipEventDisableTiming));
     const size_t coef_bytes = n * 128 + 16, wb = entropy_fused_work_bytes(n);
-    if (coef_bytes <= ln.coef_cap && wb <= ln.work_bytes) return TIC_OK;
+    if (coef_bytes <= ln.d_coef.cap && wb <= ln.d_work[0].cap && wb <= ln.d_work[1].cap) return TIC_OK;
     // (grows only between bursts of one geometry: frames in flight still use the old buffers)
     HIPCHK(ctx, hipStreamSynchronize(ln.stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const int rc = grow_dev(ctx, "lane.d_coef", ln.d_coef, ln.coef_cap, coef_bytes);
-    if (rc) return rc;
-    if (wb > ln.work_bytes) {
-        for (int k = 0; k < 2; k++) {
-            buf_drop(ctx, ln.d_work[k]);
-            if (ln.d_work[k]) HIPCHK(ctx, hipFree(ln.d_work[k]));
-            ln.d_work[k] = nullptr;
-        }
-        ln.work_bytes = 0;
-        BUF_NEW(ctx, hipMalloc(&ln.d_work[0], wb), ln.d_work[0], wb, kBufDev, kBufScratch, "lane.d_work");
-        BUF_NEW(ctx, hipMalloc(&ln.d_work[1], wb), ln.d_work[1], wb, kBufDev, kBufScratch, "lane.d_work");
-        ln.work_bytes = wb;
-    }
-    return TIC_OK;
+    int rc = ln.d_coef.grow(ctx, coef_bytes);
+    for (int k = 0; k < 2 && rc == TIC_OK; k++) rc = ln.d_work[k].grow(ctx, wb);
+    return rc;
 }
 
 // Asynchronous form of tic_compress_dev: the frame's launches (transform, pack, tile sums, place) are queued and the call returns; a
@@ -1475,7 +1431,7 @@ int tic_compress_dev_async(tic_ctx *ctx, const void *d_image, int h, int w, ptrd
         HIPCHK(ctx, launch_dctq(a, dctq_kernel_id(TIC_KERNEL_HYBRID), ln.stream));
         const size_t cap_words = ((cap - 16) / 16) * 4;
         // (the 8-lane packing kernel: it takes any block the format allows, so no second run can be needed)
-        HIPCHK(ctx, entropy_gpu_fused((const int16_t *)ln.d_coef, n, 1, ctx->d_huff, ln.d_work[wk], ln.work_bytes, d_out, 0, cap_words, h, w, quality, nullptr, ds,
+        HIPCHK(ctx, entropy_gpu_fused((const int16_t *)ln.d_coef, n, 1, ctx->d_huff, ln.d_work[wk], ln.d_work[wk].cap, d_out, 0, cap_words, h, w, quality, nullptr, ds,
                                       ln.d_err + ek, ln.d_err + ((ek + 3) & 3), kEntropyEightLanes, ln.stream, ctx->stream, ln.packed));
         HIPCHK(ctx, hipEventRecord(ln.placed[wk], ctx->stream));
         ln.placed_valid[wk] = true;
@@ -1526,13 +1482,13 @@ int tic_compress(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row
     // image -> HBM, transform stage, entropy stage, all on the device; only the finished stream returns
     const size_t need = compress_bound(h, w);
     const bool small = need <= kSmallHostBytes && !test_hook("TIC_NO_SMALL_PATH"); // the placing kernel writes the stream into host memory itself
-    rc = small ? ensure_small(ctx, kSmallHostBytes) : grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, need);
+    rc = small ? ensure_small(ctx, kSmallHostBytes) : ctx->d_stream_buf.grow(ctx, need);
     if (rc) return rc;
     size_t pitch = 0, len = 0;
     rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
     if (rc) return rc;
-    rc = tic_compress_dev(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, quality, small ? (void *)ctx->d_small : ctx->d_stream_buf,
-                          small ? ctx->small_cap : ctx->d_stream_cap, &len);
+    rc = tic_compress_dev(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, quality, small ? (void *)ctx->h_small.d : ctx->d_stream_buf,
+                          small ? ctx->h_small.cap : ctx->d_stream_buf.cap, &len);
     if (rc) return rc;
     if (len > cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", len, cap);
     if (small) {
@@ -1553,19 +1509,18 @@ int tic_compress(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row
 // and come back in ONE copy.
 static int ensure_rate(tic_ctx *ctx, size_t nres) {
     if (!ctx->d_size_tab) {
-        SizeTabDev t, *d = nullptr;
+        SizeTabDev t;
         build_size_tab(&t);
-        HIPCHK(ctx, hipMalloc((void **)&d, sizeof t));
-        const hipError_t e = hipMemcpy(d, &t, sizeof t, hipMemcpyHostToDevice);
-        if (e != hipSuccess) (void)hipFree(d);
+        const int rc = ctx->d_size_tab.grow(ctx, sizeof t);
+        if (rc) return rc;
+        const hipError_t e = hipMemcpy(ctx->d_size_tab, &t, sizeof t, hipMemcpyHostToDevice);
+        if (e != hipSuccess) ctx->d_size_tab.release(ctx); // (never a table half written: the next call builds it again)
         HIPCHK(ctx, e);
-        ctx->d_size_tab = d;
-        HIPCHK(ctx, buf_add(ctx, d, sizeof t, kBufDev, kBufState, "d_size_tab"));
     }
     // (a DistortionResult per probe as well, behind the nres SizeResults: dist_of)
     const size_t need = nres * (sizeof(SizeResult) + sizeof(DistortionResult)), alloc = align_up(need, 4096);
-    const int rc = grow_dev(ctx, "d_rate", ctx->d_rate, ctx->rate_dev_bytes, need, alloc);
-    return rc ? rc : grow_pinned(ctx, "h_rate", ctx->h_rate, ctx->rate_host_bytes, need, alloc);
+    const int rc = ctx->d_rate.grow(ctx, need, alloc);
+    return rc ? rc : ctx->h_rate.grow(ctx, need, alloc);
 }
 
 // The distortion results of a submission of nq probes lie behind its nq size results, in the device buffer and in its landing buffer alike:
@@ -1716,13 +1671,13 @@ static int chosen_stream(tic_ctx *ctx, const void *d_image, int h, int w, ptrdif
         *out_len = len;
         return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", len, cap);
     }
-    int rc = grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, compress_bound(h, w));
+    int rc = ctx->d_stream_buf.grow(ctx, compress_bound(h, w));
     if (rc) return rc;
-    rc = grow_dev(ctx, "d_ent_work", ctx->d_ent_work, ctx->ent_work_bytes, entropy_fused_work_bytes(n));
+    rc = ctx->d_ent_work.grow(ctx, entropy_fused_work_bytes(n));
     if (rc) return rc;
     DctqArgs a = make_args(ctx, d_image, h, w, row_stride, q, ctx->d_coef);
     HIPCHK(ctx, launch_dctq(a, dctq_kernel_id(TIC_KERNEL_HYBRID), ctx->stream));
-    HIPCHK(ctx, pack_and_place(ctx, ctx->d_coef, n, h, w, q, ctx->d_stream_buf, ctx->d_stream_cap, kEntropyEightLanes, 0u));
+    HIPCHK(ctx, pack_and_place(ctx, ctx->d_coef, n, h, w, q, ctx->d_stream_buf, ctx->d_stream_buf.cap, kEntropyEightLanes, 0u));
     HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_stream_buf, len, out_on_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(ctx, out_on_host ? hipStreamSynchronize(ctx->stream) : wait_stream(ctx));
     ctx->last_rate_waits++;
@@ -2171,10 +2126,10 @@ int tic_compress_scaled_dev(tic_ctx *ctx, const void *d_image, int h, int w, ptr
     if (rc) return rc;
     const size_t bound = tic_compress_scaled_bound(h, w);
     if (cap >= bound || n == 0) return entropy_encode_dev_impl(ctx, ctx->d_coef, h, w, qf, d_out, cap, out_len, true);
-    rc = grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, bound);
+    rc = ctx->d_stream_buf.grow(ctx, bound);
     if (rc) return rc;
     size_t len = 0;
-    rc = entropy_encode_dev_impl(ctx, ctx->d_coef, h, w, qf, ctx->d_stream_buf, ctx->d_stream_cap, &len, true);
+    rc = entropy_encode_dev_impl(ctx, ctx->d_coef, h, w, qf, ctx->d_stream_buf, ctx->d_stream_buf.cap, &len, true);
     if (rc) return rc;
     if (len > cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", len, cap);
     HIPCHK(ctx, hipMemcpyAsync(d_out, ctx->d_stream_buf, len, hipMemcpyDeviceToDevice, ctx->stream));
@@ -2193,12 +2148,12 @@ int tic_compress_scaled(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdif
     if (n == 0) return entropy_encode_scaled(nullptr, h, w, qf, out, cap, out_len);
     if (!image) return set_err(ctx, TIC_E_ARG, "null image pointer");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    rc = grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, tic_compress_scaled_bound(h, w));
+    rc = ctx->d_stream_buf.grow(ctx, tic_compress_scaled_bound(h, w));
     if (rc) return rc;
     size_t pitch = 0, len = 0;
     rc = upload_image(ctx, image, h, w, row_stride, n, &pitch);
     if (rc) return rc;
-    rc = tic_compress_scaled_dev(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, qf, ctx->d_stream_buf, ctx->d_stream_cap, &len);
+    rc = tic_compress_scaled_dev(ctx, ctx->d_img, h, w, (ptrdiff_t)pitch, qf, ctx->d_stream_buf, ctx->d_stream_buf.cap, &len);
     if (rc) return rc;
     if (len > cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", len, cap);
     HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_stream_buf, len, hipMemcpyDeviceToHost, ctx->stream));
@@ -2357,51 +2312,23 @@ static int ensure_batch_slots(tic_ctx *ctx, tic_ctx::SlotNeed need) {
     need.img = std::max(need.img, old.img), need.coef = std::max(need.coef, old.coef), need.pin_out = std::max(need.pin_out, old.pin_out);
     need.streams = std::max(need.streams, old.streams), need.work = std::max(need.work, old.work), need.frames = std::max(need.frames, old.frames);
     for (auto &sl : ctx->bslots) sl.release(ctx);
-    ctx->bslots.assign(kBatchSlots, Slot());
+    ctx->bslots.clear();
+    ctx->bslots.resize(kBatchSlots);
     ctx->bslot_cap = tic_ctx::SlotNeed();
     const size_t nf = (size_t)need.frames;
     for (auto &sl : ctx->bslots) {
-        hipError_t e;
-        if ((e = hipHostMalloc((void **)&sl.pin_in, need.img, hipHostMallocDefault)) != hipSuccess ||
-            (e = hipHostMalloc((void **)&sl.pin_out, need.pin_out, hipHostMallocDefault)) != hipSuccess ||
-            (e = hipMalloc(&sl.d_img, need.img)) != hipSuccess || (e = hipMalloc(&sl.d_coef, need.coef)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&sl.rb_done, hipEventDisableTiming)) != hipSuccess)
-            return set_err(ctx, TIC_E_HIP, "batch buffer allocation failed: %s", hipGetErrorString(e));
-        sl.work_bytes = need.work;
-        if ((e = hipMalloc(&sl.d_work, sl.work_bytes)) != hipSuccess ||
-            (e = hipMalloc((void **)&sl.d_lens, nf * sizeof(unsigned long long))) != hipSuccess ||
-            (e = hipHostMalloc((void **)&sl.h_lens, nf * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess ||
-            (e = hipMalloc((void **)&sl.d_err, 2 * sizeof(int))) != hipSuccess || (e = hipMemset(sl.d_err, 0, 2 * sizeof(int))) != hipSuccess ||
-            (e = hipHostMalloc((void **)&sl.h_err, sizeof(int), hipHostMallocDefault)) != hipSuccess ||
-            (e = hipMalloc(&sl.d_streams, need.streams)) != hipSuccess ||
-            (e = hipHostMalloc((void **)&sl.h_frames, sizeof(EntropyFrameTable), hipHostMallocDefault)) != hipSuccess ||
-            (e = hipMalloc((void **)&sl.d_frames, sizeof(EntropyFrameTable))) != hipSuccess ||
-            (e = hipHostMalloc((void **)&sl.h_rb_off, kEntropyMaxFrames * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess ||
-            (e = hipHostMalloc((void **)&sl.h_sframes, sizeof(ScaledFrameTable), hipHostMallocDefault)) != hipSuccess ||
-            (e = hipMalloc((void **)&sl.d_sframes, sizeof(ScaledFrameTable))) != hipSuccess)
-            return set_err(ctx, TIC_E_HIP, "batch entropy workspace allocation failed: %s", hipGetErrorString(e));
-        // (the registry of the hooks build; d_err - two flags used in turn, state - was cleared above and stays clear)
-        const struct { void *p; size_t bytes; int kind, cls; const char *name; } recs[] = {
-            {sl.pin_in, need.img, kBufPinned, kBufScratch, "bslot.pin_in"},
-            {sl.pin_out, need.pin_out, kBufPinned, kBufScratch, "bslot.pin_out"},
-            {sl.d_img, need.img, kBufDev, kBufScratch, "bslot.d_img"},
-            {sl.d_coef, need.coef, kBufDev, kBufScratch, "bslot.d_coef"},
-            {sl.d_work, sl.work_bytes, kBufDev, kBufScratch, "bslot.d_work"},
-            {sl.d_lens, nf * sizeof(unsigned long long), kBufDev, kBufScratch, "bslot.d_lens"},
-            {sl.h_lens, nf * sizeof(unsigned long long), kBufPinned, kBufScratch, "bslot.h_lens"},
-            {sl.d_err, 2 * sizeof(int), kBufDev, kBufState, "bslot.d_err"},
-            {sl.h_err, sizeof(int), kBufPinned, kBufScratch, "bslot.h_err"},
-            {sl.d_streams, need.streams, kBufDev, kBufScratch, "bslot.d_streams"},
-            {sl.h_frames, sizeof(EntropyFrameTable), kBufPinned, kBufScratch, "bslot.h_frames"},
-            {sl.d_frames, sizeof(EntropyFrameTable), kBufDev, kBufScratch, "bslot.d_frames"},
-            {sl.h_rb_off, kEntropyMaxFrames * sizeof(unsigned long long), kBufPinned, kBufScratch, "bslot.h_rb_off"},
-            {sl.h_sframes, sizeof(ScaledFrameTable), kBufPinned, kBufScratch, "bslot.h_sframes"},
-            {sl.d_sframes, sizeof(ScaledFrameTable), kBufDev, kBufScratch, "bslot.d_sframes"},
-        };
-        for (const auto &r : recs)
-            if ((e = buf_add(ctx, r.p, r.bytes, r.kind, r.cls, r.name)) != hipSuccess)
-                return set_err(ctx, TIC_E_HIP, "batch buffer poisoning failed: %s", hipGetErrorString(e));
+        HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+        HIPCHK(ctx, hipEventCreateWithFlags(&sl.rb_done, hipEventDisableTiming));
+        int rc;
+        if ((rc = sl.pin_in.grow(ctx, need.img)) || (rc = sl.pin_out.grow(ctx, need.pin_out)) || (rc = sl.d_img.grow(ctx, need.img)) ||
+            (rc = sl.d_coef.grow(ctx, need.coef)) || (rc = sl.d_work.grow(ctx, need.work)) || (rc = sl.d_lens.grow(ctx, nf * sizeof(unsigned long long))) ||
+            (rc = sl.h_lens.grow(ctx, nf * sizeof(unsigned long long))) || (rc = sl.d_err.grow(ctx, 2 * sizeof(int))) ||
+            (rc = sl.h_err.grow(ctx, sizeof(int))) || (rc = sl.d_streams.grow(ctx, need.streams)) ||
+            (rc = sl.h_frames.grow(ctx, sizeof(EntropyFrameTable))) || (rc = sl.d_frames.grow(ctx, sizeof(EntropyFrameTable))) ||
+            (rc = sl.h_rb_off.grow(ctx, kEntropyMaxFrames * sizeof(unsigned long long))) || (rc = sl.h_sframes.grow(ctx, sizeof(ScaledFrameTable))) ||
+            (rc = sl.d_sframes.grow(ctx, sizeof(ScaledFrameTable))))
+            return rc;
+        HIPCHK(ctx, hipMemset(sl.d_err, 0, 2 * sizeof(int))); // (two flags used in turn, state: cleared here, and they stay clear)
     }
     ctx->bslot_cap = need;
     return TIC_OK;
@@ -2795,7 +2722,7 @@ static int batch_device_entropy(tic_ctx *ctx, const uint8_t *const *images, int 
             const int first = c * p.chunk, cnt = n - first < p.chunk ? n - first : p.chunk;
             return enqueue_chunk(ctx, p, s, stream, images, first, cnt, row_stride, h, w, quality, [&](Slot &sl, hipStream_t st) {
                 // entropy stage of the whole chunk: pack + place (headers, lengths); no zero fill
-                hipError_t e = entropy_gpu_fused((const int16_t *)sl.d_coef, p.nblk, cnt, ctx->d_huff, sl.d_work, sl.work_bytes, sl.d_streams, p.bound,
+                hipError_t e = entropy_gpu_fused((const int16_t *)sl.d_coef, p.nblk, cnt, ctx->d_huff, sl.d_work, sl.d_work.cap, sl.d_streams, p.bound,
                                                  (p.bound - 16) / 4, h, w, quality, sl.d_lens, nullptr, sl.d_err + par, sl.d_err + (par ^ 1),
                                                  quality <= ctx->ent_lane_max_quality ? kEntropyLanePerBlock : kEntropyEightLanes, st);
                 if (e == hipSuccess) e = hipMemcpyAsync(sl.h_lens, sl.d_lens, cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
@@ -2948,7 +2875,7 @@ static hipError_t transform_chunk_scaled(Slot &s, const MixedPlan &p, const Mixe
         hs[k] = f.h, ws[k] = f.w, qfs[k] = f.quality;
     }
     uint32_t strips = 0;
-    if (!fill_scaled_table(s.h_sframes, c.count, (unsigned long long)(uintptr_t)s.d_img, (unsigned long long)(uintptr_t)s.d_coef, off, pitch, hs, ws, qfs, blk, &strips))
+    if (!fill_scaled_table(s.h_sframes, c.count, (unsigned long long)(uintptr_t)s.d_img.p, (unsigned long long)(uintptr_t)s.d_coef.p, off, pitch, hs, ws, qfs, blk, &strips))
         return hipErrorInvalidValue;
     hipError_t e = hipMemcpyAsync(s.d_sframes, s.h_sframes, sizeof(ScaledFrameTable), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = launch_fdctq_scaled_v(s.d_sframes, strips, stream);
@@ -2993,7 +2920,7 @@ static int batch_mixed_pipeline(tic_ctx *ctx, const MixedPlan &p, const MixedCal
                 [&](Slot &sl, hipStream_t st) {
                     hipError_t e = hipMemcpyAsync(sl.d_frames, sl.h_frames, sizeof(EntropyFrameTable), hipMemcpyHostToDevice, st);
                     if (e == hipSuccess)
-                        e = entropy_gpu_fused_v((const int16_t *)sl.d_coef, sl.h_frames, sl.d_frames, c.count, ctx->d_huff, sl.d_work, sl.work_bytes, sl.d_streams,
+                        e = entropy_gpu_fused_v((const int16_t *)sl.d_coef, sl.h_frames, sl.d_frames, c.count, ctx->d_huff, sl.d_work, sl.d_work.cap, sl.d_streams,
                                                 sl.d_lens, sl.d_err + par, sl.d_err + (par ^ 1), mode, st, scaled ? kFlagScaled : 0u);
                     if (e == hipSuccess) e = hipMemcpyAsync(sl.h_lens, sl.d_lens, c.count * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
                     if (e == hipSuccess) e = hipMemcpyAsync(sl.h_err, sl.d_err + par, sizeof(int), hipMemcpyDeviceToHost, st);
@@ -3150,8 +3077,8 @@ int tic_last_compress_batch_scaled(tic_ctx *ctx, int *batch_frames, int *single_
 // Room for `ntabs` tables of the transform's descriptor form outside the batch slots.  Nothing of an earlier call may be in flight.
 static int ensure_scaled_tabs(tic_ctx *ctx, size_t ntabs) {
     const size_t bytes = ntabs * sizeof(ScaledFrameTable), alloc = align_up(bytes, 16384);
-    const int rc = grow_pinned(ctx, "h_scaled_tabs", ctx->h_scaled_tabs, ctx->scaled_tabs_host_bytes, bytes, alloc);
-    return rc ? rc : grow_dev(ctx, "d_scaled_tabs", ctx->d_scaled_tabs, ctx->scaled_tabs_dev_bytes, bytes, alloc);
+    const int rc = ctx->h_scaled_tabs.grow(ctx, bytes, alloc);
+    return rc ? rc : ctx->d_scaled_tabs.grow(ctx, bytes, alloc);
 }
 
 // The kernel alone, synchronous: frames resident anywhere on the device, the coefficients of all of them back to back at d_coeffs_zz in the
@@ -3223,7 +3150,7 @@ static int check_rate_frames(tic_ctx *ctx, const RateCall &io, int n, int qualit
 static int upload_rate_chunk(tic_ctx *ctx, const MixedPlan &p, const MixedChunk &c, const RateCall &io) {
     int rc = ensure_scratch(ctx, c.img_bytes, 0);
     if (rc) return rc;
-    rc = grow_pinned(ctx, "h_rate_pix", ctx->h_rate_pix, ctx->rate_pix_cap, c.img_bytes);
+    rc = ctx->h_rate_pix.grow(ctx, c.img_bytes);
     if (rc) return rc;
     const MixedFrame *fr = &p.frames[(size_t)c.first];
     uint8_t *pin = ctx->h_rate_pix;
@@ -3251,10 +3178,10 @@ static size_t sse_group_cap() { // (TIC_SSE_MAX_GROUPS, a test hook, lowers the 
 // kernel's (0: that kernel is not launched, its buffers stay as they are).  Nothing of an earlier submission may be in flight.
 static int ensure_probe_tabs(tic_ctx *ctx, size_t size_tabs, size_t sse_tabs) {
     const size_t size_bytes = size_tabs * sizeof(SizeProbeTable), sse_bytes = sse_tabs * sizeof(SseProbeTable);
-    int rc = grow_pinned(ctx, "h_rate_tabs", ctx->h_rate_tabs, ctx->rate_tabs_host_bytes, size_bytes, align_up(size_bytes, 16384));
-    if (rc == TIC_OK) rc = grow_dev(ctx, "d_rate_tabs", ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, size_bytes, align_up(size_bytes, 16384));
-    if (rc == TIC_OK) rc = grow_pinned(ctx, "h_rd_tabs", ctx->h_rd_tabs, ctx->rd_tabs_host_bytes, sse_bytes, align_up(sse_bytes, 16384));
-    if (rc == TIC_OK) rc = grow_dev(ctx, "d_rd_tabs", ctx->d_rd_tabs, ctx->rd_tabs_dev_bytes, sse_bytes, align_up(sse_bytes, 16384));
+    int rc = ctx->h_rate_tabs.grow(ctx, size_bytes, align_up(size_bytes, 16384));
+    if (rc == TIC_OK) rc = ctx->d_rate_tabs.grow(ctx, size_bytes, align_up(size_bytes, 16384));
+    if (rc == TIC_OK) rc = ctx->h_rd_tabs.grow(ctx, sse_bytes, align_up(sse_bytes, 16384));
+    if (rc == TIC_OK) rc = ctx->d_rd_tabs.grow(ctx, sse_bytes, align_up(sse_bytes, 16384));
     return rc;
 }
 
@@ -3770,7 +3697,7 @@ int tic_rd_points_scaled_v(tic_ctx *ctx, const uint8_t *const *images, int n, co
                                    f.h, f.w, (uint32_t)pi, qfs[j]};
                 block += f.nblk;
             }
-            if (!fill_scaled_table(&ctx->h_scaled_tabs[t], cnt, (unsigned long long)(uintptr_t)ctx->d_img, (unsigned long long)(uintptr_t)ctx->d_coef, off, pitch, fh,
+            if (!fill_scaled_table(&ctx->h_scaled_tabs[t], cnt, (unsigned long long)(uintptr_t)ctx->d_img.p, (unsigned long long)(uintptr_t)ctx->d_coef.p, off, pitch, fh,
                                    fw, fq, blk, &strips[t]) ||
                 !fill_size_probe_table(&ctx->h_rate_tabs[t], cnt, nblk, result, &size_groups[t], &total) ||
                 !fill_sse_probe_table(&ctx->h_rd_tabs[t], cnt, in, sse_cap, &sse_groups[t]))
@@ -4000,16 +3927,12 @@ static int ensure_dec_tables(tic_ctx *ctx) {
     dec_luts_fill(l->dc11, l->ac11, l->ac16);
     dec_chain_luts_fill(l->mdc, l->mac, l->mlong);
     dec_pair_luts_fill(l->ac2, l->long32); // (new DecLutsDev() zeroed the entries behind the long codewords)
-    DecLutsDev *d = nullptr;
-    hipError_t e = hipMalloc((void **)&d, sizeof(DecLutsDev));
-    if (e == hipSuccess) {
-        e = hipMemcpy(d, l.get(), sizeof(DecLutsDev), hipMemcpyHostToDevice);
-        if (e != hipSuccess) (void)hipFree(d);
-    }
-    if (e != hipSuccess) return set_err(ctx, TIC_E_HIP, "device decoder set-up failed: %s", hipGetErrorString(e));
-    ctx->d_dec_luts = d;
-    HIPCHK(ctx, buf_add(ctx, d, sizeof(DecLutsDev), kBufDev, kBufState, "d_dec_luts"));
-    return TIC_OK;
+    const int rc = ctx->d_dec_luts.grow(ctx, sizeof(DecLutsDev));
+    if (rc) return rc;
+    const hipError_t e = hipMemcpy(ctx->d_dec_luts, l.get(), sizeof(DecLutsDev), hipMemcpyHostToDevice);
+    if (e == hipSuccess) return TIC_OK;
+    ctx->d_dec_luts.release(ctx);
+    return set_err(ctx, TIC_E_HIP, "device decoder set-up failed: %s", hipGetErrorString(e));
 }
 
 // The inverse stage's arguments for the device decoder's kernels: pixels into `out`, rows `stride` bytes apart; `head` (may be null)
@@ -4152,14 +4075,12 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
     // its end themselves); a host stream, or an odd address, goes through the context's stream buffer.
     const bool in_place = src_on_device && ((uintptr_t)data & 3u) == 0;
     if (!in_place) {
-        rc = grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, align_up(len, 4) + 16);
+        rc = ctx->d_stream_buf.grow(ctx, align_up(len, 4) + 16);
         if (rc) return rc;
     }
     const void *d_stream = in_place ? (const void *)data : (const void *)ctx->d_stream_buf;
-    if (!ctx->h_dec_tail) { // pinned: the stream's last bytes on their way down (device source), the tail's coefficients on their way up
-        BUF_NEW(ctx, hipHostMalloc((void **)&ctx->h_dec_tail, kDecTailEnd + kDecTailCoef, hipHostMallocDefault), ctx->h_dec_tail, kDecTailEnd + kDecTailCoef,
-                kBufPinned, kBufScratch, "h_dec_tail");
-    }
+    rc = ctx->h_dec_tail.grow(ctx, kDecTailEnd + kDecTailCoef); // pinned: the stream's last bytes on their way down (device source), the tail's
+    if (rc) return rc;                                          // coefficients on their way up
     DecWorkspace &ws = ctx->dec_ws;
     const size_t wb = entropy_decode_gpu_work_bytes(len, n);
     rc = ws.grow(ctx, wb, wb, entropy_decode_gpu_desc_words(len, n), 1, 1);
@@ -4183,7 +4104,7 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
         if (rc) return rc;
     }
     // (head16 is a guess, or the stream's own header)
-    const DecIdctArgs ia = dec_idct_args(ctx, h, w, sh.quality, sh.scaled_exp, direct ? out : host_pix ? ctx->d_small : (uint8_t *)ctx->d_img,
+    const DecIdctArgs ia = dec_idct_args(ctx, h, w, sh.quality, sh.scaled_exp, direct ? out : host_pix ? ctx->h_small.d : (uint8_t *)ctx->d_img,
                                          direct ? (long)out_stride : host_pix ? (long)pitch8 : (long)pitch, head16);
     // stream bits per lane (decode_range_bits): 2 average blocks, at least 288 bits, as an odd number of 32-bit words up to 63 (noise at q = 50,
     // 220 bits per block: 480; tiled Lenna, 41, and noise at q = 10, 70: 288; noise at q = 90, 404: 864).  The decoder's kernels are one
@@ -4217,11 +4138,11 @@ static int decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t len, const
         ctx->last_decode_tries++;
         ctx->last_decode_range = range_bits;
         if (sink.coef)
-            HIPCHK(ctx, entropy_decode_coef_gpu(d_stream, len, n, ctx->d_dec_luts, ws.work, ws.work_bytes, ws.desc, ws.desc_words, ws.epoch, head16, d_sink,
-                                                ws.d_status, range_bits, margin_bits, ctx->stream, flat_grid));
+            HIPCHK(ctx, entropy_decode_coef_gpu(d_stream, len, n, ctx->d_dec_luts, ws.work, ws.work.cap, ws.desc, ws.desc_words, ws.epoch, head16, d_sink,
+                                                ws.h_status.d, range_bits, margin_bits, ctx->stream, flat_grid));
         else
-            HIPCHK(ctx, entropy_decode_idct_gpu(d_stream, len, n, ctx->d_dec_luts, ws.work, ws.work_bytes, ws.desc, ws.desc_words, ws.epoch, ia,
-                                                ws.d_status, range_bits, margin_bits, ctx->stream, flat_grid));
+            HIPCHK(ctx, entropy_decode_idct_gpu(d_stream, len, n, ctx->d_dec_luts, ws.work, ws.work.cap, ws.desc, ws.desc_words, ws.epoch, ia,
+                                                ws.h_status.d, range_bits, margin_bits, ctx->stream, flat_grid));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         memcpy(&st, ws.h_status, sizeof st); // (host-mapped: the stream has drained)
         if (guessed_head) { // geometry and quality were a guess (tic_decompress_dev): what this run produced counts only if the stream's header is the guessed one
@@ -4350,7 +4271,7 @@ static int decode_on_host(tic_ctx *ctx, const uint8_t *data, size_t len, const S
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // coefficients land in a pinned buffer kept on the context: no page faults on a fresh 32 MB vector per call, and the upload
     // runs at PCIe speed instead of through the runtime's staging of pageable memory
-    int rc = grow_pinned(ctx, "h_zz", ctx->h_zz, ctx->h_zz_bytes, n * 128);
+    int rc = ctx->h_zz.grow(ctx, n * 128);
     if (rc) return rc;
     std::vector<DcWide> wide;
     entropy_decode(data, len, sh.h, sh.w, ctx->h_zz, &wide);
@@ -4366,7 +4287,7 @@ static int decode_on_host(tic_ctx *ctx, const uint8_t *data, size_t len, const S
         std::vector<int32_t> dc32(n);
         for (size_t b = 0; b < n; b++) dc32[b] = ctx->h_zz[b * 64];
         for (const DcWide &x : wide) dc32[x.block] = x.dc;
-        rc = grow_dev(ctx, "d_dc32", ctx->d_dc32, ctx->d_dc32_cap, n * sizeof(int32_t));
+        rc = ctx->d_dc32.grow(ctx, n * sizeof(int32_t));
         if (rc) return rc;
         HIPCHK(ctx, hipMemcpy(ctx->d_dc32, dc32.data(), n * sizeof(int32_t), hipMemcpyHostToDevice)); // (pageable, synchronous: dc32 dies with this scope)
         d_dc32 = ctx->d_dc32;
@@ -4405,16 +4326,9 @@ struct DecBatchIO { // the caller's arrays
 // The buffers both batch decoders share (ctx->dbat): the pinned upload buffer and its device mirror grow together; the chunk's pixel buffer.
 static int dbatch_grow(tic_ctx *ctx, size_t up_bytes, size_t pix_bytes) {
     tic_ctx::DecBatch &B = ctx->dbat;
-    if (up_bytes > B.in_cap) {
-        size_t hcap = B.in_cap, dcap = B.in_cap;
-        B.in_cap = 0;
-        int rc = grow_pinned(ctx, "dbat.h_in", B.h_in, hcap, up_bytes, up_bytes + up_bytes / 4);
-        if (rc) return rc;
-        rc = grow_dev(ctx, "dbat.d_in", B.d_in, dcap, up_bytes, up_bytes + up_bytes / 4);
-        if (rc) return rc;
-        B.in_cap = dcap;
-    }
-    return grow_dev(ctx, "dbat.d_pix", B.d_pix, B.pix_cap, pix_bytes, pix_bytes + pix_bytes / 4);
+    int rc = B.h_in.grow(ctx, up_bytes, up_bytes + up_bytes / 4);
+    if (rc == TIC_OK) rc = B.d_in.grow(ctx, up_bytes, up_bytes + up_bytes / 4);
+    return rc ? rc : B.d_pix.grow(ctx, pix_bytes, pix_bytes + pix_bytes / 4);
 }
 
 // Descriptors, buffers, ONE upload - descriptors, the frame of every measure wave, the frame of every fused workgroup, the streams - and the two
@@ -4459,7 +4373,7 @@ static int dbatch_enqueue(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame
     if (rc) return rc;
     BT_STOP(0);
     BT_START();
-    size_t work_held = B.ws.work_bytes;
+    size_t work_held = B.ws.work.cap;
     if (const char *e = test_hook("TIC_DBATCH_WORK_CAP")) work_held = (size_t)atoll(e) < work_held ? (size_t)atoll(e) : work_held; // (tests: a launcher that refuses)
     ctx->last_dbatch_range = c.range_bits;
     ctx->last_dbatch_work_used = dec_work_carve_bytes(F, c.ranges, c.blocks, c.range_bits);
@@ -4467,7 +4381,7 @@ static int dbatch_enqueue(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame
     HIPCHK(ctx, hipMemcpyAsync(B.d_in, B.h_in, up.up_bytes, hipMemcpyHostToDevice, ctx->stream));
     const hipError_t le = entropy_decode_idct_gpu_batch(B.d_in + up.o_streams, (const DecFrame *)(B.d_in + up.o_frames), (const uint32_t *)(B.d_in + up.o_tiles),
                                                         (const uint32_t *)(B.d_in + up.o_wgs), F, tiles, wgs, c.ranges, c.blocks, c.small_win, ctx->d_dec_luts, B.ws.work, work_held,
-                                                        B.ws.desc, B.ws.desc_words, B.ws.epoch, B.ws.d_status, c.range_bits, ctx->stream);
+                                                        B.ws.desc, B.ws.desc_words, B.ws.epoch, B.ws.h_status.d, c.range_bits, ctx->stream);
     if (le == hipErrorInvalidValue) {
         (void)hipGetLastError();
         *refused = true;
@@ -4509,7 +4423,7 @@ extern "C++" template <class Frame> static int dbatch_pixels_down(tic_ctx *ctx, 
         if (reg && hipHostUnregister(reg) != hipSuccess) (void)hipGetLastError();
     }
     if (!*direct) {
-        const int rc = grow_pinned(ctx, "dbat.h_pix", B.h_pix, B.hpix_cap, pix_bytes, pix_bytes + pix_bytes / 4);
+        const int rc = B.h_pix.grow(ctx, pix_bytes, pix_bytes + pix_bytes / 4);
         if (rc) return rc;
         HIPCHK(ctx, hipMemcpyAsync(B.h_pix, B.d_pix, pix_bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -4779,8 +4693,8 @@ int tic_decompress_dev_async(tic_ctx *ctx, const void *d_stream, size_t len, voi
         // behind everything queued on the context's stream so far (the stream may just have been written there: tic_compress_dev_async)
         HIPCHK(ctx, hipEventRecord(ctx->dec_order, ctx->stream));
         HIPCHK(ctx, hipStreamWaitEvent(sl.stream, ctx->dec_order, 0));
-        HIPCHK(ctx, entropy_decode_idct_gpu(d_stream, len, n, ctx->d_dec_luts, sl.ws.work, sl.ws.work_bytes, sl.ws.desc, sl.ws.desc_words, sl.ws.epoch, ia,
-                                            sl.ws.d_status, decode_range_bits(len, n), 0, sl.stream));
+        HIPCHK(ctx, entropy_decode_idct_gpu(d_stream, len, n, ctx->d_dec_luts, sl.ws.work, sl.ws.work.cap, sl.ws.desc, sl.ws.desc_words, sl.ws.epoch, ia,
+                                            sl.ws.h_status.d, decode_range_bits(len, n), 0, sl.stream));
         HIPCHK(ctx, hipEventRecord(sl.done, sl.stream));
         memcpy(sl.head, ctx->dec_head, 16);
         sl.n = n;
@@ -4876,16 +4790,12 @@ int tic_huffman_table_build(const uint64_t *dc_count, const uint64_t *dc_first, 
 // the 4.4 KB of statistics the host builds the table from (it also yields the stream's exact length, checked against `cap` before
 // anything is packed).
 static int adaptive_encode_dev(tic_ctx *ctx, size_t n, int h, int w, int quality, uint8_t *out, size_t cap, size_t *out_len) {
-    if (!ctx->d_adapt_stats) {
-        char *p = nullptr;
-        const size_t a = align_up(sizeof(AdaptStats), 256), b = align_up(sizeof(HuffWide), 256);
-        HIPCHK(ctx, hipMalloc((void **)&p, a + b + 256));
-        ctx->d_adapt_stats = (AdaptStats *)p;
-        ctx->d_adapt_tab = (HuffWide *)(p + a);
-        ctx->d_adapt_err = (uint32_t *)(p + a + b);
-        HIPCHK(ctx, buf_add(ctx, p, a + b + 256, kBufDev, kBufScratch, "d_adapt_stats")); // (all three rewritten per call; the context owns the block first)
-    }
-    int rc = grow_dev(ctx, "d_adapt_work", ctx->d_adapt_work, ctx->adapt_work_bytes, adaptive_work_bytes(n));
+    const size_t a = align_up(sizeof(AdaptStats), 256), b = align_up(sizeof(HuffWide), 256);
+    int rc = ctx->d_adapt_stats.grow(ctx, a + b + 256); // (statistics, table and error word: all three rewritten per call)
+    if (rc) return rc;
+    ctx->d_adapt_tab = (HuffWide *)((char *)ctx->d_adapt_stats + a);
+    ctx->d_adapt_err = (uint32_t *)((char *)ctx->d_adapt_stats + a + b);
+    rc = ctx->d_adapt_work.grow(ctx, adaptive_work_bytes(n));
     if (rc) return rc;
     AdaptStats *st = ctx->d_adapt_stats;
     HIPCHK(ctx, hipMemsetAsync(st, 0, sizeof(AdaptStats), ctx->stream));
@@ -4918,7 +4828,7 @@ static int adaptive_encode_dev(tic_ctx *ctx, size_t n, int h, int w, int quality
         *out_len = bytes;
         return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", bytes, cap);
     }
-    rc = grow_dev(ctx, "d_adapt_out", ctx->d_adapt_out, ctx->adapt_out_bytes, words * 4);
+    rc = ctx->d_adapt_out.grow(ctx, words * 4);
     if (rc) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_adapt_out, 0, words * 4, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_adapt_out, head.data(), (size_t)((base + 7) / 8), hipMemcpyHostToDevice, ctx->stream));
@@ -5010,8 +4920,8 @@ static AdaptSlotView adapt_view(const Slot &s, size_t count, size_t nblk, size_t
 static int ensure_adapt_slots(tic_ctx *ctx, const MixedPlan &p) {
     const AdaptSlotLayout l = adaptive_slot_layout((size_t)p.max_count, p.max_nblk, p.max_nblk / kAdaptGroupBlocks + (size_t)p.max_count);
     for (auto &sl : ctx->bslots) {
-        int rc = grow_dev(ctx, "bslot.d_adapt", sl.d_adapt, sl.adapt_bytes, l.end);
-        if (rc == TIC_OK) rc = grow_pinned(ctx, "bslot.h_adapt", sl.h_adapt, sl.h_adapt_bytes, l.upload_end);
+        int rc = sl.d_adapt.grow(ctx, l.end);
+        if (rc == TIC_OK) rc = sl.h_adapt.grow(ctx, l.upload_end);
         if (rc) return rc;
     }
     return TIC_OK;
@@ -5071,10 +4981,8 @@ static int adaptive_pack_chunk(tic_ctx *ctx, const MixedPlan &p, Slot &s, hipStr
         maxlen = std::max(maxlen, (size_t)s.h_lens[k]);
     }
     // (nothing is in flight on this slot's buffers: its previous chunk was handed out before this one claimed it)
-    if (!s.streams_cap) s.streams_cap = ctx->bslot_cap.streams;
-    if (!s.pin_out_cap) s.pin_out_cap = ctx->bslot_cap.pin_out;
-    int rc = grow_dev(ctx, "bslot.d_streams", s.d_streams, s.streams_cap, stream_bytes, stream_bytes + stream_bytes / 4);
-    if (rc == TIC_OK) rc = grow_pinned(ctx, "bslot.pin_out", s.pin_out, s.pin_out_cap, landing, landing + landing / 4);
+    int rc = s.d_streams.grow(ctx, stream_bytes, stream_bytes + stream_bytes / 4);
+    if (rc == TIC_OK) rc = s.pin_out.grow(ctx, landing, landing + landing / 4);
     if (rc) return rc;
     *v.h_err = 0u;
     hipError_t e = stream_bytes ? hipMemsetAsync(s.d_streams, 0, stream_bytes, st) : hipSuccess;
@@ -5111,7 +5019,7 @@ static int batch_adaptive_pipeline(tic_ctx *ctx, const MixedPlan &p, AdaptCall &
             size_t nblk, ngroups;
             if (!adaptive_chunk_table(p, c, &t, &nblk, &ngroups)) return set_err(ctx, TIC_E_ARG, "adaptive batch: chunk %d has no table", ci);
             const AdaptSlotView v = adapt_view(s, (size_t)c.count, nblk, ngroups);
-            if (v.l.end > s.adapt_bytes || v.l.upload_end > s.h_adapt_bytes) return set_err(ctx, TIC_E_HIP, "adaptive batch: slot buffers too small for chunk %d", ci);
+            if (v.l.end > s.d_adapt.cap || v.l.upload_end > s.h_adapt.cap) return set_err(ctx, TIC_E_HIP, "adaptive batch: slot buffers too small for chunk %d", ci);
             *v.h_frames = t;
             return enqueue_on_slot(
                 ctx, s, stream, c.first, c.count,
@@ -5236,22 +5144,18 @@ static int adaptive_decode_on_device(tic_ctx *ctx, const uint8_t *data, size_t l
     const bool in_place = src_on_device && ((uintptr_t)data & 3u) == 0;
     int rc = TIC_OK;
     if (!in_place) {
-        rc = grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, align_up(len, 4) + 16);
+        rc = ctx->d_stream_buf.grow(ctx, align_up(len, 4) + 16);
         if (rc) return rc;
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_stream_buf, data, len, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
     }
     const void *d_stream = in_place ? (const void *)data : (const void *)ctx->d_stream_buf;
-    if (!ctx->d_adec_tab) { // tables and status words in one allocation
-        char *p = nullptr;
-        const size_t a = align_up(sizeof(AdaptDecTab), 256);
-        HIPCHK(ctx, hipMalloc((void **)&p, a + align_up(sizeof(AdaptDecStatus), 256)));
-        ctx->d_adec_tab = (AdaptDecTab *)p;
-        ctx->d_adec_status = (AdaptDecStatus *)(p + a);
-        HIPCHK(ctx, buf_add(ctx, p, a + align_up(sizeof(AdaptDecStatus), 256), kBufDev, kBufScratch, "d_adec_tab")); // (the table is uploaded per call)
-    }
+    const size_t tab_bytes = align_up(sizeof(AdaptDecTab), 256);
+    rc = ctx->d_adec_tab.grow(ctx, tab_bytes + align_up(sizeof(AdaptDecStatus), 256)); // tables (uploaded per call) and status words in one allocation
+    if (rc) return rc;
+    ctx->d_adec_status = (AdaptDecStatus *)((char *)ctx->d_adec_tab + tab_bytes);
     const int range = adaptive_dec_range_bits(len, t.payload_bit, n);
     const size_t wb = adaptive_dec_work_bytes(len, t.payload_bit, n, range);
-    rc = grow_dev(ctx, "d_adec_work", ctx->d_adec_work, ctx->adec_work_bytes, wb, wb + wb / 8); // (room for a longer stream of the same geometry)
+    rc = ctx->d_adec_work.grow(ctx, wb, wb + wb / 8); // (room for a longer stream of the same geometry)
     if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_adec_tab, &ctx->adec_tab, sizeof ctx->adec_tab, hipMemcpyHostToDevice, ctx->stream));
     // Three launches of the stitch settle nearly every stream (the last one only proves it), so the passes behind them are launched
@@ -5333,7 +5237,7 @@ static int adaptive_read_coefs(tic_ctx *ctx, const uint8_t *data, size_t len, bo
     } else if (!src_on_device) {
         head = data;
     }
-    rc = grow_pinned(ctx, "h_zz", ctx->h_zz, ctx->h_zz_bytes, n * 128); // (the landing buffer of decode_on_host)
+    rc = ctx->h_zz.grow(ctx, n * 128); // (the landing buffer of decode_on_host)
     if (rc) return rc;
     const char *why = "";
     rc = adaptive_decode(head, len, h, w, ctx->h_zz, &why);
@@ -5405,7 +5309,7 @@ static int read_default_coefs(tic_ctx *ctx, const uint8_t *data, size_t len, boo
         HIPCHK(ctx, hipMemcpy(host.data(), data, len, hipMemcpyDeviceToHost));
         data = host.data();
     }
-    rc = grow_pinned(ctx, "h_zz", ctx->h_zz, ctx->h_zz_bytes, n * 128);
+    rc = ctx->h_zz.grow(ctx, n * 128);
     if (rc) return rc;
     std::vector<DcWide> wide;
     entropy_decode(data, len, sh.h, sh.w, ctx->h_zz, &wide);
@@ -5491,8 +5395,8 @@ int tic_entropy_decode_dev_timed(tic_ctx *ctx, const void *d_stream, size_t len,
     const int range_bits = decode_range_bits(len, n);
     rc = timed_launches(ctx, warm, iters, ms_total, nullptr, [&](int, hipEvent_t, hipEvent_t) {
         if (ws.begin(ctx, ctx->stream, 1)) return hipErrorUnknown; // (a new epoch per run; the status words are the last run's when the stream has drained)
-        return entropy_decode_coef_gpu(d_stream, len, n, ctx->d_dec_luts, ws.work, ws.work_bytes, ws.desc, ws.desc_words, ws.epoch, head,
-                                       (int16_t *)d_coeffs_zz, ws.d_status, range_bits, 0, ctx->stream);
+        return entropy_decode_coef_gpu(d_stream, len, n, ctx->d_dec_luts, ws.work, ws.work.cap, ws.desc, ws.desc_words, ws.epoch, head,
+                                       (int16_t *)d_coeffs_zz, ws.h_status.d, range_bits, 0, ctx->stream);
     });
     if (rc) return rc;
     DecStatus st;
@@ -5569,10 +5473,10 @@ int tic_retable_default(tic_ctx *ctx, const uint8_t *data, size_t len, uint8_t *
     if (n == 0) return entropy_encode(nullptr, h, w, q, out, cap, out_len); // the header alone (codec.py:151)
     if (in_h_zz) HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, ctx->h_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
     // the default device entropy stage on the context's workspace; the input stream's copy in d_stream_buf (if the device reader made one) is done with
-    rc = grow_dev(ctx, "d_stream_buf", ctx->d_stream_buf, ctx->d_stream_cap, compress_bound(h, w));
+    rc = ctx->d_stream_buf.grow(ctx, compress_bound(h, w));
     if (rc) return rc;
     size_t packed = 0;
-    rc = entropy_encode_dev_impl(ctx, ctx->d_coef, h, w, q, ctx->d_stream_buf, ctx->d_stream_cap, &packed, false);
+    rc = entropy_encode_dev_impl(ctx, ctx->d_coef, h, w, q, ctx->d_stream_buf, ctx->d_stream_buf.cap, &packed, false);
     if (rc) return rc;
     if (packed > cap) {
         *out_len = packed;
@@ -5618,9 +5522,9 @@ static int adbatch_decode(tic_ctx *ctx, const DecBatchIO &io, const AdaptDecPlan
     const AdaptDecWorkLayout wl(c);
     int rc = dbatch_grow(ctx, up.up_bytes, c.pix_bytes);
     if (rc) return rc;
-    rc = grow_dev(ctx, "adbat.d_work", A.d_work, A.work_cap, wl.bytes, wl.bytes + wl.bytes / 4);
+    rc = A.d_work.grow(ctx, wl.bytes, wl.bytes + wl.bytes / 4);
     if (rc) return rc;
-    rc = grow_pinned(ctx, "adbat.h_status", A.h_status, A.status_cap, wl.status_bytes, 2 * wl.status_bytes);
+    rc = A.h_status.grow(ctx, wl.status_bytes, 2 * wl.status_bytes);
     if (rc) return rc;
     BT_START();
     AdaptDecFrame *hf = (AdaptDecFrame *)(B.h_in + up.o_frames);
@@ -5854,17 +5758,17 @@ struct AdaptStatsLaunch {
 static int prepare_adaptive_stats(tic_ctx *ctx, const std::vector<AdaptStatsLaunch> &launches, const size_t *nblk, int np, int kernel, int max_groups,
                                   std::vector<size_t> &groups) {
     const size_t st_bytes = (size_t)np * sizeof(AdaptStats), st_alloc = align_up(st_bytes, 65536);
-    int rc = grow_dev(ctx, "d_arate_stats", ctx->d_arate_stats, ctx->arate_dev_bytes, st_bytes, st_alloc);
+    int rc = ctx->d_arate_stats.grow(ctx, st_bytes, st_alloc);
     if (rc) return rc;
-    rc = grow_pinned(ctx, "h_arate_stats", ctx->h_arate_stats, ctx->arate_host_bytes, st_bytes, st_alloc);
+    rc = ctx->h_arate_stats.grow(ctx, st_bytes, st_alloc);
     if (rc) return rc;
     const size_t nt = launches.size();
     groups.assign(nt, 0);
     if (kernel == 0) {
         const size_t tab_bytes = nt * sizeof(SizeProbeTable), tab_alloc = align_up(tab_bytes, 16384);
-        rc = grow_pinned(ctx, "h_rate_tabs", ctx->h_rate_tabs, ctx->rate_tabs_host_bytes, tab_bytes, tab_alloc);
+        rc = ctx->h_rate_tabs.grow(ctx, tab_bytes, tab_alloc);
         if (rc) return rc;
-        rc = grow_dev(ctx, "d_rate_tabs", ctx->d_rate_tabs, ctx->rate_tabs_dev_bytes, tab_bytes, tab_alloc);
+        rc = ctx->d_rate_tabs.grow(ctx, tab_bytes, tab_alloc);
         if (rc) return rc;
         for (size_t t = 0; t < nt; t++) {
             const AdaptStatsLaunch &l = launches[t];
@@ -5879,9 +5783,9 @@ static int prepare_adaptive_stats(tic_ctx *ctx, const std::vector<AdaptStatsLaun
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_rate_tabs, ctx->h_rate_tabs, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
     } else {
         const size_t tab_bytes = nt * sizeof(AdaptFrameTable), tab_alloc = align_up(tab_bytes, 16384);
-        rc = grow_pinned(ctx, "h_arate_frames", ctx->h_arate_frames, ctx->arate_frames_host_bytes, tab_bytes, tab_alloc);
+        rc = ctx->h_arate_frames.grow(ctx, tab_bytes, tab_alloc);
         if (rc) return rc;
-        rc = grow_dev(ctx, "d_arate_frames", ctx->d_arate_frames, ctx->arate_frames_dev_bytes, tab_bytes, tab_alloc);
+        rc = ctx->d_arate_frames.grow(ctx, tab_bytes, tab_alloc);
         if (rc) return rc;
         for (size_t t = 0; t < nt; t++) {
             size_t total = 0;
