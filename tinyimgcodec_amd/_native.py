@@ -360,6 +360,26 @@ TRANSCODE_SIGNATURES = {
     "tic_retable_default": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
+# ... and exactly the symbols include/tinyimgcodec_hip_transcode_batch.h declares: the batch forms of the calls above
+TRANSCODE_BATCH_SIGNATURES = {
+    "tic_entropy_decode_batch": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int),
+         C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_int)],
+    ),
+    "tic_retable_adaptive_batch": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+         C.POINTER(C.c_int)],
+    ),
+    "tic_retable_default_batch": (
+        C.c_int,
+        [_ctxp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+         C.POINTER(C.c_int)],
+    ),
+    "tic_last_transcode_batch": (C.c_int, [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+}
+
 _lib = None
 _lock = threading.RLock()  # re-entrant: default_context() creates a Context (which calls load()) under it
 
@@ -379,7 +399,8 @@ def load():
                 L = C.CDLL(path)
             except OSError as e:  # missing ROCm runtime etc.
                 raise NativeUnavailable("cannot load %s: %s" % (path, e)) from e
-            for name, (res, args) in list(SIGNATURES.items()) + list(RATE_ADAPTIVE_SIGNATURES.items()) + list(TRANSCODE_SIGNATURES.items()):
+            for name, (res, args) in (list(SIGNATURES.items()) + list(RATE_ADAPTIVE_SIGNATURES.items()) + list(TRANSCODE_SIGNATURES.items())
+                                      + list(TRANSCODE_BATCH_SIGNATURES.items())):
                 fn = getattr(L, name)
                 fn.restype = res
                 fn.argtypes = args

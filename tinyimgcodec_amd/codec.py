@@ -1326,12 +1326,8 @@ def _retable(ctx, fn, buf, cap, missing_code):
             raise
 
 
-def retable_adaptive(data, ctx=None):
-    """A stored default-table stream rewritten with its image's own Huffman tables, losslessly: the reference's reader (codec.py:167-188)
-    followed by its writer with auto_generate_huffman_table=True (codec.py:133-164) on the same coefficients.  For a stream of
-    compress(image, q) the result is compress_adaptive(image, q), byte for byte.  ValueError for scaled_dct streams, refused headers and
-    a running DC outside int16; IndexError for a frame without blocks; OverflowError as compress_adaptive."""
-    buf = _as_bytes_view(data)
+def _retable_adaptive_header(buf):
+    """retable_adaptive()'s checks that need no device, with its exceptions (the single call and the batch call share them)"""
     hdr = parse_header(buf)
     if hdr["flag"] & (1 << 31):
         raise ValueError("stream carries an embedded Huffman table already (little-endian flag bit 31)")
@@ -1341,9 +1337,19 @@ def retable_adaptive(data, ctx=None):
         raise ValueError("negative image size in the header")
     if not 1 <= hdr["quality"] <= 99:
         raise ValueError("quality %d in the header outside 1..99" % hdr["quality"])
-    L = N.load()
-    if L.tic_num_blocks(hdr["height"], hdr["width"]) == 0:
+    if N.load().tic_num_blocks(hdr["height"], hdr["width"]) == 0:
         raise IndexError("index -1 is out of bounds for axis 0 with size 0")  # calc_huffman_table on an empty symbol list
+    return hdr
+
+
+def retable_adaptive(data, ctx=None):
+    """A stored default-table stream rewritten with its image's own Huffman tables, losslessly: the reference's reader (codec.py:167-188)
+    followed by its writer with auto_generate_huffman_table=True (codec.py:133-164) on the same coefficients.  For a stream of
+    compress(image, q) the result is compress_adaptive(image, q), byte for byte.  ValueError for scaled_dct streams, refused headers and
+    a running DC outside int16; IndexError for a frame without blocks; OverflowError as compress_adaptive."""
+    buf = _as_bytes_view(data)
+    hdr = _retable_adaptive_header(buf)
+    L = N.load()
     ctx = _ctx(ctx)
     return _retable(ctx, L.tic_retable_adaptive, buf, L.tic_compress_bound(hdr["height"], hdr["width"]) + 4096, False)
 
@@ -1358,6 +1364,150 @@ def retable_default(data, ctx=None):
     # (the default stream is the longer one as a rule, by a few per cent at most qualities: one retry with the reported length otherwise)
     cap = min(L.tic_compress_bound(hdr["height"], hdr["width"]), buf.size + buf.size // 2 + 4096)
     return _retable(ctx, L.tic_retable_default, buf, cap, True)
+
+
+def _frame_exception(i, e):
+    """The exception a single call raised for frame i of a batch: the same class, the message naming the frame."""
+    if isinstance(e, N.NativeError):
+        msg = str(e).split(": ", 1)[-1]
+        return N.NativeError(e.code, "frame %d: %s" % (i, msg))
+    try:
+        return type(e)("frame %d: %s" % (i, e.args[0] if e.args else ""))
+    except Exception:  # noqa: BLE001 - a class with another constructor: the original object
+        return e
+
+
+def _check_errors_arg(errors):
+    if errors not in ("raise", "return"):
+        raise ValueError("errors must be 'raise' or 'return', not %r" % (errors,))
+
+
+def _transcode_batch(streams, ctx, errors, precheck, call, single):
+    """The common part of the batch transcoders.  precheck(i, buf): the single call's checks that need no device (raises as it does), returns what
+    call() needs of the frame; call(ctx, L, idx, bufs, pre) -> (results, rcs) runs the C-ABI batch call on the frames that passed; a frame
+    whose code is not TIC_OK goes through single(data) once more, which raises the single call's own exception.
+    (Such a frame is read up to three times - by the batch kernels, by the library's single call behind them, by single() here for the
+    exception's class and wording: nothing for the odd bad stream of an archive, a real cost for an archive of damaged streams.)"""
+    _check_errors_arg(errors)
+    streams = list(streams)
+    out = [None] * len(streams)
+    bufs, pre, idx = [], [], []
+    for i, s in enumerate(streams):
+        try:
+            b = _as_bytes_view(s)
+            p = precheck(i, b)
+        except Exception as e:  # noqa: BLE001 - whatever the single call raises for this frame
+            out[i] = _frame_exception(i, e)
+            continue
+        bufs.append(b), pre.append(p), idx.append(i)
+    if idx:
+        L = N.load()
+        ctx = _ctx(ctx)
+        with ctx.lock:
+            results, rcs = call(ctx, L, bufs, pre)
+        for k, i in enumerate(idx):
+            if rcs[k] == N.TIC_OK:
+                out[i] = results[k]
+                continue
+            try:  # (rare: the single call words the error and picks the exception's class)
+                out[i] = single(streams[i], ctx)
+            except Exception as e:  # noqa: BLE001
+                out[i] = _frame_exception(i, e)
+    if errors == "raise":  # the lowest failing index, wherever its error was found
+        for r in out:
+            if isinstance(r, Exception):
+                raise r from None
+    return out
+
+
+def _ptr_array(arrays):
+    return (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+
+def entropy_decode_zz_batch(streams, ctx=None, errors="raise"):
+    """entropy_decode_zz() of many streams in one call: [(coefficients, header), ...], frame i exactly what entropy_decode_zz(streams[i]) gives.
+    The streams of a chunk (up to 64) share one upload, the device reader's two launches and one download; a stream the batch kernels do
+    not take goes through the single call.  errors="return": a failing frame's place holds its exception (the class the single call
+    raises, the message naming the frame) instead of the first one being raised."""
+
+    def precheck(i, buf):
+        hdr = _default_header(buf)
+        return hdr, N.load().tic_num_blocks(hdr["height"], hdr["width"])
+
+    def call(ctx, L, bufs, pre):
+        n = len(bufs)
+        zzs = [np.empty((nb, 64), dtype=np.int16) for _, nb in pre]
+        lens = (C.c_size_t * n)(*[b.size for b in bufs])
+        caps = (C.c_size_t * n)(*[nb for _, nb in pre])
+        rcs = (C.c_int * n)()
+        L.tic_entropy_decode_batch(ctx.handle, _ptr_array(bufs), lens, n, _ptr_array(zzs), caps, None, None, None, None, rcs)
+        return [(zzs[k], pre[k][0]) for k in range(n)], list(rcs)
+
+    return _transcode_batch(streams, ctx, errors, precheck, call, lambda s, c: entropy_decode_zz(s, ctx=c))
+
+
+def _retable_batch(streams, ctx, errors, precheck, fn_name, single):
+    def call(ctx, L, bufs, caps0):
+        n = len(bufs)
+        fn = getattr(L, fn_name)
+        results, rcs = [None] * n, [N.TIC_OK] * n
+        todo, caps = list(range(n)), list(caps0)
+        for _ in range(2):  # (once more, with the lengths the library reported, for the frames whose first guess was short)
+            m = len(todo)
+            outs = [np.empty(caps[k], dtype=np.uint8) for k in todo]
+            lens = (C.c_size_t * m)(*[bufs[k].size for k in todo])
+            ccaps = (C.c_size_t * m)(*[caps[k] for k in todo])
+            olens = (C.c_size_t * m)()
+            crcs = (C.c_int * m)()
+            fn(ctx.handle, _ptr_array([bufs[k] for k in todo]), lens, m, _ptr_array(outs), ccaps, olens, crcs)
+            again = []
+            for j, k in enumerate(todo):
+                rcs[k] = crcs[j]
+                if crcs[j] == N.TIC_OK:
+                    results[k] = outs[j][: olens[j]].tobytes()
+                elif crcs[j] == N.TIC_E_SPACE and olens[j] > caps[k]:
+                    caps[k] = olens[j]
+                    again.append(k)
+            todo = again
+            if not todo:
+                break
+        return results, rcs
+
+    return _transcode_batch(streams, ctx, errors, precheck, call, single)
+
+
+def retable_adaptive_batch(streams, ctx=None, errors="raise"):
+    """retable_adaptive() of many stored streams in one call: a list of streams, frame i byte for byte what retable_adaptive(streams[i])
+    gives.  The coefficients of a chunk (up to 64 frames) stay on the GPU between the reader and the adaptive writer: one upload, the
+    reader's launches and one statistics launch, one read-back, the tables on the host, the packing launches, one download.
+    errors="return": a failing frame's place holds its exception instead of the first one being raised."""
+
+    def precheck(i, buf):
+        _retable_adaptive_header(buf)
+        return buf.size + 4096  # (the adaptive stream is the shorter one as a rule: once more with the reported length otherwise)
+
+    return _retable_batch(streams, ctx, errors, precheck, "tic_retable_adaptive_batch", lambda s, c: retable_adaptive(s, ctx=c))
+
+
+def retable_default_batch(streams, ctx=None, errors="raise"):
+    """retable_default() of many streams with embedded tables in one call, frame i byte for byte what retable_default(streams[i]) gives:
+    the adaptive batch reader, then the default writer's descriptor-form launches on the resident coefficients.  errors as above."""
+
+    def precheck(i, buf):
+        hdr = _adaptive_header(buf)
+        # (the default stream is the longer one, by 40 % at the lowest qualities: once more with the reported lengths otherwise)
+        return min(N.load().tic_compress_bound(hdr["height"], hdr["width"]), 2 * buf.size + 4096)
+
+    return _retable_batch(streams, ctx, errors, precheck, "tic_retable_default_batch", lambda s, c: retable_default(s, ctx=c))
+
+
+def last_transcode_batch(ctx=None):
+    """(batch_frames, single_frames, chunks) of the context's last batch transcoding call."""
+    ctx = _ctx(ctx)
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    with ctx.lock:
+        ctx.check(N.load().tic_last_transcode_batch(ctx.handle, C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
 
 
 def decode(data, ctx=None):

@@ -21,6 +21,7 @@
 #include "../../include/tinyimgcodec_hip.h"
 #include "../../include/tinyimgcodec_hip_adaptive_rate.h"
 #include "../../include/tinyimgcodec_hip_transcode.h"
+#include "../../include/tinyimgcodec_hip_transcode_batch.h"
 #include "tic_adaptive.h"
 #include "tic_adaptive_stats_gpu.h"
 #include "tic_decode_plan.h"
@@ -34,6 +35,7 @@
 #include "tic_rd_plan.h"
 #include "tic_scaled.h"
 #include "tic_size_gpu.h"
+#include "tic_transcode_plan.h"
 
 using namespace tic;
 
@@ -352,6 +354,7 @@ struct tic_ctx {
         PinBuf<char> h_status{"adbat.h_status"};
     } adbat;
     int last_adbatch_frames = 0, last_adbatch_single = 0, last_adbatch_chunks = 0, last_adbatch_direct = 0; // tic_last_decompress_batch_adaptive (_direct)
+    int last_tbatch_frames = 0, last_tbatch_single = 0, last_tbatch_chunks = 0;                             // tic_last_transcode_batch
     // rate control (tic_stream_sizes_dev, tic_compress_to_size_dev): the size kernel's table, a result per probe on the device and its
     // pinned landing buffer, and what the last search did
     DevBuf<SizeTabDev> d_size_tab{"d_size_tab", kBufState};
@@ -4334,7 +4337,10 @@ static int dbatch_grow(tic_ctx *ctx, size_t up_bytes, size_t pix_bytes) {
 // Descriptors, buffers, ONE upload - descriptors, the frame of every measure wave, the frame of every fused workgroup, the streams - and the two
 // launches.  *refused: the launcher's host-side checks said no (every one of them comes before its first launch): nothing runs, and the stream
 // has drained - the upload still read the pinned buffer the next chunk is packed into.
-static int dbatch_enqueue(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame *pf, const DecPlanChunk &c, bool *refused) {
+// The SINK: d_coef == nullptr pixels into ctx->dbat.d_pix, as described - else (the batch transcoders) the chunk's coefficient rows to d_coef, c.blocks
+// of them, frame k's from row pf[k].blk0 on: the same descriptors with the header alone in DecFrame::idct, no pixel buffer, the batch form of the
+// coefficient sink behind the same measure launch; nothing is waited for, and tic_last_decompress_batch_work does not hear of it (TBatchCall keeps the phase times).
+static int dbatch_enqueue(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame *pf, const DecPlanChunk &c, bool *refused, int16_t *d_coef = nullptr) {
     tic_ctx::DecBatch &B = ctx->dbat;
     const uint32_t F = (uint32_t)c.count;
     std::vector<DecFrame> frames(F);
@@ -4349,18 +4355,23 @@ static int dbatch_enqueue(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame
         d.blk0 = f.blk0, d.nblocks = (uint32_t)f.nblk;
         d.wg0 = wgs, d.nwgs = entropy_decode_batch_wgs(f.nblk);
         d.pad_ = 0;
-        d.idct = dec_idct_args(ctx, f.h, f.w, f.quality, -1, nullptr /* set below, when the pixel buffer exists */, (long)f.pitch, io.streams[f.index]);
+        if (d_coef) {
+            memset(&d.idct, 0, sizeof d.idct);
+            memcpy(d.idct.head, io.streams[f.index], 16); // (the sink stores a frame's rows only under the header its geometry came from)
+        } else {
+            d.idct = dec_idct_args(ctx, f.h, f.w, f.quality, -1, nullptr /* set below, when the pixel buffer exists */, (long)f.pitch, io.streams[f.index]);
+        }
         tiles += d.ntiles, wgs += d.nwgs;
     }
     const DecUploadLayout up(F, tiles, wgs, c.words);
     int rc;
-    rc = dbatch_grow(ctx, up.up_bytes, c.pix_bytes);
+    rc = dbatch_grow(ctx, up.up_bytes, d_coef ? 0 : c.pix_bytes);
     if (rc) return rc;
     const size_t wb = dec_work_provision_bytes(F, c.ranges288, c.blocks);
     rc = B.ws.grow(ctx, wb, wb + wb / 4, 4 * (size_t)((tiles > wgs ? tiles : wgs) + 2), F, F < 256 ? 256 : 2 * (size_t)F);
     if (rc) return rc;
     BT_START();
-    for (uint32_t k = 0; k < F; k++) frames[k].idct.out = B.d_pix + pf[k].pix_off;
+    for (uint32_t k = 0; k < F && !d_coef; k++) frames[k].idct.out = B.d_pix + pf[k].pix_off;
     memcpy(B.h_in + up.o_frames, frames.data(), F * sizeof(DecFrame));
     uint32_t *tf = (uint32_t *)(B.h_in + up.o_tiles), *wf = (uint32_t *)(B.h_in + up.o_wgs);
     for (uint32_t k = 0; k < F; k++) {
@@ -4375,13 +4386,19 @@ static int dbatch_enqueue(tic_ctx *ctx, const DecBatchIO &io, const DecPlanFrame
     BT_START();
     size_t work_held = B.ws.work.cap;
     if (const char *e = test_hook("TIC_DBATCH_WORK_CAP")) work_held = (size_t)atoll(e) < work_held ? (size_t)atoll(e) : work_held; // (tests: a launcher that refuses)
-    ctx->last_dbatch_range = c.range_bits;
-    ctx->last_dbatch_work_used = dec_work_carve_bytes(F, c.ranges, c.blocks, c.range_bits);
-    ctx->last_dbatch_work_held = work_held;
+    if (!d_coef) {
+        ctx->last_dbatch_range = c.range_bits;
+        ctx->last_dbatch_work_used = dec_work_carve_bytes(F, c.ranges, c.blocks, c.range_bits);
+        ctx->last_dbatch_work_held = work_held;
+    }
     HIPCHK(ctx, hipMemcpyAsync(B.d_in, B.h_in, up.up_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const hipError_t le = entropy_decode_idct_gpu_batch(B.d_in + up.o_streams, (const DecFrame *)(B.d_in + up.o_frames), (const uint32_t *)(B.d_in + up.o_tiles),
-                                                        (const uint32_t *)(B.d_in + up.o_wgs), F, tiles, wgs, c.ranges, c.blocks, c.small_win, ctx->d_dec_luts, B.ws.work, work_held,
-                                                        B.ws.desc, B.ws.desc_words, B.ws.epoch, B.ws.h_status.d, c.range_bits, ctx->stream);
+    const hipError_t le =
+        d_coef ? entropy_decode_coef_gpu_batch(B.d_in + up.o_streams, (const DecFrame *)(B.d_in + up.o_frames), (const uint32_t *)(B.d_in + up.o_tiles),
+                                               (const uint32_t *)(B.d_in + up.o_wgs), F, tiles, wgs, c.ranges, c.blocks, c.small_win, ctx->d_dec_luts, B.ws.work, work_held, B.ws.desc,
+                                               B.ws.desc_words, B.ws.epoch, B.ws.h_status.d, c.range_bits, d_coef, ctx->stream)
+               : entropy_decode_idct_gpu_batch(B.d_in + up.o_streams, (const DecFrame *)(B.d_in + up.o_frames), (const uint32_t *)(B.d_in + up.o_tiles),
+                                               (const uint32_t *)(B.d_in + up.o_wgs), F, tiles, wgs, c.ranges, c.blocks, c.small_win, ctx->d_dec_luts, B.ws.work, work_held, B.ws.desc,
+                                               B.ws.desc_words, B.ws.epoch, B.ws.h_status.d, c.range_bits, ctx->stream);
     if (le == hipErrorInvalidValue) {
         (void)hipGetLastError();
         *refused = true;
@@ -5508,19 +5525,22 @@ static bool adaptive_batch_takes(size_t nblocks, const uint8_t *data, size_t len
 
 // A chunk through the kernels: buffers, ONE upload, the rounds protocol (tic_adaptive_dec_gpu.hip header comment), the pixels in ctx->dbat.d_pix.
 // good[k]: frame k is complete there.  Every way out with an error lies in front of `good`.
-static int adbatch_decode(tic_ctx *ctx, const DecBatchIO &io, const AdaptDecPlanFrame *pf, const AdaptDecPlanChunk &c, const AdaptTable *tabs, std::vector<char> *good) {
+// pixels = false (tic_retable_default_batch): the reader stage alone - no inverse transform is set up or launched, the chunk's coefficients stay at
+// ctx->adbat.d_work + AdaptDecWorkLayout(c).o_coef, frame k's rows from row pf[k].d.blk0 on.
+static int adbatch_decode(tic_ctx *ctx, const DecBatchIO &io, const AdaptDecPlanFrame *pf, const AdaptDecPlanChunk &c, const AdaptTable *tabs, std::vector<char> *good,
+                          bool pixels = true) {
     tic_ctx::DecBatch &B = ctx->dbat;
     tic_ctx::AdaptDecBatchBuf &A = ctx->adbat;
     const uint32_t F = (uint32_t)c.count;
     size_t iwgs = 0;
     std::vector<IdctArgs> ia(F);
-    for (uint32_t k = 0; k < F; k++) {
+    for (uint32_t k = 0; k < F && pixels; k++) {
         ia[k] = idct_args(dec_idct_args(ctx, pf[k].h, pf[k].w, pf[k].quality, -1, nullptr, (long)pf[k].pitch, nullptr), nullptr);
         iwgs += (size_t)idct_batch_wgs(ia[k].ntiles);
     }
     const AdaptDecUploadLayout up(c, sizeof(IdctArgs), iwgs);
     const AdaptDecWorkLayout wl(c);
-    int rc = dbatch_grow(ctx, up.up_bytes, c.pix_bytes);
+    int rc = dbatch_grow(ctx, up.up_bytes, pixels ? c.pix_bytes : 0);
     if (rc) return rc;
     rc = A.d_work.grow(ctx, wl.bytes, wl.bytes + wl.bytes / 4);
     if (rc) return rc;
@@ -5535,10 +5555,12 @@ static int adbatch_decode(tic_ctx *ctx, const DecBatchIO &io, const AdaptDecPlan
     for (uint32_t k = 0; k < F; k++) {
         const AdaptDecPlanFrame &f = pf[k];
         hf[k] = f.d;
-        ia[k].coeffs = (const int16_t *)(A.d_work + wl.o_coef) + (size_t)f.d.blk0 * 64;
-        ia[k].out = B.d_pix + f.pix_off;
-        memcpy(&hia[k], &ia[k], sizeof(IdctArgs));
-        for (int t = 0; t < ia[k].ntiles; t += idct_batch_tiles_per_wg()) hiw[g++] = make_uint2(k, (uint32_t)t);
+        if (pixels) {
+            ia[k].coeffs = (const int16_t *)(A.d_work + wl.o_coef) + (size_t)f.d.blk0 * 64;
+            ia[k].out = B.d_pix + f.pix_off;
+            memcpy(&hia[k], &ia[k], sizeof(IdctArgs));
+            for (int t = 0; t < ia[k].ntiles; t += idct_batch_tiles_per_wg()) hiw[g++] = make_uint2(k, (uint32_t)t);
+        }
         if (!adaptive_dec_tab_build(tabs[k], (AdaptDecTab *)(B.h_in + up.o_tabs + f.tab_off))) return set_err(ctx, TIC_E_ARG, "frame %d: no look-up table for a table that parsed", f.index);
         memcpy(B.h_in + up.o_streams + (size_t)f.d.word0 * 4, io.streams[f.index], f.len); // (the bytes behind a stream's last word are never read)
     }
@@ -5559,7 +5581,7 @@ static int adbatch_decode(tic_ctx *ctx, const DecBatchIO &io, const AdaptDecPlan
     const AdaptDecFrameStatus *fs = (const AdaptDecFrameStatus *)(cs + 1);
     const auto run = [&](int round0, int nrounds, bool finish) -> int {
         HIPCHK(ctx, adaptive_decode_gpu_batch(a, round0, nrounds, finish, ctx->stream));
-        if (finish) HIPCHK(ctx, launch_idct_batch((const IdctArgs *)(B.d_in + up.o_idct_args), (const uint2 *)(B.d_in + up.o_idct_wgs), iwgs, ctx->stream));
+        if (finish && pixels) HIPCHK(ctx, launch_idct_batch((const IdctArgs *)(B.d_in + up.o_idct_args), (const uint2 *)(B.d_in + up.o_idct_wgs), iwgs, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(A.h_status, a.cs, wl.status_bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         if (test_hook("TIC_DECODE_TRACE")) {
@@ -5728,6 +5750,405 @@ int tic_decompress_adaptive_dev(tic_ctx *ctx, const void *d_stream, size_t len, 
         if (!d_out || (size_t)(h - 1) * (size_t)out_stride + (size_t)w > out_cap) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
     }
     return decompress_adaptive_impl(ctx, (const uint8_t *)d_stream, len, true, head, head_len, h, w, q, (uint8_t *)d_out, true, (size_t)out_stride);
+}
+
+// ---- batch transcoding (tinyimgcodec_hip_transcode_batch.h): tic_entropy_decode / tic_retable_adaptive / tic_retable_default of MANY streams ------
+// A single transcoding call of a small stream is per-call cost and little else (profiles/transcode.txt: 0.21-0.24 ms for a 512^2 stream whose reader
+// kernel takes 12.5 us).  The frames of a chunk (tic_transcode_plan.h: up to kEntropyMaxFrames of them) share ONE upload, one launch per kernel of the
+// reader's descriptor form, one launch per kernel of the writer's, and one download; their coefficients lie back to back in one device buffer, frame
+// k's rows from row blk0 on, and never leave the device between the reader and the writer.
+// Frame i's result is the single call's.  The batch kernels finish a frame or they do not: a frame they do not take, give up on or flag is not
+// written at all here and goes through the single call behind the chunks, which alone words errors - so do the frames of a chunk that fails on the
+// way (an allocation, a copy, a launch).  The calls leave tic_last_decode_* as they found them.
+extern "C++" {
+struct TBatchCall {
+    tic_ctx *ctx;
+    int n;
+    std::vector<int> rc;     // per frame: the code so far
+    std::vector<char> done;  // per frame: finished (by the batch kernels, or refused for space from their figures)
+    std::vector<std::pair<int, std::string>> errs; // failing frames and their messages
+    int saved[4];
+    BatchTrace saved_bt; // (the readers' stages time their phases: tic_last_batch_phases keeps the last batch call's)
+    TBatchCall(tic_ctx *c, int frames) : ctx(c), n(frames), rc((size_t)frames, TIC_OK), done((size_t)frames, 0) {
+        saved[0] = c->last_decode_path, saved[1] = c->last_decode_giveup, saved[2] = c->last_decode_range, saved[3] = c->last_decode_tries;
+        saved_bt = c->bt;
+        c->last_tbatch_frames = c->last_tbatch_single = c->last_tbatch_chunks = 0;
+    }
+    void finished(int i) { done[(size_t)i] = 1, ctx->last_tbatch_frames++; }
+    void failed(int i, int code, const std::string &msg) { done[(size_t)i] = 1, rc[(size_t)i] = code, errs.emplace_back(i, msg), ctx->last_tbatch_frames++; } // (refused from the kernels' own figures)
+    // The frames the chunks left, through `single(i)` in ascending order; then the call's result: the code and message of the lowest failing index.
+    template <class Single> int end(Single single, int *rcs) {
+        for (int i = 0; i < n; i++) {
+            if (done[(size_t)i]) continue;
+            const int r = single(i);
+            ctx->last_tbatch_single++;
+            rc[(size_t)i] = r;
+            if (r != TIC_OK) errs.emplace_back(i, ctx->err);
+        }
+        ctx->last_decode_path = saved[0], ctx->last_decode_giveup = saved[1], ctx->last_decode_range = saved[2], ctx->last_decode_tries = saved[3];
+        ctx->bt = saved_bt;
+        if (rcs) memcpy(rcs, rc.data(), (size_t)n * sizeof(int));
+        if (errs.empty()) return TIC_OK;
+        const auto first = std::min_element(errs.begin(), errs.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+        return set_err(ctx, rc[(size_t)first->first], "frame %d: %s", first->first, first->second.c_str());
+    }
+};
+}
+
+static TranscodeLimits tbatch_limits() {
+    TranscodeLimits lim = transcode_default_limits();
+    if (const char *e = test_hook("TIC_TBATCH_CHUNK")) lim.frames = atoi(e) >= 1 && atoi(e) <= kEntropyMaxFrames ? atoi(e) : lim.frames; // (tests: several chunks)
+    return lim;
+}
+
+// Which frames the default-table reader's batch kernels take: a header tic_entropy_decode accepts (`scaled_ok`: or a scaled_dct one), blocks, the
+// device decoder's size rule, no host-decoder hook.  Silent: the single call words what is wrong with a frame.
+static bool tbatch_default_takes(const uint8_t *data, size_t len, bool scaled_ok, DecPlanIn *in, uint32_t *flag_out) {
+    int h = 0, w = 0, q = 0;
+    uint32_t flag = 0;
+    if (!data || parse_header(data, len, &h, &w, &q, &flag) != TIC_OK || (flag & (1u << 31)) || h < 0 || w < 0) return false;
+    const bool scaled = (flag & kFlagScaled) != 0;
+    if (scaled ? (!scaled_ok || q < 0 || q > 62) : (q < 1 || q > 99)) return false;
+    const size_t nb = num_blocks(h, w);
+    *in = {h, w, q, len, nb != 0 && device_decoder_takes(nb, len) && !test_hook("TIC_DECODE_HOST") && !test_hook("TIC_DECODE_SERIAL")};
+    *flag_out = scaled ? kFlagScaled : 0u;
+    return in->takes;
+}
+
+// The default-table reader's stage of a chunk: dbatch_enqueue with the coefficient sink - descriptors, buffers, ONE upload and the two launches (the
+// unchanged measure / stitch kernel, the batch form of the coefficient sink), queued on the context's stream; nothing is waited for.  The chunk's
+// rows go to d_coef (c.blocks of them); frame k's status lands in ctx->dbat.ws.h_status[k] when the stream has drained.  *refused: the launcher's
+// host-side checks said no, nothing runs.
+static int tbatch_read_default(tic_ctx *ctx, const uint8_t *const *streams, const DecPlanFrame *pf, const DecPlanChunk &c, int16_t *d_coef, bool *refused) {
+    const DecBatchIO io = {streams, nullptr, nullptr, nullptr};
+    return dbatch_enqueue(ctx, io, pf, c, refused, d_coef);
+}
+
+static const char *const kTBatchShort = "output buffer too small (%zu bytes needed, %zu given)"; // (the single calls' wording)
+static std::string tbatch_short_msg(size_t need, size_t cap) {
+    char buf[128];
+    snprintf(buf, sizeof buf, kTBatchShort, need, cap);
+    return buf;
+}
+
+int tic_entropy_decode_batch(tic_ctx *ctx, const uint8_t *const *streams, const size_t *lens, int n, int16_t *const *coeffs, const size_t *cap_blocks,
+                             int *hs, int *ws, int *qualities, uint32_t *flags, int *rcs) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (n < 0 || (n > 0 && (!streams || !lens || !coeffs || !cap_blocks))) return set_err(ctx, TIC_E_ARG, "bad batch arguments");
+    TBatchCall call(ctx, n);
+    if (n == 0) return TIC_OK;
+    const auto single = [&](int i) {
+        return tic_entropy_decode(ctx, streams[i], lens[i], coeffs[i], cap_blocks[i], hs ? hs + i : nullptr, ws ? ws + i : nullptr, qualities ? qualities + i : nullptr,
+                                  flags ? flags + i : nullptr);
+    };
+    if (n == 1) return call.end(single, rcs);
+    std::vector<DecPlanIn> in((size_t)n);
+    std::vector<uint32_t> flag((size_t)n, 0u);
+    for (int i = 0; i < n; i++) {
+        in[(size_t)i] = DecPlanIn{0, 0, 0, 0, false};
+        if (tbatch_default_takes(streams[i], lens[i], true, &in[(size_t)i], &flag[(size_t)i]))
+            in[(size_t)i].takes = coeffs[i] && cap_blocks[i] >= num_blocks(in[(size_t)i].h, in[(size_t)i].w); // (else: the single call's TIC_E_SPACE)
+    }
+    // (a failure in front of the chunks leaves every frame to the single call, as a failure inside one does: only the arguments fail the whole call)
+    int rc = hipSetDevice(ctx->device) == hipSuccess ? ensure_dec_tables(ctx) : TIC_E_HIP;
+    const DecPlan plan = rc == TIC_OK ? plan_transcode_default_reader(in.data(), n, tbatch_limits()) : DecPlan();
+    for (const DecPlanChunk &c : plan.chunks) {
+        const DecPlanFrame *pf = &plan.frames[(size_t)c.first];
+        // coefficients: the context's scratch on the device, the host decoder's pinned landing buffer for the ONE download
+        if ((rc = ensure_scratch(ctx, 0, c.blocks * 128)) || (rc = ctx->h_zz.grow(ctx, c.blocks * 128))) break;
+        bool refused = false;
+        if ((rc = tbatch_read_default(ctx, streams, pf, c, (int16_t *)ctx->d_coef.p, &refused))) break;
+        if (refused) continue;
+        if (hipMemcpyAsync(ctx->h_zz, ctx->d_coef, c.blocks * 128, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            break;
+        }
+        ctx->last_tbatch_chunks++;
+        for (int k = 0; k < c.count; k++) {
+            const DecPlanFrame &f = pf[k];
+            if (!dec_status_complete(ctx->dbat.ws.h_status[k], streams[f.index], f.nblk)) continue;
+            memcpy(coeffs[f.index], ctx->h_zz + (size_t)f.blk0 * 64, f.nblk * 128);
+            if (hs) hs[f.index] = f.h;
+            if (ws) ws[f.index] = f.w;
+            if (qualities) qualities[f.index] = f.quality;
+            if (flags) flags[f.index] = flag[(size_t)f.index];
+            call.finished(f.index);
+        }
+    }
+    return call.end(single, rcs);
+}
+
+// The adaptive writer's stage of a chunk whose coefficients are resident at d_coef (rows as the reader's plan says) and whose statistics launch has
+// run on all its frames with slot table `v` (tf[k].skip: the reader did not complete frame k - its statistics are not looked at, it is not packed):
+// tables on the host, ONE upload, bits / scan / write, ONE download of the streams.  A frame whose stream does not fit caps[] gets TIC_E_SPACE and
+// the needed length; a frame the table build refuses is left to the single call.
+static int tbatch_write_adaptive(tic_ctx *ctx, TBatchCall &call, Slot &s, const AdaptSlotView &v, TranscodeFrame *tf, int count, size_t ngroups, const int16_t *d_coef,
+                                 uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
+    unsigned long long total_bits[kEntropyMaxFrames];
+    uint32_t base_bits[kEntropyMaxFrames];
+    bool any = false;
+    for (int k = 0; k < count; k++) {
+        total_bits[k] = 0ull, base_bits[k] = 0u, s.h_lens[k] = 0ull;
+        if (tf[k].skip) continue;
+        const AdaptStats &hs = v.h_stats[k];
+        uint8_t *head = v.h_heads + (size_t)k * kAdaptHeadStride;
+        memset(head, 0, kAdaptHeadStride);
+        write_header(head, tf[k].h, tf[k].w, tf[k].quality);
+        head[12] = 0x80; // write_uint(1 << 31, 32): most significant bit first (codec.py:111)
+        unsigned long long dc_code[16], ac_code[256];
+        uint8_t dc_len[16], ac_len[256];
+        size_t tbits = 0;
+        if (hs.err || huffman_table_build(hs.count + kAdaptDcBin, hs.first + kAdaptDcBin, hs.count, hs.first, dc_code, dc_len, ac_code, ac_len, head + 16,
+                                          kAdaptMaxTableBytes, &tbits) != TIC_OK) {
+            tf[k].skip = true; // (the single call words it)
+            continue;
+        }
+        HuffWide &tab = v.h_tabs[k];
+        for (int i = 0; i < kAdaptBins; i++) {
+            const bool dc = i >= kAdaptDcBin;
+            tab.code[i] = dc ? dc_code[i - kAdaptDcBin] : ac_code[i];
+            tab.len[i] = dc ? dc_len[i - kAdaptDcBin] : ac_len[i];
+        }
+        base_bits[k] = (uint32_t)(128 + tbits);
+        const unsigned long long total = adaptive_stream_bits(hs.count + kAdaptDcBin, hs.count, dc_len, ac_len, tbits);
+        const size_t bytes = (size_t)((total + 7) / 8), cap = caps[tf[k].index];
+        if (bytes > cap) { // tic_retable_adaptive's refusal, from the same figures
+            out_lens[tf[k].index] = bytes;
+            call.failed(tf[k].index, TIC_E_SPACE, tbatch_short_msg(bytes, cap));
+            tf[k].skip = true;
+            continue;
+        }
+        total_bits[k] = total, s.h_lens[k] = bytes;
+        any = true;
+    }
+    if (!any) return TIC_OK;
+    size_t stream_bytes = 0, landing = 0, maxlen = 0;
+    assign_adaptive_streams(v.h_frames, count, total_bits, base_bits, &stream_bytes);
+    for (int k = 0; k < count; k++) {
+        v.h_rb->rec[k].out_off = v.h_frames->rec[k].out_off; // (all the read-back kernel reads of its table)
+        s.h_rb_off[k] = landing;
+        landing += align_up((size_t)s.h_lens[k], 64);
+        maxlen = std::max(maxlen, (size_t)s.h_lens[k]);
+    }
+    int rc = s.d_streams.grow(ctx, stream_bytes, stream_bytes + stream_bytes / 4);
+    if (rc == TIC_OK) rc = s.pin_out.grow(ctx, landing, landing + landing / 4);
+    if (rc) return rc;
+    *v.h_err = 0u;
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemsetAsync(s.d_streams, 0, stream_bytes, st));
+    HIPCHK(ctx, hipMemcpyAsync(s.d_adapt + v.l.err, s.h_adapt + v.l.err, v.l.upload_end - v.l.err, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, adaptive_pack_v(d_coef, v.d_frames, count, ngroups, v.d_tabs, v.d_heads, (uint32_t *)(s.d_adapt + v.l.bbits), (unsigned long long *)(s.d_adapt + v.l.gsum),
+                                s.d_streams, v.d_err, st));
+    HIPCHK(ctx, hipMemcpyAsync(s.h_err, v.d_err, sizeof(int), hipMemcpyDeviceToHost, st));
+    const unsigned gx = (unsigned)std::min<size_t>(64, (maxlen / 16 + 255) / 256 + 1);
+    hipLaunchKernelGGL(readback_frames_kernel, dim3(gx, (unsigned)count), dim3(256), 0, st, (const unsigned char *)s.d_streams, v.d_rb, s.h_lens, s.h_rb_off,
+                       (unsigned char *)s.pin_out);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (*s.h_err) return set_err(ctx, TIC_E_HIP, "packing reached past a stream's computed length (statistics and packing disagree)");
+    for (int k = 0; k < count; k++) {
+        if (tf[k].skip) continue;
+        memcpy(outs[tf[k].index], (const char *)s.pin_out.p + s.h_rb_off[k], (size_t)s.h_lens[k]);
+        out_lens[tf[k].index] = (size_t)s.h_lens[k];
+        call.finished(tf[k].index);
+    }
+    return TIC_OK;
+}
+
+// The batch slot the writers borrow (slot 0: its tables, length words, error flags, stream areas and landing buffer; no batch call is in flight
+// while a transcoding call holds the context's lock).
+static int tbatch_slot(tic_ctx *ctx, size_t work_bytes, size_t stream_bytes, Slot **s) {
+    tic_ctx::SlotNeed need;
+    need.frames = kEntropyMaxFrames, need.work = work_bytes, need.streams = stream_bytes, need.pin_out = stream_bytes ? stream_bytes + 64 * (size_t)kEntropyMaxFrames : 0;
+    const int rc = ensure_batch_slots(ctx, need);
+    if (rc) return rc;
+    *s = &ctx->bslots[0];
+    return TIC_OK;
+}
+
+int tic_retable_adaptive_batch(tic_ctx *ctx, const uint8_t *const *streams, const size_t *lens, int n, uint8_t *const *outs, const size_t *caps,
+                               size_t *out_lens, int *rcs) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (n < 0 || (n > 0 && (!streams || !lens || !outs || !caps || !out_lens))) return set_err(ctx, TIC_E_ARG, "bad batch arguments");
+    TBatchCall call(ctx, n);
+    if (n == 0) return TIC_OK;
+    const auto single = [&](int i) { return tic_retable_adaptive(ctx, streams[i], lens[i], outs[i], caps[i], &out_lens[i]); };
+    if (n == 1) return call.end(single, rcs);
+    std::vector<DecPlanIn> in((size_t)n);
+    for (int i = 0; i < n; i++) {
+        uint32_t flag = 0;
+        in[(size_t)i] = DecPlanIn{0, 0, 0, 0, false};
+        if (tbatch_default_takes(streams[i], lens[i], false, &in[(size_t)i], &flag)) in[(size_t)i].takes = outs[i] != nullptr;
+    }
+    int rc = hipSetDevice(ctx->device) == hipSuccess ? ensure_dec_tables(ctx) : TIC_E_HIP; // (a failure here: every frame to the single call)
+    Slot *sp = nullptr;
+    if (rc == TIC_OK) rc = tbatch_slot(ctx, 0, 0, &sp);
+    const DecPlan plan = rc == TIC_OK ? plan_transcode_default_reader(in.data(), n, tbatch_limits()) : DecPlan();
+    for (const DecPlanChunk &c : plan.chunks) {
+        const DecPlanFrame *pf = &plan.frames[(size_t)c.first];
+        Slot &s = *sp;
+        TranscodeFrame tf[kEntropyMaxFrames];
+        for (int k = 0; k < c.count; k++) tf[k] = transcode_frame(pf[k]);
+        size_t span = 0, ngroups = 0;
+        AdaptFrameTable table;
+        if (!transcode_adaptive_table(&table, tf, c.count, &span, &ngroups)) continue; // (its frames go one by one)
+        const AdaptSlotLayout l = adaptive_slot_layout((size_t)c.count, span, ngroups);
+        if ((rc = ensure_scratch(ctx, 0, c.blocks * 128)) || (rc = s.d_adapt.grow(ctx, l.end, l.end + l.end / 4)) || (rc = s.h_adapt.grow(ctx, l.upload_end, l.upload_end + l.upload_end / 4))) break;
+        const AdaptSlotView v = adapt_view(s, (size_t)c.count, span, ngroups);
+        *v.h_frames = table;
+        // 1. one upload, 2. the reader's two launches, 3. the statistics of every frame on the resident rows, 4. ONE read-back: the statistics by copy,
+        // the reader's status words through host-mapped memory
+        bool refused = false;
+        const int16_t *d_coef = (const int16_t *)ctx->d_coef.p;
+        if ((rc = tbatch_read_default(ctx, streams, pf, c, (int16_t *)ctx->d_coef.p, &refused))) break;
+        if (refused) continue;
+        hipError_t e = hipMemcpyAsync(v.d_frames, v.h_frames, sizeof(AdaptFrameTable), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = adaptive_stats_v(d_coef, v.d_frames, c.count, ngroups, v.d_stats, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(v.h_stats, v.d_stats, (size_t)c.count * sizeof(AdaptStats), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            break;
+        }
+        ctx->last_tbatch_chunks++;
+        for (int k = 0; k < c.count; k++) tf[k].skip = !dec_status_complete(ctx->dbat.ws.h_status[k], streams[pf[k].index], pf[k].nblk);
+        // 5. tables on the host, 6. one upload, 7. bits / scan / write, 8. one download
+        if ((rc = tbatch_write_adaptive(ctx, call, s, v, tf, c.count, ngroups, d_coef, outs, caps, out_lens))) break;
+    }
+    return call.end(single, rcs);
+}
+
+// The default writer's stage of a chunk whose coefficients are resident at d_coef: the mixed batch's descriptor-form pack and place launches on the
+// frames that are not skipped, ONE read-back of the lengths and the flag, the streams' own bytes into the slot's landing buffer, hand-out.  The
+// launch has ONE error flag for all its frames: where it says that a coefficient has no default code (1), the frames [lo, hi) it ran on are halved and
+// each half is launched again - the coefficients are still resident - until the flagged frames stand alone; those are left to the single call, which
+// words the error.  (One such frame among 64: twelve more launches, no reader run again.)
+static int tbatch_write_default(tic_ctx *ctx, TBatchCall &call, Slot &s, const TranscodeFrame *chunk, int count, int lo, int hi, size_t blocks, const int16_t *d_coef,
+                                uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
+    TranscodeFrame tf[kEntropyMaxFrames];
+    for (int k = 0; k < count; k++) {
+        tf[k] = chunk[k];
+        tf[k].skip = tf[k].skip || k < lo || k >= hi;
+    }
+    int qmax = 0;
+    for (int k = 0; k < count; k++) qmax = !tf[k].skip && tf[k].quality > qmax ? tf[k].quality : qmax;
+    int mode = qmax <= ctx->ent_lane_max_quality ? kEntropyLanePerBlock : kEntropyEightLanes;
+    int entry[kEntropyMaxFrames], m = 0;
+    hipStream_t st = ctx->stream;
+    for (;;) {
+        size_t stream_bytes = 0, nparts, ngroups, nplaces;
+        if (!transcode_entropy_table(s.h_frames, mode, tf, count, entry, &m, &stream_bytes, &nparts, &ngroups, &nplaces)) return TIC_OK; // (no frame left, or one too large: one by one)
+        int rc = s.d_streams.grow(ctx, stream_bytes, stream_bytes + stream_bytes / 4);
+        if (rc == TIC_OK) rc = s.pin_out.grow(ctx, stream_bytes + 64 * (size_t)m);
+        const size_t wb = entropy_fused_work_bytes_v(blocks, (size_t)m);
+        if (rc == TIC_OK) rc = s.d_work.grow(ctx, wb, wb + wb / 4);
+        if (rc) return rc;
+        const int par = s.parity;
+        s.parity ^= 1;
+        HIPCHK(ctx, hipMemcpyAsync(s.d_frames, s.h_frames, sizeof(EntropyFrameTable), hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, entropy_gpu_fused_v(d_coef, s.h_frames, s.d_frames, m, ctx->d_huff, s.d_work, s.d_work.cap, s.d_streams, s.d_lens, s.d_err + par, s.d_err + (par ^ 1), mode, st));
+        HIPCHK(ctx, hipMemcpyAsync(s.h_lens, s.d_lens, (size_t)m * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(s.h_err, s.d_err + par, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        if (*s.h_err == 4 && mode == kEntropyLanePerBlock) { // a block exceeds the lane-per-block kernel's strings: once more with the 8-lane kernel
+            mode = kEntropyEightLanes;
+            continue;
+        }
+        break;
+    }
+    if (*s.h_err) { // (1: a symbol without a default code somewhere in [lo, hi))
+        if (hi - lo <= 1) return TIC_OK;
+        const int mid = lo + (hi - lo) / 2;
+        const int rc = tbatch_write_default(ctx, call, s, chunk, count, lo, mid, blocks, d_coef, outs, caps, out_lens);
+        return rc ? rc : tbatch_write_default(ctx, call, s, chunk, count, mid, hi, blocks, d_coef, outs, caps, out_lens);
+    }
+    size_t off = 0, maxlen = 0;
+    for (int k = 0; k < count; k++) {
+        const int j = entry[k];
+        if (j < 0) continue;
+        const size_t len = (size_t)s.h_lens[j], cap = caps[tf[k].index];
+        if (len > cap) { // tic_retable_default's refusal, from the same length
+            out_lens[tf[k].index] = len;
+            call.failed(tf[k].index, TIC_E_SPACE, tbatch_short_msg(len, cap));
+            s.h_lens[j] = 0ull;
+            entry[k] = -1;
+        }
+        s.h_rb_off[j] = off;
+        off += align_up((size_t)s.h_lens[j], 64);
+        maxlen = std::max(maxlen, (size_t)s.h_lens[j]);
+    }
+    if (maxlen == 0) return TIC_OK;
+    const unsigned gx = (unsigned)std::min<size_t>(64, (maxlen / 16 + 255) / 256 + 1);
+    hipLaunchKernelGGL(readback_frames_kernel, dim3(gx, (unsigned)m), dim3(256), 0, st, (const unsigned char *)s.d_streams, s.d_frames, s.h_lens, s.h_rb_off,
+                       (unsigned char *)s.pin_out);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    for (int k = 0; k < count; k++) {
+        const int j = entry[k];
+        if (j < 0) continue;
+        memcpy(outs[tf[k].index], (const char *)s.pin_out.p + s.h_rb_off[j], (size_t)s.h_lens[j]);
+        out_lens[tf[k].index] = (size_t)s.h_lens[j];
+        call.finished(tf[k].index);
+    }
+    return TIC_OK;
+}
+
+int tic_retable_default_batch(tic_ctx *ctx, const uint8_t *const *streams, const size_t *lens, int n, uint8_t *const *outs, const size_t *caps,
+                              size_t *out_lens, int *rcs) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (n < 0 || (n > 0 && (!streams || !lens || !outs || !caps || !out_lens))) return set_err(ctx, TIC_E_ARG, "bad batch arguments");
+    TBatchCall call(ctx, n);
+    if (n == 0) return TIC_OK;
+    const auto single = [&](int i) { return tic_retable_default(ctx, streams[i], lens[i], outs[i], caps[i], &out_lens[i]); };
+    if (n == 1) return call.end(single, rcs);
+    // the frames tic_decompress_batch_adaptive's reader takes (adaptive_batch_takes), behind the header checks of tic_retable_default
+    std::vector<AdaptDecPlanIn> in((size_t)n);
+    std::vector<AdaptTable> tabs; // of the frames taken, in order
+    {
+        AdaptTable t;
+        for (int i = 0; i < n; i++) {
+            int h = 0, w = 0, q = 0;
+            uint32_t flag = 0;
+            in[(size_t)i] = AdaptDecPlanIn{0, 0, 0, 0, 0, false};
+            if (!streams[i] || !outs[i] || parse_header(streams[i], lens[i], &h, &w, &q, &flag) != TIC_OK || h < 0 || w < 0 || q < 1 || q > 99) continue;
+            in[(size_t)i] = AdaptDecPlanIn{h, w, q, lens[i], 0, adaptive_batch_takes(num_blocks(h, w), streams[i], lens[i], &t)};
+            if (in[(size_t)i].takes) in[(size_t)i].payload_bit = t.payload_bit, tabs.push_back(t);
+        }
+    }
+    if (tabs.size() < 2) { // (adaptive_batch_takes: no batch of one)
+        for (AdaptDecPlanIn &f : in) f.takes = false;
+        tabs.clear();
+    }
+    Slot *sp = nullptr;
+    int rc = hipSetDevice(ctx->device) == hipSuccess ? tbatch_slot(ctx, 0, 0, &sp) : TIC_E_HIP; // (a failure here: every frame to the single call)
+    const AdaptDecPlan plan = rc == TIC_OK ? plan_transcode_adaptive_reader(in.data(), n, tbatch_limits()) : AdaptDecPlan();
+    const DecBatchIO io = {streams, lens, outs, caps};
+    for (const AdaptDecPlanChunk &c : plan.chunks) {
+        const AdaptDecPlanFrame *pf = &plan.frames[(size_t)c.first];
+        std::vector<char> good;
+        if ((rc = adbatch_decode(ctx, io, pf, c, &tabs[(size_t)c.first], &good, false))) break;
+        ctx->last_tbatch_chunks++;
+        TranscodeFrame tf[kEntropyMaxFrames];
+        for (int k = 0; k < c.count; k++) {
+            tf[k] = transcode_frame(pf[k]);
+            tf[k].skip = !good[(size_t)k];
+        }
+        const int16_t *d_coef = (const int16_t *)(ctx->adbat.d_work + AdaptDecWorkLayout(c).o_coef);
+        if ((rc = tbatch_write_default(ctx, call, *sp, tf, c.count, 0, c.count, c.blocks, d_coef, outs, caps, out_lens))) break;
+    }
+    return call.end(single, rcs);
+}
+
+int tic_last_transcode_batch(tic_ctx *ctx, int *batch_frames, int *single_frames, int *chunks) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (batch_frames) *batch_frames = ctx->last_tbatch_frames;
+    if (single_frames) *single_frames = ctx->last_tbatch_single;
+    if (chunks) *chunks = ctx->last_tbatch_chunks;
+    return TIC_OK;
 }
 
 // ---- rate control of the adaptive family (include/tinyimgcodec_hip_adaptive_rate.h) ------------------------------------------------------------

@@ -165,6 +165,14 @@ hipError_t entropy_decode_idct_gpu_batch(const void *d_words_all, const DecFrame
                                          size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, DecStatus *d_status, int range_bits, hipStream_t stream,
                                          int flat_grid = 4096);
 
+// ... with the coefficient sink: frame f's blocks as rows of the zz16 layout from row blk0 of d_coef on (16-byte aligned, the chunk's total_blocks rows),
+// absolute DC, the DC sum starting over with every frame; DecFrame::idct carries the frame's 16 header bytes (idct.head) and nothing else.  A frame
+// whose status is not complete (dec_status_complete) may have left any of its OWN rows unwritten or half-written; no other frame's rows are touched.
+hipError_t entropy_decode_coef_gpu_batch(const void *d_words_all, const DecFrame *d_frames, const uint32_t *d_tile_frame, const uint32_t *d_wg_frame, uint32_t nframes,
+                                         uint32_t total_tiles, uint32_t total_wgs, uint32_t total_ranges, size_t total_blocks, bool small_win, const DecLutsDev *d_luts, void *d_work,
+                                         size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, DecStatus *d_status, int range_bits, int16_t *d_coef,
+                                         hipStream_t stream, int flat_grid = 4096);
+
 #endif // TIC_DEC_WORKSPACE_ONLY
 
 } // namespace tic

@@ -903,6 +903,20 @@ __global__ __launch_bounds__(kDecodeWG, kWinWords <= 2048u ? 3 : 2) void dec_dec
                                        F.stream_bits, F.idct, status + f, blockIdx.x - F.wg0, F.nwgs);
 }
 
+// The coefficient sink's batch form (entropy_decode_coef_gpu_batch): the frames' blocks lie back to back in ONE buffer, frame f's rows from row F.blk0
+// on.  A frame's last workgroup is partial and the next frame's first row lies directly behind its last one: the copy-out's mask (no store behind the
+// frame's block m - 1) is what keeps the neighbour intact.  F.idct carries the frame's header and nothing else.
+template <uint32_t kWinWords>
+__global__ __launch_bounds__(kDecodeWG, kWinWords <= 2048u ? 3 : 2) void dec_decode_coef_batch_kernel(const uint32_t *__restrict__ words_all, const DecFrame *__restrict__ frames, const uint32_t *__restrict__ wg_frame,
+                                                                          const DecLutsDev *__restrict__ L, const uint32_t *__restrict__ bpos_all, unsigned long long *__restrict__ desc, uint32_t desc_half,
+                                                                          uint32_t flat_grid, uint32_t epoch, const long long *__restrict__ totals, DecStatus *__restrict__ status,
+                                                                          int16_t *__restrict__ coef_base) {
+    const uint32_t f = wg_frame[blockIdx.x];
+    const DecFrame &F = frames[f];
+    decode_idct_body<kWinWords, false, true>(words_all + F.word0, F.nwords, F.last_mask, L, bpos_all + F.blk0, desc + F.wg0, desc_half, flat_grid, epoch, totals + f, (unsigned long long)F.nblocks,
+                                             F.stream_bits, F.idct, status + f, blockIdx.x - F.wg0, F.nwgs, coef_base + (size_t)64 * F.blk0);
+}
+
 } // namespace
 
 // rounds of the stitch's hand-over loop (a hook for measurements: TIC_DECODE_ROUNDS)
@@ -1021,10 +1035,11 @@ hipError_t entropy_decode_coef_gpu(const void *d_stream_words, size_t stream_byt
 uint32_t entropy_decode_batch_tiles(uint32_t nranges, int range_bits) { const uint32_t owned = 64u - dec_shadows(range_bits); return (nranges + owned - 1u) / owned; }
 uint32_t entropy_decode_batch_wgs(size_t nblocks) { return (uint32_t)((nblocks + kDecodeWG - 1) / kDecodeWG); }
 
-hipError_t entropy_decode_idct_gpu_batch(const void *d_words_all, const DecFrame *d_frames, const uint32_t *d_tile_frame, const uint32_t *d_wg_frame, uint32_t nframes,
-                                         uint32_t total_tiles, uint32_t total_wgs, uint32_t total_ranges, size_t total_blocks, bool small_win, const DecLutsDev *d_luts, void *d_work,
-                                         size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, DecStatus *d_status, int range_bits, hipStream_t stream,
-                                         int flat_grid) {
+// both sinks of the batch form: d_coef == nullptr pixels through every frame's DecIdctArgs, else the chunk's coefficient rows from d_coef on
+static hipError_t decode_launch_batch(const void *d_words_all, const DecFrame *d_frames, const uint32_t *d_tile_frame, const uint32_t *d_wg_frame, uint32_t nframes,
+                                      uint32_t total_tiles, uint32_t total_wgs, uint32_t total_ranges, size_t total_blocks, bool small_win, const DecLutsDev *d_luts, void *d_work,
+                                      size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, DecStatus *d_status, int range_bits, hipStream_t stream,
+                                      int flat_grid, int16_t *d_coef) {
     if (!entropy_decode_gpu_range_ok(range_bits) || nframes == 0 || total_tiles == 0 || total_wgs == 0) return hipErrorInvalidValue;
     const uint32_t range = (uint32_t)range_bits;
     if (!d_desc || desc_words < 4 * (size_t)(total_tiles > total_wgs ? total_tiles : total_wgs) || epoch == 0 || epoch >= (1u << 22) || flat_grid < 0) return hipErrorInvalidValue;
@@ -1045,13 +1060,36 @@ hipError_t entropy_decode_idct_gpu_batch(const void *d_words_all, const DecFrame
                            range, starts, hand, desc_r, desc_half, (uint32_t)flat_grid, 2u * epoch, bpos, totals, d_status, stitch_rounds(), dec_shadows(range_bits));
     };
     total_tiles <= kEveryStepTiles ? measure(dec_measure_stitch_batch_kernel<true>) : measure(dec_measure_stitch_batch_kernel<false>);
-    if (small_win)
+    if (d_coef) {
+        auto sink = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(total_wgs), dim3(kDecodeWG), 0, stream, (const uint32_t *)d_words_all, d_frames, d_wg_frame, d_luts, (const uint32_t *)bpos, desc_b, desc_half,
+                               (uint32_t)flat_grid, 2u * epoch + 1u, (const long long *)totals, d_status, d_coef);
+        };
+        small_win ? sink(dec_decode_coef_batch_kernel<2048>) : sink(dec_decode_coef_batch_kernel<4096>);
+    } else if (small_win)
         hipLaunchKernelGGL(dec_decode_idct_batch_kernel<2048>, dim3(total_wgs), dim3(kDecodeWG), 0, stream, (const uint32_t *)d_words_all, d_frames, d_wg_frame, d_luts, (const uint32_t *)bpos, desc_b,
                            desc_half, (uint32_t)flat_grid, 2u * epoch + 1u, (const long long *)totals, d_status);
     else
         hipLaunchKernelGGL(dec_decode_idct_batch_kernel<4096>, dim3(total_wgs), dim3(kDecodeWG), 0, stream, (const uint32_t *)d_words_all, d_frames, d_wg_frame, d_luts, (const uint32_t *)bpos, desc_b,
                            desc_half, (uint32_t)flat_grid, 2u * epoch + 1u, (const long long *)totals, d_status);
     return hipGetLastError();
+}
+
+hipError_t entropy_decode_idct_gpu_batch(const void *d_words_all, const DecFrame *d_frames, const uint32_t *d_tile_frame, const uint32_t *d_wg_frame, uint32_t nframes,
+                                         uint32_t total_tiles, uint32_t total_wgs, uint32_t total_ranges, size_t total_blocks, bool small_win, const DecLutsDev *d_luts, void *d_work,
+                                         size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, DecStatus *d_status, int range_bits, hipStream_t stream,
+                                         int flat_grid) {
+    return decode_launch_batch(d_words_all, d_frames, d_tile_frame, d_wg_frame, nframes, total_tiles, total_wgs, total_ranges, total_blocks, small_win, d_luts, d_work, work_bytes, d_desc,
+                               desc_words, epoch, d_status, range_bits, stream, flat_grid, nullptr);
+}
+
+hipError_t entropy_decode_coef_gpu_batch(const void *d_words_all, const DecFrame *d_frames, const uint32_t *d_tile_frame, const uint32_t *d_wg_frame, uint32_t nframes,
+                                         uint32_t total_tiles, uint32_t total_wgs, uint32_t total_ranges, size_t total_blocks, bool small_win, const DecLutsDev *d_luts, void *d_work,
+                                         size_t work_bytes, unsigned long long *d_desc, size_t desc_words, uint32_t epoch, DecStatus *d_status, int range_bits, int16_t *d_coef,
+                                         hipStream_t stream, int flat_grid) {
+    if (!d_coef || ((uintptr_t)d_coef & 15u)) return hipErrorInvalidValue;
+    return decode_launch_batch(d_words_all, d_frames, d_tile_frame, d_wg_frame, nframes, total_tiles, total_wgs, total_ranges, total_blocks, small_win, d_luts, d_work, work_bytes, d_desc,
+                               desc_words, epoch, d_status, range_bits, stream, flat_grid, d_coef);
 }
 
 } // namespace tic
