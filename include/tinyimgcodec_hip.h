@@ -76,7 +76,12 @@ int tic_encode(tic_ctx *ctx, const uint8_t *image, int h, int w, ptrdiff_t row_s
 
 /* The same for integer images whose values lie outside 0..255 (the reference casts with astype(int32), codec.py:29, and
  * transforms any integers): int32 pixels (row stride in ELEMENTS), float64 exact operation order on the device, int32
- * coefficients.  A drop-in edge, not a hot path. */
+ * coefficients.  A drop-in edge, not a hot path.
+ * Domain: exact - the reference's dc / ac, integer for integer - wherever every rounded quotient fits int32, for every int32 pixel.  `- 128`
+ * is int32's wrapping subtraction as in the reference (pixels INT32_MIN .. INT32_MIN + 127 wrap to the top of the range), and so is the DC
+ * difference (np.diff of an int32 array).  Where a rounded quotient leaves int32 the reference's own result is numpy's invalid cast (a
+ * RuntimeWarning; INT32_MIN for either sign where it was tried) while the device's conversion saturates: nothing is promised there.  At
+ * quality 10 every int32 image is inside the domain. */
 int tic_encode_wide(tic_ctx *ctx, const int32_t *image, int h, int w, ptrdiff_t row_stride_elems, int quality, int32_t *dc,
                     int32_t *ac);
 /* encode() / decode() with a non-integral quality (utils.py:50-53 computes with any number; the device holds one constant block

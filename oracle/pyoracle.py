@@ -131,7 +131,13 @@ def encode_wide(image, quality=50):
     n = nblocks(h, w)
     dc = np.zeros(max(n, 1), dtype=np.int32)
     ac = np.zeros((max(n, 1), 63), dtype=np.int32)
-    rc = lib().tico_encode_i32(_p(a, C.c_int32), h, w, (a.strides[0] // 4) if a.size else w, int(quality), _p(dc, C.c_int32), _p(ac, C.c_int32))
+    stride = (a.strides[0] // 4) if a.size else w
+    if isinstance(quality, (float, np.floating)) and quality != int(quality):  # utils.py:50-53 on a float that is not an integer
+        L = lib()
+        L.tico_encode_i32_f.argtypes = [C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_ssize_t, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        rc = L.tico_encode_i32_f(_p(a, C.c_int32), h, w, stride, float(quality), _p(dc, C.c_int32), _p(ac, C.c_int32))
+    else:
+        rc = lib().tico_encode_i32(_p(a, C.c_int32), h, w, stride, int(quality), _p(dc, C.c_int32), _p(ac, C.c_int32))
     if rc:
         raise OracleError(rc)
     return dc[:n], ac[:n]

@@ -302,7 +302,10 @@ static int transform_zz_div(const uint8_t *image, const int32_t *image32, int h,
                 int y = reflect_index(by * 8 + i, h);
                 for (int j = 0; j < 8; j++) {
                     int x = reflect_index(bx * 8 + j, w);
-                    px[i * 8 + j] = (image ? (int32_t)image[(ptrdiff_t)y * stride + x] : image32[(ptrdiff_t)y * stride + x]) - 128; /* codec.py:29 */
+                    /* codec.py:29 subtracts in int32: INT32_MIN .. INT32_MIN + 127 wrap to the top of the range (numpy's arrays wrap; a signed
+                     * subtraction in C would be undefined there) */
+                    uint32_t p = image ? (uint32_t)image[(ptrdiff_t)y * stride + x] : (uint32_t)image32[(ptrdiff_t)y * stride + x];
+                    px[i * 8 + j] = (int32_t)(p - 128u);
                 }
             }
             tico_block_dct(px, X);
@@ -322,27 +325,30 @@ static int transform_zz(const uint8_t *image, int h, int w, ptrdiff_t stride, in
     return transform_zz_any(image, NULL, h, w, stride, quality, zz);
 }
 
+/* codec.py:34-36: DPCM over all blocks in raster order.  np.diff of an int32 array wraps; so does this. */
+static void split_dpcm(const int32_t *zz, size_t n, int32_t *dc, int32_t *ac) {
+    int32_t prev = 0;
+    for (size_t b = 0; b < n; b++) {
+        int32_t cur = zz[b * 64];
+        dc[b] = b ? (int32_t)((uint32_t)cur - (uint32_t)prev) : cur;
+        prev = cur;
+        memcpy(ac + b * 63, zz + b * 64 + 1, 63 * sizeof(int32_t));
+    }
+}
+
 static int encode_any(const uint8_t *image, const int32_t *image32, int h, int w, ptrdiff_t stride, int quality, int32_t *dc, int32_t *ac) {
     size_t n = (size_t)((h + 7) / 8) * (size_t)((w + 7) / 8);
     if (h == 0 || w == 0) n = 0;
     int32_t *zz = (int32_t *)malloc((n ? n : 1) * 64 * sizeof(int32_t));
     if (!zz) return TICO_E_SPACE;
     int rc = transform_zz_any(image, image32, h, w, stride, quality, zz);
-    if (rc == TICO_OK) {
-        int32_t prev = 0;
-        for (size_t b = 0; b < n; b++) { /* codec.py:34-36: DPCM over all blocks in raster order */
-            int32_t cur = zz[b * 64];
-            dc[b] = b ? cur - prev : cur;
-            prev = cur;
-            memcpy(ac + b * 63, zz + b * 64 + 1, 63 * sizeof(int32_t));
-        }
-    }
+    if (rc == TICO_OK) split_dpcm(zz, n, dc, ac);
     free(zz);
     return rc;
 }
 
 /* encode() with a non-integral quality (codec.py:26-43 with utils.py:50-53 on a float): dc (DPCM'd), ac as tico_encode */
-int tico_encode_f(const uint8_t *image, int h, int w, ptrdiff_t stride, double quality, int32_t *dc, int32_t *ac) {
+static int encode_any_f(const uint8_t *image, const int32_t *image32, int h, int w, ptrdiff_t stride, double quality, int32_t *dc, int32_t *ac) {
     double div[64];
     int rc = tico_divisors_f(quality, div);
     if (rc) return rc;
@@ -350,18 +356,19 @@ int tico_encode_f(const uint8_t *image, int h, int w, ptrdiff_t stride, double q
     if (h == 0 || w == 0) n = 0;
     int32_t *zz = (int32_t *)malloc((n ? n : 1) * 64 * sizeof(int32_t));
     if (!zz) return TICO_E_SPACE;
-    rc = transform_zz_div(image, NULL, h, w, stride, div, zz);
-    if (rc == TICO_OK) {
-        int32_t prev = 0;
-        for (size_t b = 0; b < n; b++) { /* codec.py:34-36 */
-            int32_t cur = zz[b * 64];
-            dc[b] = b ? cur - prev : cur;
-            prev = cur;
-            memcpy(ac + b * 63, zz + b * 64 + 1, 63 * sizeof(int32_t));
-        }
-    }
+    rc = transform_zz_div(image, image32, h, w, stride, div, zz);
+    if (rc == TICO_OK) split_dpcm(zz, n, dc, ac);
     free(zz);
     return rc;
+}
+
+int tico_encode_f(const uint8_t *image, int h, int w, ptrdiff_t stride, double quality, int32_t *dc, int32_t *ac) {
+    return encode_any_f(image, NULL, h, w, stride, quality, dc, ac);
+}
+
+/* ... for integer images outside 0..255: int32 pixels, stride in elements */
+int tico_encode_i32_f(const int32_t *image, int h, int w, ptrdiff_t stride, double quality, int32_t *dc, int32_t *ac) {
+    return encode_any_f(NULL, image, h, w, stride, quality, dc, ac);
 }
 
 int tico_encode(const uint8_t *image, int h, int w, ptrdiff_t stride, int quality, int32_t *dc, int32_t *ac) {

@@ -693,6 +693,8 @@ EXEMPT = {
     "tic_dctq": "transform stage of tic_compress alone (d_img, d_coef: covered by compress)",
     "tic_encode": "transform stage of tic_compress alone, host layout",
     "tic_encode_wide": "float64 transform for wide pixels: host entropy coder behind it, no context buffer beside d_img / d_coef",
+    # (tic_entropy_encode_dpcm, that host coder, takes no context and is declared in tinyimgcodec_hip_wide.h: nothing to record here;
+    #  tests/test_wide_blocks_gpu.py runs tic_encode_wide between the calls of other families and on poisoned contexts)
     "tic_dctq_dev_frames": "transform stage on the caller's device buffers: no context buffer",
     "tic_dctq_batch": "transform stage of tic_compress_batch alone (batch slots: covered by compress_batch)",
     "tic_dctq_scaled": "transform stage of tic_compress_scaled alone", "tic_dctq_scaled_dev": "transform stage of tic_compress_scaled alone",

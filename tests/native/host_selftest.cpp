@@ -73,6 +73,19 @@ int main() {
             cases++;
             if (rc != 0) continue; // |DC difference| > 2047 has no code in either coder
             if (got_len != ref_len || memcmp(probe.data(), ref.data(), ref_len) != 0) return fail("stream mismatch", h, w, mode);
+            { // the coder of the int32 differences (compress() of wide images): the same stream from exact-size arrays, into an exact-size buffer
+                std::vector<int32_t> dc_x(dc.begin(), dc.begin() + n), ac_x(ac.begin(), ac.begin() + n * 63);
+                std::vector<uint8_t> ex(got_len);
+                size_t l3 = 0;
+                if (tic::entropy_encode_dpcm(dc_x.data(), ac_x.data(), h, w, 50, ex.data(), ex.size(), &l3) != 0 || l3 != got_len ||
+                    memcmp(ex.data(), ref.data(), ref_len) != 0)
+                    return fail("dpcm coder: stream mismatch", h, w, mode);
+                if (got_len > 16) {
+                    std::vector<uint8_t> small(got_len - 1);
+                    if (tic::entropy_encode_dpcm(dc_x.data(), ac_x.data(), h, w, 50, small.data(), small.size(), &l3) == 0)
+                        return fail("dpcm coder: undersized buffer accepted", h, w, mode);
+                }
+            }
             // exact-size output buffer (ASan guards its end), then one byte too small
             std::vector<uint8_t> exact(got_len);
             size_t l2 = 0;
@@ -98,6 +111,59 @@ int main() {
                 (void)tic::entropy_decode(t.data(), t.size(), h, w, back.data());
             }
         }
+    }
+    // ---- the coder of int32 differences where the zz16 layout ends: a running DC far outside int16 in codable steps, the last values with a
+    //      code and the first without (differences of +-2047 / +-2048, AC values of +-1023 / +-1024), and int32's extremes - against the oracle
+    {
+        const int h = 192, w = 8; // 24 blocks
+        const size_t n = tic::num_blocks(h, w);
+        struct Probe {
+            int32_t step, first, ac;
+            bool codable;
+        };
+        const Probe probes[] = {{2000, 0, 0, true},   {-2000, 0, 0, true},       {2047, -2047, 1023, true},     {-2047, 2047, -1023, true},
+                                {2048, 0, 0, false},  {-2048, 0, 0, false},      {0, 2048, 0, false},           {0, 0, 1024, false},
+                                {0, 0, -1024, false}, {INT32_MIN, 0, 0, false},  {0, INT32_MIN, 0, false},      {0, 0, INT32_MIN, false},
+                                {0, 0, INT32_MAX, false}, {INT32_MAX, 0, 0, false}};
+        for (const Probe &p : probes) {
+            std::vector<int32_t> dc(n), ac(n * 63, 0);
+            for (size_t b = 0; b < n; b++) dc[b] = b ? p.step : p.first;
+            ac[(n - 1) * 63 + 62] = p.ac; // the last value of the last block: behind three ZRLs
+            ac[5 * 63] = p.ac / 3;
+            const size_t bound = tic::compress_bound(h, w);
+            std::vector<uint8_t> ref(bound), got(bound);
+            size_t ref_len = 0, got_len = 0;
+            const int rc_ref = tico_entropy_encode(dc.data(), ac.data(), h, w, 50, ref.data(), ref.size(), &ref_len);
+            const int rc = tic::entropy_encode_dpcm(dc.data(), ac.data(), h, w, 50, got.data(), got.size(), &got_len);
+            if ((rc == 0) != p.codable || (rc_ref == 0) != p.codable) return fail("dpcm coder: codability", p.step, p.first, p.ac);
+            cases++;
+            if (!p.codable) continue;
+            if (got_len != ref_len || memcmp(got.data(), ref.data(), ref_len) != 0) return fail("dpcm coder: wide running DC", p.step, p.first, p.ac);
+            std::vector<int16_t> back(n * 64);
+            std::vector<tic::DcWide> wide;
+            if (tic::entropy_decode(got.data(), got_len, h, w, back.data(), &wide) != 0) return fail("dpcm coder: decode", p.step, p.first, p.ac);
+            int64_t run = 0;
+            size_t seen = 0;
+            for (size_t b = 0; b < n; b++) {
+                run += dc[b];
+                const bool out16 = run < -32768 || run > 32767;
+                if (out16) {
+                    if (seen >= wide.size() || wide[seen].block != b || wide[seen].dc != (int32_t)run) return fail("dpcm coder: wide list", p.step, p.first, (int)b);
+                    seen++;
+                } else if (back[b * 64] != (int16_t)run)
+                    return fail("dpcm coder: running DC", p.step, p.first, (int)b);
+                for (int k = 1; k < 64; k++)
+                    if (back[b * 64 + k] != ac[b * 63 + k - 1]) return fail("dpcm coder: AC", p.step, p.first, (int)b);
+            }
+            if (seen != wide.size()) return fail("dpcm coder: wide list length", p.step, p.first, p.ac);
+        }
+        size_t l = 0;
+        uint8_t hdr[16];
+        std::vector<int32_t> z(64, 0);
+        if (tic::entropy_encode_dpcm(nullptr, nullptr, 0, 8, 50, hdr, sizeof hdr, &l) != 0 || l != 16) return fail("dpcm coder: no blocks", 0, 8, 0);
+        if (tic::entropy_encode_dpcm(nullptr, z.data(), 8, 8, 50, hdr, sizeof hdr, &l) == 0) return fail("dpcm coder: null dc accepted", 8, 8, 0);
+        if (tic::entropy_encode_dpcm(z.data(), z.data(), 8, 8, 0, hdr, sizeof hdr, &l) == 0) return fail("dpcm coder: quality 0 accepted", 8, 8, 0);
+        if (tic::entropy_encode_dpcm(z.data(), z.data(), 8, 8, 50, hdr, 15, &l) == 0) return fail("dpcm coder: 15-byte buffer accepted", 8, 8, 0);
     }
     // ---- long streams: the parallel decoder (ranges measured speculatively, stitched, decoded in parallel) against the serial one
     //      (TIC_DECODE_SERIAL), on well-formed streams and on streams damaged in the middle, where the parallel path has to notice

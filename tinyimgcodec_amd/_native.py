@@ -380,6 +380,12 @@ TRANSCODE_BATCH_SIGNATURES = {
     "tic_last_transcode_batch": (C.c_int, [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
+# ... and exactly the symbol include/tinyimgcodec_hip_wide.h declares: compress()'s writer on the int32 DC differences and AC values of
+# tic_encode_wide (host code, no context)
+WIDE_SIGNATURES = {
+    "tic_entropy_encode_dpcm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+}
+
 _lib = None
 _lock = threading.RLock()  # re-entrant: default_context() creates a Context (which calls load()) under it
 
@@ -400,7 +406,7 @@ def load():
             except OSError as e:  # missing ROCm runtime etc.
                 raise NativeUnavailable("cannot load %s: %s" % (path, e)) from e
             for name, (res, args) in (list(SIGNATURES.items()) + list(RATE_ADAPTIVE_SIGNATURES.items()) + list(TRANSCODE_SIGNATURES.items())
-                                      + list(TRANSCODE_BATCH_SIGNATURES.items())):
+                                      + list(TRANSCODE_BATCH_SIGNATURES.items()) + list(WIDE_SIGNATURES.items())):
                 fn = getattr(L, name)
                 fn.restype = res
                 fn.argtypes = args

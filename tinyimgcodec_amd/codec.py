@@ -31,8 +31,10 @@ entropy coder (C++) serves encode()-style callers that hold coefficients on the 
 functions raise tinyimgcodec_amd.NativeUnavailable.
 
 Documented differences from the reference (all outside its working domain):
-  * integer pixel values outside 0..255 are transformed as the reference does (exact float64 path on the device) by
-    encode() and compress(); the batch and device-layout helpers (compress_batch, dctq) are 8-bit only;
+  * integer pixel values outside 0..255 are transformed as the reference does (exact float64 path on the device, `- 128` and the DC
+    difference wrapping in int32) by encode() and compress(), exactly wherever every rounded quotient fits int32 - beyond that the
+    reference's own result is numpy's invalid cast and nothing is promised; compress() codes the DC differences as they stand, so the
+    running DC may leave int16; the batch and device-layout helpers (compress_batch, dctq) are 8-bit only;
   * encode()/decode() accept float qualities like the reference, integral or not (utils.py:50-53 computes with any number: the
     constants of a non-integral quality in [1, 99] are built per call, tic_set_custom_quality); qualities below 1 or negative (for
     which the reference computes with huge or negative divisors) raise ValueError;
@@ -178,13 +180,9 @@ def compress(image, quality=50, auto_generate_huffman_table=False, ctx=None):
     ctx = _ctx(ctx)
     L = N.load()
     if wide:  # integer pixels outside 0..255: exact float64 transform on the device, host entropy coder
+        # (the reference codes the DC differences as encode() returns them, codec.py:153-162: the running DC may leave int16)
         dc, ac = _encode_wide(img, h, w, q, ctx)
-        zz = np.empty((dc.shape[0], 64), dtype=np.int64)
-        zz[:, 0] = np.cumsum(dc.astype(np.int64))
-        zz[:, 1:] = ac
-        if zz.size and np.abs(zz).max() > 32767:
-            raise KeyError("coefficient magnitude has no Huffman code")  # (>= 1024 already has none in the reference)
-        return entropy_encode(zz.astype(np.int16), h, w, q)
+        return _entropy_encode_dpcm(dc, ac, h, w, q)
     cap = L.tic_compress_bound(h, w)
     # worst-case sized landing buffer kept on the context: a fresh 50 MB mapping per call would be faulted in page by page
     # under the device-to-host copy (20+ ms for a 4096x4096 frame whose whole C-level round trip takes 0.6 ms)
@@ -331,6 +329,26 @@ def entropy_encode(coeffs_zz, height, width, quality):
     if rc != N.TIC_OK:
         raise N.NativeError(rc, "tic_entropy_encode failed")
     return out[: n.value].tobytes()
+
+
+def _entropy_encode_dpcm(dc, ac, height, width, quality):
+    """Host entropy stage on encode()'s own arrays (no GPU needed): int32 [N] DC differences and int32 [N, 63] AC values -> stream
+    bytes.  KeyError where a difference or an AC value has no Huffman code, as the reference's dict lookup - never for the running DC."""
+    L = N.load()
+    n = L.tic_num_blocks(int(height), int(width))
+    dc = np.ascontiguousarray(dc, dtype=np.int32)
+    ac = np.ascontiguousarray(ac, dtype=np.int32)
+    if dc.shape != (n,) or ac.shape != (n, 63):
+        raise ValueError("dc of shape %r and ac of shape %r do not match %d blocks" % (dc.shape, ac.shape, n))
+    cap = L.tic_compress_bound(int(height), int(width))
+    out = np.empty(cap, dtype=np.uint8)
+    length = C.c_size_t(0)
+    rc = L.tic_entropy_encode_dpcm(dc.ctypes.data, ac.ctypes.data, int(height), int(width), int(quality), out.ctypes.data, cap, C.byref(length))
+    if rc == N.TIC_E_RANGE:
+        raise KeyError("coefficient magnitude has no Huffman code")
+    if rc != N.TIC_OK:
+        raise N.NativeError(rc, "tic_entropy_encode_dpcm failed")
+    return out[: length.value].tobytes()
 
 
 def entropy_size(coeffs_zz, height, width):

@@ -22,6 +22,7 @@
 #include "../../include/tinyimgcodec_hip_adaptive_rate.h"
 #include "../../include/tinyimgcodec_hip_transcode.h"
 #include "../../include/tinyimgcodec_hip_transcode_batch.h"
+#include "../../include/tinyimgcodec_hip_wide.h"
 #include "tic_adaptive.h"
 #include "tic_adaptive_stats_gpu.h"
 #include "tic_decode_plan.h"
@@ -1244,6 +1245,10 @@ int tic_entropy_encode(const int16_t *coeffs_zz, int h, int w, int quality, uint
 }
 
 int tic_entropy_size(const int16_t *coeffs_zz, int h, int w, size_t *bytes) { return entropy_size(coeffs_zz, h, w, bytes); }
+// (include/tinyimgcodec_hip_wide.h) compress() of a wide image: the writer on tic_encode_wide's own int32 differences
+int tic_entropy_encode_dpcm(const int32_t *dc, const int32_t *ac, int h, int w, int quality, uint8_t *out, size_t cap, size_t *out_len) {
+    return entropy_encode_dpcm(dc, ac, h, w, quality, out, cap, out_len);
+}
 
 int tic_parse_header(const uint8_t *data, size_t len, int *h, int *w, int *quality, uint32_t *flag) {
     return parse_header(data, len, h, w, quality, flag);

@@ -156,6 +156,42 @@ void write_header(uint8_t *out, int h, int w, int quality) {
 }
 
 namespace {
+// One block's symbols: the DC difference as it stands, then the 63 AC values (ac[0] is scan position 1).  false: a value without a code.
+template <typename V>
+inline bool put_block(BitWriter &bw, const EncTables &T, int32_t diff, const V *ac) {
+    {
+        const uint32_t a = diff < 0 ? 0u - (uint32_t)diff : (uint32_t)diff;
+        const int size = bit_length(a);
+        if (size > 11) return false;
+        bw.put(T.dc_code[size], T.dc_len[size]);
+        if (size) bw.put((diff < 0 ? ~a : a) & ((1u << size) - 1u), size);
+    }
+    // AC: (run,size) symbols; ZRL per 16 zeros; EOB always (huffman.py:12-33)
+    int last = 62;
+    while (last >= 0 && ac[last] == 0) last--;
+    int run = 0;
+    for (int k = 0; k <= last; k++) {
+        const int32_t v = ac[k];
+        if (v == 0) {
+            run++;
+            continue;
+        }
+        while (run >= 16) {
+            bw.put(T.ac_code[0xF0], T.ac_len[0xF0]);
+            run -= 16;
+        }
+        const uint32_t a = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+        const int size = bit_length(a);
+        if (size > 10) return false;
+        const int sym = (run << 4) | size;
+        // codeword (<= 16 bits) and value bits (<= 10) in one append; v < 0 -> one's complement of |v|
+        bw.put((T.ac_code[sym] << size) | ((uint32_t)(v + (v >> 31)) & ((1u << size) - 1u)), T.ac_len[sym] + size);
+        run = 0;
+    }
+    bw.put(T.ac_code[0], T.ac_len[0]); // EOB
+    return true;
+}
+
 // scaled: a stream of the reference's integer encoder (c/img.c) - same symbols, same tables; the header carries the setting 0..3 and
 // flag 1 << 30 (IMG_encodeHeader, img.c:183-192), and the stream ends as BB_flushBits ends it (img.h:36-40): one byte with the pending
 // bits behind the last whole byte, written also when nothing is pending.
@@ -179,39 +215,10 @@ int entropy_encode_impl(const int16_t *zz, int h, int w, int quality, uint8_t *o
     for (size_t b = 0; b < n; b++) {
         const int16_t *c = zz + b * 64;
         // DC: difference to the previous block in raster order, first block raw (codec.py:34-35)
-        int dc = c[0];
-        int diff = b ? dc - prev_dc : dc;
+        const int dc = c[0];
+        const int diff = b ? dc - prev_dc : dc;
         prev_dc = dc;
-        {
-            uint32_t a = (uint32_t)(diff < 0 ? -diff : diff);
-            int size = bit_length(a);
-            if (size > 11) return TIC_E_RANGE;
-            bw.put(T.dc_code[size], T.dc_len[size]);
-            if (size) bw.put((diff < 0 ? ~a : a) & ((1u << size) - 1u), size);
-        }
-        // AC: (run,size) symbols; ZRL per 16 zeros; EOB always (huffman.py:12-33)
-        int last = 63;
-        while (last > 0 && c[last] == 0) last--;
-        int run = 0;
-        for (int k = 1; k <= last; k++) {
-            int v = c[k];
-            if (v == 0) {
-                run++;
-                continue;
-            }
-            while (run >= 16) {
-                bw.put(T.ac_code[0xF0], T.ac_len[0xF0]);
-                run -= 16;
-            }
-            const uint32_t a = (uint32_t)(v < 0 ? -v : v);
-            const int size = bit_length(a);
-            if (size > 10) return TIC_E_RANGE;
-            const int sym = (run << 4) | size;
-            // codeword (<= 16 bits) and value bits (<= 10) in one append; v < 0 -> one's complement of |v|
-            bw.put((T.ac_code[sym] << size) | ((uint32_t)(v + (v >> 31)) & ((1u << size) - 1u)), T.ac_len[sym] + size);
-            run = 0;
-        }
-        bw.put(T.ac_code[0], T.ac_len[0]); // EOB
+        if (!put_block(bw, T, diff, c + 1)) return TIC_E_RANGE;
         if (bw.overflow) return TIC_E_SPACE;
     }
     const bool pending = (bw.nacc & 7) != 0;
@@ -232,6 +239,27 @@ int entropy_encode(const int16_t *zz, int h, int w, int quality, uint8_t *out, s
 
 int entropy_encode_scaled(const int16_t *zz, int h, int w, int qf, uint8_t *out, size_t cap, size_t *out_len) {
     return entropy_encode_impl(zz, h, w, qf, out, cap, out_len, true);
+}
+
+// compress()'s writer (codec.py:133-164) on encode()'s own arrays: the DC differences are coded as they stand, so the running DC may
+// be anything - only a difference of magnitude 2,048 or an AC value of magnitude 1,024 and more has no code (huffman.py:62: KeyError).
+int entropy_encode_dpcm(const int32_t *dc, const int32_t *ac, int h, int w, int quality, uint8_t *out, size_t cap, size_t *out_len) {
+    if (!out || !out_len || h < 0 || w < 0) return TIC_E_ARG;
+    const size_t n = num_blocks(h, w);
+    if ((!dc || !ac) && n) return TIC_E_ARG;
+    if (quality < 1 || quality > 99) return TIC_E_QUALITY;
+    if (cap < 16) return TIC_E_SPACE;
+    const EncTables &T = tables();
+    write_header(out, h, w, quality);
+    BitWriter bw(out + 16, out + cap);
+    for (size_t b = 0; b < n; b++) {
+        if (!put_block(bw, T, dc[b], ac + b * 63)) return TIC_E_RANGE;
+        if (bw.overflow) return TIC_E_SPACE;
+    }
+    bw.finish();
+    if (bw.overflow) return TIC_E_SPACE;
+    *out_len = (size_t)(bw.p - out);
+    return TIC_OK;
 }
 
 // The length of the default-table stream entropy_encode would write, from a walk that only sums code lengths: per block the DC

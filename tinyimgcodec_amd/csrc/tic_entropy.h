@@ -10,6 +10,9 @@ size_t num_blocks(int h, int w);
 size_t compress_bound(int h, int w);
 void write_header(uint8_t *out, int h, int w, int quality);
 int entropy_encode(const int16_t *zz, int h, int w, int quality, uint8_t *out, size_t cap, size_t *out_len);
+// compress()'s writer on encode()'s own arrays: dc int32 [N] the DC DIFFERENCES (first block raw), ac int32 [N][63].  The running DC is
+// never formed: TIC_E_RANGE only where a difference (|d| >= 2048) or an AC value (|v| >= 1024) has no code.
+int entropy_encode_dpcm(const int32_t *dc, const int32_t *ac, int h, int w, int quality, uint8_t *out, size_t cap, size_t *out_len);
 // The length of the stream entropy_encode would write (any quality: the header's fields do not change it), from a walk of its own that
 // only sums code lengths; TIC_E_RANGE exactly where entropy_encode returns it.
 int entropy_size(const int16_t *zz, int h, int w, size_t *bytes);

@@ -970,7 +970,8 @@ __global__ __launch_bounds__(kWavesPerWG * 64) void dctq_exact_wide_kernel(WideA
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             const int y = reflect_index(s.by * 8 + r, a.h);
-            c[r] = (double)a.img[(long)y * a.stride + x] - 128.0; // (int32 - 128 is exact in float64)
+            // codec.py:29 subtracts in int32, so INT32_MIN .. INT32_MIN + 127 wrap to the top of the range; the conversion is exact
+            c[r] = (double)(int32_t)((uint32_t)a.img[(long)y * a.stride + x] - 128u);
         }
     }
     dct8_exact(c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]); // axis -2: down the column
