@@ -14,7 +14,9 @@ within a byte budget, with the image's own tables), compressed_sizes_adaptive_ba
 entropy_size_adaptive (the same length from coefficients, on the host); and for the way back from a stream to its coefficients:
 entropy_decode (the dictionary the reference's decompress() hands to decode()), entropy_decode_zz (the int16 [N, 64] layout the entropy_*
 functions take), entropy_decode_adaptive, and lossless re-tabling of stored streams, retable_adaptive / retable_default, with their batch forms
-entropy_decode_zz_batch, retable_adaptive_batch and retable_default_batch (a list of streams in one call: an archive of small streams).
+entropy_decode_zz_batch, retable_adaptive_batch and retable_default_batch (a list of streams in one call: an archive of small streams); and
+for a stored stream at another quality or within a byte budget, without pixels: requantize, requantize_zz (the coefficients alone),
+requantized_sizes (the length per quality, the stream read once) and requantize_to_size.
 """
 from ._native import Context, NativeError, NativeUnavailable
 from .codec import (compress, compress_adaptive, compress_batch, compress_batch_adaptive, compress_batch_to_psnr, compress_batch_scaled, compress_batch_to_size, compress_scaled, compress_to_psnr, compress_to_size,
@@ -24,6 +26,7 @@ from .codec import (compress, compress_adaptive, compress_batch, compress_batch_
 from .codec import compress_adaptive_to_size, compressed_size_adaptive, compressed_sizes_adaptive, compressed_sizes_adaptive_batch, entropy_size_adaptive
 from .codec import entropy_decode, entropy_decode_adaptive, entropy_decode_zz, retable_adaptive, retable_default
 from .codec import entropy_decode_zz_batch, last_transcode_batch, retable_adaptive_batch, retable_default_batch
+from .codec import last_requantize, requantize, requantize_to_size, requantize_zz, requantized_sizes
 
 __version__ = "0.1.0"
 __all__ = ["encode", "decode", "compress", "decompress"]

@@ -386,6 +386,29 @@ WIDE_SIGNATURES = {
     "tic_entropy_encode_dpcm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
+# ... and exactly the symbols include/tinyimgcodec_hip_requantize.h declares: a stored stream at another quality or within a byte budget,
+# without pixels
+REQUANT_SIGNATURES = {
+    "tic_requantize_zz": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
+    "tic_requantize_zz_dev": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
+    "tic_requantize_zz_v_dev": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
+         C.c_size_t, C.POINTER(C.c_int)],
+    ),
+    "tic_requantize": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tic_requantized_sizes": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "tic_requantize_to_size": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)],
+    ),
+    "tic_requant_kernels_timed": (
+        C.c_int,
+        [_ctxp, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p],
+    ),
+    "tic_last_requantize": (C.c_int, [_ctxp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+}
+
 _lib = None
 _lock = threading.RLock()  # re-entrant: default_context() creates a Context (which calls load()) under it
 
@@ -406,7 +429,7 @@ def load():
             except OSError as e:  # missing ROCm runtime etc.
                 raise NativeUnavailable("cannot load %s: %s" % (path, e)) from e
             for name, (res, args) in (list(SIGNATURES.items()) + list(RATE_ADAPTIVE_SIGNATURES.items()) + list(TRANSCODE_SIGNATURES.items())
-                                      + list(TRANSCODE_BATCH_SIGNATURES.items()) + list(WIDE_SIGNATURES.items())):
+                                      + list(TRANSCODE_BATCH_SIGNATURES.items()) + list(WIDE_SIGNATURES.items()) + list(REQUANT_SIGNATURES.items())):
                 fn = getattr(L, name)
                 fn.restype = res
                 fn.argtypes = args

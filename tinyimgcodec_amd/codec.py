@@ -1384,6 +1384,145 @@ def retable_default(data, ctx=None):
     return _retable(ctx, L.tic_retable_default, buf, cap, True)
 
 
+def _requant_header(buf):
+    """The checks of requantize() / requantized_sizes() / requantize_to_size() that need no device, with their exceptions: struct.error
+    below 16 bytes, ValueError for the header refusals."""
+    hdr = parse_header(buf)
+    if hdr["flag"] & (1 << 31):
+        raise ValueError("stream carries an embedded Huffman table (little-endian flag bit 31): requantisation reads default-table streams")
+    if hdr["flag"] & (1 << 30):
+        raise ValueError("a scaled_dct stream has no quality to requantise from")
+    if hdr["height"] < 0 or hdr["width"] < 0:
+        raise ValueError("negative image size in the header")
+    if not 1 <= hdr["quality"] <= 99:
+        raise ValueError("quality %d in the header outside 1..99" % hdr["quality"])
+    return hdr
+
+
+def _requant_quality(quality):
+    """A target quality of the requantisation calls: compress()'s exceptions (it ends in a header), integers only."""
+    q = _check_quality(quality, packs_header=True)
+    if isinstance(q, float):
+        raise ValueError("non-integral quality %r: requantisation takes the integers 1..99" % (quality,))
+    return q
+
+
+def requantize_zz(coeffs_zz, from_quality, to_quality, ctx=None):
+    """int16 [N, 64] zig-zag coefficients (absolute DC) of quality from_quality at quality to_quality, on the GPU: per coefficient the
+    reference's block_quantize(block_quantize(c, q1, inverse=True), q2) (utils.py:48-53), its three float64 operations in its order.
+    requantize_zz(c, q, q) is c.  KeyError where a result leaves int16 (the reference's writer has no code for it)."""
+    q1, q2 = _requant_quality(from_quality), _requant_quality(to_quality)
+    zz = np.ascontiguousarray(coeffs_zz, dtype=np.int16)
+    if zz.ndim != 2 or zz.shape[1] != 64:
+        raise ValueError("coefficients of shape %r are not [N, 64]" % (zz.shape,))
+    out = np.empty_like(zz)
+    if zz.shape[0] == 0:
+        return out
+    ctx = _ctx(ctx)
+    with ctx.lock:
+        rc = N.load().tic_requantize_zz(ctx.handle, zz.ctypes.data, zz.shape[0], q1, q2, out.ctypes.data)
+        if rc == N.TIC_E_RANGE:
+            raise KeyError(N.load().tic_last_error(ctx.handle).decode())
+        ctx.check(rc)
+    return out
+
+
+def _requant_call(ctx, L, call):
+    """rc of a requantisation call with its exceptions (call with ctx.lock held): KeyError for TIC_E_RANGE, ValueError for a refused stream."""
+    rc = call()
+    if rc == N.TIC_E_RANGE:
+        raise KeyError(L.tic_last_error(ctx.handle).decode())
+    if rc == N.TIC_E_STREAM:
+        raise ValueError(L.tic_last_error(ctx.handle).decode())
+    return rc
+
+
+def requantize(stream, quality, adaptive=False, ctx=None):
+    """A stored default-table stream at another quality, without pixels -> bytes: the reference's reader (codec.py:167-188), its
+    block_quantize(block_quantize(c, q_of_stream, inverse=True), quality) on the coefficients, its writer (codec.py:133-164; adaptive=True:
+    with the image's own Huffman tables, as compress_adaptive) with `quality` in the header.  requantize(s, q_of_s) is s for a stream our
+    encoders wrote.  struct.error below 16 bytes, ValueError for scaled_dct streams, embedded tables and refused headers, KeyError where
+    the reference's writer raises it (a value without a Huffman code), IndexError for adaptive output of a frame without blocks."""
+    buf = _as_bytes_view(stream)
+    hdr = _requant_header(buf)
+    q = _requant_quality(quality)
+    L = N.load()
+    if adaptive and L.tic_num_blocks(hdr["height"], hdr["width"]) == 0:
+        raise IndexError("index -1 is out of bounds for axis 0 with size 0")  # calc_huffman_table on an empty symbol list
+    ctx = _ctx(ctx)
+    cap = L.tic_compress_bound(hdr["height"], hdr["width"]) + (4096 if adaptive else 0)
+    with ctx.lock:
+        for _ in range(2):
+            out = getattr(ctx, "_adapt_buf", None)
+            if out is None or out.size < cap:
+                out = ctx._adapt_buf = np.empty(cap, dtype=np.uint8)
+            n = C.c_size_t(0)
+            rc = _requant_call(ctx, L, lambda: L.tic_requantize(ctx.handle, buf.ctypes.data, buf.size, q, int(bool(adaptive)), out.ctypes.data, cap, C.byref(n)))
+            if rc == N.TIC_E_SPACE and n.value > cap:  # (an adaptive table longer than the guess: once more with the reported length)
+                cap = n.value
+                continue
+            break
+        ctx.check(rc)
+        return out[: n.value].tobytes()
+
+
+def requantized_sizes(stream, qualities, ctx=None):
+    """len(requantize(stream, q)) for every q of `qualities` -> int64 array, -1 where requantize() raises KeyError.  The stream is read
+    once; no stream is produced."""
+    buf = _as_bytes_view(stream)
+    _requant_header(buf)
+    qs = [_requant_quality(q) for q in qualities]
+    sizes = np.zeros(len(qs), dtype=np.int64)
+    if not qs:
+        return sizes
+    ctx = _ctx(ctx)
+    L = N.load()
+    qarr = np.asarray(qs, dtype=np.intc)
+    with ctx.lock:
+        ctx.check(_requant_call(ctx, L, lambda: L.tic_requantized_sizes(ctx.handle, buf.ctypes.data, buf.size, qarr.ctypes.data, len(qs), sizes.ctypes.data)))
+    return sizes
+
+
+def requantize_to_size(stream, max_bytes, min_quality=1, max_quality=None, ctx=None):
+    """The best requantised stream within a byte budget -> (bytes, quality): requantize(stream, quality) of the quality at which
+    compress_to_size()'s bisection over min_quality..max_quality ends, with "requantize() succeeds and len(...) <= max_bytes" as its
+    test.  max_quality=None: the stream's own quality.  The stream is read once and the probes run on the resident coefficients.
+    ValueError naming the size at min_quality when even that exceeds the budget, KeyError when min_quality has no stream."""
+    buf = _as_bytes_view(stream)
+    hdr = _requant_header(buf)
+    qmin = _requant_quality(min_quality)
+    qmax = hdr["quality"] if max_quality is None else _requant_quality(max_quality)
+    if qmin > qmax:
+        raise ValueError("min_quality %d above max_quality %d" % (qmin, qmax))
+    max_bytes = int(max_bytes)
+    if max_bytes < 0:
+        raise ValueError("max_bytes must not be negative")
+    ctx = _ctx(ctx)
+    L = N.load()
+    cap = L.tic_compress_bound(hdr["height"], hdr["width"])
+    with ctx.lock:
+        out = getattr(ctx, "_out_buf", None)  # compress()'s landing buffer
+        if out is None or out.size < cap:
+            out = ctx._out_buf = np.empty(cap, dtype=np.uint8)
+        n, q = C.c_size_t(0), C.c_int(0)
+        rc = _requant_call(ctx, L, lambda: L.tic_requantize_to_size(ctx.handle, buf.ctypes.data, buf.size, max_bytes, qmin, qmax, out.ctypes.data, cap,
+                                                                     C.byref(n), C.byref(q)))
+        if rc == N.TIC_E_SPACE:
+            raise ValueError("%d bytes at quality %d exceed max_bytes = %d" % (n.value, qmin, max_bytes))
+        ctx.check(rc)
+        return out[: n.value].tobytes(), int(q.value)
+
+
+def last_requantize(ctx=None):
+    """What the context's last requantisation call did: {"route": 1 device reader / 2 host reader / 0 none, "measure_launches",
+    "store_launches", "rounds"} (tic_last_requantize)."""
+    ctx = _ctx(ctx)
+    v = [C.c_int(0) for _ in range(4)]
+    with ctx.lock:
+        ctx.check(N.load().tic_last_requantize(ctx.handle, *[C.byref(x) for x in v]))
+    return dict(zip(("route", "measure_launches", "store_launches", "rounds"), (int(x.value) for x in v)))
+
+
 def _frame_exception(i, e):
     """The exception a single call raised for frame i of a batch: the same class, the message naming the frame."""
     if isinstance(e, N.NativeError):

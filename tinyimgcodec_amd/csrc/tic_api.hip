@@ -20,6 +20,7 @@
 
 #include "../../include/tinyimgcodec_hip.h"
 #include "../../include/tinyimgcodec_hip_adaptive_rate.h"
+#include "../../include/tinyimgcodec_hip_requantize.h"
 #include "../../include/tinyimgcodec_hip_transcode.h"
 #include "../../include/tinyimgcodec_hip_transcode_batch.h"
 #include "../../include/tinyimgcodec_hip_wide.h"
@@ -34,6 +35,7 @@
 #include "tic_kernels.h"
 #include "tic_math.h"
 #include "tic_rd_plan.h"
+#include "tic_requant_gpu.h"
 #include "tic_scaled.h"
 #include "tic_size_gpu.h"
 #include "tic_transcode_plan.h"
@@ -388,6 +390,12 @@ struct tic_ctx {
     PinBuf<AdaptFrameTable> h_arate_frames{"h_arate_frames"};
     DevBuf<AdaptFrameTable> d_arate_frames{"d_arate_frames"};
     int last_arate_probes = 0, last_arate_waits = 0, last_arate_launches = 0;
+    // requantisation (tinyimgcodec_hip_requantize.h): the store launches' tables and range flags, the workspace tic_requant_kernels_timed
+    // stores into (the calls themselves requantise in place in d_coef, where the reader left the rows), and what the last call did.
+    DevBuf<int16_t> d_requant{"d_requant"};
+    PinBuf<RequantLaunch> h_requant_tabs{"h_requant_tabs"};
+    DevBuf<RequantLaunch> d_requant_tabs{"d_requant_tabs"};
+    int last_rq_route = 0, last_rq_measure = 0, last_rq_store = 0, last_rq_rounds = 0;
 };
 
 // NUMA node of a device (its PCI function's numa_node in sysfs) and the CPUs of that node within this process's affinity mask.
@@ -6489,6 +6497,374 @@ int tic_last_adaptive_rate(tic_ctx *ctx, int *probes, int *host_waits, int *stat
     if (probes) *probes = ctx->last_arate_probes;
     if (host_waits) *host_waits = ctx->last_arate_waits;
     if (stats_launches) *stats_launches = ctx->last_arate_launches;
+    return TIC_OK;
+}
+
+// ---- requantisation (tinyimgcodec_hip_requantize.h): a stream's coefficients at another quality, and the streams written from them -------------
+// The reader is tic_entropy_decode's (read_default_coefs), the writers are tic_retable_default's and tic_retable_adaptive's; in between the
+// store kernel (tic_requant_gpu.hip) works IN PLACE on ctx->d_coef for a stream that is written; a size table or a search runs the measuring
+// kernel on ctx->d_coef, which stores nothing: the source stays where the reader left it, so the stream is read once whatever the number
+// of qualities.
+static void reset_requant(tic_ctx *ctx) { ctx->last_rq_route = ctx->last_rq_measure = ctx->last_rq_store = ctx->last_rq_rounds = 0; }
+
+static int ensure_requant_tabs(tic_ctx *ctx, size_t launches) {
+    const size_t bytes = launches * sizeof(RequantLaunch);
+    const int rc = ctx->h_requant_tabs.grow(ctx, bytes, align_up(bytes, 16384));
+    return rc ? rc : ctx->d_requant_tabs.grow(ctx, bytes, align_up(bytes, 16384));
+}
+
+// Launch t of a call, queued: the n jobs go up in its table together with their zeroed flags, the kernel runs, the flags come back into
+// ctx->h_requant_tabs[t].flags.  The caller waits for the stream before it reads them, and before it fills table t again.
+static int queue_requant(tic_ctx *ctx, size_t t, const RequantJobIn *jobs, int n, const int16_t *d_src, size_t src_cap, int16_t *d_dst, size_t dst_cap) {
+    RequantLaunch *h = ctx->h_requant_tabs + t, *d = ctx->d_requant_tabs + t;
+    size_t ngroups = 0;
+    if (!fill_requant_job_table(&h->tab, n, jobs, src_cap, dst_cap, &ngroups)) return set_err(ctx, TIC_E_ARG, "requantise: %d jobs have no table", n);
+    memset(h->flags, 0, sizeof h->flags);
+    HIPCHK(ctx, hipMemcpyAsync(d, h, sizeof *h, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, requant_gpu_v(d_src, d_dst, &d->tab, ngroups, ctx->d_consts, d->flags, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(h->flags, d->flags, sizeof h->flags, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->last_rq_store++;
+    return TIC_OK;
+}
+
+static int check_requant_quality(tic_ctx *ctx, int q, const char *which) {
+    return q < 1 || q > 99 ? set_err(ctx, TIC_E_QUALITY, "%s quality %d outside 1..99", which, q) : TIC_OK;
+}
+
+static int requantize_zz_impl(tic_ctx *ctx, const void *coeffs, size_t n, int q_from, int q_to, void *out, bool on_device) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    reset_requant(ctx);
+    int rc = check_requant_quality(ctx, q_from, "source");
+    if (rc == TIC_OK) rc = check_requant_quality(ctx, q_to, "target");
+    if (rc) return rc;
+    if (n == 0) return TIC_OK;
+    if (!coeffs || !out) return set_err(ctx, TIC_E_ARG, "null coefficient pointer");
+    if (n > (~(size_t)0 >> 8)) return set_err(ctx, TIC_E_ARG, "%zu blocks are more than an address holds", n);
+    const int16_t *d_src = (const int16_t *)coeffs;
+    int16_t *d_dst = (int16_t *)out;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (on_device) {
+        if ((((uintptr_t)coeffs) | ((uintptr_t)out)) & 15u) return set_err(ctx, TIC_E_ARG, "device coefficient buffers must be 16-byte aligned");
+        const uintptr_t a = (uintptr_t)coeffs, b = (uintptr_t)out;
+        if (a != b && a < b + n * 128 && b < a + n * 128) return set_err(ctx, TIC_E_ARG, "source and destination overlap without being the same buffer");
+    } else {
+        rc = ensure_scratch(ctx, 0, n * 128);
+        if (rc) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, coeffs, n * 128, hipMemcpyHostToDevice, ctx->stream));
+        d_src = d_dst = (int16_t *)ctx->d_coef;
+    }
+    rc = ensure_requant_tabs(ctx, 1);
+    if (rc) return rc;
+    const RequantJobIn job = {0, 0, n, q_from, q_to, 0};
+    rc = queue_requant(ctx, 0, &job, 1, d_src, n, d_dst, n);
+    if (rc) return rc;
+    if (!on_device) HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_coef, n * 128, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->h_requant_tabs[0].flags[0]) return set_err(ctx, TIC_E_RANGE, "a coefficient requantised from quality %d to %d leaves int16", q_from, q_to);
+    return TIC_OK;
+}
+
+int tic_requantize_zz(tic_ctx *ctx, const int16_t *coeffs_zz, size_t nblocks, int from_quality, int to_quality, int16_t *out_zz) {
+    return requantize_zz_impl(ctx, coeffs_zz, nblocks, from_quality, to_quality, out_zz, false);
+}
+
+int tic_requantize_zz_dev(tic_ctx *ctx, const void *d_coeffs_zz, size_t nblocks, int from_quality, int to_quality, void *d_out_zz) {
+    return requantize_zz_impl(ctx, d_coeffs_zz, nblocks, from_quality, to_quality, d_out_zz, true);
+}
+
+int tic_requantize_zz_v_dev(tic_ctx *ctx, const void *d_coeffs_zz, size_t src_blocks, int njobs, const size_t *src_block, const size_t *nblocks,
+                            const int *from_quality, const int *to_quality, void *d_out_zz, size_t out_blocks, int *range) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    reset_requant(ctx);
+    if (njobs < 0 || (njobs > 0 && (!src_block || !nblocks || !from_quality || !to_quality || !range))) return set_err(ctx, TIC_E_ARG, "bad job list");
+    if (njobs == 0) return TIC_OK;
+    if (src_blocks > (~(size_t)0 >> 8) || out_blocks > (~(size_t)0 >> 8)) return set_err(ctx, TIC_E_ARG, "more blocks than an address holds");
+    size_t total = 0;
+    for (int k = 0; k < njobs; k++) {
+        int rc = check_requant_quality(ctx, from_quality[k], "source");
+        if (rc == TIC_OK) rc = check_requant_quality(ctx, to_quality[k], "target");
+        if (rc) return rc;
+        if (nblocks[k] == 0) return set_err(ctx, TIC_E_ARG, "job %d has no blocks", k);
+        if (src_block[k] > src_blocks || nblocks[k] > src_blocks - src_block[k])
+            return set_err(ctx, TIC_E_ARG, "job %d reads blocks %zu + %zu of %zu", k, src_block[k], nblocks[k], src_blocks);
+        if (nblocks[k] > out_blocks - total) return set_err(ctx, TIC_E_SPACE, "coefficient buffer too small (job %d ends at block %zu)", k, total + nblocks[k]);
+        total += nblocks[k];
+    }
+    if (!d_coeffs_zz || !d_out_zz) return set_err(ctx, TIC_E_ARG, "null coefficient pointer");
+    if ((((uintptr_t)d_coeffs_zz) | ((uintptr_t)d_out_zz)) & 15u) return set_err(ctx, TIC_E_ARG, "device coefficient buffers must be 16-byte aligned");
+    const uintptr_t a = (uintptr_t)d_coeffs_zz, b = (uintptr_t)d_out_zz;
+    if (a < b + out_blocks * 128 && b < a + src_blocks * 128) return set_err(ctx, TIC_E_ARG, "source and destination overlap");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t launches = ((size_t)njobs + kSizeMaxProbes - 1) / kSizeMaxProbes;
+    int rc = ensure_requant_tabs(ctx, launches);
+    if (rc) return rc;
+    size_t at = 0;
+    for (size_t t = 0; t < launches; t++) {
+        RequantJobIn jobs[kSizeMaxProbes];
+        const int first = (int)t * kSizeMaxProbes, cnt = std::min(kSizeMaxProbes, njobs - first);
+        for (int k = 0; k < cnt; k++) {
+            jobs[k] = RequantJobIn{src_block[first + k], at, nblocks[first + k], from_quality[first + k], to_quality[first + k], (uint32_t)k};
+            at += nblocks[first + k];
+        }
+        rc = queue_requant(ctx, t, jobs, cnt, (const int16_t *)d_coeffs_zz, src_blocks, (int16_t *)d_out_zz, out_blocks);
+        if (rc) break;
+    }
+    if (const hipError_t e = hipStreamSynchronize(ctx->stream); e != hipSuccess && rc == TIC_OK) // (the call ends drained, also one that could not queue all its launches)
+        rc = set_err(ctx, TIC_E_HIP, "waiting for the stream failed: %s", hipGetErrorString(e));
+    if (rc) return rc;
+    for (int k = 0; k < njobs; k++) range[k] = ctx->h_requant_tabs[k / kSizeMaxProbes].flags[k % kSizeMaxProbes] ? 1 : 0;
+    return TIC_OK;
+}
+
+// The refusals the stream calls share (tic_retable_adaptive's, in its order), all before GPU work.
+static int check_requant_header(tic_ctx *ctx, const uint8_t *data, size_t len, StreamHead *sh) {
+    if (!data && len) return set_err(ctx, TIC_E_ARG, "null stream pointer");
+    int h = 0, w = 0, q = 0;
+    uint32_t flag = 0;
+    if (parse_header(data, len, &h, &w, &q, &flag) != TIC_OK) return set_err(ctx, TIC_E_STREAM, "stream shorter than the 16-byte header");
+    if (flag & (1u << 31)) return set_err(ctx, TIC_E_STREAM, "the stream has an embedded Huffman table: requantisation reads default-table streams");
+    if (flag & kFlagScaled) return set_err(ctx, TIC_E_STREAM, "a scaled_dct stream has no quality to requantise from");
+    if (h < 0 || w < 0) return set_err(ctx, TIC_E_STREAM, "negative image size in the header");
+    if (q < 1 || q > 99) return set_err(ctx, TIC_E_STREAM, "quality %d in the header outside 1..99", q);
+    *sh = {h, w, q, -1};
+    return TIC_OK;
+}
+
+// The stream's n >= 1 blocks into ctx->d_coef: the device reader's never left, the host reader's go up.
+static int requant_read(tic_ctx *ctx, const uint8_t *data, size_t len, const StreamHead &sh, size_t n) {
+    ctx->last_decode_giveup = 0;
+    ctx->last_decode_tries = 0;
+    bool dev = false;
+    int rc = read_default_coefs(ctx, data, len, false, sh, data, nullptr, &dev);
+    if (rc) return rc;
+    ctx->last_rq_route = dev ? 1 : 2;
+    if (dev) return TIC_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    rc = ensure_scratch(ctx, 0, n * 128);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_coef, ctx->h_zz, n * 128, hipMemcpyHostToDevice, ctx->stream));
+    return TIC_OK;
+}
+
+// The n blocks in ctx->d_coef from quality q_from to q_to in place, then the stream of quality q_to into the caller's host buffer.
+static int requant_write(tic_ctx *ctx, size_t n, int h, int w, int q_from, int q_to, bool adaptive, uint8_t *out, size_t cap, size_t *out_len) {
+    int rc = ensure_requant_tabs(ctx, 1);
+    if (rc) return rc;
+    const RequantJobIn job = {0, 0, n, q_from, q_to, 0};
+    rc = queue_requant(ctx, 0, &job, 1, (const int16_t *)ctx->d_coef, n, (int16_t *)ctx->d_coef, n);
+    if (rc) return rc;
+    // the range flag decides before anything is written: a value that left int16 is unspecified in d_coef, and so would its stream be
+    HIPCHK(ctx, wait_stream(ctx));
+    if (ctx->h_requant_tabs[0].flags[0]) return set_err(ctx, TIC_E_RANGE, "a coefficient requantised from quality %d to %d leaves int16", q_from, q_to);
+    if (adaptive) return adaptive_encode_dev(ctx, n, h, w, q_to, out, cap, out_len);
+    rc = ctx->d_stream_buf.grow(ctx, compress_bound(h, w)); // (the input stream's copy there, if the device reader made one, is done with)
+    if (rc) return rc;
+    size_t packed = 0;
+    rc = entropy_encode_dev_impl(ctx, ctx->d_coef, h, w, q_to, ctx->d_stream_buf, ctx->d_stream_buf.cap, &packed, false);
+    if (rc) return rc;
+    if (packed > cap) {
+        *out_len = packed;
+        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", packed, cap);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_stream_buf, packed, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *out_len = packed;
+    return TIC_OK;
+}
+
+int tic_requantize(tic_ctx *ctx, const uint8_t *data, size_t len, int to_quality, int adaptive, uint8_t *out, size_t cap, size_t *out_len) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    reset_requant(ctx);
+    if (!out || !out_len) return set_err(ctx, TIC_E_ARG, "null output pointer");
+    StreamHead sh;
+    int rc = check_requant_header(ctx, data, len, &sh);
+    if (rc == TIC_OK) rc = check_requant_quality(ctx, to_quality, "target");
+    if (rc) return rc;
+    const size_t n = num_blocks(sh.h, sh.w);
+    if (n == 0) {
+        if (adaptive) return set_err(ctx, TIC_E_ARG, "an image without blocks has no symbols to build a table from (the reference raises IndexError)");
+        *out_len = 16;
+        if (cap < 16) return set_err(ctx, TIC_E_SPACE, "output buffer too small (16 bytes needed, %zu given)", cap);
+        write_header(out, sh.h, sh.w, to_quality); // the header alone (codec.py:151)
+        return TIC_OK;
+    }
+    rc = requant_read(ctx, data, len, sh, n);
+    if (rc) return rc;
+    return requant_write(ctx, n, sh.h, sh.w, sh.quality, to_quality, adaptive != 0, out, cap, out_len);
+}
+
+// One measuring launch, queued: the sizes of the frame of n blocks at d_src at the nq qualities q[0 .. nq) (at most kSizeMaxProbes), added
+// into ctx->d_rate[res0 .. res0 + nq) by the measuring kernel; nothing is stored.  The caller has zeroed and provisioned the results
+// (ensure_rate); it waits.  (The composition this replaced - the store kernel into a workspace, then the size kernel's descriptor form -
+// lives on in tic_requant_kernels_timed alone, where the two are timed side by side: DESIGN.md 5.14.)
+static int queue_requant_sizes(tic_ctx *ctx, const int16_t *d_src, size_t n, int q_from, const int *q, int nq, uint32_t res0) {
+    RequantQualities qs;
+    qs.nq = nq, qs.q_from = q_from;
+    for (int k = 0; k < kSizeMaxProbes; k++) qs.q_to[k] = (uint8_t)(k < nq ? q[k] : 0);
+    HIPCHK(ctx, requant_size_gpu_v(d_src, n, qs, ctx->d_consts, ctx->d_size_tab, ctx->d_rate + res0, ctx->stream));
+    ctx->last_rq_measure++;
+    return TIC_OK;
+}
+
+int tic_requantized_sizes(tic_ctx *ctx, const uint8_t *data, size_t len, const int *qualities, int nq, long long *sizes) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    reset_requant(ctx);
+    if (nq < 0 || (nq > 0 && (!qualities || !sizes))) return set_err(ctx, TIC_E_ARG, "bad quality list");
+    StreamHead sh;
+    int rc = check_requant_header(ctx, data, len, &sh);
+    for (int i = 0; i < nq && rc == TIC_OK; i++) rc = check_requant_quality(ctx, qualities[i], "target");
+    if (rc || nq == 0) return rc;
+    const size_t n = num_blocks(sh.h, sh.w);
+    if (n == 0) { // header only (codec.py:151)
+        for (int i = 0; i < nq; i++) sizes[i] = 16;
+        return TIC_OK;
+    }
+    rc = requant_read(ctx, data, len, sh, n);
+    if (rc) return rc;
+    // (the measuring kernel writes nothing: a launch takes as many qualities as its table holds)
+    const size_t per = (size_t)kSizeMaxProbes, launches = ((size_t)nq + per - 1) / per;
+    rc = ensure_rate(ctx, (size_t)nq);
+    if (rc == TIC_OK && hipMemsetAsync(ctx->d_rate, 0, (size_t)nq * sizeof(SizeResult), ctx->stream) != hipSuccess)
+        rc = set_err(ctx, TIC_E_HIP, "hipMemsetAsync of the size results failed");
+    for (size_t t = 0; t < launches && rc == TIC_OK; t++) {
+        const size_t first = t * per;
+        rc = queue_requant_sizes(ctx, (const int16_t *)ctx->d_coef, n, sh.quality, qualities + first, (int)std::min(per, (size_t)nq - first), (uint32_t)first);
+    }
+    if (rc == TIC_OK && hipMemcpyAsync(ctx->h_rate, ctx->d_rate, (size_t)nq * sizeof(SizeResult), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        rc = set_err(ctx, TIC_E_HIP, "hipMemcpyAsync of the size results failed");
+    if (const hipError_t e = wait_stream(ctx); e != hipSuccess && rc == TIC_OK) // (the call ends drained, also one that could not queue all its passes)
+        rc = set_err(ctx, TIC_E_HIP, "waiting for the stream failed: %s", hipGetErrorString(e));
+    if (rc) return rc;
+    ctx->last_rq_rounds = 1;
+    for (int i = 0; i < nq; i++) sizes[i] = probe_size(ctx->h_rate[i]); // (-1: a value without a code or outside int16)
+    return TIC_OK;
+}
+
+int tic_requantize_to_size(tic_ctx *ctx, const uint8_t *data, size_t len, size_t max_bytes, int qmin, int qmax, uint8_t *out, size_t cap,
+                           size_t *out_len, int *quality) {
+    TIC_LOCK(ctx);
+    if (!ctx || !out_len || !quality) return TIC_E_ARG;
+    reset_requant(ctx);
+    StreamHead sh;
+    int rc = check_requant_header(ctx, data, len, &sh);
+    if (rc) return rc;
+    if (qmax == 0) qmax = sh.quality;
+    if (qmin < 1 || qmax > 99 || qmin > qmax) return set_err(ctx, TIC_E_QUALITY, "quality range %d..%d is not inside 1..99", qmin, qmax);
+    if (!out || cap < 16) return set_err(ctx, TIC_E_SPACE, "output buffer too small");
+    const size_t n = num_blocks(sh.h, sh.w);
+    if (n == 0) { // a header at every quality: the bisection ends at qmax
+        *out_len = 16;
+        if (max_bytes < 16) return set_err(ctx, TIC_E_SPACE, "16 bytes at quality %d exceed the budget of %zu", qmin, max_bytes);
+        write_header(out, sh.h, sh.w, qmax);
+        *quality = qmax;
+        return TIC_OK;
+    }
+    rc = requant_read(ctx, data, len, sh, n);
+    if (rc) return rc;
+    RateSearch rs;
+    rate_search_begin(rs, qmin, qmax, (unsigned long long)max_bytes);
+    int cand[kRateMaxCandidates];
+    while (const int nc = rate_search_round(rs, single_frame_depth(n), cand)) {
+        rc = ensure_rate(ctx, (size_t)nc);
+        if (rc) return rc;
+        if (hipMemsetAsync(ctx->d_rate, 0, (size_t)nc * sizeof(SizeResult), ctx->stream) != hipSuccess)
+            rc = set_err(ctx, TIC_E_HIP, "hipMemsetAsync of the size results failed");
+        if (rc == TIC_OK) rc = queue_requant_sizes(ctx, (const int16_t *)ctx->d_coef, n, sh.quality, cand, nc, 0);
+        if (rc == TIC_OK && hipMemcpyAsync(ctx->h_rate, ctx->d_rate, (size_t)nc * sizeof(SizeResult), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+            rc = set_err(ctx, TIC_E_HIP, "hipMemcpyAsync of the size results failed");
+        if (const hipError_t e = wait_stream(ctx); e != hipSuccess && rc == TIC_OK) // (a round ends drained, also one that could not queue all of itself)
+            rc = set_err(ctx, TIC_E_HIP, "waiting for the stream failed: %s", hipGetErrorString(e));
+        if (rc) return rc;
+        ctx->last_rq_rounds++;
+        for (int i = 0; i < nc; i++) rs.known[cand[i]] = probe_size(ctx->h_rate[i]); // (-1: a value without a code or outside int16)
+        rate_search_replay(rs);
+    }
+    if (rs.state == kRateNoCode)
+        return set_err(ctx, TIC_E_RANGE, "a coefficient outside int16 or without a Huffman code at quality %d (reference raises KeyError)", qmin);
+    if (rs.state == kRateTooLarge) {
+        *out_len = (size_t)rs.known[qmin];
+        return set_err(ctx, TIC_E_SPACE, "%lld bytes at quality %d exceed the budget of %zu", rs.known[qmin], qmin, max_bytes);
+    }
+    const size_t want = (size_t)rs.known[rs.lo];
+    if (want > cap) {
+        *out_len = want;
+        return set_err(ctx, TIC_E_SPACE, "output buffer too small (%zu bytes needed, %zu given)", want, cap);
+    }
+    rc = requant_write(ctx, n, sh.h, sh.w, sh.quality, rs.lo, false, out, cap, out_len);
+    if (rc) return rc;
+    if (*out_len != want) // (two independent walks over the same coefficients: cannot differ)
+        return set_err(ctx, TIC_E_HIP, "the packed stream (%zu bytes) contradicts its probe (%zu bytes)", *out_len, want);
+    *quality = rs.lo;
+    return TIC_OK;
+}
+
+int tic_requant_kernels_timed(tic_ctx *ctx, const void *d_coeffs_zz, size_t nblocks, int from_quality, const int *qualities, int nq, int mode,
+                              int warm, int iters, float *ms_total, long long *sizes) {
+    TIC_LOCK(ctx);
+    if (!ctx || !ms_total || warm < 0 || iters <= 0) return TIC_E_ARG;
+    if (!d_coeffs_zz || ((uintptr_t)d_coeffs_zz & 15u) || nblocks == 0 || nblocks > (~(size_t)0 >> 8) || !qualities || nq < 1 || nq > kSizeMaxProbes ||
+        mode < 0 || mode > 2)
+        return set_err(ctx, TIC_E_ARG, "bad argument");
+    int rc = check_requant_quality(ctx, from_quality, "source");
+    for (int i = 0; i < nq && rc == TIC_OK; i++) rc = check_requant_quality(ctx, qualities[i], "target");
+    if (rc) return rc;
+    reset_requant(ctx);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    rc = ensure_rate(ctx, (size_t)nq);
+    if (rc == TIC_OK && mode != 1) rc = ctx->d_requant.grow(ctx, (size_t)nq * nblocks * 128); // the composition's workspace, tables and flags
+    if (rc == TIC_OK && mode != 1) rc = ensure_probe_tabs(ctx, 1, 0);
+    if (rc == TIC_OK && mode != 1) rc = ensure_requant_tabs(ctx, 1);
+    if (rc) return rc;
+    // tables once, in front of the timed interval: what is timed is the kernels (and the memset every measuring run begins with)
+    size_t job_groups = 0, size_groups = 0;
+    RequantLaunch *const hl = ctx->h_requant_tabs, *const dl = ctx->d_requant_tabs; // (null for mode 1, which uses neither)
+    RequantQualities qs;
+    qs.nq = nq, qs.q_from = from_quality;
+    for (int k = 0; k < kSizeMaxProbes; k++) qs.q_to[k] = (uint8_t)(k < nq ? qualities[k] : 0);
+    if (mode != 1) {
+        RequantJobIn jobs[kSizeMaxProbes];
+        size_t nblk[kSizeMaxProbes], total = 0;
+        uint32_t result[kSizeMaxProbes];
+        for (int k = 0; k < nq; k++) {
+            jobs[k] = RequantJobIn{0, (size_t)k * nblocks, nblocks, from_quality, qualities[k], (uint32_t)k};
+            nblk[k] = nblocks, result[k] = (uint32_t)k;
+        }
+        if (!fill_requant_job_table(&hl->tab, nq, jobs, nblocks, ctx->d_requant.cap / 128, &job_groups) ||
+            !fill_size_probe_table(ctx->h_rate_tabs, nq, nblk, result, &size_groups, &total))
+            return set_err(ctx, TIC_E_ARG, "requantise: %d jobs have no table", nq);
+        memset(hl->flags, 0, sizeof hl->flags);
+        HIPCHK(ctx, hipMemcpyAsync(dl, hl, sizeof *hl, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_rate_tabs, ctx->h_rate_tabs, sizeof(SizeProbeTable), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    rc = timed_launches(ctx, warm, iters, ms_total, nullptr, [&](int, hipEvent_t, hipEvent_t) {
+        if (mode == 0) return requant_gpu_v((const int16_t *)d_coeffs_zz, ctx->d_requant, &dl->tab, job_groups, ctx->d_consts, dl->flags, ctx->stream);
+        hipError_t e = hipMemsetAsync(ctx->d_rate, 0, (size_t)nq * sizeof(SizeResult), ctx->stream); // (every run starts from zeroed results)
+        if (e != hipSuccess) return e;
+        if (mode == 1) return requant_size_gpu_v((const int16_t *)d_coeffs_zz, nblocks, qs, ctx->d_consts, ctx->d_size_tab, ctx->d_rate, ctx->stream);
+        e = requant_gpu_v((const int16_t *)d_coeffs_zz, ctx->d_requant, &dl->tab, job_groups, ctx->d_consts, dl->flags, ctx->stream);
+        return e != hipSuccess ? e : stream_size_gpu_v(ctx->d_requant, ctx->d_rate_tabs, size_groups, ctx->d_size_tab, ctx->d_rate, ctx->stream);
+    });
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_rate, ctx->d_rate, (size_t)nq * sizeof(SizeResult), hipMemcpyDeviceToHost, ctx->stream));
+    if (mode != 1) HIPCHK(ctx, hipMemcpyAsync(hl->flags, dl->flags, sizeof hl->flags, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; sizes && i < nq; i++)
+        sizes[i] = mode == 0 ? 0 : (mode == 2 && hl->flags[i]) ? -1ll : probe_size(ctx->h_rate[i]);
+    return TIC_OK;
+}
+
+int tic_last_requantize(tic_ctx *ctx, int *route, int *measure_launches, int *store_launches, int *rounds) {
+    TIC_LOCK(ctx);
+    if (!ctx) return TIC_E_ARG;
+    if (route) *route = ctx->last_rq_route;
+    if (measure_launches) *measure_launches = ctx->last_rq_measure;
+    if (store_launches) *store_launches = ctx->last_rq_store;
+    if (rounds) *rounds = ctx->last_rq_rounds;
     return TIC_OK;
 }
 
